@@ -16,6 +16,9 @@ Rank 0 prints ONE JSON line.
 child processes (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1) BEFORE
 anything touches the GPU, relays their output and exits non-zero if any child fails.  `--dry-run` exercises exactly
 that launcher + rendezvous + JSON plumbing on the CPU (gloo), without the model.
+
+`--dump-outputs DIR` writes what the last timed step returned (losses, gradients: `dump_outputs`) as DIR/<name>.npy.  Weights,
+patches and dropout streams are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -150,7 +153,13 @@ def parse_args(argv=None):
     ap.add_argument('--tail-mb', type=float, default=0.5)
     ap.add_argument('--dry-run', action='store_true',
                     help='CPU/gloo rehearsal of the launcher, rendezvous, barrier / max-over-ranks timing and the JSON line; no GPU, no model')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, rank 0 writes what the last timed step returned (level losses, loss terms, gradients) '
+                         'as DIR/<name>.npy, for comparing two builds output for output')
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.steps < 1 and not args.dry_run:
+        ap.error('--dump-outputs needs at least one timed step')
+    return args
 
 
 def _free_port():
@@ -223,6 +232,36 @@ def largest_kernel(group, pmc_json, stats_csv):
             out.update(traffic=(fam['hbm_read_GB_per_step'] + fam['hbm_write_GB_per_step']) * 1e9,
                        traffic_source=f'profiles/{os.path.basename(pmc_json)} (bytes per step)')
     return out
+
+
+DUMP_GRAD_ELEMS = 8 << 20         # gradient elements kept by --dump-outputs (32 MB of fp32); the whole model has ~21 M
+
+
+def dump_outputs(out_dir, model, totals, named):
+    """--dump-outputs: what a caller of the timed step received from its last replay, in float64 / float32 .npy files.
+      level_losses [levels]  the weighted level totals the step returns (their sum is the loss that was back-propagated)
+      loss_terms   [terms]   every named loss term, level by level, names in sorted order within a level
+      grad_norms   [params]  L2 norm of every parameter gradient, in model.named_parameters() order (parameters without one skipped)
+      grads        [n]       the gradients of those parameters concatenated in the same order: all of them if they fit
+                             DUMP_GRAD_ELEMS, else the elements at the sorted indices numpy.random.default_rng(0).choice(total,
+                             DUMP_GRAD_ELEMS, replace=False) - the same sample in every run with the same arguments"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    grads = [p.grad.detach() for _, p in model.named_parameters() if p.grad is not None]
+    flat = torch.cat([g.reshape(-1).float() for g in grads])
+    if flat.numel() > DUMP_GRAD_ELEMS:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_GRAD_ELEMS, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    arrays = {
+        'level_losses': np.array([float(t) for t in totals], dtype=np.float64),
+        'loss_terms': np.array([float(lvl[k]) for lvl in named for k in sorted(lvl)], dtype=np.float64),
+        'grad_norms': torch.stack([g.double().norm() for g in grads]).cpu().numpy(),
+        'grads': flat.cpu().numpy().astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    print(f'[bench] wrote {", ".join(f"{k}{list(a.shape)}" for k, a in arrays.items())} to {out_dir}', file=sys.stderr)
 
 
 def quiet_stdout():
@@ -467,7 +506,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        last = step(i)
     torch.cuda.synchronize()
     if world > 1:
         comm.barrier()
@@ -475,6 +514,9 @@ def main():
     timer.on = False
     if world > 1:
         dt = comm.max_float(dt)
+    if args.dump_outputs and rank == 0:
+        # before anything below replays kernels into the same loss tensors and gradient buffers
+        dump_outputs(args.dump_outputs, model, *last)
     if (world > 1 or args.rehearse_comm or os.environ.get('LTU_BENCH_LOCAL') == '1') and launch == 'hip-graph replay':
         # what the exchange costs: the same replayed step without its collectives, and where in the step each bucket closes
         for i in range(2):

@@ -241,3 +241,27 @@ def test_bench_default_path_with_family_table():
     assert out['config']['launch'].startswith('hip-graph replay (segments')
     fams = {f['family']: f for f in out['roofline']['families']}
     assert {'transformer', 'conv3', 'instnorm'} <= set(fams) and all(f['ms_per_step'] > 0 for f in fams.values())
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """`bench.py --dump-outputs DIR`: what the last timed step returned (level losses, loss terms, gradient norms, a fixed sample of
+    the gradients) lands in float .npy files within 64 MB, and two runs with the same arguments write the same numbers"""
+    import os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f'run{run}'
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--size', '32', '--steps', '2', '--warmup', '1',
+                            '--no-cpu-baseline', '--no-families', '--dump-outputs', str(d)], env=env, capture_output=True, text=True,
+                           timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        files = sorted(os.listdir(d))
+        assert files == ['grad_norms.npy', 'grads.npy', 'level_losses.npy', 'loss_terms.npy'], files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f[:-len('.npy')]: np.load(d / f) for f in files})
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), f
+        assert np.array_equal(a, dumps[1][f]), f
+    assert dumps[0]['level_losses'].shape == (5,) and (dumps[0]['grad_norms'] > 0).mean() > 0.5

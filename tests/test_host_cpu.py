@@ -223,8 +223,6 @@ def test_bench_parent_does_not_import_torch_before_launch():
 
 def test_comm_surface_without_gpu():
     """LocalComm is a no-op communicator; the RCCL entry points refuse to work before ltu_comm_load (no compute, no GPU)"""
-    import ctypes
-    from lintransunet_amd import _lib
     from lintransunet_amd import comm as C
     c = C.LocalComm()
     t = torch.ones(4)
@@ -232,11 +230,23 @@ def test_comm_surface_without_gpu():
     c.broadcast(t)
     c.barrier()
     assert c.max_float(2.5) == 2.5 and torch.equal(t, torch.ones(4))
-    lib = _lib.load()
-    assert lib.ltu_comm_load(None) == -4                       # LTU_E_ARG
-    assert lib.ltu_comm_load(b'/nonexistent/librccl.so') == -100        # LTU_E_COMM: not loadable
-    buf = (ctypes.c_char * 128)()
-    assert lib.ltu_comm_unique_id(ctypes.addressof(buf)) == -100        # not loaded
+    # RCCL, once loaded, stays loaded for the life of the process (a GPU test earlier in the same session may have loaded it):
+    # the not-loaded state is checked in a fresh interpreter
+    import subprocess
+    import sys
+    code = f'''if True:
+        import ctypes, sys
+        sys.path.insert(0, {ROOT!r})
+        from lintransunet_amd import _lib
+        lib = _lib.load()
+        assert lib.ltu_comm_load(None) == -4                                # LTU_E_ARG
+        assert lib.ltu_comm_load(b'/nonexistent/librccl.so') == -100        # LTU_E_COMM: not loadable
+        buf = (ctypes.c_char * 128)()
+        assert lib.ltu_comm_unique_id(ctypes.addressof(buf)) == -100        # not loaded
+        print('ok')'''
+    r = subprocess.run([sys.executable] + (['-s'] if sys.flags.no_user_site else []) + ['-c', code], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == 'ok', r.stderr[-3000:]
     with pytest.raises(RuntimeError):
         C.GlooComm()                                           # needs an initialised gloo group
 
