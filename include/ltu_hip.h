@@ -418,6 +418,32 @@ int ltu_seg_metrics(const float* pred, const uint8_t* target, float* rows, float
 int ltu_keep_largest_component(float* pred, int* labels, int* counts, unsigned long long* best, int* changed, int C, int H, int W,
                                int D, int step, ltu_stream_t s);
 
+/* surface-distance metrics of the evaluation (no reference counterpart; csrc/surface.hip): per (sample b, class k) with
+ * A = pred[b][k] >= threshold and B = target[b] == k, the boundary dX = voxels of X with a face neighbour outside X (beyond the
+ * volume counts as outside), d(x, dY) = min over y in dY of sqrt(sum_i ((x_i - y_i) s_i)^2), DA = d(dA, dB), DB = d(dB, dA):
+ * HD = max(max DA, max DB), HD95 = max(P95 DA, P95 DB) (numpy's linear percentile), ASSD = (sum DA + sum DB) / (|dA| + |dB|),
+ * NSD = (#{DA <= tau} + #{DB <= tau}) / (|dA| + |dB|) (boundary-voxel counts, not surfel areas).  Both boundaries empty:
+ * 0 / 0 / 0 / 1; exactly one empty: inf / inf / inf / 0.  A box (h0, w0, d0, h, w, d) is a crop of the [H][W][D] volume.
+ *   boundary: pred f32 [B][C][H][W][D], target u8 [B][H][W][D] -> edges u8 [B][H][W][D] (bit 0 = dA, bit 1 = dB) and bbox int32
+ *             [B][6] = (min h, w, d, max h, w, d) of dA u dB (max < 0: both empty), found with integer atomics.
+ *   edt:      dist f32 [2][h][w][d] = exact squared distance, spacing (sh, sw, sd) > 0, from every voxel of the box to the
+ *             nearest voxel of bit 0 (channel 0) and of bit 1 (channel 1) of edges [H][W][D] inside the box, +inf without one;
+ *             with unit spacing every finite value is an integer below 2^24 (axes up to 2048) and exact.
+ *   stats:    from edges + dist over the same box, rec f64 [12] = |dA|, |dB|, max DA, max DB, sum DA, sum DB, #{DA <= tau},
+ *             #{DB <= tau}, then the floor / ceil order statistics of the 95th percentile of DA and of DB (radix select on the
+ *             device).  Per-workgroup partials folded in a fixed order: two calls give bit-identical records.
+ *   finalize: out f32 [4][B][K] = HD, HD95, ASSD, NSD from rec [K][B][12] (a pair whose boundaries are both empty keeps its
+ *             zero-filled record).
+ * scratch of edt and stats: ltu_surface_ws_elems(h, w, d) 4-byte elements of the box. */
+int ltu_surface_boundary(const float* pred, const uint8_t* target, uint8_t* edges, int* bbox, int B, int C, int k, int H, int W,
+                         int D, float threshold, ltu_stream_t s);
+long long ltu_surface_ws_elems(int h, int w, int d);
+int ltu_surface_edt(const uint8_t* edges, float* dist, void* scratch, long long scratch_elems, int H, int W, int D, int h0, int w0,
+                    int d0, int h, int w, int d, float sh, float sw, float sd, ltu_stream_t s);
+int ltu_surface_stats(const uint8_t* edges, const float* dist, double* rec, void* scratch, long long scratch_elems, int H, int W,
+                      int D, int h0, int w0, int d0, int h, int w, int d, float tau, ltu_stream_t s);
+int ltu_surface_finalize(const double* rec, float* out, int B, int K, ltu_stream_t s);
+
 /* ---- optimizer (train3D.py:193: torch.optim.AdamW(lr=1e-4)) -----------------------------------------------------
  * One AdamW step on flat, 16-byte aligned fp32 buffers (a gradient bucket and the parameters / moments laid out the same way):
  * decoupled weight decay, bias correction with `step` (>= 1), gradient multiplied by grad_scale on load. */

@@ -78,6 +78,11 @@ SIGNATURES = {
     'ltu_vote_finalize': [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     'ltu_keep_largest_component': [P, P, P, P, P, I, I, I, I, I, P],
     'ltu_seg_metrics': [P, P, P, P, I, I, I, I, L, F, P],
+    'ltu_surface_boundary': [P, P, P, P, I, I, I, I, I, I, F, P],
+    'ltu_surface_ws_elems': [I, I, I],
+    'ltu_surface_edt': [P, P, P, L, I, I, I, I, I, I, I, I, I, F, F, F, P],
+    'ltu_surface_stats': [P, P, P, P, L, I, I, I, I, I, I, I, I, I, F, P],
+    'ltu_surface_finalize': [P, P, I, I, P],
     'ltu_ct_preprocess': [P, P, P, P, I, I, I, F, F, F, F, P],
     'ltu_crop_flip': [P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_adamw': [P, P, P, P, L, F, F, F, F, F, L, F, P],

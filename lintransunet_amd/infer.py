@@ -132,6 +132,66 @@ def keep_largest_component(predict, sweeps_per_check=8):
     return out
 
 
+SURFACE_METRIC_NAMES = ('HD', 'HD95', 'ASSD', 'NSD')
+
+
+def surface_metrics(predict, masks, class_indices=(1,), spacing=(1.0, 1.0, 1.0), threshold=0.5, nsd_tolerance=1.0):
+    """Boundary metrics of predict [B, C, H, W, D] (the votes of sliding_window_inference or the one-hot output of
+    keep_largest_component) against the integer label volume masks [B, 1, H, W, D], on the GPU (csrc/surface.hip).
+
+    For sample b and class k: A = predict[b, k] >= threshold, B = masks[b, 0] == k.  The boundary dX holds the voxels of X with
+    at least one of their 6 face neighbours outside X; voxels beyond the volume count as outside (X & ~binary_erosion(X,
+    6-connected cross, border_value=0)).  d(x, dY) = min over y in dY of sqrt(sum_i ((x_i - y_i) * s_i)^2) with the spacing
+    s = (s_H, s_W, s_D) in tensor-axis order; DA = {d(a, dB) : a in dA}, DB = {d(b, dA) : b in dB}.
+        HD   = max(max DA, max DB)
+        HD95 = max(P95(DA), P95(DB))                          numpy's default linear percentile
+        ASSD = (sum DA + sum DB) / (|dA| + |dB|)
+        NSD  = (#{DA <= tol} + #{DB <= tol}) / (|dA| + |dB|)  boundary-voxel counts, not the surfel-area form
+    Both boundaries empty: HD = HD95 = ASSD = 0, NSD = 1; exactly one empty: HD = HD95 = ASSD = +inf, NSD = 0.
+
+    Returns {name: f32 device tensor [B, len(class_indices)]} for SURFACE_METRIC_NAMES.  The exact Euclidean distance transform
+    runs over the bounding box of the two boundaries only; the boxes are read to the host once per call (launch geometry),
+    as keep_largest_component reads its convergence flag.  No CPU fallback."""
+    if not predict.is_cuda:
+        raise _lib.LtuError('surface_metrics runs on the GPU only (no CPU fallback)')
+    if predict.dim() != 5 or masks.dim() != 5 or masks.shape[1] != 1 or masks.shape[0] != predict.shape[0] \
+            or tuple(masks.shape[2:]) != tuple(predict.shape[2:]):
+        raise _lib.LtuError(f'predict [B, C, H, W, D] and masks [B, 1, H, W, D] expected, got {tuple(predict.shape)} and '
+                            f'{tuple(masks.shape)}')
+    sp = tuple(float(v) for v in spacing)
+    if len(sp) != 3 or not all(v > 0 and math.isfinite(v) for v in sp):
+        raise _lib.LtuError(f'spacing must be three finite values > 0, got {spacing}')
+    B, C, H, W, D = (int(v) for v in predict.shape)
+    classes = tuple(int(k) for k in class_indices)
+    if not classes or not all(0 <= k < C for k in classes):
+        raise _lib.LtuError(f'class_indices {class_indices} outside 0 .. {C - 1}')
+    K = len(classes)
+    dev = predict.device
+    pred = predict.to(torch.float32).contiguous()
+    tgt = masks.to(dev).reshape(B, H, W, D).to(torch.uint8).contiguous()
+    edges = torch.empty((K, B, H, W, D), device=dev, dtype=torch.uint8)
+    bbox = torch.empty((K, B, 6), device=dev, dtype=torch.int32)
+    for kk, k in enumerate(classes):
+        _lib.call('ltu_surface_boundary', _p(pred), _p(tgt), _p(edges[kk]), _p(bbox[kk]), B, C, k, H, W, D, float(threshold), _s())
+    rec = torch.zeros((K, B, 12), device=dev, dtype=torch.float64)
+    boxes = bbox.cpu().tolist()              # the one host read of the call: crop geometry
+    crops = [(kk, b, box[:3], [box[3 + i] - box[i] + 1 for i in range(3)])
+             for kk, per in enumerate(boxes) for b, box in enumerate(per) if box[3] >= 0]     # both boundaries empty: no crop
+    if crops:
+        most = max(h * w * d for _, _, _, (h, w, d) in crops)
+        dist = torch.empty(2 * most, device=dev, dtype=torch.float32)
+        ws = max(_lib.load().ltu_surface_ws_elems(h, w, d) for _, _, _, (h, w, d) in crops)
+        scratch = torch.empty(ws, device=dev, dtype=torch.float32)
+        for kk, b, (h0, w0, d0), (h, w, d) in crops:
+            e = edges[kk, b]
+            _lib.call('ltu_surface_edt', _p(e), _p(dist), _p(scratch), ws, H, W, D, h0, w0, d0, h, w, d, *sp, _s())
+            _lib.call('ltu_surface_stats', _p(e), _p(dist), _p(rec[kk, b]), _p(scratch), ws, H, W, D, h0, w0, d0, h, w, d,
+                      float(nsd_tolerance), _s())
+    out = torch.empty((4, B, K), device=dev, dtype=torch.float32)
+    _lib.call('ltu_surface_finalize', _p(rec), _p(out), B, K, _s())
+    return {name: out[i] for i, name in enumerate(SURFACE_METRIC_NAMES)}
+
+
 class GraphedPredictor:
     """The eval-mode forward for a fixed window batch captured once into a HIP graph and replayed per window batch: an eager
     forward is ~500 launches of ~35 us host time each, several times what the kernels need.  A short last batch is padded with
