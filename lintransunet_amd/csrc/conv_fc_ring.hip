@@ -228,7 +228,8 @@ int launch_conv_fc_ring_bf16(const HaloArgs& a, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_fc_ring_bf16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, FC_SMEM);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_fc_ring_bf16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, FC_SMEM);
   }
-  const int nblk = (int)(bricks < 256 ? bricks : 256);
+  const int want = ltu_knob_pos("LTU_FC_RING_BLOCKS", 256);
+  const int nblk = (int)(bricks < want ? bricks : want);
   if (a.flip) hipLaunchKernelGGL(conv3_fc_ring_bf16_kernel<true>, dim3(nblk), dim3(256), FC_SMEM, st, a, (int)bricks);
   else hipLaunchKernelGGL(conv3_fc_ring_bf16_kernel<false>, dim3(nblk), dim3(256), FC_SMEM, st, a, (int)bricks);
   return ltu_check_launch();

@@ -26,9 +26,11 @@ __device__ __forceinline__ void wr_glds16(const void* src, uint32_t lds_byte_add
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
 }
+// vmcnt: this wave's pieces of the next brick have landed; lgkmcnt(0): its LDS reads of the buffer about to be refilled have returned
+// (as ring_sync_all in gemm_ring.hip) - the barrier then hands that buffer to the LDS-DMA of every wave
 template <int N>
 __device__ __forceinline__ void wr_sync() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
 __global__ void __launch_bounds__(256, 1) conv3_wgrad_halo_ring_bf16_kernel(const WHaloArgs a) {
