@@ -19,6 +19,13 @@ that launcher + rendezvous + JSON plumbing on the CPU (gloo), without the model.
 
 `--dump-outputs DIR` writes what the last timed step returned (losses, gradients: `dump_outputs`) as DIR/<name>.npy.  Weights,
 patches and dropout streams are seeded, so two builds run with the same arguments can be compared output for output.
+
+A plain run does only what the headline needs: set up (model, two eager steps that record the gradient-ready order, graph capture),
+warm up, time the steps, dump if asked, print the line (`roofline` then holds only the whole-step `step_roofline_ms` / `step_frac`;
+at N > 1 the per-bucket checksum comparison after the warm-up stays: a broken exchange must not yield a headline).
+`--full` adds the measurements that take runs of their own: the chain-kernel roofline object, the per-family table and the largest
+kernel (`roofline.*`), the CPU baseline of the oracle (`cpu_baseline`) and, at N > 1 or with `--rehearse-comm`, the same step
+replayed without its collectives (`config.multi_rank_diagnosis`).
 """
 import argparse
 import glob
@@ -137,8 +144,11 @@ def parse_args(argv=None):
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
     ap.add_argument('--classes', type=int, default=2, choices=[2, 3],
                     help='model outputs: 2 = single-class pancreas (BASELINE configs 2/3), 3 = multi-class path (config 4)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-families', action='store_true', help='skip the per-family timing table of the roofline object')
+    ap.add_argument('--full', action='store_true',
+                    help='beyond the headline: chain-kernel roofline object, per-family table, largest kernel, CPU baseline and, at N > 1 '
+                         'or with --rehearse-comm, the step without its collectives (a plain run measures the timed steps only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-families', action='store_true', help='with --full: skip the per-family timing table of the roofline object')
     ap.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly instead of replaying a captured HIP graph')
     ap.add_argument('--allreduce', default=None, choices=['segments', 'graph', 'after'],
                     help="gradient all-reduce of the graph-replayed step: between linear graph segments (overlapped, default), captured as "
@@ -354,7 +364,7 @@ def main():
     # multi-class script (train3D_multi_class.py / utils_3D_multi_class.py:85-102): CE + Dice(class 1) + Dice(class 2), weights 10/1/2
     specs = train.level_specs(5, ('CrossEntroLoss', 'DiceClassLoss', 'DiceClassLoss2'), criterion_weight=[10, 1, 2]) if args.classes == 3 else None
 
-    # live timing of the dominant kernel family: the transformer layer chain kernels (csrc/tlayer.hip: tail_fwd_kernel and
+    # --full, live timing of the dominant kernel family: the transformer layer chain kernels (csrc/tlayer.hip: tail_fwd_kernel and
     # tail_bwd_kernel carry the post-attention half of every transformer layer, forward and backward; together the largest family by
     # time).  Their (tokens, d, second-gradient) shapes are recorded over one eager step; the same launches are then re-issued on
     # buffers of those shapes from a small captured graph and bracketed by ONE HIP event pair on the launching stream.
@@ -371,7 +381,8 @@ def main():
         M, d = x.shape
         nxt = len(rest) > 16 and rest[-1] is not None
         return float((11 + 13 + (3 if nxt else 0)) * M * d + (16 + (3 if nxt else 0)) * d * d) * 2.0
-    ops._LayerTail.forward = staticmethod(timer.wrap(ops._LayerTail.forward, tail_bytes, 'tail'))
+    if args.full:
+        ops._LayerTail.forward = staticmethod(timer.wrap(ops._LayerTail.forward, tail_bytes, 'tail'))
     chain_cache = {}
 
     def chain_buffers(M, d):
@@ -419,9 +430,10 @@ def main():
         x, lab = batches[i % 2]
         return train.train_step(model, x, lab, weights, specs=specs, reducer=reducer)
 
-    # The dominant kernel family is recorded over one eager step and re-timed below from a graph of exactly those launches (forward
-    # and backward chain of every transformer layer); the timed region of the headline number replays the whole step from a captured
-    # HIP graph.
+    # With --full the dominant kernel family is recorded over one eager step and re-timed below from a graph of exactly those launches
+    # (forward and backward chain of every transformer layer); the timed region of the headline number replays the whole step from a
+    # captured HIP graph.  A plain run takes both eager steps too: they record the gradient-ready order rebucket() needs and advance
+    # the model's dropout seed stream, so what the captured step computes does not depend on --full.
     eager_step(0)
     torch.cuda.synchronize()
     timer.on = True
@@ -433,14 +445,16 @@ def main():
     # per-family device time of the step (lintransunet_amd/family_timer.py): the C-ABI calls that go into the captured step graph are
     # logged; AFTER the timed region each family's launches are replayed alone from a graph of their own between one HIP event pair
     families, ft, group = None, None, None
-    if not args.no_families and not args.no_graph:
+    if args.full and not args.no_families and not args.no_graph:
         from lintransunet_amd.family_timer import FamilyTimer
         ft = FamilyTimer()
-    for c in timer.calls:
-        chain_buffers(*c[1].shape)            # allocate / prepare outside the timed replay
-    ms_lin, n_lin = timer.measure(replay)
-    n_lin *= 2                                # one forward and one backward launch per recorded layer
-    timer.calls = []
+    ms_lin, n_lin = 0.0, 0
+    if args.full:
+        for c in timer.calls:
+            chain_buffers(*c[1].shape)            # allocate / prepare outside the timed replay
+        ms_lin, n_lin = timer.measure(replay)
+        n_lin *= 2                                # one forward and one backward launch per recorded layer
+        timer.calls = []
 
     launch, graph_mode, graphed = 'eager', None, None
     allreduce = 'hooks (overlapped with backward)' if (world > 1 or args.rehearse_comm) else 'none (1 rank)'
@@ -517,7 +531,7 @@ def main():
     if args.dump_outputs and rank == 0:
         # before anything below replays kernels into the same loss tensors and gradient buffers
         dump_outputs(args.dump_outputs, model, *last)
-    if (world > 1 or args.rehearse_comm or os.environ.get('LTU_BENCH_LOCAL') == '1') and launch == 'hip-graph replay':
+    if args.full and (world > 1 or args.rehearse_comm or os.environ.get('LTU_BENCH_LOCAL') == '1') and launch == 'hip-graph replay':
         # what the exchange costs: the same replayed step without its collectives, and where in the step each bucket closes
         for i in range(2):
             graphed.replay_local(*batches[i % 2])
@@ -554,21 +568,38 @@ def main():
 
     if rank == 0:
         patches = args.batch * world * args.steps
-        achieved = timer.work / (ms_lin * 1e-3) / 1e9 if ms_lin > 0 else 0.0       # GB/s
-        # HBM traffic of the same kernel family from the PMC counters (FETCH_SIZE x2 on gfx950 + WRITE_SIZE): counters need their
-        # own rocprofv3 --pmc passes, so this is the committed offline collection of tools/pmc_step.sh, not a live number
-        traffic, traffic_src = None, None
-        pmcs = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r*_pmc_step.json')))
-        pmc = pmcs[-1] if pmcs else ''
-        if pmc:
-            fam = json.load(open(pmc))['families'].get('transformer layer chain kernels (forward + backward)')
-            if fam and fam['dispatches_per_step']:
-                traffic = (fam['hbm_read_GB_per_step'] + fam['hbm_write_GB_per_step']) * 1e9 / fam['dispatches_per_step']
-                traffic_src = f'profiles/{os.path.basename(pmc)} (offline rocprofv3 --pmc passes of the same step)'
         ms_step = dt / args.steps * 1e3
         roof_ms = ROOF_MS_PER_PATCH.get(args.size)
-        stats_all = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r*_bench_kernel_stats.csv')))
-        stats_csv = stats_all[-1] if stats_all and args.size == 128 and args.batch == 2 and args.classes == 2 else None
+        # the whole step against SURVEY 8d's mixed roofline (convs at the MFMA peak + everything else at the HBM peak)
+        roofline = {'step_roofline_ms': roof_ms * args.batch if roof_ms else None,
+                    'step_frac': (roof_ms * args.batch / ms_step) if roof_ms else None}
+        if args.full:
+            achieved = timer.work / (ms_lin * 1e-3) / 1e9 if ms_lin > 0 else 0.0       # GB/s
+            # HBM traffic of the same kernel family from the PMC counters (FETCH_SIZE x2 on gfx950 + WRITE_SIZE): counters need their
+            # own rocprofv3 --pmc passes, so this is the committed offline collection of tools/pmc_step.sh, not a live number
+            traffic, traffic_src = None, None
+            pmcs = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r*_pmc_step.json')))
+            pmc = pmcs[-1] if pmcs else ''
+            if pmc:
+                fam = json.load(open(pmc))['families'].get('transformer layer chain kernels (forward + backward)')
+                if fam and fam['dispatches_per_step']:
+                    traffic = (fam['hbm_read_GB_per_step'] + fam['hbm_write_GB_per_step']) * 1e9 / fam['dispatches_per_step']
+                    traffic_src = f'profiles/{os.path.basename(pmc)} (offline rocprofv3 --pmc passes of the same step)'
+            stats_all = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r*_bench_kernel_stats.csv')))
+            stats_csv = stats_all[-1] if stats_all and args.size == 128 and args.batch == 2 and args.classes == 2 else None
+            roofline = {'bound': 'hbm', 'kernel': 'tail_fwd_kernel + tail_bwd_kernel (row-block chain kernels: post-attention half of every transformer layer - with the next layer\'s q|k|v projection where the layers are adjacent - forward and backward)',
+                        'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+                        'launches': n_lin, 'avg_launch_ms': ms_lin / max(n_lin, 1),
+                        'algorithmic_bytes_per_launch': timer.work / max(n_lin, 1), 'traffic': traffic,
+                        'traffic_source': traffic_src,
+                        'timing': 'one HIP event pair around a graph replay of exactly these launches',
+                        **roofline,
+                        # every op family of the step, replayed alone (graph of exactly its launches, one HIP event pair), against the
+                        # algorithmic work SURVEY 8d assigns it (fwd + bwd = 3 x forward) and the peak that bounds it
+                        'families': families,
+                        # the largest SINGLE kernel of the step (11-12 % of all kernel time), on the side stream: the grouped
+                        # projection weight gradient; algorithmic bytes = its operands read once ((M K + M N) 2 B per job)
+                        'largest_kernel': largest_kernel(group, pmcs[-1] if pmcs else None, stats_csv)}
         out = {
             'metric': f'{args.size}^3 CT patches/sec (fwd+bwd)', 'value': patches / dt, 'unit': 'patches/s', 'n_gpus': world,
             'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True,
@@ -586,23 +617,9 @@ def main():
                        'peak_memory_gb': round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2),
                        **({'multi_rank_diagnosis': diag} if diag else {}),
                        'allreduce': allreduce + (' [REHEARSAL: host-staged test communicator, ranks share one GPU - not a measurement]' if args.test_comm else '')},
-            'roofline': {'bound': 'hbm', 'kernel': 'tail_fwd_kernel + tail_bwd_kernel (row-block chain kernels: post-attention half of every transformer layer - with the next layer\'s q|k|v projection where the layers are adjacent - forward and backward)',
-                         'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
-                         'launches': n_lin, 'avg_launch_ms': ms_lin / max(n_lin, 1),
-                         'algorithmic_bytes_per_launch': timer.work / max(n_lin, 1), 'traffic': traffic,
-                         'traffic_source': traffic_src,
-                         'timing': 'one HIP event pair around a graph replay of exactly these launches',
-                         # the whole step against SURVEY 8d's mixed roofline (convs at the MFMA peak + everything else at the HBM peak)
-                         'step_roofline_ms': roof_ms * args.batch if roof_ms else None,
-                         'step_frac': (roof_ms * args.batch / ms_step) if roof_ms else None,
-                         # every op family of the step, replayed alone (graph of exactly its launches, one HIP event pair), against the
-                         # algorithmic work SURVEY 8d assigns it (fwd + bwd = 3 x forward) and the peak that bounds it
-                         'families': families,
-                         # the largest SINGLE kernel of the step (11-12 % of all kernel time), on the side stream: the grouped
-                         # projection weight gradient; algorithmic bytes = its operands read once ((M K + M N) 2 B per job)
-                         'largest_kernel': largest_kernel(group, pmcs[-1] if pmcs else None, stats_csv)},
+            'roofline': roofline,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(size)
         print(json.dumps(out))
     if world > 1:

@@ -225,15 +225,15 @@ def test_bench_with_two_ranks_on_one_gpu():
 
 
 def test_bench_default_path_with_family_table():
-    """the driver's invocation shape of bench.py on one GPU (HIP-graph replay as linear segments + side-stream weight gradients, the
+    """`bench.py --full` on one GPU (HIP-graph replay as linear segments + side-stream weight gradients, the
     chain-kernel roofline object AND the per-family table, whose replay re-issues every recorded C-ABI call of the step: it runs
     under the launch-geometry knobs of the capture - sized differently, the replayed weight-gradient kernels overran their
     workspaces and the benchmark died of a GPU fault in round 4), small patch, no CPU baseline"""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--size', '64', '--steps', '2', '--warmup', '1', '--no-cpu-baseline'],
-                       env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--size', '64', '--steps', '2', '--warmup', '1', '--full',
+                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, r.stdout
@@ -241,6 +241,25 @@ def test_bench_default_path_with_family_table():
     assert out['config']['launch'].startswith('hip-graph replay (segments')
     fams = {f['family']: f for f in out['roofline']['families']}
     assert {'transformer', 'conv3', 'instnorm'} <= set(fams) and all(f['ms_per_step'] > 0 for f in fams.values())
+
+
+def test_bench_plain_run_is_the_headline_only():
+    """a plain `bench.py` run (no --full, no --no-* switches): set-up, warm-up, timed steps and ONE line with the headline fields;
+    the chain-kernel roofline object, the family table, the largest kernel and the CPU baseline are left to --full"""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--size', '32', '--steps', '2', '--warmup', '1'],
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1 and lines[0].startswith('{'), r.stdout
+    out = json.loads(lines[0])
+    assert out['metric'] == '32^3 CT patches/sec (fwd+bwd)' and out['unit'] == 'patches/s' and out['higher_is_better'] is True
+    assert out['dtype'] == 'bf16' and out['steps'] == 2 and out['warmup'] == 1
+    assert out['value'] > 0 and abs(out['value'] * out['ms_per_step'] * 1e-3 - 2) < 1e-6          # 2 patches per step
+    assert out['config']['launch'].startswith('hip-graph replay (segments')
+    assert 'cpu_baseline' not in out and set(out['roofline']) == {'step_roofline_ms', 'step_frac'}
 
 
 def test_bench_dump_outputs_repeatable(tmp_path):

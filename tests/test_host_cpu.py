@@ -212,6 +212,20 @@ def test_bench_self_launch_propagates_failure():
     assert r.returncode != 0
 
 
+def test_bench_full_is_opt_in():
+    """a plain bench run measures the headline only: what takes runs of its own (roofline objects, family table, CPU baseline) is
+    behind --full, off by default, and accepted by the ranks of a self-launched run"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.parse_args(['--gpus', '1', '--steps', '3', '--warmup', '1']).full is False
+    assert bench.parse_args(['--gpus', '1', '--full']).full is True
+    r = _run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--dry-run', '--full'])
+    assert r.returncode == 0, r.stderr
+    assert len(r.stdout.strip().splitlines()) == 1, r.stdout
+
+
 def test_bench_parent_does_not_import_torch_before_launch():
     """the self-launching parent must not initialise HIP: it forks its children before importing torch at all"""
     src = open(os.path.join(ROOT, 'bench.py')).read()

@@ -4,7 +4,8 @@
 set -e
 R=${1:-r05}
 ROOT=$(pwd)
-python3 bench.py > gpurun_out/${R}_bench.json 2> gpurun_out/${R}_bench.err
+# the full benchmark line (roofline object, family table, CPU baseline) goes straight to profiles/, where tools/design_numbers.py reads it
+python3 bench.py --full > "profiles/${R}_bench.json" 2> "/tmp/${R}_bench.err"
 bash tools/profile_bench.sh
 {
   echo "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-families --steps 10 --warmup 3   (MI355X).  EXACT per-step figures: tools/prof_summary.py --last-steps 8 counts only the kernels of the last 8 complete replays of the step (of the timed region), nothing of the eager / warm-up steps or of the chain-kernel timing graph.  The step is replayed as linear graph segments on the main stream and batches of weight gradients on a side stream: kernel durations include what the concurrency costs them, and their sum exceeds the step time."
