@@ -444,6 +444,27 @@ int ltu_surface_stats(const uint8_t* edges, const float* dist, double* rec, void
                       int D, int h0, int w0, int d0, int h, int w, int d, float tau, ltu_stream_t s);
 int ltu_surface_finalize(const double* rec, float* out, int B, int K, ltu_stream_t s);
 
+/* multi-class evaluation metrics of inference_multi_classes.py:153 (loss/multi_criterions.py: DiceClassLoss0 30-56, DiceClassLoss /
+ * DiceClassLoss2 58-110, LocalizationLoss 219-281, Recall / Recall2 320-375, Precision / Precision2 406-462) and its label map
+ * (argmax(predict2, 1), line 158); csrc/class_metrics.hip.  pred f32 [B][C][H][W][D] (2 <= C <= 8), target u8 class ids
+ * [B][H][W][D]; p = pred as given, or [pred >= threshold] when threshold >= 0.
+ *   pass:     one read of pred and target: per (sample, row h, chunk of the row) the sums over (W, D) of p_c, [t == c],
+ *             p_c [t == c] for every class and of 1 - p_0, [t != 0], (1 - p_0) [t != 0] into scratch (fp64 partials, no
+ *             atomics); label_map u8 [B][H][W][D] = the arg-max over C of pred, first maximal index on ties (nullable: not written).
+ *   finalize: folds the partials in a fixed order in fp64 and writes out f32 [B + 1][3C + 2].  Row b < B: Dice[C] =
+ *             (2 sum pt + 1e-9) / (sum p + sum t + 1e-9), Recall[C] = (sum pt + 1e-5) / (sum t + 1e-5), Precision[C] =
+ *             (sum pt + 1e-5) / (sum p + 1e-5), the foreground Dice of 1 - p_0 against [t != 0] (eps 1e-9), LocalizationLoss =
+ *             mean over h of |cp_h - ct_h|, cp / ct = cumulative sums over H of sigmoid(foreground profile - 10) divided by
+ *             (their sum + 1e-6).  Row B: 1 - mean Dice[C], mean Recall[C], mean Precision[C], 1 - mean foreground Dice, mean
+ *             LocalizationLoss (means over the batch).  Two calls give bit-identical results.
+ * scratch: ltu_class_metrics_ws_elems(B, C, H, W, D) doubles (0 for a shape the entry points refuse), written by the pass
+ * and read by finalize. */
+long long ltu_class_metrics_ws_elems(int B, int C, int H, int W, int D);
+int ltu_class_metrics_pass(const float* pred, const uint8_t* target, uint8_t* label_map, double* scratch, long long scratch_elems,
+                           int B, int C, int H, int W, int D, float threshold, ltu_stream_t s);
+int ltu_class_metrics_finalize(const double* scratch, long long scratch_elems, float* out, int B, int C, int H, int W, int D,
+                               ltu_stream_t s);
+
 /* ---- optimizer (train3D.py:193: torch.optim.AdamW(lr=1e-4)) -----------------------------------------------------
  * One AdamW step on flat, 16-byte aligned fp32 buffers (a gradient bucket and the parameters / moments laid out the same way):
  * decoupled weight decay, bias correction with `step` (>= 1), gradient multiplied by grad_scale on load. */

@@ -83,6 +83,9 @@ SIGNATURES = {
     'ltu_surface_edt': [P, P, P, L, I, I, I, I, I, I, I, I, I, F, F, F, P],
     'ltu_surface_stats': [P, P, P, P, L, I, I, I, I, I, I, I, I, I, F, P],
     'ltu_surface_finalize': [P, P, I, I, P],
+    'ltu_class_metrics_ws_elems': [I, I, I, I, I],
+    'ltu_class_metrics_pass': [P, P, P, P, L, I, I, I, I, I, F, P],
+    'ltu_class_metrics_finalize': [P, L, P, I, I, I, I, I, P],
     'ltu_ct_preprocess': [P, P, P, P, I, I, I, F, F, F, F, P],
     'ltu_crop_flip': [P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_adamw': [P, P, P, P, L, F, F, F, F, F, L, F, P],

@@ -192,6 +192,93 @@ def surface_metrics(predict, masks, class_indices=(1,), spacing=(1.0, 1.0, 1.0),
     return {name: out[i] for i, name in enumerate(SURFACE_METRIC_NAMES)}
 
 
+MULTI_METRIC_NAMES = ('DiceClassLoss0', 'DiceClassLoss', 'DiceClassLoss2', 'Recall', 'Precision', 'Recall2', 'Precision2',
+                      'LocalizationLoss')
+
+
+def _class_metrics_run(predict, masks, threshold, label_map):
+    """one statistics pass + one finalize (csrc/class_metrics.hip): f32 [B + 1, 3C + 2] (row b < B: Dice[C], Recall[C],
+    Precision[C], foreground Dice, LocalizationLoss of sample b; row B: 1 - mean Dice[C], mean Recall[C], mean Precision[C],
+    1 - mean foreground Dice, mean LocalizationLoss) and the u8 label map [B, H, W, D] when asked for"""
+    from .losses import _labels
+    if not predict.is_cuda:
+        raise _lib.LtuError('class_metrics runs on the GPU only (no CPU fallback)')
+    if predict.dim() != 5:
+        raise _lib.LtuError(f'predict [B, C, H, W, D] expected, got {tuple(predict.shape)}')
+    B, C, H, W, D = (int(v) for v in predict.shape)
+    if not 2 <= C <= 8:
+        raise _lib.LtuError(f'class_metrics supports 2 .. 8 classes, got C = {C}')
+    if masks.dim() != 5 or masks.shape[0] != B or masks.shape[1] not in (1, C) or tuple(masks.shape[2:]) != (H, W, D):
+        raise _lib.LtuError(f'masks [B, 1, H, W, D] (class ids) or [B, C, H, W, D] (one-hot) expected for predict '
+                            f'{tuple(predict.shape)}, got {tuple(masks.shape)}')
+    thr = -1.0 if threshold is None else float(threshold)
+    if threshold is not None and not thr >= 0.0:
+        raise _lib.LtuError(f'threshold must be >= 0 or None, got {threshold}')
+    dev = predict.device
+    pred = predict.to(torch.float32).contiguous()
+    tgt = _labels(masks.to(dev), C)
+    lmap = torch.empty((B, H, W, D), device=dev, dtype=torch.uint8) if label_map else None
+    ws = _lib.load().ltu_class_metrics_ws_elems(B, C, H, W, D)
+    scratch = torch.empty(ws, device=dev, dtype=torch.float64)
+    out = torch.empty((B + 1, 3 * C + 2), device=dev, dtype=torch.float32)
+    _lib.call('ltu_class_metrics_pass', _p(pred), _p(tgt), _p(lmap) if label_map else None, _p(scratch), ws, B, C, H, W, D, thr, _s())
+    _lib.call('ltu_class_metrics_finalize', _p(scratch), ws, _p(out), B, C, H, W, D, _s())
+    return out, lmap
+
+
+def class_metrics(predict, masks, class_indices=None, threshold=None, return_label_map=False):
+    """Overlap metrics of loss/multi_criterions.py per sample and class, on the GPU (csrc/class_metrics.hip), from one read of
+    predict [B, C, H, W, D] f32 (2 <= C <= 8: the votes of sliding_window_inference or the output of keep_largest_component)
+    and masks, the class ids [B, 1, H, W, D] (a one-hot [B, C, H, W, D] is reduced to ids as losses._labels does; ids >= C count
+    as foreground of no class).  p = predict as given (threshold=None) or [predict >= threshold]; t_c = [mask == c]:
+        Dice      = (2 sum p_c t_c + 1e-9) / (sum p_c + sum t_c + 1e-9)       DiceClassLoss / DiceClassLoss2 = 1 - its batch mean
+        Recall    = (sum p_c t_c + 1e-5) / (sum t_c + 1e-5)                   Recall / Recall2 = its batch mean
+        Precision = (sum p_c t_c + 1e-5) / (sum p_c + 1e-5)                   Precision / Precision2 = its batch mean
+        ForegroundDice of 1 - p_0 against [mask != 0] (eps 1e-9)                DiceClassLoss0 = 1 - its batch mean
+        LocalizationLoss (multi_criterions.py:219-281, no factor 8): the H profiles of 1 - p_0 and [mask != 0] (sums over W, D)
+                    through sigmoid(x - 10), cumulative sums over H divided by (their sum + 1e-6), mean over H of |cp - ct|
+    Sums are exact for integer-valued inputs and folded in fp64 in a fixed order: two calls are bit-identical.
+
+    Returns f32 device tensors {'Dice', 'Recall', 'Precision'} [B, K] (column j = class class_indices[j], all C classes when
+    None), 'ForegroundDice' [B], 'LocalizationLoss' [B], and with return_label_map 'label_map' u8 [B, H, W, D] = the arg-max
+    over C of predict (the first maximal index on ties, as torch.argmax).  No host synchronisation; an int64 or one-hot masks
+    costs a conversion pass of its own (uint8 class ids are read as they are)."""
+    if predict.dim() == 5 and class_indices is not None:
+        C = int(predict.shape[1])
+        if not all(0 <= int(k) < C for k in class_indices) or not len(class_indices):
+            raise _lib.LtuError(f'class_indices {class_indices} outside 0 .. {C - 1}')
+    out, lmap = _class_metrics_run(predict, masks, threshold, return_label_map)
+    B, C = int(predict.shape[0]), int(predict.shape[1])
+    res = {}
+    for i, name in enumerate(('Dice', 'Recall', 'Precision')):
+        block = out[:B, i * C:(i + 1) * C]
+        res[name] = block if class_indices is None else torch.stack([block[:, int(k)] for k in class_indices], 1)
+    res['ForegroundDice'] = out[:B, 3 * C]
+    res['LocalizationLoss'] = out[:B, 3 * C + 1]
+    if return_label_map:
+        res['label_map'] = lmap
+    return res
+
+
+def evaluate_multiclass(predict, masks, threshold=None, return_label_map=False):
+    """The metrics of inference_multi_classes.py:153 (loss/multi_criterions.py, its default criterion_list) on predict
+    [B, C >= 3, H, W, D] against masks (class ids [B, 1, H, W, D] or their one-hot): {name: device scalar} for
+    MULTI_METRIC_NAMES, the values `[l(predict, label).item() for l in criterions.values()]` prints (see class_metrics for the
+    definitions).  One statistics pass and one finalize; the scalars are views of the finalize output, so no further launch and
+    no host synchronisation.  With return_label_map, 'label_map' is the driver's is_save map argmax(predict, 1) as u8
+    [B, H, W, D] from the same pass."""
+    if predict.dim() == 5 and predict.shape[1] < 3:
+        raise _lib.LtuError(f'evaluate_multiclass needs C >= 3 (classes 1 and 2), got C = {predict.shape[1]}')
+    out, lmap = _class_metrics_run(predict, masks, threshold, return_label_map)
+    B, C = int(predict.shape[0]), int(predict.shape[1])
+    m = out[B]
+    res = {'DiceClassLoss0': m[3 * C], 'DiceClassLoss': m[1], 'DiceClassLoss2': m[2], 'Recall': m[C + 1],
+           'Precision': m[2 * C + 1], 'Recall2': m[C + 2], 'Precision2': m[2 * C + 2], 'LocalizationLoss': m[3 * C + 1]}
+    if return_label_map:
+        res['label_map'] = lmap
+    return res
+
+
 class GraphedPredictor:
     """The eval-mode forward for a fixed window batch captured once into a HIP graph and replayed per window batch: an eager
     forward is ~500 launches of ~35 us host time each, several times what the kernels need.  A short last batch is padded with

@@ -1,7 +1,8 @@
 """Loss surface of loss/criterions.py (binary labels) and loss/multi_criterions.py (class labels) over
 the fused HIP loss kernels.
 
-`get_criterions(name_list) -> {name: nn.Module}` keeps the reference contract (loss/criterions.py:773-782):
+`get_criterions(name_list) -> {name: nn.Module}` keeps the reference contract (loss/criterions.py:773-782);
+`get_multi_criterions(name_list)` is its multi-class counterpart (loss/multi_criterions.py:704-714):
 every module is `forward(predict[N,C,...], target) -> 0-dim tensor`.  `target` is an integer label
 volume [N,1,...] (or a one-hot [N,C,...] tensor, as the multi-class scripts pass).  All losses of one
 decoder level share one streaming reduction (`LevelCriterion`).
@@ -147,3 +148,77 @@ Loss_Dict = {
 def get_criterions(name_list):
     """loss/criterions.py:773-782"""
     return {name: Loss_Dict[name]() for name in name_list}
+
+
+class _MultiEvalMetric(nn.Module):
+    """the evaluation criteria of loss/multi_criterions.py that the multi-class drivers only read (inference_multi_classes.py:153,
+    utils_3D_multi_class.py:146-208): one entry of infer.evaluate_multiclass (csrc/class_metrics.hip) on the values as given;
+    evaluation only, no gradient"""
+    NAME, COMPLEMENT = None, False
+
+    def forward(self, predict, target):
+        from . import infer
+        with torch.no_grad():
+            v = infer.evaluate_multiclass(predict, target)[self.NAME]
+        return 1.0 - v if self.COMPLEMENT else v
+
+
+class MultiRecall(_MultiEvalMetric):
+    """loss/multi_criterions.py:320-346: mean_b (sum p_1 t_1 + 1e-5) / (sum t_1 + 1e-5)"""
+    NAME = 'Recall'
+
+
+class MultiRecall2(_MultiEvalMetric):
+    """loss/multi_criterions.py:348-375: Recall of class 2"""
+    NAME = 'Recall2'
+
+
+class MultiRecallLoss(_MultiEvalMetric):
+    """loss/multi_criterions.py:377-404: 1 - Recall"""
+    NAME, COMPLEMENT = 'Recall', True
+
+
+class MultiPrecision(_MultiEvalMetric):
+    """loss/multi_criterions.py:406-433: mean_b (sum p_1 t_1 + 1e-5) / (sum p_1 + 1e-5)"""
+    NAME = 'Precision'
+
+
+class MultiPrecision2(_MultiEvalMetric):
+    """loss/multi_criterions.py:435-462: Precision of class 2"""
+    NAME = 'Precision2'
+
+
+class MultiPrecisionLoss(_MultiEvalMetric):
+    """loss/multi_criterions.py:464-491: 1 - Precision"""
+    NAME, COMPLEMENT = 'Precision', True
+
+
+class MultiLocalizationLoss(_MultiEvalMetric):
+    """loss/multi_criterions.py:219-281: on the foreground union 1 - channel 0 of both sides, no factor 8"""
+    NAME = 'LocalizationLoss'
+
+
+Multi_Loss_Dict = {
+    'CrossEntroLoss': CrossEntroLoss,
+    'DiceClassLoss0': DiceClassLoss0,
+    'DiceClassLoss': DiceClassLoss,
+    'DiceClassLoss2': DiceClassLoss2,
+    'Recall': MultiRecall,
+    'Precision': MultiPrecision,
+    'Recall2': MultiRecall2,
+    'Precision2': MultiPrecision2,
+    'RecallLoss': MultiRecallLoss,
+    'PrecisionLoss': MultiPrecisionLoss,
+    'LocalizationLoss': MultiLocalizationLoss,
+}
+
+
+def get_multi_criterions(name_list):
+    """loss/multi_criterions.py:704-714 for the names the multi-class scripts request: CrossEntroLoss and DiceClassLoss0 /
+    DiceClassLoss / DiceClassLoss2 are the differentiable modules above (train3D_multi_class.py trains with them); Recall,
+    Precision, Recall2, Precision2, RecallLoss, PrecisionLoss and the multi-class LocalizationLoss are evaluation-only modules
+    over csrc/class_metrics.hip.  Any other name raises KeyError."""
+    unknown = [name for name in name_list if name not in Multi_Loss_Dict]
+    if unknown:
+        raise KeyError(f'no HIP kernel for multi-class criteria {unknown}')
+    return {name: Multi_Loss_Dict[name]() for name in name_list}
