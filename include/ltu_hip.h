@@ -465,6 +465,39 @@ int ltu_class_metrics_pass(const float* pred, const uint8_t* target, uint8_t* la
 int ltu_class_metrics_finalize(const double* scratch, long long scratch_elems, float* out, int B, int C, int H, int W, int D,
                                ltu_stream_t s);
 
+/* connected components and lesion-wise detection metrics of the evaluation (no reference counterpart; csrc/components.hip).
+ * Connectivity c = 1, 2, 3 (6, 18, 26 neighbours: coordinates differ by at most 1 on at most c axes); voxels beyond the volume
+ * are background; every sample is labelled on its own; S = H W D < 2^31 (else LTU_E_SHAPE), c outside 1 .. 3 is LTU_E_ARG.
+ * Union-find over voxel indices in a fixed number of launches (no host loop, capturable): the root of a component is its
+ * smallest (raster-first) voxel, so the numbering does not depend on scheduling.
+ *   label:   mask u8 [B][H][W][D] (nonzero = foreground) -> labels int32 [B][H][W][D], 0 background, components numbered
+ *            1 .. n_b in raster order of their first voxel (= scipy.ndimage.label with generate_binary_structure(3, c)), counts
+ *            int32 [B] = n_b.  scratch: ltu_label_ws_elems(B, H, W, D) int32.
+ *   remove_small: pred f32 [B][C][H][W][D] (2 <= C <= 31, rounded values) in place: for each class k with bit k of `classes` set
+ *            (bit 0 must be clear), every component of pred[b][k] > 0 with fewer than min_voxels voxels is cleared in channel k;
+ *            then channel 0 = 1 - the sum of the others.  scratch: ltu_remove_small_ws_elems(B, H, W, D) int32.
+ *   lesion:  for sample b and class k, P = pred[b][k] >= threshold (pred f32 [B][C][H][W][D]) and G = target[b] == k (target u8
+ *            [B][H][W][D]) are labelled into P_1 .. P_m and G_1 .. G_n; o_j = |G_j n P|, G_j is detected iff o_j >= 1, P_i is a
+ *            false positive iff P_i n G is empty, U_j = the union of the P_i touching G_j, Dice_j = 2 o_j / (|G_j| + |U_j|).
+ *            heads: heads int32 [B] = the voxels of P n G with no half-neighbour in P n G (a bound on the distinct (P_i, G_j)
+ *            pairs).  stats: with pairs >= max_b heads[b], writes column kk of ints int32 [5][B][K] = NumTrue n, NumPred m,
+ *            TruePositives, FalseNegatives, FalsePositives and rates f32 [4][B][K] = Sensitivity TP / n (1 if n = 0),
+ *            Precision (m - FP) / m (1 if m = 0), F1 = 2 S P / (S + P) (0 if S + P = 0), LesionDice = sum_j Dice_j / (n + FP)
+ *            (1 if n + FP = 0); a pair bound found short gives -1 / NaN for that sample instead.  Integer counts and a fixed-order
+ *            fp64 fold: two calls are bit-identical.  scratch: ltu_lesion_ws_elems(B, H, W, D, pairs) 4-byte elements. */
+long long ltu_label_ws_elems(int B, int H, int W, int D);
+int ltu_label_components(const uint8_t* mask, int* labels, int* counts, int* scratch, long long scratch_elems, int B, int H, int W,
+                         int D, int connectivity, ltu_stream_t s);
+long long ltu_remove_small_ws_elems(int B, int H, int W, int D);
+int ltu_remove_small_components(float* pred, int* scratch, long long scratch_elems, int B, int C, int classes, int H, int W, int D,
+                                int min_voxels, int connectivity, ltu_stream_t s);
+long long ltu_lesion_ws_elems(int B, int H, int W, int D, long long pairs);
+int ltu_lesion_heads(const float* pred, const uint8_t* target, int* heads, int B, int C, int k, int H, int W, int D, float threshold,
+                     int connectivity, ltu_stream_t s);
+int ltu_lesion_stats(const float* pred, const uint8_t* target, int* ints, float* rates, void* scratch, long long scratch_elems,
+                     long long pairs, int B, int C, int k, int kk, int K, int H, int W, int D, float threshold, int connectivity,
+                     ltu_stream_t s);
+
 /* ---- optimizer (train3D.py:193: torch.optim.AdamW(lr=1e-4)) -----------------------------------------------------
  * One AdamW step on flat, 16-byte aligned fp32 buffers (a gradient bucket and the parameters / moments laid out the same way):
  * decoupled weight decay, bias correction with `step` (>= 1), gradient multiplied by grad_scale on load. */

@@ -86,6 +86,13 @@ SIGNATURES = {
     'ltu_class_metrics_ws_elems': [I, I, I, I, I],
     'ltu_class_metrics_pass': [P, P, P, P, L, I, I, I, I, I, F, P],
     'ltu_class_metrics_finalize': [P, L, P, I, I, I, I, I, P],
+    'ltu_label_ws_elems': [I, I, I, I],
+    'ltu_label_components': [P, P, P, P, L, I, I, I, I, I, P],
+    'ltu_remove_small_ws_elems': [I, I, I, I],
+    'ltu_remove_small_components': [P, P, L, I, I, I, I, I, I, I, I, P],
+    'ltu_lesion_ws_elems': [I, I, I, I, L],
+    'ltu_lesion_heads': [P, P, P, I, I, I, I, I, I, F, I, P],
+    'ltu_lesion_stats': [P, P, P, P, P, L, L, I, I, I, I, I, I, I, I, F, I, P],
     'ltu_ct_preprocess': [P, P, P, P, I, I, I, F, F, F, F, P],
     'ltu_crop_flip': [P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_adamw': [P, P, P, P, L, F, F, F, F, F, L, F, P],

@@ -279,6 +279,130 @@ def evaluate_multiclass(predict, masks, threshold=None, return_label_map=False):
     return res
 
 
+def _connectivity(connectivity):
+    if connectivity not in (1, 2, 3):
+        raise _lib.LtuError(f'connectivity must be 1, 2 or 3 (6-, 18-, 26-neighbourhood), got {connectivity}')
+    return int(connectivity)
+
+
+def label_components(mask, connectivity=3):
+    """Connected components of every sample of mask [B, H, W, D] or [B, 1, H, W, D] (any dtype, nonzero = foreground), on the GPU
+    (csrc/components.hip).  connectivity 1 / 2 / 3: the 6- / 18- / 26-neighbourhood (voxels whose coordinates differ by at most 1
+    on at most that many axes), as scipy.ndimage.generate_binary_structure(3, connectivity); voxels beyond the volume are
+    background.  Returns (labels int32 [B, H, W, D], counts int32 [B]): background 0, the components of sample b numbered
+    1 .. counts[b] in raster order of their first voxel, exactly scipy.ndimage.label(mask[b], structure).  A union-find in a fixed
+    number of launches: no host synchronisation, two calls are bit-identical.  S = H W D < 2^31."""
+    if not mask.is_cuda:
+        raise _lib.LtuError('label_components runs on the GPU only (no CPU fallback)')
+    if mask.dim() == 5 and mask.shape[1] == 1:
+        mask = mask[:, 0]
+    if mask.dim() != 4:
+        raise _lib.LtuError(f'mask [B, H, W, D] or [B, 1, H, W, D] expected, got {tuple(mask.shape)}')
+    conn = _connectivity(connectivity)
+    B, H, W, D = (int(v) for v in mask.shape)
+    if mask.dtype == torch.bool:
+        m = mask.contiguous().view(torch.uint8)
+    elif mask.dtype == torch.uint8:
+        m = mask.contiguous()
+    else:
+        m = (mask != 0).contiguous().view(torch.uint8)
+    ws = _lib.load().ltu_label_ws_elems(B, H, W, D)
+    if ws <= 0:
+        raise _lib.LtuError(f'label_components: shape {tuple(mask.shape)} refused (H * W * D must be < 2^31)')
+    dev = mask.device
+    labels = torch.empty((B, H, W, D), device=dev, dtype=torch.int32)
+    counts = torch.empty(B, device=dev, dtype=torch.int32)
+    scratch = torch.empty(ws, device=dev, dtype=torch.int32)
+    _lib.call('ltu_label_components', _p(m), _p(labels), _p(counts), _p(scratch), ws, B, H, W, D, conn, _s())
+    return labels, counts
+
+
+def remove_small_components(predict, min_voxels, class_indices=None, connectivity=3):
+    """Small-object removal on predict [B, C, H, W, D] f32 (the votes of sliding_window_inference or a one-hot), on the GPU
+    (csrc/components.hip): out = torch.round(predict); then for each class k of class_indices (default 1 .. C-1), each class on its
+    own, every component (see label_components for the connectivity) of out[b, k] > 0 with fewer than min_voxels voxels is
+    cleared in channel k; channel 0 = 1 - the sum of the other channels.  min_voxels <= 1 returns the rounded input unchanged.
+    Returns a new tensor; no host synchronisation."""
+    if not predict.is_cuda:
+        raise _lib.LtuError('remove_small_components runs on the GPU only (no CPU fallback)')
+    if predict.dim() != 5:
+        raise _lib.LtuError(f'predict [B, C, H, W, D] expected, got {tuple(predict.shape)}')
+    conn = _connectivity(connectivity)
+    B, C, H, W, D = (int(v) for v in predict.shape)
+    if not 2 <= C <= 31:
+        raise _lib.LtuError(f'remove_small_components supports 2 .. 31 classes, got C = {C}')
+    classes = tuple(range(1, C)) if class_indices is None else tuple(int(k) for k in class_indices)
+    if not classes or not all(1 <= k < C for k in classes):
+        raise _lib.LtuError(f'class_indices {class_indices} outside 1 .. {C - 1}')
+    out = torch.round(predict.to(torch.float32)).contiguous()
+    if min_voxels <= 1:
+        return out
+    ws = _lib.load().ltu_remove_small_ws_elems(B, H, W, D)
+    if ws <= 0:
+        raise _lib.LtuError(f'remove_small_components: shape {tuple(predict.shape)} refused (H * W * D must be < 2^31)')
+    bits = 0
+    for k in classes:
+        bits |= 1 << k
+    scratch = torch.empty(ws, device=out.device, dtype=torch.int32)
+    _lib.call('ltu_remove_small_components', _p(out), _p(scratch), ws, B, C, bits, H, W, D, int(min(min_voxels, 2 ** 31 - 1)), conn,
+              _s())
+    return out
+
+
+LESION_METRIC_NAMES = ('NumTrue', 'NumPred', 'TruePositives', 'FalseNegatives', 'FalsePositives', 'Sensitivity', 'Precision', 'F1',
+                       'LesionDice')
+
+
+def lesion_metrics(predict, masks, class_indices=(1,), threshold=0.5, connectivity=3):
+    """Lesion-wise (object) detection metrics of predict [B, C, H, W, D] against the class ids masks [B, 1, H, W, D], on the GPU
+    (csrc/components.hip).  For sample b and class k: P = predict[b, k] >= threshold and G = masks[b, 0] == k, both labelled with
+    the given connectivity (see label_components) into components P_1 .. P_m and G_1 .. G_n.  o_j = |G_j n P|; GT lesion j is
+    detected iff o_j >= 1; predicted component i is a false positive iff P_i n G is empty; U_j = the union of the P_i touching G_j;
+    Dice_j = 2 o_j / (|G_j| + |U_j|) (0 for a missed lesion; |G_j n U_j| = o_j).
+        NumTrue = n, NumPred = m, TruePositives = detected GT lesions, FalseNegatives = n - TruePositives, FalsePositives
+        Sensitivity = TP / n, 1 when n = 0                 Precision = (m - FP) / m, 1 when m = 0
+        F1 = 2 S P / (S + P), 0 when S + P = 0            LesionDice = sum_j Dice_j / (n + FP), 1 when n + FP = 0
+    (LesionDice is the BraTS-2023 lesion-wise form without its GT dilation.)  Returns {name: [B, len(class_indices)] device
+    tensor} for LESION_METRIC_NAMES: the five counts int32, the four rates f32; callers pool counts across scans themselves.
+    Integer statistics and a fixed-order fp64 fold: two calls are bit-identical.  One host read per call, for sizing: the bound
+    on distinct (P_i, G_j) pairs that sizes the device hash set."""
+    if not predict.is_cuda:
+        raise _lib.LtuError('lesion_metrics runs on the GPU only (no CPU fallback)')
+    if predict.dim() != 5 or masks.dim() != 5 or masks.shape[1] != 1 or masks.shape[0] != predict.shape[0] \
+            or tuple(masks.shape[2:]) != tuple(predict.shape[2:]):
+        raise _lib.LtuError(f'predict [B, C, H, W, D] and masks [B, 1, H, W, D] expected, got {tuple(predict.shape)} and '
+                            f'{tuple(masks.shape)}')
+    conn = _connectivity(connectivity)
+    B, C, H, W, D = (int(v) for v in predict.shape)
+    classes = tuple(int(k) for k in class_indices)
+    if not classes or not all(0 <= k < min(C, 256) for k in classes):
+        raise _lib.LtuError(f'class_indices {class_indices} outside 0 .. {min(C, 256) - 1}')
+    thr = float(threshold)
+    if thr != thr:
+        raise _lib.LtuError('threshold must not be NaN')
+    K = len(classes)
+    dev = predict.device
+    lib = _lib.load()
+    if lib.ltu_label_ws_elems(B, H, W, D) <= 0:
+        raise _lib.LtuError(f'lesion_metrics: shape {tuple(predict.shape)} refused (H * W * D must be < 2^31)')
+    pred = predict.to(torch.float32).contiguous()
+    tgt = masks.to(dev).reshape(B, H, W, D).to(torch.uint8).contiguous()
+    heads = torch.empty((K, B), device=dev, dtype=torch.int32)
+    for kk, k in enumerate(classes):
+        _lib.call('ltu_lesion_heads', _p(pred), _p(tgt), _p(heads[kk]), B, C, k, H, W, D, thr, conn, _s())
+    pairs = int(heads.max().item())          # the one host read of the call: sizes the pair hash set
+    ws = lib.ltu_lesion_ws_elems(B, H, W, D, pairs)
+    scratch = torch.empty(ws, device=dev, dtype=torch.int32)
+    ints = torch.empty((5, B, K), device=dev, dtype=torch.int32)
+    rates = torch.empty((4, B, K), device=dev, dtype=torch.float32)
+    for kk, k in enumerate(classes):
+        _lib.call('ltu_lesion_stats', _p(pred), _p(tgt), _p(ints), _p(rates), _p(scratch), ws, pairs, B, C, k, kk, K, H, W, D, thr,
+                  conn, _s())
+    res = {name: ints[i] for i, name in enumerate(LESION_METRIC_NAMES[:5])}
+    res.update({name: rates[i] for i, name in enumerate(LESION_METRIC_NAMES[5:])})
+    return res
+
+
 class GraphedPredictor:
     """The eval-mode forward for a fixed window batch captured once into a HIP graph and replayed per window batch: an eager
     forward is ~500 launches of ~35 us host time each, several times what the kernels need.  A short last batch is padded with
