@@ -389,6 +389,29 @@ int ltu_loss_fwd(const float* p, const uint8_t* label, float* sums, long long su
                  float w_ce, float w_bal, const float* w_dice, const float* scale_dev, ltu_stream_t s);
 int ltu_loss_bwd(const float* p, const uint8_t* label, const float* coef, const float* gscale, float* dp, int B,
                  long long S, int C, ltu_stream_t s);
+/* ---- the wider loss family of one level: loss/criterions.py:8-32,466-530,563-615,618-644,738-751;
+ *      loss/multi_criterions.py:517-541,617-663, and the five terms of ltu_loss_fwd ---------------------------------------
+ * p f32 [B][S][C] probabilities, label u8 [B][S], 2 <= C <= 4 and B (7 C + 3) <= 256 (else LTU_E_SHAPE).  cfg: LTU_LOSS_EXT_NCFG
+ * host floats, the weight of every term (index LTU_LOSS_EXT_CE .. LTU_LOSS_EXT_CLASSIFY; DICE0 + c = DiceClassLoss of class c)
+ * followed by gamma (FocalLoss), sigma (SSLoss), alpha (ContainLoss), alpha2 (ContainLoss2) and eps (the new terms' epsilon);
+ * a non-finite entry, or a Dice weight of a class c >= C, is LTU_E_ARG.  total = sum_k cfg[k] * term_k over the terms with
+ * cfg[k] != 0 (a term switched off adds nothing to total or gradient, even where its value is inf / NaN on the data; its value
+ * is still reported), every weight times scale_dev[0] when scale_dev is given
+ * (device-resident, read at run time, as in ltu_loss_fwd).  values (LTU_LOSS_EXT_NTERM + 2 floats): [0] = total, [1 + k] = term
+ * k, [1 + NTERM] = total again.  sums: scratch of ltu_loss_ext_ws_floats(B, S, C) floats, no initialisation, folded in a fixed
+ * order (bit-reproducible); shorter is LTU_E_ARG.  coef [B][C][8] feeds ltu_loss_ext_bwd (same cfg): dp = gscale[0] * dTotal/dp.
+ * Argument errors return before anything is launched.  Terms switched off by a zero weight cost nothing in the streaming passes. */
+enum { LTU_LOSS_EXT_CE = 0, LTU_LOSS_EXT_BAL = 1, LTU_LOSS_EXT_DICE0 = 2 /* .. 5 */, LTU_LOSS_EXT_FG = 6, LTU_LOSS_EXT_DICE = 7,
+       LTU_LOSS_EXT_IOU = 8, LTU_LOSS_EXT_SS = 9, LTU_LOSS_EXT_FOCAL = 10, LTU_LOSS_EXT_MSE = 11, LTU_LOSS_EXT_CONTAIN = 12,
+       LTU_LOSS_EXT_CONTAIN2 = 13, LTU_LOSS_EXT_BAL2 = 14, LTU_LOSS_EXT_CE0 = 15, LTU_LOSS_EXT_CLASSIFY = 16,
+       LTU_LOSS_EXT_NTERM = 17,
+       LTU_LOSS_EXT_GAMMA = 17, LTU_LOSS_EXT_SIGMA = 18, LTU_LOSS_EXT_ALPHA = 19, LTU_LOSS_EXT_ALPHA2 = 20, LTU_LOSS_EXT_EPS = 21,
+       LTU_LOSS_EXT_NCFG = 22 };
+long long ltu_loss_ext_ws_floats(int B, long long S, int C);
+int ltu_loss_ext_fwd(const float* p, const uint8_t* label, float* sums, long long sums_floats, float* values, float* coef, int B, long long S,
+                     int C, const float* cfg, const float* scale_dev, ltu_stream_t s);
+int ltu_loss_ext_bwd(const float* p, const uint8_t* label, const float* coef, const float* cfg, const float* gscale, float* dp, int B,
+                     long long S, int C, ltu_stream_t s);
 /* label pyramid (utils/utils_3D_embed_full.py:64,73-76): u8 [B,H,W,D] -> max over (2,2,kd) windows */
 int ltu_label_maxpool(const uint8_t* x, uint8_t* y, int B, int H, int W, int D, int kd, ltu_stream_t s);
 

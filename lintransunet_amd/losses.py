@@ -30,28 +30,43 @@ def _labels(target, n_class):
 
 
 class LevelCriterion(nn.Module):
-    """Weighted sum of CE / balanced Dice / per-class Dice on one prediction, one kernel pass.
+    """Weighted sum of the training losses of one decoder level on one prediction, one kernel pass.
 
-    spec: {'CrossEntroLoss': w, 'BalanceDiceLoss': w, 'DiceClassLoss': w (class 1), 'DiceClassLoss2': w (class 2),
-           'DiceClassLoss0c': w (class 0), 'DiceClassLoss0': w (foreground union 1 - class 0, multi_criterions.py:30-56)}.  Returns (total, {name: w * value}) with values detached: what the reference
-    scripts log (`criterions_w * l(...)`, utils_3D_multi_class.py:85; all weights are 1 in the single-class script).
+    spec: {name: weight}.  A spec made only of the names of the original family, {'CrossEntroLoss', 'BalanceDiceLoss',
+    'DiceClassLoss' (class 1), 'DiceClassLoss2' (class 2), 'DiceClassLoss0c' (class 0), 'DiceClassLoss0' (foreground union
+    1 - class 0, multi_criterions.py:30-56)}, runs ops.level_loss (csrc/loss.hip).  A spec with any name of `EXT` runs the
+    whole spec through ops.level_loss_ext (csrc/loss_ext.hip), which also carries the original terms.  params: the parameters
+    of the wider family (ops.LOSS_EXT_PARAMS: gamma, sigma, alpha, alpha2, eps; defaults ops.LOSS_EXT_DEFAULTS).  Returns
+    (total, {name: w * value}) with values detached: what the reference scripts log (`criterions_w * l(...)`,
+    utils_3D_multi_class.py:85; all weights are 1 in the single-class script).
     """
     _DICE = {'DiceClassLoss': 1, 'DiceClassLoss2': 2, 'DiceClassLoss0c': 0, 'DiceClassLoss0': 4}      # 4 = foreground union
+    # every name -> its term of the wider family (ops.LOSS_EXT_TERMS)
+    _TERM = {'CrossEntroLoss': 'CE', 'BalanceDiceLoss': 'BAL', 'DiceClassLoss0c': 'DICE0', 'DiceClassLoss': 'DICE1',
+             'DiceClassLoss2': 'DICE2', 'DiceClassLoss0': 'FG'}
+    EXT = {'DiceLoss': 'DICE', 'IOULoss': 'IOU', 'SSLoss': 'SS', 'FocalLoss': 'FOCAL', 'MSELoss': 'MSE', 'ContainLoss': 'CONTAIN',
+           'ContainLoss2': 'CONTAIN2', 'BalanceDiceLoss2': 'BAL2', 'CrossEntroLoss0': 'CE0', 'ClassifyLoss': 'CLASSIFY'}
 
-    def __init__(self, spec: dict, scale: float = 1.0, scale_dev=None):
+    def __init__(self, spec: dict, scale: float = 1.0, scale_dev=None, params=None):
         super().__init__()
-        unknown = set(spec) - {'CrossEntroLoss', 'BalanceDiceLoss', *self._DICE}
+        if 'DistributionLoss' in spec:
+            raise KeyError(_DISTRIBUTION_REFUSED)
+        unknown = set(spec) - set(self._TERM) - set(self.EXT)
         if unknown:
             raise KeyError(f'no HIP kernel for losses {sorted(unknown)}')
         self.spec = dict(spec)
         self.scale = scale
         self.scale_dev = scale_dev          # 1-element fp32 device tensor: run-time factor on top of `scale` (captured graphs)
+        self.params = dict(params or {})
+        self.extended = any(name in self.EXT for name in self.spec)
 
-    def forward(self, predict, target):
+    def forward(self, predict, target, params=None):
         p = _channels_last(predict)
         C = p.shape[-1]
         lab = _labels(target, C)
         sc = self.scale
+        if self.extended:
+            return self._forward_ext(p, lab, dict(self.params, **(params or {})))
         wd = [0.0] * 5
         for name, cls in self._DICE.items():
             if name in self.spec:
@@ -69,13 +84,33 @@ class LevelCriterion(nn.Module):
             named[name] = v if w == 1.0 else v * w
         return total, named
 
+    def _forward_ext(self, p, lab, params):
+        C = p.shape[-1]
+        absent = [name for name in self.spec if name in self._DICE and self._DICE[name] < 4 and self._DICE[name] >= C]
+        if absent:
+            raise ValueError(f'{absent}: the Dice of a class the prediction does not have ({C} classes)')
+        weights = {}
+        for name, w in self.spec.items():
+            term = self.EXT.get(name) or self._TERM[name]
+            weights[term] = weights.get(term, 0.0) + w * self.scale
+        total, values = ops.level_loss_ext(p, lab, weights, params, self.scale_dev)
+        named = {}
+        for name, w in self.spec.items():
+            v = values[1 + ops.LOSS_EXT_TERMS.index(self.EXT.get(name) or self._TERM[name])]
+            named[name] = v if w == 1.0 else v * w
+        return total, named
+
+
+_DISTRIBUTION_REFUSED = ('no HIP kernel for DistributionLoss: the reference module (loss/criterions.py:119-176) raises a shape '
+                         'error on ordinary inputs such as 2x2x8x6x4, so there is no behaviour to port')
+
 
 class _Single(nn.Module):
     NAME = None
 
-    def __init__(self):
+    def __init__(self, **params):
         super().__init__()
-        self.impl = LevelCriterion({self.NAME: 1.0})
+        self.impl = LevelCriterion({self.NAME: 1.0}, params=params)
 
     def forward(self, predict, target):
         return self.impl(predict, target)[0]
@@ -106,6 +141,105 @@ class DiceClassLoss0(_Single):
     NAME = 'DiceClassLoss0'
 
 
+class DiceLoss(_Single):
+    """loss/criterions.py:8-32, loss/multi_criterions.py:8-28: 1 - mean_{b,c} (2I + eps) / (P + T + eps)"""
+    NAME = 'DiceLoss'
+
+    def __init__(self, eps: float = 1e-5):
+        super().__init__(eps=eps)
+
+
+class IOULoss(_Single):
+    """loss/criterions.py:563-585, multi_criterions.py:544-565: 1 - mean_{b,c} (I + eps) / (P + T - I); the eps cancels in the
+    denominator as in the reference, which has no guard there"""
+    NAME = 'IOULoss'
+
+    def __init__(self, eps: float = 1e-5):
+        super().__init__(eps=eps)
+
+
+class SSLoss(_Single):
+    """loss/criterions.py:588-615: mean_{b,c} sigma sum t (p-1)^2 / (T + eps) + (1 - sigma) sum (1-t) p^2 / (S - T + eps)"""
+    NAME = 'SSLoss'
+
+    def __init__(self, sigma: float = 0.05, eps: float = 1e-5):
+        super().__init__(sigma=sigma, eps=eps)
+
+
+class FocalLoss(_Single):
+    """loss/criterions.py:618-644, multi_criterions.py:568-591: -(1/(B S C)) sum t (1-p)^gamma log p, the log not clamped.
+    `eps` is unused, as in the reference.  Deviation: voxels with t = 0 contribute exactly 0; the reference gives NaN there when
+    p == 0 exactly (0 * log 0).  At p == 1 exactly the gradient is its limit (0 for gamma > 0), also for gamma < 1 where the
+    reference's autograd gives NaN."""
+    NAME = 'FocalLoss'
+
+    def __init__(self, gamma: float = 2, eps: float = 1e-9):
+        super().__init__(gamma=gamma)
+
+
+class MSEcLoss(_Single):
+    """loss/criterions.py:738-751, multi_criterions.py:666-679 (registered as 'MSELoss'): the mean of (p - onehot)^2 over all
+    B S C entries; reduction='sum' gives the sum.  reduction='none' has no scalar to return and is refused."""
+    NAME = 'MSELoss'
+
+    def __init__(self, size_average=None, reduce=None, reduction: str = 'mean'):
+        if size_average is not None or reduce is not None:
+            reduction = nn._reduction.legacy_get_string(size_average, reduce)
+        if reduction not in ('mean', 'sum'):
+            raise ValueError(f"MSEcLoss: reduction {reduction!r} is not supported (use 'mean' or 'sum')")
+        super().__init__()
+        self.reduction = reduction
+
+    def forward(self, predict, target):
+        v = self.impl(predict, target)[0]
+        return v * predict.numel() if self.reduction == 'sum' else v
+
+
+class ContainLoss(_Single):
+    """loss/criterions.py:466-497, class 1: 1 - mean_b (I + eps) / ((1 - alpha)(T + eps) + alpha (P + eps)).  Deviation: the
+    target is t = [label == 1] where the reference reads the raw label; the two agree on the binary labels criterions.py is
+    written for."""
+    NAME, PARAM, ALPHA = 'ContainLoss', 'alpha', 0.4
+
+    def __init__(self, class_index: int = 1, eps: float = 1e-5):
+        if class_index != 1:
+            raise ValueError(f'{self.NAME}: only class_index=1 has a HIP kernel')
+        super().__init__(eps=eps)
+
+    def forward(self, predict, target, alpha: float = None):
+        return self.impl(predict, target, {self.PARAM: self.ALPHA if alpha is None else alpha})[0]
+
+
+class ContainLoss2(ContainLoss):
+    """loss/criterions.py:500-530: ContainLoss with alpha = 0.3 by default"""
+    NAME, PARAM, ALPHA = 'ContainLoss2', 'alpha2', 0.3
+
+
+class BalanceDiceLoss2(_Single):
+    """loss/multi_criterions.py:517-541: the balanced Dice of BalanceDiceLoss over classes 1 .. C-1 only"""
+    NAME = 'BalanceDiceLoss2'
+
+    def __init__(self, eps: float = 1e-5):
+        super().__init__(eps=eps)
+
+
+class CrossEntroLoss0(_Single):
+    """loss/multi_criterions.py:640-663: the CrossEntroLoss of the two channels (p_0, 1 - p_0) against (t_0, 1 - t_0)"""
+    NAME = 'CrossEntroLoss0'
+
+    def __init__(self, eps: float = 1e-5):
+        super().__init__(eps=eps)
+
+
+class ClassifyLoss(_Single):
+    """loss/multi_criterions.py:617-637: with m = 1 - t_0 and y = sum_c c p_c, sum m (y - label)^2 / (sum m + eps), pooled over
+    the batch"""
+    NAME = 'ClassifyLoss'
+
+    def __init__(self, eps: float = 1e-5):
+        super().__init__(eps=eps)
+
+
 class _EvalMetric(nn.Module):
     """the evaluation losses train3D.py:143 requests besides the Dice losses (`eval_list`): computed on the un-thresholded class
     probabilities by the metric kernels of the inference driver (csrc/infer.hip); evaluation only, no gradient"""
@@ -128,6 +262,16 @@ class PrecisionLoss(_EvalMetric):
     INDEX, COMPLEMENT = 2, True
 
 
+class Recall(_EvalMetric):
+    """loss/criterions.py:280-311: mean_b (sum p t + 1e-5) / (sum t + 1e-5)"""
+    INDEX = 1
+
+
+class Precision(_EvalMetric):
+    """loss/criterions.py:348-379: mean_b (sum p t + 1e-5) / (sum p + 1e-5)"""
+    INDEX = 2
+
+
 class LocalizationLoss(_EvalMetric):
     """loss/criterions.py:179-241 (as written there: all three "axes" reduce to the H profile)"""
     INDEX = 3
@@ -142,11 +286,26 @@ Loss_Dict = {
     'RecallLoss': RecallLoss,
     'PrecisionLoss': PrecisionLoss,
     'LocalizationLoss': LocalizationLoss,
+    'DiceLoss': DiceLoss,
+    'IOULoss': IOULoss,
+    'SSLoss': SSLoss,
+    'FocalLoss': FocalLoss,
+    'MSELoss': MSEcLoss,
+    'ContainLoss': ContainLoss,
+    'ContainLoss2': ContainLoss2,
+    'BalanceDiceLoss2': BalanceDiceLoss2,
+    'CrossEntroLoss0': CrossEntroLoss0,
+    'ClassifyLoss': ClassifyLoss,
+    'Recall': Recall,
+    'Precision': Precision,
 }
 
 
 def get_criterions(name_list):
-    """loss/criterions.py:773-782"""
+    """loss/criterions.py:773-782, and the training losses of loss/multi_criterions.py that a `--criterion_list` can name
+    (BalanceDiceLoss2, CrossEntroLoss0, ClassifyLoss, DiceClassLoss0, DiceClassLoss2).  DistributionLoss is refused."""
+    if 'DistributionLoss' in name_list:
+        raise KeyError(_DISTRIBUTION_REFUSED)
     return {name: Loss_Dict[name]() for name in name_list}
 
 

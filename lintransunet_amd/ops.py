@@ -1678,3 +1678,63 @@ def level_loss(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
     (w_dice[c], c < 4) + Dice of the foreground union (w_dice[4]).
     scale_dev: optional 1-element fp32 device tensor multiplying all weights at run time."""
     return _LevelLoss.apply(p, label, w_ce, w_bal, tuple(w_dice), scale_dev)
+
+
+# term and parameter slots of the config array of ltu_loss_ext_fwd / ltu_loss_ext_bwd (the LTU_LOSS_EXT_* enum of include/ltu_hip.h)
+LOSS_EXT_TERMS = ('CE', 'BAL', 'DICE0', 'DICE1', 'DICE2', 'DICE3', 'FG', 'DICE', 'IOU', 'SS', 'FOCAL', 'MSE', 'CONTAIN', 'CONTAIN2',
+                  'BAL2', 'CE0', 'CLASSIFY')
+LOSS_EXT_PARAMS = ('gamma', 'sigma', 'alpha', 'alpha2', 'eps')
+LOSS_EXT_DEFAULTS = {'gamma': 2.0, 'sigma': 0.05, 'alpha': 0.4, 'alpha2': 0.3, 'eps': 1e-5}
+
+
+def loss_ext_cfg(weights, params=None):
+    """{term: weight} (names of LOSS_EXT_TERMS) and {param: value} -> the float array the C-ABI takes"""
+    unknown = (set(weights) - set(LOSS_EXT_TERMS)) | (set(params or {}) - set(LOSS_EXT_PARAMS))
+    if unknown:
+        raise KeyError(f'unknown loss terms or parameters {sorted(unknown)}')
+    pr = dict(LOSS_EXT_DEFAULTS, **(params or {}))
+    vals = [float(weights.get(k, 0.0)) for k in LOSS_EXT_TERMS] + [float(pr[k]) for k in LOSS_EXT_PARAMS]
+    return (ctypes.c_float * len(vals))(*vals)
+
+
+class _LevelLossExt(torch.autograd.Function):
+    """The wider loss family of one decoder level; returns (total, values[1 + NTERM]) with values detached."""
+
+    @staticmethod
+    def forward(ctx, p, label, cfg, scale_dev):
+        ctx.lc = current()
+        _chk(p, 'p'); _chk(label, 'label')
+        B, C = p.shape[0], p.shape[-1]
+        S = p.numel() // (B * C)
+        dev = p.device
+        nt = len(LOSS_EXT_TERMS)
+        sums = torch.empty(_lib.load().ltu_loss_ext_ws_floats(B, S, C), device=dev, dtype=torch.float32)      # no zero fill
+        buf = torch.empty(nt + 2, device=dev, dtype=torch.float32)
+        values = buf[:nt + 1]            # the report; buf[nt + 1] repeats the total as the differentiable output
+        coef = torch.empty((B, C, 8), device=dev, dtype=torch.float32)
+        _lib.call('ltu_loss_ext_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(values), _p(coef), B, S, C, cfg, _p(scale_dev), _s())
+        ctx.cfg = cfg
+        ctx.save_for_backward(p, label, coef)
+        ctx.mark_non_differentiable(values)
+        ctx.set_materialize_grads(False)
+        return buf[nt + 1], values
+
+    @staticmethod
+    def backward(ctx, g, _gv):
+        p, label, coef = ctx.saved_tensors
+        B, C = p.shape[0], p.shape[-1]
+        S = p.numel() // (B * C)
+        if g is None:
+            return None, None, None, None
+        g = g.contiguous().to(torch.float32)
+        dp = torch.empty_like(p)
+        _lib.call('ltu_loss_ext_bwd', _p(p), _p(label), _p(coef), ctx.cfg, _p(g), _p(dp), B, S, C, _s())
+        return dp, None, None, None
+
+
+def level_loss_ext(p, label, weights, params=None, scale_dev=None):
+    """p fp32 [B,...,C] channels-last probabilities (2 <= C <= 4), label uint8 [B,...]: sum_k weights[k] * term_k over the terms of
+    LOSS_EXT_TERMS, with the parameters of LOSS_EXT_PARAMS (defaults LOSS_EXT_DEFAULTS).  Returns (total, values) with
+    values[0] = total and values[1 + i] = term LOSS_EXT_TERMS[i] (unweighted, detached); no host synchronisation.
+    scale_dev: optional 1-element fp32 device tensor multiplying all weights at run time."""
+    return _LevelLossExt.apply(p, label, loss_ext_cfg(weights, params), scale_dev)
