@@ -229,11 +229,11 @@ CASES = [
 ]
 
 # Kernels of the conv family in a profile: names matching FAMILY, and the GEMM instantiations matching GEMMS that strided convs
-# reach.  wgrad_ring_bf16_kernel is a dense-GEMM kernel only: launch_tn_ring_bf16 declines every multi-tap gather (ntaps != 1),
-# so no 3x3x3 conv reaches it.
+# reach.  wgrad_ring_bf16_kernel is a dense-GEMM kernel only (launch_tn_ring_bf16 declines every multi-tap gather, ntaps != 1):
+# no 3x3x3 conv reaches it, test_gpu_token_paths.py names it.
 FAMILY = re.compile(r'conv3_|conv_class|sdgrad_|updgrad_|upconv_|conv_halo_fold')
 GEMMS = re.compile(r'igemm_nt_bf16|wgrad_tn_bf16')
-NOT_CONV = {'wgrad_ring_bf16_kernel<6>': 'dense GEMM only: launch_tn_ring_bf16 declines ntaps != 1'}
+NOT_CONV = {}
 
 
 def kernel_base(name):
