@@ -564,6 +564,33 @@ int ltu_affine_sample(const float* in, float* out, const float* mats, int n, int
 int ltu_zoom_sample(const float* in, float* out, const int* zsize, int n, int H, int W, int D, ltu_stream_t s);
 int ltu_adjust_contrast(const float* in, float* out, const float* gamma, int* minmax_ws, int n, long long per, ltu_stream_t s);
 
+/* ---- data side of the monai driver (dataset/CT_pancreas_monai.py:37-58, 91-105; monai 0.7.0 Spacingd + Orientationd('RAS'),
+ * RandCropByPosNegLabeld, RandFlipd(spatial_axis 0), RandRotate90d(spatial_axes (0, 1))); csrc/resample.hip.
+ * resample_grid: for every output voxel p (shape O0 x O1 x O2, element strides os0..2) the source coordinate is c = M (p, 1), M =
+ *   mat, a float64 [3][4] pull matrix in device memory (row s = source axis s of the source of shape S0 x S1 x S2, element strides
+ *   ss0..2).  c is clamped to [0, size - 1] per axis (grid_sample border padding, align_corners False, in voxel units).
+ *   image: trilinear over the 8 taps, each tap mapped first: clamp(alpha * v + beta, lo, hi) (NIfTI slope / intercept, then
+ *          ScaleIntensityRange and its clip folded into one affine map by the caller); src_dtype LTU_U8 / LTU_I16 / LTU_F32, out f32.
+ *   label: u8 source voxel at the round-half-even of the clamped c (grid_sample nearest), out u8.
+ *   Either pair (src_img, out_img) / (src_lab, out_lab) may be NULL, not both; given both, one launch writes both outputs.
+ *   lane_axis: the output axis whose step moves the source address least (the caller knows M); the kernel walks it across the lanes
+ *   of a wave and, when it is not the output's fastest axis, transposes 64 x 64 tiles through LDS before the store.
+ *   No workspace.  LTU_E_ARG: NULL mat, unpaired pointers, lane_axis outside 0..2; LTU_E_DTYPE: src_dtype; LTU_E_SHAPE: a size or
+ *   stride < 1. */
+enum { LTU_U8 = 2, LTU_I16 = 3 };
+int ltu_resample_grid(const void* src_img, int src_dtype, const uint8_t* src_lab, int S0, int S1, int S2, long long ss0, long long ss1,
+                      long long ss2, float* out_img, uint8_t* out_lab, int O0, int O1, int O2, long long os0, long long os1,
+                      long long os2, const double* mat, int lane_axis, float alpha, float beta, float lo, float hi, ltu_stream_t s);
+/* crop_orient: patches [n][h][w][d] (f32 and / or u8, either pair NULL, not both) cut from vol [H][W][D] at desc, a HOST int32 array
+ * [n][6] = (h0, w0, d0, flip_h, flip_w, swap_hw): out[k][x][y][z] = vol[h0 + a][w0 + b][d0 + z] with (u, v) = swap_hw ? (y, x) :
+ * (x, y), a = flip_h ? h-1-u : u, b = flip_w ? w-1-v : v - a signed permutation of the (h, w) plane, which expresses "flip along
+ * axis 0, then rot90(k, axes (0, 1))" for every k.  n <= LTU_CROP_ORIENT_MAX (the descriptors travel as kernel arguments).
+ * LTU_E_SHAPE: a crop outside the volume, swap_hw with h != w; LTU_E_ALIGN: d % 4 == 0 with out_img not 16-byte or out_lab not
+ * 4-byte aligned. */
+#define LTU_CROP_ORIENT_MAX 64
+int ltu_crop_orient(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const int* desc, int n, int H, int W,
+                    int D, int h, int w, int d, ltu_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,8 @@ class WgradJob(ctypes.Structure):
 
 
 WGRAD_GROUP_MAX = 32      # LTU_WGRAD_GROUP_MAX of include/ltu_hip.h
+CROP_ORIENT_MAX = 64      # LTU_CROP_ORIENT_MAX of include/ltu_hip.h
+U8, I16 = 2, 3            # LTU_U8 / LTU_I16 source dtypes of ltu_resample_grid (LTU_F32 = 0)
 
 
 # name -> argument types (return type is always int).  Mirrors include/ltu_hip.h one to one.
@@ -95,6 +97,8 @@ SIGNATURES = {
     'ltu_lesion_stats': [P, P, P, P, P, L, L, I, I, I, I, I, I, I, I, F, I, P],
     'ltu_ct_preprocess': [P, P, P, P, I, I, I, F, F, F, F, P],
     'ltu_crop_flip': [P, P, P, I, I, I, I, I, I, I, I, P],
+    'ltu_resample_grid': [P, I, P, I, I, I, L, L, L, P, P, I, I, I, L, L, L, P, I, F, F, F, F, P],
+    'ltu_crop_orient': [P, P, P, P, P, I, I, I, I, I, I, I, P],
     'ltu_adamw': [P, P, P, P, L, F, F, F, F, F, L, F, P],
     'ltu_norm_ws_floats': [],
     'ltu_instnorm_stats': [P, P, P, L, I, L, I, I, P],

@@ -6,11 +6,14 @@ is uploaded once; preprocessing, cropping and flipping are HIP kernels (csrc/dat
 the label's foreground / background index lists exactly as monai does (the label comes from disk, so it is host-resident anyway).
 `augment` applies the remaining augmentations of the reference (RandRotated, RandAdjustContrastd, RandZoomd, RandFlipd;
 CT_pancreas_ids.py:121-134) to a batch of patches on the device; the random draws stay on the host.
+The third driver's data side (train3D_monai_version.py with dataset/CT_pancreas_monai.py: NIfTI scans of the Medical
+Segmentation Decathlon layout, ScaleIntensityRanged -> Spacingd -> Orientationd('RAS'), then crop + RandFlipd + RandRotate90d) is
+`SpacedScan` / `sample` / `to_native` at the end of this file.
 """
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, geometry, nifti
 from .ops import _p, _s
 
 LOW_CLIP, HIGH_CLIP, MEAN, STD = -91.0, 250.0, 86.9, 39.4
@@ -200,3 +203,165 @@ def synthetic_patches(batch, size, seed, device, n_classes=2, n_blobs=2):
             if n_classes == 3:
                 lab[b, 0][dist <= 0.25] = 2
     return x.to(device), lab.to(device)
+
+
+# ---- the monai driver's data side (dataset/CT_pancreas_monai.py:37-58 training, :91-105 evaluation) ---------------------------
+# LoadImaged (nifti.py) -> ScaleIntensityRanged(a_min -96, a_max 215, b = (a - 77.99) / 75.4, clip) -> Spacingd((0.5, 0.5, 2.0),
+# bilinear / nearest) -> Orientationd('RAS') as ONE resampling kernel through the float64 pull matrix of geometry.spacing_plan
+# (csrc/resample.hip), then RandCropByPosNegLabeld -> RandFlipd(0.5, axis 0) -> RandRotate90d(0.5, axes (0, 1)) as one gather.
+
+MONAI_CT_WINDOW = (-96.0, 215.0, (-96.0 - 77.99) / 75.4, (215.0 - 77.99) / 75.4)      # a_min, a_max, b_min, b_max (clip=True)
+
+
+def intensity_map(window=MONAI_CT_WINDOW, slope=1.0, inter=0.0):
+    """(alpha, beta, lo, hi) with clamp(alpha * v + beta, lo, hi) = ScaleIntensityRange(window, clip)(v * slope + inter);
+    window None leaves the (slope / intercept-scaled) voxels unchanged"""
+    if window is None:
+        return float(slope), float(inter), -np.inf, np.inf
+    a_min, a_max, b_min, b_max = (float(v) for v in window)
+    if a_max - a_min == 0.0:                       # monai: img - a_min + b_min
+        return float(slope), float(inter) - a_min + b_min, min(b_min, b_max), max(b_min, b_max)
+    k = (b_max - b_min) / (a_max - a_min)
+    return float(slope) * k, (float(inter) - a_min) * k + b_min, min(b_min, b_max), max(b_min, b_max)
+
+
+def _source_dtype(a):
+    """the three source dtypes the kernel reads; anything else goes through float32"""
+    a = np.asarray(a)
+    if a.dtype == np.uint8:
+        return a, _lib.U8
+    if a.dtype == np.int16:
+        return a, _lib.I16
+    return a.astype(np.float32), 0
+
+
+def label_u8(a):
+    """label voxels as uint8 class ids; values outside 0..255 or not integral are refused"""
+    a = np.asarray(a)
+    if a.dtype == np.uint8:
+        return a
+    if a.size and (a.min() < 0 or a.max() > 255 or not np.array_equal(a, np.round(a))):
+        raise ValueError('labels must be integers in 0..255')
+    return a.astype(np.uint8)
+
+
+def resample(src_img, src_lab, matrix, out_shape, imap=(1.0, 0.0, -np.inf, np.inf), src_dtype=0, src_strides=None,
+             out_strides=None, lane_axis=None):
+    """ltu_resample_grid: device sources (image of src_dtype / u8 label, either None) of shape (S0, S1, S2) read through
+    `src_strides` (default: x fastest, i.e. a [S2][S1][S0] array), resampled through the 3x4 float64 pull matrix to outputs of
+    out_shape (default layout: [O0][O1][O2], the last axis fastest).  Returns (f32 image or None, u8 label or None)."""
+    src = src_img if src_img is not None else src_lab
+    if src is None or not src.is_cuda:
+        raise _lib.LtuError('data.resample runs on the GPU only (no CPU fallback)')
+    if src_img is not None and src_lab is not None and (src_img.shape != src_lab.shape or src_img.stride() != src_lab.stride()):
+        raise ValueError(f'image {tuple(src_img.shape)} and label {tuple(src_lab.shape)} are sampled through one matrix: same layout needed')
+    S = tuple(int(n) for n in src.shape[::-1]) if src_strides is None else None
+    if src_strides is None:
+        src_strides = (1, S[0], S[0] * S[1])
+    else:
+        S = tuple(int(n) for n in src.shape)
+    O = tuple(int(n) for n in out_shape)
+    if out_strides is None:
+        out_strides, alloc = (O[1] * O[2], O[2], 1), O
+    else:
+        alloc = tuple(O[a] for a in np.argsort(out_strides)[::-1])
+    m = np.asarray(matrix, dtype=np.float64).reshape(3, 4)
+    mat = torch.as_tensor(m.ravel().copy()).to(src.device)
+    lane = geometry.lane_axis(m, src_strides) if lane_axis is None else lane_axis
+    oi = torch.empty(alloc, device=src.device, dtype=torch.float32) if src_img is not None else None
+    ol = torch.empty(alloc, device=src.device, dtype=torch.uint8) if src_lab is not None else None
+    _lib.call('ltu_resample_grid', _p(src_img), int(src_dtype), _p(src_lab), *S, *(int(s) for s in src_strides), _p(oi), _p(ol),
+              *O, *(int(s) for s in out_strides), _p(mat), lane, *(float(v) for v in imap), _s())
+    return oi, ol
+
+
+class SpacedScan:
+    """The deterministic half of the driver's CacheDataset: one NIfTI image (and label) read, uploaded once as stored, and
+    resampled on the device to `pixdim` in `axcodes` orientation.  img: f32 [H, W, D]; lab: u8 [H, W, D] (or None);
+    label_host: the resampled label on the host (crop centres are drawn from it); affine: the output's 4x4 affine; matrix: the
+    3x4 float64 pull matrix (RAS voxel -> file voxel); native_shape / native_affine / native: the file's grid and header."""
+
+    def __init__(self, img_path, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda'):
+        ni = nifti.load(img_path)
+        nl = nifti.load(lab_path) if lab_path is not None else None
+        if nl is not None:
+            geometry.check_pair(ni.shape, ni.affine, nl.shape, nl.affine)
+        self.native, self.native_shape, self.native_affine = ni, ni.shape, ni.affine
+        self.matrix, self.shape, self.affine = geometry.spacing_plan(ni.shape, ni.affine, pixdim, axcodes)
+        raw, code = _source_dtype(ni.data)
+        ri = torch.as_tensor(np.ascontiguousarray(raw)).to(device)
+        rl = None
+        if nl is not None:
+            lv = nl.data if (nl.slope, nl.inter) == (1.0, 0.0) else nl.scaled()
+            rl = torch.as_tensor(np.ascontiguousarray(label_u8(lv))).to(device)
+        self.img, self.lab = resample(ri, rl, self.matrix, self.shape, intensity_map(intensity, ni.slope, ni.inter), code)
+        self.label_host = self.lab.cpu().numpy() if self.lab is not None else None
+
+
+def orient_desc(flip, k):
+    """(flip_h, flip_w, swap_hw) of "flip along axis 0 (if flip), then np.rot90(k, axes=(0, 1))" as the signed permutation
+    out[x][y] = crop[a][b], (u, v) = swap ? (y, x) : (x, y), a = flip_h ? h-1-u : u, b = flip_w ? w-1-v : v"""
+    k %= 4
+    h, w = (3, 3) if k % 2 else (2, 3)
+    idx = np.arange(h * w).reshape(h, w)
+    out = np.rot90(np.flip(idx, 0) if flip else idx, k, (0, 1))
+    a, b = divmod(int(out[0, 0]), w)
+    return int(a != 0), int(b != 0), k % 2
+
+
+def draw_monai_sample(label_host, spatial_size, rs, flip_prob=0.5, rot90_prob=0.5, max_k=3):
+    """one sample's draws in the driver's transform order from one RandomState: the crop centre (RandCropByPosNegLabeld,
+    num_samples 1), the flip (RandFlipd), then RandRotate90d's k = randint(max_k) + 1 before its probability draw (monai 0.7.0's
+    RandRotate90.randomize; recalled, not pinned).  Every draw is made whether or not its transform fires.
+    Returns (centre, flip, k) with k = 0 when the rotation does not fire."""
+    center = crop_centers(label_host, spatial_size, 1, rand_state=rs)[0]
+    flip = rs.rand() < flip_prob
+    k = rs.randint(max_k) + 1
+    rot = rs.rand() < rot90_prob
+    return center, bool(flip), int(k) if rot else 0
+
+
+def crop_orient(img, lab, draws, spatial_size):
+    """device patches ([n,1,h,w,d] f32 or None, [n,1,h,w,d] u8 or None) = rot90(flip(crop, 0), k, (0, 1)) from img / lab
+    [H,W,D] for draws [(centre, flip, k)]; an odd k needs h == w (the patch would change shape)"""
+    vol = img if img is not None else lab
+    if vol is None or not vol.is_cuda:
+        raise _lib.LtuError('data.crop_orient runs on the GPU only (no CPU fallback)')
+    H, W, D = vol.shape
+    h, w, d = (int(s) for s in spatial_size)
+    desc = np.array([[max(c[0] - h // 2, 0), max(c[1] - w // 2, 0), max(c[2] - d // 2, 0), *orient_desc(f, k)]
+                     for c, f, k in draws], dtype=np.int32).reshape(-1, 6)
+    if (desc[:, 5] != 0).any() and h != w:
+        raise ValueError(f'rot90 by an odd k of a non-square patch ({h} x {w}) is not supported')
+    n = len(draws)
+    oi = torch.empty((n, 1, h, w, d), device=vol.device, dtype=torch.float32) if img is not None else None
+    ol = torch.empty((n, 1, h, w, d), device=vol.device, dtype=torch.uint8) if lab is not None else None
+    for s in range(0, n, _lib.CROP_ORIENT_MAX):
+        e = min(n, s + _lib.CROP_ORIENT_MAX)
+        chunk = np.ascontiguousarray(desc[s:e])
+        _lib.call('ltu_crop_orient', _p(img), _p(lab), _p(oi[s:e]) if oi is not None else 0, _p(ol[s:e]) if ol is not None else 0,
+                  chunk.ctypes.data, e - s, H, W, D, h, w, d, _s())
+    return oi, ol
+
+
+def sample(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_prob=0.5):
+    """the random half of the driver's dataset: num_samples patches ([n,1,h,w,d] f32, u8) of a SpacedScan, each with its own
+    crop centre, flip and rot90 drawn by draw_monai_sample"""
+    if scan.label_host is None:
+        raise ValueError('sampling needs a label (RandCropByPosNegLabeld draws centres from it)')
+    draws = [draw_monai_sample(scan.label_host, spatial_size, rand_state, flip_prob, rot90_prob) for _ in range(num_samples)]
+    return crop_orient(scan.img, scan.lab, draws, spatial_size)
+
+
+def to_native(label_map, scan):
+    """nearest resampling of an RAS u8 label map [H,W,D] (leading size-1 axes allowed; e.g. evaluate_multiclass's 'label_map')
+    back onto the file's grid through the inverse pull matrix: u8 [Z][Y][X] on the device, ready for nifti.save(...,
+    scan.native_affine, like=scan.native)"""
+    lm = label_map.reshape(scan.shape)
+    if lm.dtype != torch.uint8:
+        raise ValueError(f'to_native takes a uint8 label map, got {lm.dtype}')
+    lm = lm.contiguous()
+    H, W, D = scan.shape
+    X, Y, Z = scan.native_shape
+    _, out = resample(None, lm, geometry.invert(scan.matrix), (X, Y, Z), src_strides=(W * D, D, 1), out_strides=(1, X, X * Y))
+    return out

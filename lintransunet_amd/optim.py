@@ -119,6 +119,11 @@ def reference_schedule(optimizer):
     return ReduceLROnPlateau(optimizer, mode='min', factor=0.8, patience=5, threshold=1e-2, cooldown=1, min_lr=1e-7)
 
 
+def monai_schedule(optimizer):
+    """the scheduler of train3D_monai_version.py:199-205"""
+    return ReduceLROnPlateau(optimizer, mode='min', factor=0.6, patience=4, threshold=1e-2, cooldown=1, min_lr=1e-7)
+
+
 class BestCheckpoint:
     """Best-checkpoint logic of train3D.py:254-268: whenever the eval loss does not exceed the best so far, write
     `model.state_dict()` to `<dir>/temp_model.pt` (loadable by the reference's get_model, train3D.py:104-120).  What the
