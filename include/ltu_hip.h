@@ -427,6 +427,24 @@ int ltu_vote_accumulate(const float* seg, float* votes, float* count, const int*
                         int d, int C, ltu_stream_t s);
 int ltu_vote_finalize(const float* votes, const float* count, float* out, int B, int C, int H, int W, int D, int Hp, int Wp, int Dp,
                       int ph, int pw, int pd, ltu_stream_t s);
+/* ---- weighted and mirrored blending (monai 0.7.0 sliding_window_inference mode="gaussian", plus mirror test-time augmentation) --
+ * desc is a HOST int32 array [n][5] = (sample b, h0, w0, d0, mask) of n <= LTU_BLEND_ITEMS_MAX items (the descriptors travel as
+ * kernel arguments); (h0, w0, d0) is the window start in the padded image Hp x Wp x Dp, which holds vol [B][H][W][D] at offset
+ * pad_lo = (Hp - H) / 2 per axis (zeros elsewhere); bit a of mask flips axis a (0 = H, 1 = W, 2 = D) of the window.
+ * gather_mirror: win [n][h][w][d] with win[k][u] = padded[b][start + u'], u'_a = r_a - 1 - u_a on a flipped axis, else u_a.
+ * blend: seg f32 [n][h][w][d][C] channels-last (the model's softmax), 1 <= C <= 8; for every padded voxel p covered by item k,
+ * v = p - start_k, u = v flipped as above: votes[b][c][p] += w(v) seg[k][u][c], wsum[b][p] += w(v), w(v) = max(g0[v0] g1[v1]
+ * g2[v2], wmin) with device tables g0 [h], g1 [w], g2 [d] (tables of ones and wmin = 1: constant weights).  No atomics: each covered
+ * voxel is read and written once per launch by one thread, which applies the covering items in item order, so the sums do not
+ * depend on how the items are split into launches.  ltu_vote_finalize(votes, wsum, ...) divides and crops.
+ * LTU_E_ARG: a NULL pointer, n outside 0 .. LTU_BLEND_ITEMS_MAX, a mask above 7; LTU_E_SHAPE: C outside 1 .. 8, a window larger
+ * than the padded image, an image larger than the padded one, h w d >= 2^31, b outside 0 .. B-1, a window not inside the padded
+ * image.  Both refuse before any HIP call. */
+#define LTU_BLEND_ITEMS_MAX 32
+int ltu_window_gather_mirror(const float* vol, float* win, const int* desc, int n, int B, int H, int W, int D, int Hp, int Wp, int Dp,
+                             int h, int w, int d, ltu_stream_t s);
+int ltu_window_blend(const float* seg, float* votes, float* wsum, const float* g0, const float* g1, const float* g2, float wmin,
+                     const int* desc, int n, int B, int C, int Hp, int Wp, int Dp, int h, int w, int d, ltu_stream_t s);
 /* evaluation metrics of the driver on p = [pred[b][ci] >= threshold] against target u8 [B][H][W][D] (0/1):
  * values[0..3] = DiceClassLoss (criterions.py:35-70), Recall (280-311), Precision (348-379), LocalizationLoss (179-241),
  * means over the batch; rows f32 [B][3][H] scratch (per-h sums of p, t, p*t over W*D = WD elements). */

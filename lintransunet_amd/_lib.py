@@ -28,6 +28,7 @@ class WgradJob(ctypes.Structure):
 
 WGRAD_GROUP_MAX = 32      # LTU_WGRAD_GROUP_MAX of include/ltu_hip.h
 CROP_ORIENT_MAX = 64      # LTU_CROP_ORIENT_MAX of include/ltu_hip.h
+BLEND_ITEMS_MAX = 32      # LTU_BLEND_ITEMS_MAX of include/ltu_hip.h
 U8, I16 = 2, 3            # LTU_U8 / LTU_I16 source dtypes of ltu_resample_grid (LTU_F32 = 0)
 
 
@@ -78,6 +79,8 @@ SIGNATURES = {
     'ltu_window_gather': [P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     'ltu_vote_accumulate': [P, P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_vote_finalize': [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
+    'ltu_window_gather_mirror': [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
+    'ltu_window_blend': [P, P, P, P, P, P, F, P, I, I, I, I, I, I, I, I, I, P],
     'ltu_keep_largest_component': [P, P, P, P, P, I, I, I, I, I, P],
     'ltu_seg_metrics': [P, P, P, P, I, I, I, I, L, F, P],
     'ltu_surface_boundary': [P, P, P, P, I, I, I, I, I, I, F, P],

@@ -6,9 +6,11 @@ Mirrors the reference driver inference_embed_attn.py:92-185:
     DiceClassLoss / Recall / Precision / LocalizationLoss (predict2, masks)
 with the same argument meaning.  Window scheduling is host integer logic; the windows, the votes of the model's eval
 (one-hot arg-max) output and the metrics stay in HBM and go through the C-ABI (csrc/infer.hip).  No CPU fallback.
+Gaussian-weighted and mirrored blending of the model's softmax (mode='gaussian', mirror_axes, probs) run on csrc/blend.hip.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -44,10 +46,128 @@ def patch_starts(image_size, roi_size, interval):
     return out
 
 
-def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.25):
+BLEND_MODES = ('constant', 'gaussian')
+
+
+def _blend_options(mode, sigma_scale, mirror_axes):
+    """(mode, sigma_scale per axis, mirror_axes) checked; ValueError on anything else"""
+    if not isinstance(mode, str) or mode not in BLEND_MODES:
+        raise ValueError(f"mode must be one of {BLEND_MODES}, got {mode!r}")
+    try:
+        sig = tuple(float(v) for v in sigma_scale) if isinstance(sigma_scale, (tuple, list)) else (float(sigma_scale),) * 3
+    except (TypeError, ValueError):
+        raise ValueError(f'sigma_scale must be a number or one number per axis, got {sigma_scale!r}') from None
+    if len(sig) != 3:
+        raise ValueError(f'sigma_scale must be a number or one number per axis, got {sigma_scale!r}')
+    if mode == 'gaussian' and not all(v > 0 and math.isfinite(v) for v in sig):
+        raise ValueError(f"mode='gaussian' needs sigma_scale > 0 (finite), got {sigma_scale!r}")
+    if not isinstance(mirror_axes, (tuple, list)) or not all(isinstance(a, int) and not isinstance(a, bool) for a in mirror_axes) \
+            or not all(0 <= a <= 2 for a in mirror_axes) or len(set(mirror_axes)) != len(mirror_axes):
+        raise ValueError(f'mirror_axes must be distinct spatial axes from (0, 1, 2), got {mirror_axes!r}')
+    return mode, sig, tuple(mirror_axes)
+
+
+def importance_tables(roi, mode='gaussian', sigma_scale=0.125):
+    """The blending weight of sliding_window_inference as three float64 per-axis tables and a floor: the weight of window voxel u
+    (in volume orientation) is w(u) = max(g0[u0] g1[u1] g2[u2], wmin).  Returns (g0, g1, g2, wmin), numpy arrays of the roi's
+    extents and a float.  mode='constant': tables of ones, wmin = 1.  mode='gaussian' restates monai 0.7.0's
+    compute_importance_map (GaussianFilter(truncated=4.0, approx="erf") on a delta at the centre, normalised to a maximum of 1,
+    clamped to its smallest non-zero value) axis by axis, for an axis of extent r:
+        c = r // 2, sigma = r * sigma_scale, tail = int(max(4 sigma, 0.5) + 0.5)
+        k(x) = max(0, (erf((x + 1/2) / (sigma sqrt 2)) - erf((x - 1/2) / (sigma sqrt 2))) / 2)
+        g[i] = k(i - c) / k(0), and 0 where |i - c| > tail
+    wmin = the product of each axis's smallest non-zero entry = the smallest non-zero value of the 3-D map."""
+    mode, sig, _ = _blend_options(mode, sigma_scale, ())
+    roi = tuple(int(r) for r in roi)
+    if len(roi) != 3 or min(roi) < 1:
+        raise ValueError(f'roi must be three extents >= 1, got {roi}')
+    if mode == 'constant':
+        return np.ones(roi[0]), np.ones(roi[1]), np.ones(roi[2]), 1.0
+    tabs, wmin = [], 1.0
+    for r, s in zip(roi, sig):
+        c, sigma = r // 2, r * s
+        tail = int(max(4.0 * sigma, 0.5) + 0.5)
+        den = sigma * math.sqrt(2.0)
+
+        def k(x):
+            return max(0.0, 0.5 * (math.erf((x + 0.5) / den) - math.erf((x - 0.5) / den)))
+
+        k0 = k(0)
+        g = np.array([k(i - c) / k0 if abs(i - c) <= tail else 0.0 for i in range(r)])
+        wmin *= float(g[g > 0].min())
+        tabs.append(g)
+    return tabs[0], tabs[1], tabs[2], wmin
+
+
+def mirror_masks(mirror_axes=()):
+    """flip masks of the 2^|A| variants of a window, variant m first to last: variant m flips axis A[j] for every bit j set in m;
+    bit a of a mask is axis a (0 = H, 1 = W, 2 = D), so variant 0 is the window as it is"""
+    return [sum(1 << a for j, a in enumerate(mirror_axes) if (m >> j) & 1) for m in range(1 << len(mirror_axes))]
+
+
+def window_items(batch, starts, mirror_axes=()):
+    """the blending items in order: (b, h0, w0, d0, mask) for idx in range(batch * len(starts)) (sample-major, b = idx // nwin,
+    start = starts[idx % nwin]) and, within a window, its mirror variants (mirror_masks) - the variants of a window are adjacent"""
+    nwin, masks = len(starts), mirror_masks(mirror_axes)
+    return [(idx // nwin, *starts[idx % nwin], m) for idx in range(batch * nwin) for m in masks]
+
+
+def item_batches(items, sw_batch_size):
+    """the predictor's batches: consecutive chunks of sw_batch_size items"""
+    return [items[g:g + sw_batch_size] for g in range(0, len(items), sw_batch_size)]
+
+
+def _blend_inference(vol, roi, pad_lo, img, starts, sw_batch_size, predictor, mode, sigma_scale, mirror_axes):
+    """the weighted / mirrored path of sliding_window_inference (csrc/blend.hip)"""
+    B, img0, dev = vol.shape[0], tuple(int(v) for v in vol.shape[2:]), vol.device
+    if int(sw_batch_size) < 1:
+        raise ValueError(f'sw_batch_size must be >= 1, got {sw_batch_size}')
+    g0, g1, g2, wmin = importance_tables(roi, mode, sigma_scale)
+    tab = torch.tensor(np.concatenate((g0, g1, g2)), dtype=torch.float32).to(dev)
+    t0, t1, t2 = tab[:roi[0]], tab[roi[0]:roi[0] + roi[1]], tab[roi[0] + roi[1]:]
+    votes = wsum = None
+    C = None
+    for chunk in item_batches(window_items(B, starts, mirror_axes), sw_batch_size):
+        n = len(chunk)
+        parts = [(s, np.ascontiguousarray(chunk[s:s + _lib.BLEND_ITEMS_MAX], dtype=np.int32))
+                 for s in range(0, n, _lib.BLEND_ITEMS_MAX)]
+        win = torch.empty((n, 1) + roi, device=dev, dtype=torch.float32)
+        for s, desc in parts:
+            _lib.call('ltu_window_gather_mirror', _p(vol), _p(win[s:]), desc.ctypes.data, len(desc), B, *img0, *img, *roi, _s())
+        seg = predictor(win)
+        if seg.dim() != 5 or tuple(seg.shape[2:]) != roi or seg.shape[0] != n:
+            raise _lib.LtuError(f'predictor returned {tuple(seg.shape)} for windows {(n, 1) + roi}')
+        seg_cl = seg.permute(0, 2, 3, 4, 1)
+        if seg_cl.dtype != torch.float32 or not seg_cl.is_contiguous():
+            seg_cl = seg_cl.to(torch.float32).contiguous()
+        if votes is None:
+            C = seg.shape[1]
+            votes = torch.zeros((B, C) + img, device=dev, dtype=torch.float32)
+            wsum = torch.zeros((B,) + img, device=dev, dtype=torch.float32)
+        elif seg.shape[1] != C:
+            raise _lib.LtuError(f'predictor returned {seg.shape[1]} channels after {C}')
+        for s, desc in parts:
+            _lib.call('ltu_window_blend', _p(seg_cl[s:]), _p(votes), _p(wsum), _p(t0), _p(t1), _p(t2), wmin, desc.ctypes.data,
+                      len(desc), B, C, *img, *roi, _s())
+    out = torch.empty((B, C) + img0, device=dev, dtype=torch.float32)
+    _lib.call('ltu_vote_finalize', _p(votes), _p(wsum), _p(out), B, C, *img0, *img, *pad_lo, _s())
+    return out
+
+
+def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.25, mode='constant', sigma_scale=0.125,
+                             mirror_axes=()):
     """inputs f32 [B, 1, H, W, D] on the GPU; predictor(windows [n, 1, h, w, d]) -> [n, C, h, w, d] (the eval-mode
-    MaskTransUnet: channels-last one-hot exposed in the reference's shape).  Returns f32 [B, C, H, W, D], the per-voxel
-    average of the window outputs (constant blending), exactly as monai's function does for mode="constant"."""
+    MaskTransUnet: channels-last one-hot exposed in the reference's shape, or its softmax with probs=True).  Returns f32
+    [B, C, H, W, D], the per-voxel weighted average of the window outputs.
+
+    mode='constant' without mirror_axes is monai's mode="constant" (the reference's call): the plain average, on the vote
+    kernels of csrc/infer.hip.  Otherwise (csrc/blend.hip): mode='gaussian' weights window voxel u by importance_tables(roi,
+    'gaussian', sigma_scale) (monai's mode="gaussian"), and mirror_axes = A (distinct axes of (0, 1, 2) = H, W, D) predicts every
+    window 2^|A| times, variant m flipped along the axes of mirror_masks(A)[m], and blends each prediction flipped back, with the
+    weight of its un-flipped position.  The predictor sees consecutive chunks of sw_batch_size items of window_items (the variants
+    of a window adjacent).  Each voxel's sums are formed in fp32 in item order: the result is bit-identical between calls and for
+    every sw_batch_size.  Bad mode, sigma_scale or mirror_axes raise ValueError before anything runs."""
+    mode, sig, axes = _blend_options(mode, sigma_scale, mirror_axes)
     if not inputs.is_cuda:
         raise _lib.LtuError('sliding_window_inference runs on the GPU only (no CPU fallback)')
     if inputs.dim() != 5 or inputs.shape[1] != 1:
@@ -61,6 +181,8 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     nwin, total = len(starts), len(starts) * B
     dev = inputs.device
     vol = inputs.to(torch.float32).contiguous()
+    if mode != 'constant' or axes:
+        return _blend_inference(vol, roi, pad_lo, img, starts, int(sw_batch_size), predictor, mode, sig, axes)
     votes = count = None
     C = None
     for g in range(0, total, sw_batch_size):
@@ -406,22 +528,24 @@ def lesion_metrics(predict, masks, class_indices=(1,), threshold=0.5, connectivi
 class GraphedPredictor:
     """The eval-mode forward for a fixed window batch captured once into a HIP graph and replayed per window batch: an eager
     forward is ~500 launches of ~35 us host time each, several times what the kernels need.  A short last batch is padded with
-    copies of its first window (their outputs are dropped)."""
+    copies of its first window (their outputs are dropped).  probs=True captures model(x, probs=True), the softmax the one-hot
+    arg-max is taken from (the input of mode='gaussian' / mirrored blending)."""
 
-    def __init__(self, model, batch, roi, device):
-        self.model, self.n = model, batch
+    def __init__(self, model, batch, roi, device, probs=False):
+        self.model, self.n, self.probs = model, batch, bool(probs)
         self.x = torch.zeros((batch, 1) + tuple(roi), device=device, dtype=torch.float32)
         self.ctx = ops.Context()          # own scratch arena: the graph bakes its addresses in, nobody else may move it
+        fwd = (lambda x: model(x, probs=True)) if self.probs else model
         side = torch.cuda.Stream(device=device)
         side.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(side), torch.no_grad(), ops.use(self.ctx):
             for _ in range(2):
-                model(self.x)
+                fwd(self.x)
         torch.cuda.current_stream(device).wait_stream(side)
         torch.cuda.synchronize(device)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode='thread_local'), torch.no_grad(), ops.use(self.ctx):
-            self.y = model(self.x)
+            self.y = fwd(self.x)
         self.ctx.freeze()
         self.sig = tuple(p.data_ptr() for p in model.parameters())
 
@@ -437,19 +561,24 @@ class GraphedPredictor:
         return self.y[:n]
 
 
-def infer_volume(model, images, depth_size=32, roi_xy=512, sw_batch_size=4, overlap=0.6, graph=False):
+def infer_volume(model, images, depth_size=32, roi_xy=512, sw_batch_size=4, overlap=0.6, graph=False, mode='constant',
+                 sigma_scale=0.125, mirror_axes=(), probs=False):
     """one patient of inference_embed_attn.py:main: eval-mode model, (roi_xy, roi_xy, depth_size) windows, overlap 0.6.
-    graph=True (or a GraphedPredictor built earlier) replays the forward from a captured HIP graph."""
+    graph=True (or a GraphedPredictor built earlier) replays the forward from a captured HIP graph.  mode, sigma_scale and
+    mirror_axes go to sliding_window_inference; probs=True blends the model's softmax instead of its one-hot arg-max (a
+    GraphedPredictor passed as graph brings its own probs).  The defaults are the reference's call."""
+    _blend_options(mode, sigma_scale, mirror_axes)
     was_training = model.training
     model.eval()
     try:
         with torch.no_grad():
-            predictor = model
+            predictor = (lambda w: model(w, probs=True)) if probs else model
             if isinstance(graph, GraphedPredictor):
                 predictor = graph
             elif graph:
                 roi = tuple(r if r and r > 0 else i for r, i in zip((roi_xy, roi_xy, depth_size), images.shape[2:]))
-                predictor = GraphedPredictor(model, sw_batch_size, roi, images.device)
-            return sliding_window_inference(images, (roi_xy, roi_xy, depth_size), sw_batch_size, predictor, overlap=overlap)
+                predictor = GraphedPredictor(model, sw_batch_size, roi, images.device, probs=probs)
+            return sliding_window_inference(images, (roi_xy, roi_xy, depth_size), sw_batch_size, predictor, overlap=overlap,
+                                            mode=mode, sigma_scale=sigma_scale, mirror_axes=mirror_axes)
     finally:
         model.train(was_training)

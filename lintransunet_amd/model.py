@@ -404,11 +404,15 @@ class MaskTransUnet(nn.Module):
         return ops.roi_unwarp(e, plan)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x):
+    def forward(self, x, probs=False):
+        """training: (probabilities, masks) in the reference's shape; eval: the one-hot arg-max [B, C, H, W, D] (channels-last
+        memory), or with probs=True the fp32 softmax it is taken from (same layout; refused in training mode)"""
+        if probs and self.training:
+            raise ValueError('probs=True is an eval-mode output; call model.eval() first')
         if not x.is_cuda:
             raise RuntimeError('lintransunet_amd.MaskTransUnet runs on MI355X only (no CPU fallback); move the input to cuda')
         if torch.is_grad_enabled():
-            return self._forward(x)              # training: the caller's context (train.train_step recycles its arena per step)
+            return self._forward(x, probs)       # training: the caller's context (train.train_step recycles its arena per step)
         # inference: nothing of an earlier forward is needed any more -> recycle (and re-zero) a scratch arena.  Unless the caller
         # brought a context of its own (infer.GraphedPredictor), that is this model's private inference context, so an evaluation
         # between a training forward and its backward cannot clobber the statistics the backward still needs.
@@ -419,9 +423,9 @@ class MaskTransUnet(nn.Module):
             lc = self._infer_ctx
         with ops.use(lc):
             lc.begin_step(x.device)
-            return self._forward(x)
+            return self._forward(x, probs)
 
-    def _forward(self, x):
+    def _forward(self, x, probs=False):
         L, nl, C = self.num_layers, len(self.num_layers), self.dim_output
         p = float(self.dropout) if self.training else 0.0
         self._step += 1
@@ -490,6 +494,8 @@ class MaskTransUnet(nn.Module):
         out = ops.final_softmax(z, C)
         if self.training:
             return _cl(out), [_cl(m) for m in masks]
+        if probs:
+            return _cl(out.detach())
         return _cl(ops.onehot_argmax(out.detach()))
 
 
