@@ -11,6 +11,7 @@
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;       // one MFMA operand of 8 bf16 (16 bytes)
 
 struct bf16_t {
   uint16_t bits;
@@ -240,6 +241,12 @@ struct LtuDevOnce {
     return !(mask.fetch_or(bit) & bit);
   }
 };
+// raises a kernel's dynamic-LDS limit above the default 64 KB.  Per device: call it behind an LtuDevOnce latch of the call site (two
+// instantiations of a kernel template share a function-pointer type, so the latch cannot live in here)
+template <class K>
+static inline void ltu_dyn_lds(K* kern, int bytes) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
 #endif
 
 static inline int ltu_check_launch() {

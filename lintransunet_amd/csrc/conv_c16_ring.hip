@@ -10,8 +10,7 @@
 //   * 32-byte voxel rows at a d pitch of 12 rows, the two 16-byte halves XOR-ed with the halo w coordinate's low bit: conflict-free
 //     for ds_read_b128 (tools/lds_conflicts.py); tap offsets are compile-time immediates (FLIP = data gradient: mirrored taps).
 #include "gemm_desc.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+#include "lds_dma.h"
 
 #define C16_PITCH 12
 #define C16_HROWS 768                     // 6 x 10 x 12 rows = 720, padded to 24 LDS-DMA pieces of 32 rows
@@ -21,30 +20,14 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 #define C16_SMEM (C16_BIAS + 128)
 #define C16_CENTER ((1 * 10 + 1) * C16_PITCH + 1)      // row of halo voxel (1, 1, 1): the largest negative tap offset
 
-__device__ __attribute__((aligned(64))) uint32_t ltu_zero_c16[16];      // source of out-of-volume halo rows / padding rows
-
-__device__ __forceinline__ void c16_glds16(const void* src, uint32_t lds_byte_addr) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void c16_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    c16_static_for<I + 1, N>(f);
-  }
-}
-
 template <bool FLIP>
 __global__ void __launch_bounds__(256, 2) conv3_c16_ring_bf16_kernel(const HaloArgs a, int bricks) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int nbh = (a.H + 3) / 4, nbw = (a.W + 7) / 8, nbd = (a.D + 7) / 8;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
-  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_c16) + (lane & 1) * 16;
+  const uint32_t lds0 = lds_addr(smem);
+  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_line) + (lane & 1) * 16;
 
   // this workgroup's run of bricks
   const int per = (bricks + (int)gridDim.x - 1) / (int)gridDim.x;
@@ -79,13 +62,8 @@ __global__ void __launch_bounds__(256, 2) conv3_c16_ring_bf16_kernel(const HaloA
   // were a seventh of a trip, in-kernel clock stamps)
   struct Coord { int b, h0, w0, d0; };
   auto decompose = [&](int brick) {
-    int t = brick;
-    Coord c;
-    const int bd = t % nbd; t /= nbd;
-    const int bw = t % nbw; t /= nbw;
-    const int bh = t % nbh;
-    c.b = t / nbh; c.h0 = bh * 4; c.w0 = bw * 8; c.d0 = bd * 8;
-    return c;
+    const Brick bk = split_brick(brick, nbh, nbw, nbd);
+    return Coord{bk.b, bk.bh * 4, bk.bw * 8, bk.bd * 8};
   };
   auto advance = [&](Coord c) {
     c.d0 += 8;
@@ -107,7 +85,7 @@ __global__ void __launch_bounds__(256, 2) conv3_c16_ring_bf16_kernel(const HaloA
 #pragma unroll
       for (int s = 0; s < 6; ++s) {
         const char* src = ((hpos[s] >> 24) & 1) ? hbase[s] + (((hpos[s] >> 25) & 1) ? off1 : off0) : zsrc;
-        c16_glds16(src, hb + s * 1024);
+        glds16(src, hb + s * 1024);
       }
       return;
     }
@@ -116,7 +94,7 @@ __global__ void __launch_bounds__(256, 2) conv3_c16_ring_bf16_kernel(const HaloA
       const int h = h0 - 1 + (hpos[s] & 255), w = w0 - 1 + ((hpos[s] >> 8) & 255), d = d0 - 1 + ((hpos[s] >> 16) & 255);
       const bool in = ((hpos[s] >> 24) & 1) != 0 && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W && (unsigned)d < (unsigned)a.D;
       const char* src = in ? hbase[s] + (((hpos[s] >> 25) & 1) ? off1 : off0) : zsrc;
-      c16_glds16(src, hb + s * 1024);
+      glds16(src, hb + s * 1024);
     }
   };
 
@@ -166,7 +144,7 @@ __global__ void __launch_bounds__(256, 2) conv3_c16_ring_bf16_kernel(const HaloA
   issue_halo(cur, 0);
   int buf = 0;
   for (int brick = b_first; brick < b_end; ++brick) {
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");      // this brick's halo has landed, everybody has left the other buffer
+    ring_sync<0>();                    // this brick's halo has landed, everybody has left the other buffer
     if (brick > b_first) store_brick(prev);
     if (brick + 1 < b_end) issue_halo(next, buf ^ 1);
     prev = cur; cur = next; next = advance(next);
@@ -191,7 +169,7 @@ __global__ void __launch_bounds__(256, 2) conv3_c16_ring_bf16_kernel(const HaloA
     };
     bf16x8 afA[2], afB[2];
     load_frags(std::integral_constant<int, 0>{}, afA);
-    c16_static_for<0, 14>([&](auto TP) {
+    static_for<0, 14>([&](auto TP) {
       constexpr int t = decltype(TP)::value * 2;
       if constexpr (t + 1 < 27) load_frags(std::integral_constant<int, t + 1>{}, afB);
       __builtin_amdgcn_sched_barrier(0);
@@ -233,8 +211,8 @@ int launch_conv_c16_ring_bf16(const HaloArgs& a, hipStream_t st) {
   if (bricks >= (1LL << 31) || bricks < 128) return 1;        // tiny grids: the generic path splits channels over workgroups
   static LtuDevOnce attr_once;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_c16_ring_bf16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, C16_SMEM);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_c16_ring_bf16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, C16_SMEM);
+    ltu_dyn_lds(&conv3_c16_ring_bf16_kernel<false>, C16_SMEM);
+    ltu_dyn_lds(&conv3_c16_ring_bf16_kernel<true>, C16_SMEM);
   }
   const int want = ltu_knob_pos("LTU_C16_RING_BLOCKS", 512);
   const int nblk = (int)(bricks < want ? bricks : want);

@@ -11,8 +11,7 @@
 //     4 MFMAs; outputs leave through a wave-private 4 KB staging tile as 16-byte stores.
 // Measured against the first generation at the shapes of the step: see profiles/r04_microbench.txt (bench_conv.py).
 #include "gemm_desc.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+#include "lds_dma.h"
 
 #define FC_HROWS 640                      // 6 x 10 x 10 halo voxels padded to 40 LDS-DMA pieces of 16 rows
 #define FC_HBUF (FC_HROWS * 64)
@@ -20,30 +19,14 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 #define FC_STAGE (FC_W + 27 * 2048)       // 4 wave-private output tiles of 64 voxels x 64 B
 #define FC_SMEM (FC_STAGE + 4 * 4096)
 
-__device__ __attribute__((aligned(64))) uint32_t ltu_zero_fc[32];      // source of out-of-volume halo rows / padding weight rows
-
-__device__ __forceinline__ void fc_glds16(const void* src, uint32_t lds_byte_addr) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void fc_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    fc_static_for<I + 1, N>(f);
-  }
-}
-
 template <bool FLIP>
 __global__ void __launch_bounds__(256) conv3_fc_ring_bf16_kernel(const HaloArgs a, int bricks) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int nbh = (a.H + 3) / 4, nbw = (a.W + 7) / 8, nbd = (a.D + 7) / 8;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
-  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_fc) + (lane & 3) * 16;
+  const uint32_t lds0 = lds_addr(smem);
+  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_line) + (lane & 3) * 16;
 
   // this workgroup's run of bricks
   const int per = (bricks + (int)gridDim.x - 1) / (int)gridDim.x;
@@ -58,7 +41,7 @@ __global__ void __launch_bounds__(256) conv3_fc_ring_bf16_kernel(const HaloArgs 
     for (int p = wave; p < 54; p += 4) {
       const int t = p >> 1, n = (p & 1) * 16 + prow;
       const char* src = n < a.N ? reinterpret_cast<const char*>(a.w) + (((long long)n * 27 + t) * 32 + wchunk * 8) * 2 : zsrc;
-      fc_glds16(src, lds0 + FC_W + p * 1024);
+      glds16(src, lds0 + FC_W + p * 1024);
     }
   }
   // ---- halo pieces of this lane: 10 per wave; row hv -> (hh, hw, hd); 16-byte slot lane & 3 holds channel quarter (lane & 3) ^ (hw & 3),
@@ -77,11 +60,8 @@ __global__ void __launch_bounds__(256) conv3_fc_ring_bf16_kernel(const HaloArgs 
     hpos[s] = hh | (hw << 8) | (hd << 16) | ((hv < 600 ? 1 : 0) << 24);
   }
   auto decompose = [&](int brick, int& b, int& h0, int& w0, int& d0) {
-    int t = brick;
-    const int bd = t % nbd; t /= nbd;
-    const int bw = t % nbw; t /= nbw;
-    const int bh = t % nbh;
-    b = t / nbh; h0 = bh * 4; w0 = bw * 8; d0 = bd * 8;
+    const Brick bk = split_brick(brick, nbh, nbw, nbd);
+    b = bk.b; h0 = bk.bh * 4; w0 = bk.bw * 8; d0 = bk.bd * 8;
   };
   auto issue_halo = [&](int brick, int buf) {
     int b, h0, w0, d0;
@@ -93,7 +73,7 @@ __global__ void __launch_bounds__(256) conv3_fc_ring_bf16_kernel(const HaloArgs 
       const int h = h0 - 1 + (hpos[s] & 255), w = w0 - 1 + ((hpos[s] >> 8) & 255), d = d0 - 1 + ((hpos[s] >> 16) & 255);
       const bool in = (hpos[s] >> 24) != 0 && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W && (unsigned)d < (unsigned)a.D;
       const char* src = in ? hbase[s] + (vox0 + hrel[s]) * hld[s] : zsrc;
-      fc_glds16(src, hb + s * 1024);
+      glds16(src, hb + s * 1024);
     }
   };
 
@@ -152,7 +132,7 @@ __global__ void __launch_bounds__(256) conv3_fc_ring_bf16_kernel(const HaloArgs 
   issue_halo(b_first, 0);
   int buf = 0;
   for (int brick = b_first; brick < b_end; ++brick) {
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");      // this brick's halo (the first time: and the weights) has landed
+    ring_sync<0>();                    // this brick's halo (the first time: and the weights) has landed
     if (brick > b_first) store_brick(brick - 1);
     if (brick + 1 < b_end) issue_halo(brick + 1, buf ^ 1);
     const int hoff = buf * FC_HBUF;
@@ -188,7 +168,7 @@ __global__ void __launch_bounds__(256) conv3_fc_ring_bf16_kernel(const HaloArgs 
     };
     bf16x8 afA[2][2], wfA[2], afB[2][2], wfB[2];
     load_frags(std::integral_constant<int, 0>{}, afA, wfA);
-    fc_static_for<0, 14>([&](auto TP) {
+    static_for<0, 14>([&](auto TP) {
       constexpr int t = decltype(TP)::value * 2;
       if constexpr (t + 1 < 27) load_frags(std::integral_constant<int, t + 1>{}, afB, wfB);
       __builtin_amdgcn_sched_barrier(0);
@@ -225,8 +205,8 @@ int launch_conv_fc_ring_bf16(const HaloArgs& a, hipStream_t st) {
   if (bricks >= (1LL << 31) || bricks < 128) return 1;        // tiny grids: the generic path splits channels over workgroups
   static LtuDevOnce attr_once;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_fc_ring_bf16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, FC_SMEM);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_fc_ring_bf16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, FC_SMEM);
+    ltu_dyn_lds(&conv3_fc_ring_bf16_kernel<false>, FC_SMEM);
+    ltu_dyn_lds(&conv3_fc_ring_bf16_kernel<true>, FC_SMEM);
   }
   const int want = ltu_knob_pos("LTU_FC_RING_BLOCKS", 256);
   const int nblk = (int)(bricks < want ? bricks : want);

@@ -11,11 +11,8 @@
 //   K     = 27 taps x C channels, walked chunk by chunk (outer) and tap by tap (inner)
 //   N     = output channels, BN per workgroup (32 / 64 / 128)
 // Data gradient = same kernel on the output gradient with mirrored tap offsets and the [Ci][27][Co] operand.
-#include <type_traits>
-
 #include "gemm_desc.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+#include "lds_dma.h"
 
 #define HALO_H 6
 #define HALO_W 6
@@ -49,12 +46,8 @@ __global__ void __launch_bounds__(256) conv3_halo_bf16_kernel(const HaloArgs a) 
   const int wm = wave / WN, wn = wave % WN;
   const int li = lane & 31, lh = lane >> 5;
   const int nbh = (a.H + 3) / 4, nbw = (a.W + 3) / 4, nbd = (a.D + 7) / 8;
-  int bid = blockIdx.x;
-  const int bd = bid % nbd; bid /= nbd;
-  const int bw = bid % nbw; bid /= nbw;
-  const int bh = bid % nbh;
-  const int b = bid / nbh;
-  const int h0 = bh * 4, w0 = bw * 4, d0 = bd * 8;
+  const Brick bk = split_brick(blockIdx.x, nbh, nbw, nbd);
+  const int b = bk.b, h0 = bk.bh * 4, w0 = bk.bw * 4, d0 = bk.bd * 8;
   const int n_blk = blockIdx.y * BN;
   const int nchunk = (a.C + CC - 1) / CC;
 
@@ -292,16 +285,7 @@ __global__ void __launch_bounds__(256) conv3_halo_ws_bf16_kernel(const HaloArgs 
   // Index arithmetic is hoisted out of the brick loop: a thread always stages the same halo pieces and stores the same output
   // pieces relative to the brick origin, and the brick coordinates advance incrementally (a first version re-derived all of
   // it per brick: ~900 scalar / vector ALU instructions around 27 MFMAs).
-  struct BrickPos { int b, bh, bw, bd; };
-  auto decompose = [&](int brick) {
-    BrickPos q;
-    int t = brick;
-    q.bd = t % nbd; t /= nbd;
-    q.bw = t % nbw; t /= nbw;
-    q.bh = t % nbh;
-    q.b = t / nbh;
-    return q;
-  };
+  auto decompose = [&](int brick) { return split_brick(brick, nbh, nbw, nbd); };
   // brick order: a contiguous run per workgroup, adjacent runs on one XCD (see conv3_halo_wr_bf16_kernel)
   const bool xcd_order = (gridDim.x & 7) == 0 && !a.no_xcd_order;
   const int slot = xcd_order ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
@@ -309,8 +293,8 @@ __global__ void __launch_bounds__(256) conv3_halo_ws_bf16_kernel(const HaloArgs 
   const int brick_first = xcd_order ? slot * per : (int)blockIdx.x;
   const int brick_step = xcd_order ? 1 : (int)gridDim.x;
   const int brick_end = xcd_order ? min(bricks, brick_first + per) : bricks;
-  const BrickPos stepd = decompose(brick_step);
-  auto advance = [&](BrickPos& q) {
+  const Brick stepd = decompose(brick_step);
+  auto advance = [&](Brick& q) {
     q.bd += stepd.bd; if (q.bd >= nbd) { q.bd -= nbd; ++q.bw; }
     q.bw += stepd.bw; if (q.bw >= nbw) { q.bw -= nbw; ++q.bh; }
     q.bh += stepd.bh; if (q.bh >= nbh) { q.bh -= nbh; ++q.b; }
@@ -332,7 +316,7 @@ __global__ void __launch_bounds__(256) conv3_halo_ws_bf16_kernel(const HaloArgs 
     p_rel[p] = ((long long)(p_hh[p] - 1) * a.W + (p_hw[p] - 1)) * a.D + (p_hd[p] - 1);
   }
   uint4 hreg[NH];
-  auto load_halo = [&](const BrickPos& q) {
+  auto load_halo = [&](const Brick& q) {
     const int h0 = q.bh * 4, w0 = q.bw * 4, d0 = q.bd * 8;
     const long long vox0 = (((long long)q.b * a.H + h0) * a.W + w0) * a.D + d0;
 #pragma unroll
@@ -373,7 +357,7 @@ __global__ void __launch_bounds__(256) conv3_halo_ws_bf16_kernel(const HaloArgs 
   uint16_t* Cs = halo;
 
   int brick = brick_first;
-  BrickPos cur = decompose(min(brick, bricks - 1)), nxt = cur;
+  Brick cur = decompose(min(brick, bricks - 1)), nxt = cur;
   if (brick < brick_end) load_halo(cur);
   // output pieces of this thread: rows (tid >> 3) + 32 it, 4 channels from (tid & 7) * 4
   const int o_w = tid >> 6, o_d = (tid >> 3) & 7, o_n = (tid & 7) * 4;
@@ -499,16 +483,7 @@ __global__ void __launch_bounds__(256) conv3_halo_wr_bf16_kernel(const HaloArgs 
       }
   }
 
-  struct BrickPos { int b, bh, bw, bd; };
-  auto decompose = [&](int brick) {
-    BrickPos q;
-    int t = brick;
-    q.bd = t % nbd; t /= nbd;
-    q.bw = t % nbw; t /= nbw;
-    q.bh = t % nbh;
-    q.b = t / nbh;
-    return q;
-  };
+  auto decompose = [&](int brick) { return split_brick(brick, nbh, nbw, nbd); };
   // Brick order: workgroup -> a CONTIGUOUS run of bricks (consecutive bricks along d share a halo face), and the runs of the 64
   // workgroups that land on one XCD (linear id % 8 under round-robin dispatch) are adjacent, so the in-plane halo overlap of
   // neighbouring rows is served by that XCD's L2.  Strided (brick = id + k * grid) every brick fetched its whole 2.8x halo through
@@ -519,14 +494,14 @@ __global__ void __launch_bounds__(256) conv3_halo_wr_bf16_kernel(const HaloArgs 
   const int brick_first = xcd_order ? slot * per : (int)blockIdx.x;
   const int brick_step = xcd_order ? 1 : (int)gridDim.x;
   const int brick_end = xcd_order ? min(bricks, brick_first + per) : bricks;
-  const BrickPos stepd = decompose(brick_step);
-  auto advance = [&](BrickPos& q) {
+  const Brick stepd = decompose(brick_step);
+  auto advance = [&](Brick& q) {
     q.bd += stepd.bd; if (q.bd >= nbd) { q.bd -= nbd; ++q.bw; }
     q.bw += stepd.bw; if (q.bw >= nbw) { q.bw -= nbw; ++q.bh; }
     q.bh += stepd.bh; if (q.bh >= nbh) { q.bh -= nbh; ++q.b; }
     q.b += stepd.b;
   };
-  auto origin = [&](const BrickPos& q) { return (((long long)q.b * a.H + q.bh * 4) * a.W + q.bw * 4) * a.D + q.bd * 8; };
+  auto origin = [&](const Brick& q) { return (((long long)q.b * a.H + q.bh * 4) * a.W + q.bw * 4) * a.D + q.bd * 8; };
 
   // ---- halo pieces of this thread (loop invariants): source pointer at the brick origin's offset, LDS slot, halo coordinates
   const char* h_ptr[NH];
@@ -547,7 +522,7 @@ __global__ void __launch_bounds__(256) conv3_halo_wr_bf16_kernel(const HaloArgs 
   }
   uint4 hreg[NH];
   bool hin[NH];                            // piece inside the volume (decided at request time, applied when it goes to LDS)
-  auto load_halo = [&](const BrickPos& q) {
+  auto load_halo = [&](const Brick& q) {
     const long long vox0 = origin(q);
     const long long sb0 = vox0 * a.lda0 * 2, sb1 = vox0 * a.lda1 * 2;       // scalar byte offsets of the brick origin
     const int h0 = q.bh * 4 - 1, w0 = q.bw * 4 - 1, d0 = q.bd * 8 - 1;
@@ -602,7 +577,7 @@ __global__ void __launch_bounds__(256) conv3_halo_wr_bf16_kernel(const HaloArgs 
 
   int brick = brick_first;
   if (brick >= brick_end) return;
-  BrickPos cur = decompose(brick), nxt = cur;
+  Brick cur = decompose(brick), nxt = cur;
   load_halo(cur);
   store_halo(smem);
   advance(nxt);
@@ -660,7 +635,7 @@ __global__ void __launch_bounds__(256) conv3_halo_wr_bf16_kernel(const HaloArgs 
     uint2 ov[4];
 #pragma unroll
     for (int it = 0; it < 4; ++it) ov[it] = *reinterpret_cast<const uint2*>(&Cs[o_lds[it]]);
-    const BrickPos done = cur;
+    const Brick done = cur;
     cur = nxt;
     if (more) {
       store_halo(smem + (buf ^ 1) * HELEMS);
@@ -797,7 +772,7 @@ int launch_conv_halo_bf16(HaloArgs a, hipStream_t st) {
     auto kern = &conv3_halo_bf16_kernel<WM, WN, TM, TN, TS, CCV>;                                                    \
     constexpr int bytes = halo_smem_bytes<WN, TN, TS>();                                                            \
     static LtuDevOnce once;                                                                                          \
-    if (once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); \
+    if (once.first()) ltu_dyn_lds(kern, bytes);                                                                      \
     hipLaunchKernelGGL(kern, grid, dim3(256), bytes, st, a);                                                         \
   } while (0)
 #define HALO_LAUNCH(WM, WN, TM, TN, TS)                     \
@@ -887,12 +862,8 @@ __global__ void __launch_bounds__(256, PACK ? 3 : 2) conv3_wgrad_halo_bf16_kerne
   uint4 hreg[6], greg[2];
   unsigned hin = 0, gin = 0;
   auto load_brick = [&](int brick) {
-    int t = brick;
-    const int bd = t % nbd; t /= nbd;
-    const int bw = t % nbw; t /= nbw;
-    const int bh = t % nbh;
-    const int b = t / nbh;
-    const int h0 = bh * 4, w0 = bw * 4, d0 = bd * 8;
+    const Brick bk = split_brick(brick, nbh, nbw, nbd);
+    const int b = bk.b, h0 = bk.bh * 4, w0 = bk.bw * 4, d0 = bk.bd * 8;
     hin = 0; gin = 0;
 #pragma unroll
     for (int p = 0; p < 6; ++p) {
@@ -1069,12 +1040,8 @@ __global__ void __launch_bounds__(256) conv_class_halo_bf16_kernel(const ClassHa
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int nbh = (a.H + 3) / 4, nbw = (a.W + 3) / 4, nbd = (a.D + 7) / 8;
-  int bid = blockIdx.x;
-  const int bd = bid % nbd; bid /= nbd;
-  const int bw = bid % nbw; bid /= nbw;
-  const int bh = bid % nbh;
-  const int b = bid / nbh;
-  const int h0 = bh * 4, w0 = bw * 4, d0 = bd * 8;
+  const Brick bk = split_brick(blockIdx.x, nbh, nbw, nbd);
+  const int b = bk.b, h0 = bk.bh * 4, w0 = bk.bw * 4, d0 = bk.bd * 8;
   const int n_blk = blockIdx.y * BN;
   const int nchunk = a.C / 32;
   const int nstage = (a.nent + TS - 1) / TS;
@@ -1224,31 +1191,11 @@ __global__ void __launch_bounds__(256) conv_class_halo_bf16_kernel(const ClassHa
 // The register-staged version above keeps 8 accumulator tiles per wave, which leaves one workgroup per CU: nothing hides the
 // L2 round trip of each weight stage.  Here a workgroup owns a 4x8x8 brick (256 coarse voxels, 4 waves x 64 rows), the weight
 // tiles stream through a 4-deep ring of 16 KB stages and the halo of the next channel chunk lands in a second buffer, all by
-// global_load_lds with hand-counted vmcnt (see gemm_ring.hip for the idiom).  64-byte LDS rows, chunk c of row r at slot
+// global_load_lds with hand-counted vmcnt (see lds_dma.h for the idiom).  64-byte LDS rows, chunk c of row r at slot
 // c ^ ((r >> 2) & 1) (conflict-free ds_read_b128 per 8-lane group).  Entries arrive sorted by offset so that an A fragment
 // is fetched once per distinct offset (27 instead of 64 for the un-embedding); each B fragment feeds two row tiles.
-__device__ __attribute__((aligned(64))) uint32_t ltu_zero_line[32];     // source of out-of-volume / padding rows
-
-__device__ __forceinline__ void cglds16(const uint16_t* src, uint16_t* lds_wave_base) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lds_wave_base);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void cring_sync() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-
 #define CR_HVOX 600          // 6 x 10 x 10 halo voxels
 #define CR_HROWS 640         // padded to 40 LDS-DMA pieces of 16 rows
-template <int I, int N, class F>
-__device__ __forceinline__ void cr_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    cr_static_for<I + 1, N>(f);
-  }
-}
 // The weight stream is organised class by class: stage (chunk, class c, sub-stage sc) holds up to TS entries of class c, so
 // the accumulator a stage updates is known at compile time (a run-time class index makes hipcc shuffle all 256 accumulator
 // registers around every entry).  SPCLS sub-stages per class; entries e in [cls_begin[c], cls_begin[c + 1]).
@@ -1263,12 +1210,8 @@ __global__ void __launch_bounds__(256) conv_class_ring_bf16_kernel(const ClassHa
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int nbh = (a.H + 3) / 4, nbw = (a.W + 7) / 8, nbd = (a.D + 7) / 8;
-  int bid = blockIdx.x;
-  const int bd = bid % nbd; bid /= nbd;
-  const int bw = bid % nbw; bid /= nbw;
-  const int bh = bid % nbh;
-  const int b = bid / nbh;
-  const int h0 = bh * 4, w0 = bw * 8, d0 = bd * 8;
+  const Brick bk = split_brick(blockIdx.x, nbh, nbw, nbd);
+  const int b = bk.b, h0 = bk.bh * 4, w0 = bk.bw * 8, d0 = bk.bd * 8;
   const int n_blk = blockIdx.y * BN;
   const int nchunk = a.C / 32;
   const int total = nchunk * SPC;
@@ -1314,7 +1257,7 @@ __global__ void __launch_bounds__(256) conv_class_ring_bf16_kernel(const ClassHa
       const uint16_t* src = zsrc;
       if (hv < CR_HVOX && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W && (unsigned)d < (unsigned)a.D)
         src = reinterpret_cast<const uint16_t*>(a.x) + ((((long long)b * a.H + h) * a.W + w) * a.D + d) * a.lda + chunk * 32 + lc * 8;
-      cglds16(src, hb + piece * 512);
+      glds16(src, hb + piece * 512);
     }
   };
   auto issue_w = [&](int g) {
@@ -1334,7 +1277,7 @@ __global__ void __launch_bounds__(256) conv_class_ring_bf16_kernel(const ClassHa
       const int e = e0 + __builtin_amdgcn_readfirstlane(wt[s]);
       const int wbase = e < e1 ? __builtin_amdgcn_readlane(ent_wbase, e & 63) : -1;
       const uint16_t* src = (wbase >= 0 && woff[s] >= 0) ? wsrc + wbase + woff[s] : zsrc;
-      cglds16(src, wb + s * 512);
+      glds16(src, wb + s * 512);
     }
   };
 
@@ -1359,15 +1302,15 @@ __global__ void __launch_bounds__(256) conv_class_ring_bf16_kernel(const ClassHa
   for (int g = 0; g < R - 1 && g < total; ++g) issue_w(g);
   for (int chunk = 0; chunk < nchunk; ++chunk) {
     const uint16_t* hb = halo + (chunk & 1) * HBUF;
-    cr_static_for<0, SPC>([&](auto ST) {
+    static_for<0, SPC>([&](auto ST) {
       constexpr int st = decltype(ST)::value, c = st / SPCLS, sc = st % SPCLS;
       const int g = chunk * SPC + st;
       if (g + 2 < total) {
         // LDS-DMA issued after W(g): W(g+1), W(g+2) and the halos issued at iterations g-3..g-1 (those with st == 0)
         constexpr bool near0 = st >= 1 && st <= 3;
-        if (near0 && chunk + 1 < nchunk) cring_sync<18>(); else cring_sync<8>();
+        if (near0 && chunk + 1 < nchunk) ring_sync<18>(); else ring_sync<8>();
       } else {
-        cring_sync<0>();
+        ring_sync<0>();
       }
       if (g + R - 1 < total) issue_w(g + R - 1);
       if (st == 0 && chunk + 1 < nchunk) issue_halo(chunk + 1);
@@ -1497,9 +1440,9 @@ int launch_conv_class_halo_bf16(const ClassHaloArgs& a, hipStream_t st) {
       constexpr int smem_bytes = 2 * CR_HROWS * 64 + 4 * 16384;
       static LtuDevOnce attr_once;
       if (attr_once.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_class_ring_bf16_kernel<8, 1, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_class_ring_bf16_kernel<8, 1, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_class_ring_bf16_kernel<4, 2, 3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
+        ltu_dyn_lds(&conv_class_ring_bf16_kernel<8, 1, 1, true>, smem_bytes);
+        ltu_dyn_lds(&conv_class_ring_bf16_kernel<8, 1, 1, false>, smem_bytes);
+        ltu_dyn_lds(&conv_class_ring_bf16_kernel<4, 2, 3, false>, smem_bytes);
       }
       bool full = a.ncls == 8;
       for (int c = 0; c < a.ncls; ++c) full = full && (r.cls_begin[c + 1] - r.cls_begin[c] == 8);
@@ -1551,12 +1494,8 @@ __global__ void __launch_bounds__(256) upconv_wgrad_class_bf16_kernel(const UpWg
 
   uint4 xreg[6], greg[16];
   auto load_brick = [&](int brick) {
-    int t = brick;
-    const int bd = t % nbd; t /= nbd;
-    const int bw = t % nbw; t /= nbw;
-    const int bh = t % nbh;
-    const int b = t / nbh;
-    const int h0 = bh * 4, w0 = bw * 4, d0 = bd * 8;
+    const Brick bk = split_brick(brick, nbh, nbw, nbd);
+    const int b = bk.b, h0 = bk.bh * 4, w0 = bk.bw * 4, d0 = bk.bd * 8;
 #pragma unroll
     for (int p = 0; p < 6; ++p) {
       const int idx = tid + p * 256;

@@ -9,31 +9,10 @@
 //     4 TN MFMAs;
 //   * epilogue: the 256 x BN tile staged once, 16-byte stores into the two destinations (conv pairs / gradient concat).
 #include "gemm_desc.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+#include "lds_dma.h"
 
 #define CR_HBUF (640 * 64)                // 6 x 10 x 10 halo rows padded to 40 pieces
 #define CR_RING (2 * CR_HBUF)
-
-__device__ __attribute__((aligned(64))) uint32_t ltu_zero_cr[512];
-
-__device__ __forceinline__ void cr_glds16(const void* src, uint32_t lds_byte_addr) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void cr_sync() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void cr_sfor(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    cr_sfor<I + 1, N>(f);
-  }
-}
 
 // HB = halo buffers.  2: the next chunk's halo lands while this chunk is multiplied (one workgroup per CU at 116-152 KB of LDS).
 // 1 (TN = 2 only: 64 accumulator registers): 76 KB of LDS and <= 256 registers = TWO workgroups per CU - the halo of a chunk is then
@@ -56,19 +35,15 @@ __global__ void __launch_bounds__(NW * 64, (HB == 1 && NW == 4) ? 2 : 1) conv3_r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int nbh = (a.H + NW - 1) / NW, nbw = (a.W + 7) / 8, nbd = (a.D + 7) / 8;
-  int bid = blockIdx.x;
-  const int bd = bid % nbd; bid /= nbd;
-  const int bw = bid % nbw; bid /= nbw;
-  const int bh = bid % nbh;
-  const int b = bid / nbh;
-  const int h0 = bh * NW, w0 = bw * 8, d0 = bd * 8;
+  const Brick bk = split_brick(blockIdx.x, nbh, nbw, nbd);
+  const int b = bk.b, h0 = bk.bh * NW, w0 = bk.bw * 8, d0 = bk.bd * 8;
   const int n_blk = blockIdx.y * BN;
   const int c_lo = SPLIT ? blockIdx.z * a.cps : 0;                       // first chunk of this workgroup; `chunk` below counts from it
   const int nchunk = SPLIT ? min(a.C / 32 - c_lo, a.cps) : a.C / 32;
   const int total = nchunk * 9;
   const bool wissue = NW == 4 || wave < 4;   // this wave issues weight pieces
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
-  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_cr) + (lane & 3) * 16;
+  const uint32_t lds0 = lds_addr(smem);
+  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_line) + (lane & 3) * 16;
   const int prow = lane >> 2;
 
   // ---- halo pieces: 10 per wave; voxel offset of the row and whether it lies inside the volume (the brick is fixed per workgroup) ----
@@ -92,7 +67,7 @@ __global__ void __launch_bounds__(NW * 64, (HB == 1 && NW == 4) ? 2 : 1) conv3_r
 #pragma unroll
     for (int s = 0; s < HPW; ++s) {
       const char* src = hvox[s] >= 0 ? base + hvox[s] * ld2 + hslot[s] * 2 : zsrc;
-      cr_glds16(src, hb + s * 1024);
+      glds16(src, hb + s * 1024);
     }
   };
   // ---- weight pieces of a stage (3 taps x BN rows): PW per wave -------------------------------------------------------------------
@@ -109,7 +84,7 @@ __global__ void __launch_bounds__(NW * 64, (HB == 1 && NW == 4) ? 2 : 1) conv3_r
     const uint32_t wb = lds0 + RING + (st % 3) * WSTAGE + (wave & 3) * PW * 1024;
     if (!wissue) return;
 #pragma unroll
-    for (int s = 0; s < PW; ++s) cr_glds16(woff[s] >= 0 ? reinterpret_cast<const char*>(wsrc + woff[s]) : zsrc, wb + s * 1024);
+    for (int s = 0; s < PW; ++s) glds16(woff[s] >= 0 ? reinterpret_cast<const char*>(wsrc + woff[s]) : zsrc, wb + s * 1024);
   };
 
   // ---- fragment read addresses (see upconv_ring.hip) --------------------------------------------------------------------------------
@@ -147,23 +122,23 @@ __global__ void __launch_bounds__(NW * 64, (HB == 1 && NW == 4) ? 2 : 1) conv3_r
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int dwi = 0; dwi < 3; ++dwi) bA[i][ks][dwi] = baseA[i][ks][dwi] + hoff;
-    cr_sfor<0, 9>([&](auto ST) {
+    static_for<0, 9>([&](auto ST) {
       constexpr int st = decltype(ST)::value;
       const int g = chunk * 9 + st;
       // LDS-DMA issued after W(g): W(g+1) (PW pieces) and - at stages 1 and 2 - the next chunk's halo (10 pieces, issued in stage 0
       // behind W(g+2))
       if constexpr (HB == 2) {
         if (g + 1 < total) {
-          if ((st == 1 || st == 2) && chunk + 1 < nchunk) cr_sync<PW + HPW>(); else cr_sync<PW>();
+          if ((st == 1 || st == 2) && chunk + 1 < nchunk) ring_sync<PW + HPW>(); else ring_sync<PW>();
         } else {
-          cr_sync<0>();
+          ring_sync<0>();
         }
         if (g + 2 < total) issue_w(g + 2);
         if (st == 0 && chunk + 1 < nchunk) issue_halo(chunk + 1);
       } else {
         // one halo buffer: the chunk's halo was requested behind W(g+1) at the end of the previous chunk (the youngest request: it has
         // landed only when nothing is outstanding)
-        if (st == 0 || g + 1 >= total || !wissue) cr_sync<0>(); else cr_sync<PW>();      // (waves that issue no weight pieces have nothing else in flight)
+        if (st == 0 || g + 1 >= total || !wissue) ring_sync<0>(); else ring_sync<PW>();      // (waves that issue no weight pieces have nothing else in flight)
         if (g + 2 < total) issue_w(g + 2);
       }
       auto load_frags = [&](auto TT, bf16x8 (&af)[2][2], bf16x8 (&wf)[TN][2]) {
@@ -309,12 +284,12 @@ int launch_conv_ring_bf16(HaloArgs& a, hipStream_t st) {
   static LtuDevOnce attr_once;
   constexpr int smem2 = CR_HBUF + 3 * 3 * 64 * 64, smem4 = 2 * CR_HBUF + 3 * 3 * 128 * 64, smem8 = 64 * 1024 + 3 * 3 * 64 * 64;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_ring_bf16_kernel<2, false, 1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, smem2);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_ring_bf16_kernel<2, true, 1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, smem2);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_ring_bf16_kernel<4, false, 2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, smem4);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_ring_bf16_kernel<4, true, 2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, smem4);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_ring_bf16_kernel<2, false, 1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, smem8);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_ring_bf16_kernel<2, true, 1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, smem8);
+    ltu_dyn_lds(&conv3_ring_bf16_kernel<2, false, 1, 4>, smem2);
+    ltu_dyn_lds(&conv3_ring_bf16_kernel<2, true, 1, 4>, smem2);
+    ltu_dyn_lds(&conv3_ring_bf16_kernel<4, false, 2, 4>, smem4);
+    ltu_dyn_lds(&conv3_ring_bf16_kernel<4, true, 2, 4>, smem4);
+    ltu_dyn_lds(&conv3_ring_bf16_kernel<2, false, 1, 8>, smem8);
+    ltu_dyn_lds(&conv3_ring_bf16_kernel<2, true, 1, 8>, smem8);
   }
   if (nwg < ltu_knob_pos("LTU_CONV_RING_MIN_WG", 200)) {
     // small grid: 64-column tiles and the channel chunks split over up to 8 workgroups (two workgroups per CU: 512 slots)
@@ -326,8 +301,8 @@ int launch_conv_ring_bf16(HaloArgs& a, hipStream_t st) {
     if ((long long)a.ksplit * a.B * a.H * a.W * a.D * a.N > a.part_floats) { a.ksplit = 1; return LTU_E_ARG; }
     static LtuDevOnce split_once;
     if (split_once.first()) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_ring_bf16_kernel<2, false, 1, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem2);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_ring_bf16_kernel<2, true, 1, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem2);
+      ltu_dyn_lds(&conv3_ring_bf16_kernel<2, false, 1, 4, true>, smem2);
+      ltu_dyn_lds(&conv3_ring_bf16_kernel<2, true, 1, 4, true>, smem2);
     }
     const dim3 sgrid((unsigned)bricks, (unsigned)((a.N + 63) / 64), (unsigned)a.ksplit);
     if (a.flip) hipLaunchKernelGGL((conv3_ring_bf16_kernel<2, true, 1, 4, true>), sgrid, dim3(256), smem2, st, a);

@@ -9,37 +9,11 @@
 // LDS-DMA writes lane-linear (wave base + 16 B x lane), so bank spreading is done on the SOURCE address: a 16-byte chunk c
 // of row r is fetched by the lane whose linear slot is c ^ f(r), and the fragment reads apply the same involution.
 #include "gemm_desc.h"
-#include <type_traits>
+#include "lds_dma.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) short rs16x4;
 typedef __attribute__((address_space(3))) rs16x4 lds_rs16x4;
-typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_void;
-
-// The LDS-DMA is issued from inline asm on purpose: hipcc then keeps no book on it and inserts no vmcnt(0) ahead of the
-// fragment reads (it would, conservatively, for the builtin); completion is counted by hand below.  M0 = wave-uniform LDS
-// byte address of the 1 KiB piece; lane l lands at M0 + 16 l.
-__device__ __forceinline__ void glds16(const uint16_t* src, uint16_t* lds_wave_base) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void*)lds_wave_base);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-// 4-byte variant: lane l lands at M0 + 4 l (used for the bias row of the projection kernel)
-__device__ __forceinline__ void glds4(const float* src, float* lds_wave_base) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void*)lds_wave_base);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-__device__ __attribute__((aligned(16))) float ring_zero_f32[4];          // source of absent / out-of-range bias entries
-// retire all but the youngest N LDS-DMA of this wave, then meet the other waves: after it every wave's pieces of the
-// oldest unit have landed and every wave has finished reading the unit before it
-template <int N>
-__device__ __forceinline__ void ring_sync() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 // ------------------------------------------------------------------------------------------------ TN (weight gradient)
 // dW[n][k] = sum_m G[m][n] X[m][k] for one 128 x 128 tile over the rows of one split.  Unit = 32 rows: G [32][128] then
@@ -279,7 +253,7 @@ __global__ void __launch_bounds__(128 * WM) linear_ring_bf16_kernel(const IGemmA
   // round trip in front of the first asynchronous issue of every launch (~1 us of a 6 us fixed cost).
   for (int p = wave; p < BN / 64; p += NW) {
     const int n = n_blk + p * 64 + lane;
-    const float* src = ring_zero_f32;
+    const float* src = reinterpret_cast<const float*>(ltu_zero_line);      // absent / out-of-range bias entries
     if (n < g.N) {
       const int seg = n / nper;
       const float* bp = seg == 0 ? g.bias[0] : (seg == 1 ? g.bias[1] : g.bias[2]);
@@ -434,8 +408,7 @@ static int launch_lin_ring_e(const IGemmArgs& g, hipStream_t st) {
   const int smem_bytes = BN * g.K * 2 + R * 16384 + BN * 4;
   static LtuDevOnce attr_once;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_ring_bf16_kernel<WM, TNW, R, GELU>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    ltu_dyn_lds(&linear_ring_bf16_kernel<WM, TNW, R, GELU>, 160 * 1024);
   }
   hipLaunchKernelGGL((linear_ring_bf16_kernel<WM, TNW, R, GELU>), dim3(P, nt), dim3(128 * WM), smem_bytes, st, g, tiles_m);
   return ltu_check_launch();
@@ -536,8 +509,7 @@ int launch_tn_ring_bf16(WGradArgs& wa, hipStream_t st, int* nsplit_out) {
   constexpr int smem_bytes = TN_RING * 2 * 32 * 128 * 2;
   static LtuDevOnce attr_once;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_ring_bf16_kernel<TN_RING>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              smem_bytes);
+    ltu_dyn_lds(&wgrad_ring_bf16_kernel<TN_RING>, smem_bytes);
   }
   hipLaunchKernelGGL((wgrad_ring_bf16_kernel<TN_RING>), dim3(t.nk, t.nn, t.nsplit), dim3(256), smem_bytes, st, wa);
   int rc = ltu_check_launch();
@@ -723,8 +695,7 @@ int launch_tn_ring_group_bf16(const ltu_wgrad_job* jobs, int njobs, int blocks, 
   constexpr int smem_bytes = TN_RING * 2 * 32 * 128 * 2;
   static LtuDevOnce attr_once;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_group_ring_bf16_kernel<TN_RING>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              smem_bytes);
+    ltu_dyn_lds(&wgrad_group_ring_bf16_kernel<TN_RING>, smem_bytes);
   }
   nblocks = ga.nsplit >= 8 ? ((ga.nsplit + 7) / 8) * ga.tiles * 8 : ga.nsplit * ga.tiles;
   hipLaunchKernelGGL((wgrad_group_ring_bf16_kernel<TN_RING>), dim3(nblocks), dim3(256), smem_bytes, st, ga);
@@ -789,11 +760,6 @@ struct WFatView {     // one job as scalars (built field by field from the kerne
   float* outb0; float* outb1; float* outb2;
   int ldg, lda, N, K, nper, nsplit, direct;
 };
-// retire all but the youngest N LDS-DMA of this wave AND every LDS read it has issued, then meet the other waves
-template <int N>
-__device__ __forceinline__ void ring_sync_all() {
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 // column sums of a bf16 pair, accumulated in fp32: c += lo + hi (v_dot2c_f32_bf16 against (1, 1); the builtin does not select in
 // hipcc 7.2).  Not volatile: the scheduler places it in the shadow of the MFMAs.
 __device__ __forceinline__ void bf16_pair_sum(float& c, uint32_t w) {
@@ -1153,10 +1119,10 @@ int launch_wgrad_fat_group_bf16(const ltu_wgrad_job* jobs, int njobs, int blocks
   fo.njobs = nf;
   static LtuDevOnce attr_once;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_fat_group_bf16_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, WFAT_RING_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_fat_group_bf16_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, WFAT_RING_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_fat_group_bf16_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, WFAT_RING_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_fat_group_bf16_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, WFAT_RING_BYTES);
+    ltu_dyn_lds(&wgrad_fat_group_bf16_kernel<0>, WFAT_RING_BYTES);
+    ltu_dyn_lds(&wgrad_fat_group_bf16_kernel<1>, WFAT_RING_BYTES);
+    ltu_dyn_lds(&wgrad_fat_group_bf16_kernel<2>, WFAT_RING_BYTES);
+    ltu_dyn_lds(&wgrad_fat_group_bf16_kernel<3>, WFAT_RING_BYTES);
   }
   const int dbg = ltu_knob("LTU_WFAT_DBG", 0);     // ablation: 1 = no fragment reads / MFMAs, 2 = no LDS-DMA (results invalid)
   if (dbg == 1) hipLaunchKernelGGL(wgrad_fat_group_bf16_kernel<1>, dim3(grid), dim3(256), WFAT_RING_BYTES, st, fa);

@@ -42,7 +42,6 @@ __device__ __forceinline__ float xhalf_max(float v) { return xhalf_combine<LtuMa
 // bf16 storage: the 32x32 products run on v_mfma_f32_32x32x16_bf16 (2 instructions of 8 passes per product instead of 16
 // fp32 instructions of 16 passes, which had made the per-token kernels matrix-core-bound).  Lane (li, lh) supplies the 8
 // k-elements 16*lh + 8*u + e of k-step u, i.e. elements 8u..8u+7 of the same per-lane arrays the fp32 path walks with s.
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 __device__ __forceinline__ bf16x8 pack8(const float* v) {
   bf16x8 r;
 #pragma unroll

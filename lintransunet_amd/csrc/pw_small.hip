@@ -11,8 +11,6 @@
 // 40.4 -> 20.8, 16 -> 32: 43.1 -> 25.6; 262 144 rows 32 -> 32: 12.3 -> 7.5, 64 -> 32: 15.0 -> 10.1, 32 -> 64: 16.5 -> 11.3.
 #include "gemm_desc.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
 struct PwArgs {
   const uint16_t* x;
   const uint16_t* w;      // [N][K] bf16

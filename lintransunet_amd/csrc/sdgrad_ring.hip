@@ -10,10 +10,7 @@
 // ds_read_b128 with immediate offsets + 4 MFMAs; every address that depends on the lane is computed once in the prologue.
 // Operands: g [B][Ho][Wo][Do][Co] (bf16), wd [CiP][27][Co] (weight-prep kind 3), dx [B][Hl][Wl][Dl][N] with N = Ci.
 #include "gemm_desc.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
-__device__ __attribute__((aligned(64))) uint32_t ltu_zero_sd[512];      // 2 KB of zeros: source of out-of-volume halo rows and padding tiles (any chunk)
+#include "lds_dma.h"
 
 struct SdEnt { int c, dh, dw, dd, tap; };
 // entry e (0..26) of the class table, classes in (ph, pw, pd) order, entries in (h, w, d) nesting - the order ltu_conv3d_dgrad used
@@ -42,24 +39,6 @@ __host__ __device__ constexpr SdEnt sd_entry(int e) {
   return SdEnt{0, 0, 0, 0, -1};
 }
 
-__device__ __forceinline__ void sg_glds16(const uint16_t* src, uint32_t lds_byte_addr) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void sg_sync() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void sg_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    sg_static_for<I + 1, N>(f);
-  }
-}
-
 struct SdgradArgs {
   const uint16_t* g;
   const uint16_t* w;
@@ -82,17 +61,13 @@ __global__ void __launch_bounds__(256) sdgrad_ring_bf16_kernel(const SdgradArgs 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int nbh = (a.Ho + 3) / 4, nbw = (a.Wo + 7) / 8, nbd = (a.Do + 7) / 8;
-  int bid = blockIdx.x;
-  const int bd = bid % nbd; bid /= nbd;
-  const int bw = bid % nbw; bid /= nbw;
-  const int bh = bid % nbh;
-  const int b = bid / nbh;
-  const int h0 = bh * 4, w0 = bw * 8, d0 = bd * 8;
+  const Brick bk = split_brick(blockIdx.x, nbh, nbw, nbd);
+  const int b = bk.b, h0 = bk.bh * 4, w0 = bk.bw * 8, d0 = bk.bd * 8;
   const int n_blk = blockIdx.y * 32;
   const int nchunk = a.Co / 32;
   const int total = nchunk * 3;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
-  const uint16_t* zsrc = reinterpret_cast<const uint16_t*>(ltu_zero_sd) + (lane & 3) * 8;
+  const uint32_t lds0 = lds_addr(smem);
+  const uint16_t* zsrc = reinterpret_cast<const uint16_t*>(ltu_zero_line) + (lane & 3) * 8;
 
   // ---- LDS-DMA sources: per-lane constants (piece = 16 rows x 64 B; lane -> row lane >> 2, 16-byte slot lane & 3) ---------------
   const int prow = lane >> 2;
@@ -123,13 +98,13 @@ __global__ void __launch_bounds__(256) sdgrad_ring_bf16_kernel(const SdgradArgs 
   auto issue_halo = [&](int chunk) {
     const uint32_t hb = lds0 + (chunk & 1) * HBUF + wave * HP * 1024;
 #pragma unroll
-    for (int s = 0; s < HP; ++s) sg_glds16(hsrc[s] + chunk * 32, hb + s * 1024);
+    for (int s = 0; s < HP; ++s) glds16(hsrc[s] + chunk * 32, hb + s * 1024);
   };
   auto issue_w = [&](int chunk, auto ST) {
     constexpr int st = decltype(ST)::value;
     const uint32_t wb = lds0 + RING + st * WSTAGE + wave * 5 * 1024;
 #pragma unroll
-    for (int s = 0; s < 5; ++s) sg_glds16(wsrc[st][s] + chunk * 32, wb + s * 1024);
+    for (int s = 0; s < 5; ++s) glds16(wsrc[st][s] + chunk * 32, wb + s * 1024);
   };
 
   // ---- fragment read addresses: wave w = h-plane w; tile i = w positions 4i..4i+3; lane li -> (w 4i + (li >> 3), d li & 7) ----------
@@ -167,15 +142,15 @@ __global__ void __launch_bounds__(256) sdgrad_ring_bf16_kernel(const SdgradArgs 
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int dw = 0; dw < 2; ++dw) bA[i][ks][dw] = baseA[i][ks][dw] + hoff;
-    sg_static_for<0, 3>([&](auto ST) {
+    static_for<0, 3>([&](auto ST) {
       constexpr int st = decltype(ST)::value;
       const int g = chunk * 3 + st;
       // LDS-DMA issued after W(g): W(g+1) (5 pieces) and, at stages 1 and 2, the halo of the next chunk (HP pieces; it is issued in
       // stage 0 behind W(g+2))
       if (g + 1 < total) {
-        if (st != 0 && chunk + 1 < nchunk) sg_sync<5 + HP>(); else sg_sync<5>();
+        if (st != 0 && chunk + 1 < nchunk) ring_sync<5 + HP>(); else ring_sync<5>();
       } else {
-        sg_sync<0>();
+        ring_sync<0>();
       }
       if (g + 2 < total) {
         if constexpr (st == 0) issue_w(chunk, std::integral_constant<int, 2>{});
@@ -204,7 +179,7 @@ __global__ void __launch_bounds__(256) sdgrad_ring_bf16_kernel(const SdgradArgs 
       };
       bf16x8 afA[2][2], wfA[2], afB[2][2], wfB[2];
       load_frags(std::integral_constant<int, 0>{}, afA, wfA);
-      sg_static_for<0, (NE + 1) / 2>([&](auto TP) {
+      static_for<0, (NE + 1) / 2>([&](auto TP) {
         constexpr int t = decltype(TP)::value * 2;
         if constexpr (t + 1 < NE) load_frags(std::integral_constant<int, t + 1>{}, afB, wfB);
         __builtin_amdgcn_sched_barrier(0);
@@ -274,7 +249,7 @@ static int launch_sdgrad(const SdgradArgs& a0, hipStream_t st) {
   constexpr int smem_bytes = opnd > epi ? opnd : epi;          // the epilogue stages every class tile over the (dead) operand buffers
   static LtuDevOnce attr_once;
   if (attr_once.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sdgrad_ring_bf16_kernel<SD>), hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
+    ltu_dyn_lds(&sdgrad_ring_bf16_kernel<SD>, smem_bytes);
   const long long rb = (long long)a.B * ((a.Ho + 3) / 4) * ((a.Wo + 7) / 8) * ((a.Do + 7) / 8);
   if (rb >= (1LL << 31)) return 1;
   hipLaunchKernelGGL(sdgrad_ring_bf16_kernel<SD>, dim3((unsigned)rb, (a.N + 31) / 32), dim3(256), smem_bytes, st, a);

@@ -17,8 +17,6 @@
 // paths agree to bf16 rounding noise of the LayerNorm sums.
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 tl_bf16x8;
-
 #define TL_ROWS 32
 #ifndef TL_QDEPTH
 #define TL_QDEPTH 8
@@ -66,7 +64,7 @@ struct TailArgs {
   int dbg;                // ablation (tools/bench_tail.py): 2 = no GELU / dropout arithmetic, 4 = u and h are not stored
 };
 
-__device__ __forceinline__ tl_bf16x8 as_bf16x8(uint4 v) { return __builtin_bit_cast(tl_bf16x8, v); }
+__device__ __forceinline__ bf16x8 as_bf16x8(uint4 v) { return __builtin_bit_cast(bf16x8, v); }
 
 // One column tile of a GEMM stage: acc[..] = sum_k W[ct*32 + ..][k] X[..][k] (transposed product, see above).
 // X: LDS, bf16, row stride LDX elements; W: fragment order in global memory (served by L2: every workgroup streams the same
@@ -274,10 +272,10 @@ __global__ void __launch_bounds__(D >= 256 ? 512 : 256, OCC) tail_fwd_kernel(con
     constexpr int H = D / 32;
     const long long bh = (row0 / ta.ntok) * H + wave;
     const float* cx = ta.ctx + bh * 1024;
-    tl_bf16x8 ca[2];
+    bf16x8 ca[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      tl_bf16x8 t;
+      bf16x8 t;
 #pragma unroll
       for (int e = 0; e < 8; ++e) t[e] = (__bf16)cx[(16 * lh + 8 * u + e) * 32 + li];
       ca[u] = t;
@@ -299,7 +297,7 @@ __global__ void __launch_bounds__(D >= 256 ? 512 : 256, OCC) tail_fwd_kernel(con
     sum = xhalf_combine<LtuAdd>(sum);
     const float inv = 0.17677669529663688110f / sum;      // 1 / (sqrt(32) * row sum)
     if (lh == 0) *reinterpret_cast<float2*>(QS + (li * H + wave) * 2) = make_float2(mx, inv);
-    tl_bf16x8 p0, p1;
+    bf16x8 p0, p1;
 #pragma unroll
     for (int k = 0; k < 8; ++k) { p0[k] = (__bf16)(a[k] * inv); p1[k] = (__bf16)(a[8 + k] * inv); }
     f32x16 oa;
@@ -711,7 +709,7 @@ extern "C" int ltu_layer_tail_bwd(const void* dy, const void* dy2, const void* z
   const size_t lds = (size_t)TL_ROWS * (2 * (d + 8) + (2 * d + 8)) * sizeof(uint16_t);
   auto launch = [&](auto kern, unsigned threads) {
     static LtuDevOnce once;                // one latch per kernel instantiation (the lambda body is instantiated per `kern` type)
-    if (once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (once.first()) ltu_dyn_lds(kern, 160 * 1024);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, (hipStream_t)s, ta);
   };
   if (d == 256) {
@@ -762,7 +760,7 @@ extern "C" int ltu_layer_tail_fwd(const void* a, const void* x, const void* wo, 
                      (qkv != nullptr ? (size_t)TL_ROWS * (d / 32) * 2 * sizeof(float) : 0);
   auto launch = [&](auto kern, unsigned threads) {
     static LtuDevOnce once;                // one latch per kernel instantiation
-    if (once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (once.first()) ltu_dyn_lds(kern, 160 * 1024);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, (hipStream_t)s, ta);
   };
   if (d == 256) {

@@ -16,8 +16,7 @@
 //     per-thread voxel offsets computed once: 2 barriers instead of 16.
 // Weights: wsub_f [8 classes][Co][8 slots][Ci] (weight-prep kind 5).  Output y [B][2H][2W][2D][Co].
 #include "gemm_desc.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+#include "lds_dma.h"
 
 #define UR_HROWS 640                      // 6 x 10 x 10 halo voxels padded to 40 LDS-DMA pieces of 16 rows
 #define UR_HBUF (UR_HROWS * 64)           // bytes per halo buffer (64-byte rows: 32 channels)
@@ -25,27 +24,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 #define UR_WSTAGE 16384                   // 8 slots x 32 n x 64 bytes
 #define UR_SMEM (UR_RING + 4 * UR_WSTAGE)
 
-__device__ __attribute__((aligned(64))) uint32_t ltu_zero_wide[512];      // 2 KB of zeros: source of out-of-volume halo rows (any chunk)
-
 __host__ __device__ constexpr int ur_off(int p, int a) { return p == 0 ? (a == 0 ? -1 : 0) : (a == 0 ? 0 : 1); }
-
-__device__ __forceinline__ void ur_glds16(const uint16_t* src, uint32_t lds_byte_addr) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ur_sync() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void ur_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    ur_static_for<I + 1, N>(f);
-  }
-}
 
 struct UpRingArgs {
   const uint16_t* x;
@@ -60,16 +39,12 @@ __global__ void __launch_bounds__(256) upconv_ring_bf16_kernel(const UpRingArgs 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int nbh = (a.H + 3) / 4, nbw = (a.W + 7) / 8, nbd = (a.D + 7) / 8;
-  int bid = blockIdx.x;
-  const int bd = bid % nbd; bid /= nbd;
-  const int bw = bid % nbw; bid /= nbw;
-  const int bh = bid % nbh;
-  const int b = bid / nbh;
-  const int h0 = bh * 4, w0 = bw * 8, d0 = bd * 8;
+  const Brick bk = split_brick(blockIdx.x, nbh, nbw, nbd);
+  const int b = bk.b, h0 = bk.bh * 4, w0 = bk.bw * 8, d0 = bk.bd * 8;
   const int n_blk = blockIdx.y * 32;
   const int nchunk = a.Ci / 32;
   const int total = nchunk * 8;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
+  const uint32_t lds0 = lds_addr(smem);
 
   // ---- per-lane constants of the LDS-DMA pieces (piece = 16 rows x 64 B; lane -> row lane >> 2, 16-byte slot lane & 3) ----------
   const int prow = lane >> 2;
@@ -82,7 +57,7 @@ __global__ void __launch_bounds__(256) upconv_ring_bf16_kernel(const UpRingArgs 
     const int lc = (lane & 3) ^ (hw & 3);                    // slot = channel quarter ^ (halo w & 3): conflict-free fragment reads
     const bool in = hv < 600 && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W && (unsigned)d < (unsigned)a.D;
     hsrc[s] = in ? a.x + ((((long long)b * a.H + h) * a.W + w) * a.D + d) * a.Ci + lc * 8
-                 : reinterpret_cast<const uint16_t*>(ltu_zero_wide) + (lane & 3) * 8;
+                 : reinterpret_cast<const uint16_t*>(ltu_zero_line) + (lane & 3) * 8;
   }
   int woff[4];                            // weight piece s of a stage: rows (wave * 4 + s) * 16 + prow = slot t * 32 + n
 #pragma unroll
@@ -97,13 +72,13 @@ __global__ void __launch_bounds__(256) upconv_ring_bf16_kernel(const UpRingArgs 
   auto issue_halo = [&](int chunk) {
     const uint32_t hb = lds0 + (chunk & 1) * UR_HBUF + wave * 10 * 1024;
 #pragma unroll
-    for (int s = 0; s < 10; ++s) ur_glds16(hsrc[s] + chunk * 32, hb + s * 1024);
+    for (int s = 0; s < 10; ++s) glds16(hsrc[s] + chunk * 32, hb + s * 1024);
   };
   auto issue_w = [&](int g) {             // stage g = (chunk g >> 3, class g & 7)
     const uint16_t* wsrc = a.w + (long long)(g & 7) * wcls + (g >> 3) * 32;
     const uint32_t wb = lds0 + UR_RING + (g & 3) * UR_WSTAGE + wave * 4 * 1024;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) ur_glds16(wsrc + woff[s], wb + s * 1024);
+    for (int s = 0; s < 4; ++s) glds16(wsrc + woff[s], wb + s * 1024);
   };
 
   // ---- fragment read addresses ---------------------------------------------------------------------------------------------------
@@ -142,16 +117,16 @@ __global__ void __launch_bounds__(256) upconv_ring_bf16_kernel(const UpRingArgs 
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int dwi = 0; dwi < 3; ++dwi) bA[i][ks][dwi] = baseA[i][ks][dwi] + hoff;
-    ur_static_for<0, 8>([&](auto ST) {
+    static_for<0, 8>([&](auto ST) {
       constexpr int c = decltype(ST)::value;           // stage = class c; ring slot c & 3 (8 stages per chunk = 2 x the ring depth)
       const int g = chunk * 8 + c;
       if (g + 2 < total) {
         // LDS-DMA pieces issued after W(g): W(g+1), W(g+2) (4 each) and the halo of the next chunk (10) when it was issued
         // at stages 0 (iterations g-3 .. g-1 with class 0)
         constexpr bool near0 = c >= 1 && c <= 3;
-        if (near0 && chunk + 1 < nchunk) ur_sync<18>(); else ur_sync<8>();
+        if (near0 && chunk + 1 < nchunk) ring_sync<18>(); else ring_sync<8>();
       } else {
-        ur_sync<0>();
+        ring_sync<0>();
       }
       if (g + 3 < total) issue_w(g + 3);
       if (c == 0 && chunk + 1 < nchunk) issue_halo(chunk + 1);
@@ -177,7 +152,7 @@ __global__ void __launch_bounds__(256) upconv_ring_bf16_kernel(const UpRingArgs 
       };
       bf16x8 afA[2][2], wfA[2], afB[2][2], wfB[2];
       load_frags(std::integral_constant<int, 0>{}, afA, wfA);
-      ur_static_for<0, 4>([&](auto TP) {
+      static_for<0, 4>([&](auto TP) {
         constexpr int t = decltype(TP)::value * 2;
         load_frags(std::integral_constant<int, t + 1>{}, afB, wfB);
         __builtin_amdgcn_sched_barrier(0);
@@ -247,7 +222,7 @@ int launch_upconv_ring_bf16(const void* x, const void* wsub_f, const float* bias
   if (rb >= (1LL << 31) || (long long)8 * Co * 8 * Ci >= (1LL << 31)) return 1;
   static LtuDevOnce attr_once;
   if (attr_once.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&upconv_ring_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, UR_SMEM);
+    ltu_dyn_lds(&upconv_ring_bf16_kernel, UR_SMEM);
   UpRingArgs a;
   a.x = (const uint16_t*)x; a.w = (const uint16_t*)wsub_f; a.bias = bias; a.y = (uint16_t*)y;
   a.B = B; a.H = H; a.W = W; a.D = D; a.Ci = Ci; a.Co = Co;

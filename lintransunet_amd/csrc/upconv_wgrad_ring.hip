@@ -9,8 +9,8 @@
 //     same banks at any row pitch that LDS-DMA can write): here the 16-byte parts of a row are stored with their 32-byte halves swapped
 //     on every other 8-row block (gradient) / every other w (halo) - the lanes fetch the swapped part, the readers address it.
 #include "gemm_desc.h"
+#include "lds_dma.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float uw_f32x4;
 typedef __attribute__((ext_vector_type(4))) short uw16x4;
 typedef __attribute__((address_space(3))) uw16x4 lds_uw16x4;
@@ -21,30 +21,11 @@ typedef __attribute__((address_space(3))) uw16x4 lds_uw16x4;
 #define UW_NB 3
 #define UW_PIECES 12                       // LDS-DMA pieces per wave and unit
 
-__device__ __attribute__((aligned(64))) uint32_t ltu_zero_uw[16];
-
-__device__ __forceinline__ void uw_glds16(const void* src, uint32_t lds_byte_addr) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
 typedef __attribute__((ext_vector_type(4))) int uw_i32x4;
 // in-place accumulation on AGPRs: the builtin lets the register allocator rename the accumulator per MFMA and copy 256 registers back
 // at the loop's back edge (993 v_accvgpr moves per 128 MFMAs in the first version of this kernel, 1 179 per 256 in the first generation)
 __device__ __forceinline__ void uw_mfma(uw_f32x4& c, const uw_i32x4& a, const uw_i32x4& b) {
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void uw_sfor(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    uw_sfor<I + 1, N>(f);
-  }
-}
-template <int N>
-__device__ __forceinline__ void uw_sync() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
 __global__ void __launch_bounds__(256, 1) upconv_wgrad_ring_bf16_kernel(const UpWgradArgs a) {
@@ -56,7 +37,7 @@ __global__ void __launch_bounds__(256, 1) upconv_wgrad_ring_bf16_kernel(const Up
   const int unit_lo = 2 * blockIdx.z * a.bricks_per_split;
   int unit_hi = unit_lo + 2 * a.bricks_per_split;
   if (unit_hi > 2 * a.bricks) unit_hi = 2 * a.bricks;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
+  const uint32_t lds0 = lds_addr(smem);
 
   // ---- LDS-DMA pieces of a unit: 48 of 1 KB (16 rows of 64 bytes); wave w issues pieces w, w + 4, ..: 15 halo pieces, 32 gradient pieces
   // (class c = 4 of them), one spare.  Lane -> (row = lane >> 2, 16-byte slot = lane & 3); the slot holds part (slot ^ swap) of the row
@@ -85,20 +66,16 @@ __global__ void __launch_bounds__(256, 1) upconv_wgrad_ring_bf16_kernel(const Up
   }
   const uint16_t* xsrc = reinterpret_cast<const uint16_t*>(a.x) + chunk * 32;
   const uint16_t* gsrc = reinterpret_cast<const uint16_t*>(a.grad) + n_blk;
-  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_uw) + slot * 16;
+  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_line) + slot * 16;
   // origin of a unit (wave-uniform, scalar registers) and the issue of ONE of this wave's 12 pieces: the pieces of unit i + 2 are spread
   // over the MFMA groups of unit i (their address arithmetic runs in the shadow of the matrix pipe instead of in front of it)
   struct UnitOrg { int hq, wq, dq; long long xvox0, gvox0; uint32_t bb; };
   auto unit_org = [&](int unit, int buf) {
     UnitOrg u;
-    int t = unit >> 1;
-    const int bd = t % nbd; t /= nbd;
-    const int bw = t % nbw; t /= nbw;
-    const int bh = t % nbh;
-    const int b = t / nbh;
-    u.hq = bh * 4 + (unit & 1) * 2, u.wq = bw * 4, u.dq = bd * 8;          // origin of the unit (coarse)
-    u.xvox0 = ((((long long)b * a.H + u.hq) * a.W + u.wq) * a.D + u.dq) * a.Ci;
-    u.gvox0 = ((((long long)b * 2 * a.H + 2 * u.hq) * 2 * a.W + 2 * u.wq) * 2 * a.D + 2 * u.dq) * a.Co;
+    const Brick bk = split_brick(unit >> 1, nbh, nbw, nbd);
+    u.hq = bk.bh * 4 + (unit & 1) * 2, u.wq = bk.bw * 4, u.dq = bk.bd * 8;          // origin of the unit (coarse)
+    u.xvox0 = ((((long long)bk.b * a.H + u.hq) * a.W + u.wq) * a.D + u.dq) * a.Ci;
+    u.gvox0 = ((((long long)bk.b * 2 * a.H + 2 * u.hq) * 2 * a.W + 2 * u.wq) * 2 * a.D + 2 * u.dq) * a.Co;
     u.bb = lds0 + buf * (UW_BUF * 2);
     return u;
   };
@@ -109,11 +86,11 @@ __global__ void __launch_bounds__(256, 1) upconv_wgrad_ring_bf16_kernel(const Up
     const int h = u.hq - 1 + (pk[s] >> 16), w = u.wq - 1 + ((pk[s] >> 8) & 255), d = u.dq - 1 + (pk[s] & 255);
     const bool in = pk[s] >= 0 && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W && (unsigned)d < (unsigned)a.D;
     const char* ptr = reinterpret_cast<const char*>((isx ? xsrc : gsrc) + (isx ? u.xvox0 : u.gvox0) + rel[s]);
-    uw_glds16(in ? ptr : zsrc, u.bb + p * 1024);
+    glds16(in ? ptr : zsrc, u.bb + p * 1024);
   };
   auto issue_unit = [&](int unit, int buf) {
     const UnitOrg u = unit_org(unit, buf);
-    uw_sfor<0, UW_PIECES>([&](auto S) { issue_piece(u, S); });
+    static_for<0, UW_PIECES>([&](auto S) { issue_piece(u, S); });
   };
 
   uw_f32x4 acc[64];
@@ -136,12 +113,12 @@ __global__ void __launch_bounds__(256, 1) upconv_wgrad_ring_bf16_kernel(const Up
   if (nu > 1) issue_unit(unit_lo + 1, 1);
   int buf = 0;
   for (int i = 0; i < nu; ++i) {
-    if (i + 1 < nu) uw_sync<UW_PIECES>(); else uw_sync<0>();
+    if (i + 1 < nu) ring_sync<UW_PIECES>(); else ring_sync<0>();
     const bool more = i + 2 < nu;
     const UnitOrg nxt = unit_org(more ? unit_lo + i + 2 : unit_lo, buf >= 1 ? buf - 1 : UW_NB - 1);
     const uint16_t* base = smem + buf * UW_BUF;
     buf = buf + 1 == UW_NB ? 0 : buf + 1;
-    uw_sfor<0, 2>([&](auto KS) {
+    static_for<0, 2>([&](auto KS) {
       constexpr int ks = decltype(KS)::value;
       uw_i32x4 ga[8];
 #pragma unroll
@@ -172,7 +149,7 @@ __global__ void __launch_bounds__(256, 1) upconv_wgrad_ring_bf16_kernel(const Up
       };
       load_x(std::integral_constant<int, 0>{});
       load_x(std::integral_constant<int, 1>{});
-      uw_sfor<0, 27>([&](auto O) {
+      static_for<0, 27>([&](auto O) {
         constexpr int o = decltype(O)::value, oh = o / 9 - 1, ow = (o / 3) % 3 - 1, od = o % 3 - 1;
         if constexpr (o + 2 < 27) load_x(std::integral_constant<int, o + 2>{});
         __builtin_amdgcn_sched_barrier(0);
@@ -237,7 +214,7 @@ int launch_upconv_wgrad_ring_bf16(const UpWgradArgs& a, int nchunk, int ntile, i
   constexpr int smem_bytes = UW_NB * UW_BUF * 2;
   static LtuDevOnce attr_once;
   if (attr_once.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&upconv_wgrad_ring_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
+    ltu_dyn_lds(&upconv_wgrad_ring_bf16_kernel, smem_bytes);
   hipLaunchKernelGGL(upconv_wgrad_ring_bf16_kernel, dim3(nchunk, ntile, nsplit), dim3(256), smem_bytes, st, a);
   return ltu_check_launch();
 }

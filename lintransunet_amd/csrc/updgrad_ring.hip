@@ -9,34 +9,13 @@
 // immediate offset; LDS-DMA per MFMA is the same as in the forward kernel (0.18 pieces).
 // Operands: g [B][2H][2W][2D][Co], wsub_d [Ci][64][Co] (weight-prep kind 6), dx [B][H][W][D][Ci]; Ci % 128 == 0, Co % 32 == 0.
 #include "gemm_desc.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+#include "lds_dma.h"
 
 #define UG_HP 7                           // LDS-DMA pieces per wave and halo: 5 x 9 x 9 = 405 rows -> 26 pieces -> 28 (padding rows: zero line)
 #define UG_HBUF (4 * UG_HP * 1024)
 #define UG_RING (2 * UG_HBUF)
 #define UG_WSTAGE 16384                   // 2 slots x 128 n x 64 B
 #define UG_SMEM (UG_RING + 4 * UG_WSTAGE)
-
-__device__ __attribute__((aligned(64))) uint32_t ltu_zero_ug[512];      // 2 KB of zeros (any chunk offset)
-
-__device__ __forceinline__ void ug_glds16(const void* src, uint32_t lds_byte_addr) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ug_sync() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void ug_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    ug_static_for<I + 1, N>(f);
-  }
-}
 
 struct UpDgradArgs {
   const uint16_t* g;
@@ -52,18 +31,14 @@ __global__ void __launch_bounds__(256) updgrad_ring_bf16_kernel(const UpDgradArg
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int nbh = (a.H + 3) / 4, nbw = (a.W + 7) / 8, nbd = (a.D + 7) / 8;
-  int bid = blockIdx.x;
-  const int bd = bid % nbd; bid /= nbd;
-  const int bw = bid % nbw; bid /= nbw;
-  const int bh = bid % nbh;
-  const int b = bid / nbh;
-  const int h0 = bh * 4, w0 = bw * 8, d0 = bd * 8;
+  const Brick bk = split_brick(blockIdx.x, nbh, nbw, nbd);
+  const int b = bk.b, h0 = bk.bh * 4, w0 = bk.bw * 8, d0 = bk.bd * 8;
   const int n_blk = blockIdx.y * BN;
   const int nchunk = a.Co / 32;
   const int total = nchunk * 32;            // stages: (chunk, class p, slot pair q)
   const int Hf = 2 * a.H, Wf = 2 * a.W, Df = 2 * a.D;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
-  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_ug) + (lane & 3) * 16;
+  const uint32_t lds0 = lds_addr(smem);
+  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_line) + (lane & 3) * 16;
   const int prow = lane >> 2;
 
   // ---- halo pieces: row hv -> (hh, hw, hd) of the 5x9x9 halo; class p reads fine voxel 2 (q0 + h) - p ------------------------------
@@ -87,7 +62,7 @@ __global__ void __launch_bounds__(256) updgrad_ring_bf16_kernel(const UpDgradArg
       const int fh = (hfc[s] & 1023) - ph, fw = ((hfc[s] >> 10) & 1023) - pw, fd = (hfc[s] >> 20) - pd;
       const bool in = hoffs[s] >= 0 && (unsigned)fh < (unsigned)Hf && (unsigned)fw < (unsigned)Wf && (unsigned)fd < (unsigned)Df;
       const char* src = in ? reinterpret_cast<const char*>(a.g + (hoffs[s] - delta)) : zsrc;
-      ug_glds16(src, hb + s * 1024);
+      glds16(src, hb + s * 1024);
     }
   };
   // ---- weight pieces of a stage: 16 pieces = rows [slot 2][n 128] ------------------------------------------------------------------
@@ -103,7 +78,7 @@ __global__ void __launch_bounds__(256) updgrad_ring_bf16_kernel(const UpDgradArg
     const uint16_t* wsrc = a.w + e0 * a.Co + chunk * 32;
     const uint32_t wb = lds0 + UG_RING + (g & 3) * UG_WSTAGE + wave * TN * 1024;
 #pragma unroll
-    for (int s = 0; s < TN; ++s) ug_glds16(wsrc + woff[s], wb + s * 1024);
+    for (int s = 0; s < TN; ++s) glds16(wsrc + woff[s], wb + s * 1024);
   };
 
   // ---- fragment read addresses: wave w = h-plane w; tile i = w positions 4i..4i+3; lane li -> (w 4i + (li >> 3), d li & 7) ----------
@@ -132,15 +107,15 @@ __global__ void __launch_bounds__(256) updgrad_ring_bf16_kernel(const UpDgradArg
   issue_halo(0, std::integral_constant<int, 0>{});
   for (int g = 0; g < 3 && g < total; ++g) issue_w(g);
   for (int chunk = 0; chunk < nchunk; ++chunk) {
-    ug_static_for<0, 32>([&](auto ST) {
+    static_for<0, 32>([&](auto ST) {
       constexpr int st = decltype(ST)::value, p = st >> 2, q = st & 3;
       const int g = chunk * 32 + st;
       const bool halo_next = p < 7 || chunk + 1 < nchunk;        // a halo is requested during this class (for the next class)
       if (g + 2 < total) {
         // LDS-DMA issued after W(g): W(g+1), W(g+2) (TN pieces each) and - at q = 1, 2, 3 - the next class's halo (7 pieces)
-        if (q != 0 && halo_next) ug_sync<2 * TN + UG_HP>(); else ug_sync<2 * TN>();
+        if (q != 0 && halo_next) ring_sync<2 * TN + UG_HP>(); else ring_sync<2 * TN>();
       } else {
-        ug_sync<0>();
+        ring_sync<0>();
       }
       if (g + 3 < total) issue_w(g + 3);
       if constexpr (q == 0) {
@@ -216,8 +191,8 @@ int launch_updgrad_ring_bf16(const void* grad, const void* wsub_d, void* dx, int
   if (rb >= (1LL << 31) || (long long)Ci * 64 * Co >= (1LL << 31)) return 1;
   static LtuDevOnce attr_once;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&updgrad_ring_bf16_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, UG_SMEM);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&updgrad_ring_bf16_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, UG_SMEM);
+    ltu_dyn_lds(&updgrad_ring_bf16_kernel<4>, UG_SMEM);
+    ltu_dyn_lds(&updgrad_ring_bf16_kernel<2>, UG_SMEM);
   }
   UpDgradArgs a;
   a.g = (const uint16_t*)grad; a.w = (const uint16_t*)wsub_d; a.dx = (uint16_t*)dx;

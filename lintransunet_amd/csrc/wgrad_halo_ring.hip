@@ -8,8 +8,8 @@
 //     launches read them back - most of those kernels' time was their epilogue.  Half to a quarter of the splits here.
 // Partial layout, bias partials and the fold (wgrad_reduce_kernel) are the first generation's.
 #include "gemm_desc.h"
+#include "lds_dma.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) short wr16x4;
 typedef __attribute__((address_space(3))) wr16x4 lds_wr16x4;
 
@@ -17,21 +17,6 @@ typedef __attribute__((address_space(3))) wr16x4 lds_wr16x4;
 #define WR_GOFF (WR_HROWS * 32)           // element offset of the G tile [128][32] inside a brick buffer
 #define WR_BUF (16384)                    // elements per brick buffer: halo 11 776 + G 4 096 + one spare piece (512) = 32 KB
 #define WR_NB 3
-
-__device__ __attribute__((aligned(64))) uint32_t ltu_zero_wr[16];     // source of out-of-volume / padding rows (16 bytes per lane)
-
-__device__ __forceinline__ void wr_glds16(const void* src, uint32_t lds_byte_addr) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-// vmcnt: this wave's pieces of the next brick have landed; lgkmcnt(0): its LDS reads of the buffer about to be refilled have returned
-// (as ring_sync_all in gemm_ring.hip) - the barrier then hands that buffer to the LDS-DMA of every wave
-template <int N>
-__device__ __forceinline__ void wr_sync() {
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 __global__ void __launch_bounds__(256, 1) conv3_wgrad_halo_ring_bf16_kernel(const WHaloArgs a) {
   constexpr int NA = 7, LD = 32, HW_ = 6, HD_ = 10;
@@ -43,7 +28,7 @@ __global__ void __launch_bounds__(256, 1) conv3_wgrad_halo_ring_bf16_kernel(cons
   const int brick_lo = blockIdx.z * a.bricks_per_split;
   int brick_hi = brick_lo + a.bricks_per_split;
   if (brick_hi > a.bricks) brick_hi = a.bricks;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
+  const uint32_t lds0 = lds_addr(smem);
 
   // ---- LDS-DMA pieces of a brick: 32 of 1 KB (16 rows of 64 bytes); wave w issues pieces w, w + 4, ...: 23 halo pieces, 8 G pieces,
   // one spare (so that every wave has 8 in flight per brick: one counted wait for all).  Lane -> (row = lane >> 2, 16-byte part = lane & 3)
@@ -57,7 +42,7 @@ __global__ void __launch_bounds__(256, 1) conv3_wgrad_halo_ring_bf16_kernel(cons
   const uint16_t* gbase_p = g_from1 ? reinterpret_cast<const uint16_t*>(a.grad1) + (ng - a.gn0) : reinterpret_cast<const uint16_t*>(a.grad) + ng;
   const long long gld = g_from1 ? a.ldg1 : a.ldg;
   const bool g_ok = ng < a.N, x_ok = cx < a.C;
-  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_wr) + part * 16;
+  const char* zsrc = reinterpret_cast<const char*>(ltu_zero_line) + part * 16;
   // brick-independent part of a lane's 8 fetches: voxel offset relative to the brick origin and the (h, w, d) step for the bounds test
   int rel[8], pk[8];
 #pragma unroll
@@ -77,13 +62,9 @@ __global__ void __launch_bounds__(256, 1) conv3_wgrad_halo_ring_bf16_kernel(cons
     pk[s] = ok ? (eh << 16 | ew << 8 | ed) : -1;
   }
   auto issue_brick = [&](int brick, int buf) {
-    int t = brick;
-    const int bd = t % nbd; t /= nbd;
-    const int bw = t % nbw; t /= nbw;
-    const int bh = t % nbh;
-    const int b = t / nbh;
-    const int h0 = bh * 4 - 1, w0 = bw * 4 - 1, d0 = bd * 8 - 1;
-    const long long vox0 = (((long long)b * a.H + bh * 4) * a.W + bw * 4) * a.D + bd * 8;
+    const Brick bk = split_brick(brick, nbh, nbw, nbd);
+    const int h0 = bk.bh * 4 - 1, w0 = bk.bw * 4 - 1, d0 = bk.bd * 8 - 1;
+    const long long vox0 = (((long long)bk.b * a.H + bk.bh * 4) * a.W + bk.bw * 4) * a.D + bk.bd * 8;
     const uint32_t bb = lds0 + buf * (WR_BUF * 2);
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -92,7 +73,7 @@ __global__ void __launch_bounds__(256, 1) conv3_wgrad_halo_ring_bf16_kernel(cons
       const int h = h0 + (pk[s] >> 16), w = w0 + ((pk[s] >> 8) & 255), d = d0 + (pk[s] & 255);
       const bool in = pk[s] >= 0 && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W && (unsigned)d < (unsigned)a.D;
       const char* ptr = reinterpret_cast<const char*>((isx ? xbase : gbase_p) + (vox0 + rel[s]) * (isx ? xld : gld));
-      wr_glds16(in ? ptr : zsrc, bb + p * 1024);
+      glds16(in ? ptr : zsrc, bb + p * 1024);
     }
   };
 
@@ -124,8 +105,9 @@ __global__ void __launch_bounds__(256, 1) conv3_wgrad_halo_ring_bf16_kernel(cons
   int buf = 0;
   for (int i = 0; i < nb; ++i) {
     // brick i has landed (this wave's pieces: the counted wait; the other waves': the barrier) and every wave has left brick i - 1,
-    // whose buffer takes brick i + 2
-    if (i + 1 < nb) wr_sync<8>(); else wr_sync<0>();
+    // whose buffer takes brick i + 2 (ring_sync_all: this wave's LDS reads of that buffer have returned before the barrier hands it to
+    // the LDS-DMA of every wave)
+    if (i + 1 < nb) ring_sync_all<8>(); else ring_sync_all<0>();
     if (i + 2 < nb) issue_brick(brick_lo + i + 2, buf >= 1 ? buf - 1 : WR_NB - 1);
     const uint16_t* halo = smem + buf * WR_BUF;
     const uint16_t* Gs = halo + WR_GOFF;
@@ -195,7 +177,7 @@ int launch_conv_wgrad_halo_ring_bf16(WHaloArgs a, int* nsplit_out, hipStream_t s
   constexpr int smem_bytes = WR_NB * WR_BUF * 2;
   static LtuDevOnce attr_once;
   if (attr_once.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_wgrad_halo_ring_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
+    ltu_dyn_lds(&conv3_wgrad_halo_ring_bf16_kernel, smem_bytes);
   hipLaunchKernelGGL(conv3_wgrad_halo_ring_bf16_kernel, dim3(nchunk, ntile, nsplit), dim3(256), smem_bytes, st, a);
   return ltu_check_launch();
 }
