@@ -315,7 +315,8 @@ int ltu_gelu_dropout_bwd(const void* dh, const void* u, void* du, long long n, f
                          ltu_stream_t s);
 
 /* ---- class-probability heads ---------------------------------------------------------------------
- * mask head softmax (model/Unet_3Dblock.py:1380-1381): logits T [M][CP] (first C valid) -> p f32 [M][C] */
+ * mask head softmax (model/Unet_3Dblock.py:1380-1381): logits T [M][CP] (first C valid) -> p f32 [M][C]; C <= 8 in both heads
+ * (else LTU_E_SHAPE); the backward writes the padding columns C .. CP-1 of dz as zero */
 int ltu_head_softmax_fwd(const void* z, float* p, long long M, int C, int CP, int dtype, ltu_stream_t s);
 int ltu_head_softmax_bwd(const float* dp, const float* p, void* dz, long long M, int C, int CP, int dtype, ltu_stream_t s);
 /* final head (model/Unet_3Dblock.py:1392-1394): z [B,h,w,D,4C] -> window un-embedding + softmax -> p f32 [B,2h,2w,D,C] */
@@ -389,6 +390,18 @@ int ltu_loss_fwd(const float* p, const uint8_t* label, float* sums, long long su
                  float w_ce, float w_bal, const float* w_dice, const float* scale_dev, ltu_stream_t s);
 int ltu_loss_bwd(const float* p, const uint8_t* label, const float* coef, const float* gscale, float* dp, int B,
                  long long S, int C, ltu_stream_t s);
+/* ---- the same losses for 2 <= C <= 8 classes (csrc/manyclass.hip; loss/multi_criterions.py:58-83, DiceClassLoss(class_index)) ----
+ * The arithmetic of ltu_loss_fwd with room for 8 classes.  w_dice: C + 1 host floats, the Dice weight of every class, then that
+ * of the foreground union.  values (C + 5 floats): [0] = total, [1] = CE, [2] = balanced Dice, [3 + c] = Dice_c, [3 + C] = union
+ * Dice, [4 + C] = total again.  sums: scratch of ltu_loss_wide_ws_floats(B, S, C) floats, no initialisation, folded in a fixed
+ * order (no floating-point atomics: two calls agree bit for bit).  coef [B][C][3] feeds ltu_loss_wide_bwd (ltu_loss_bwd hands C > 4
+ * over to it).  LTU_E_SHAPE: C outside 2 .. 8 or B C 4 > 256 (the finalize's row limit; the size query then returns 0); LTU_E_ARG:
+ * a NULL pointer or sums shorter than the geometry needs; both before anything is launched. */
+long long ltu_loss_wide_ws_floats(int B, long long S, int C);
+int ltu_loss_wide_fwd(const float* p, const uint8_t* label, float* sums, long long sums_floats, float* values, float* coef, int B, long long S,
+                      int C, float w_ce, float w_bal, const float* w_dice, const float* scale_dev, ltu_stream_t s);
+int ltu_loss_wide_bwd(const float* p, const uint8_t* label, const float* coef, const float* gscale, float* dp, int B, long long S, int C,
+                      ltu_stream_t s);
 /* ---- the wider loss family of one level: loss/criterions.py:8-32,466-530,563-615,618-644,738-751;
  *      loss/multi_criterions.py:517-541,617-663, and the five terms of ltu_loss_fwd ---------------------------------------
  * p f32 [B][S][C] probabilities, label u8 [B][S], 2 <= C <= 4 and B (7 C + 3) <= 256 (else LTU_E_SHAPE).  cfg: LTU_LOSS_EXT_NCFG

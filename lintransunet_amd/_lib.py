@@ -131,6 +131,9 @@ SIGNATURES = {
     'ltu_loss_ws_floats': [I, L, I],
     'ltu_loss_fwd': [P, P, P, L, P, P, I, L, I, F, F, P, P, P],
     'ltu_loss_bwd': [P, P, P, P, P, I, L, I, P],
+    'ltu_loss_wide_ws_floats': [I, L, I],
+    'ltu_loss_wide_fwd': [P, P, P, L, P, P, I, L, I, F, F, P, P, P],
+    'ltu_loss_wide_bwd': [P, P, P, P, P, I, L, I, P],
     'ltu_loss_ext_ws_floats': [I, L, I],
     'ltu_loss_ext_fwd': [P, P, P, L, P, P, I, L, I, P, P, P],
     'ltu_loss_ext_bwd': [P, P, P, P, P, P, I, L, I, P],

@@ -326,6 +326,7 @@ extern "C" int ltu_loss_fwd(const float* p, const uint8_t* label, float* sums, l
 
 extern "C" int ltu_loss_bwd(const float* p, const uint8_t* label, const float* coef, const float* gscale, float* dp, int B,
                             long long S, int C, ltu_stream_t s) {
+  if (C > LOSS_MAXC) return ltu_loss_wide_bwd(p, label, coef, gscale, dp, B, S, C, s);      // coefficients of ltu_loss_wide_fwd (manyclass.hip)
   const long long n = (long long)B * S;
   long long blocks = (n + 255) / 256;
   if (blocks > 8192) blocks = 8192;

@@ -2,6 +2,7 @@
 // window (un)embedding, weight repacking, GELU+dropout, class softmax heads, the attention gate,
 // the depthwise positional conv and the nearest-upsampling adjoint.  Channels-last, 4-wide vectors.
 #include "common.h"
+#include "manyclass.h"
 
 static unsigned sgrid(long long n, int per_block = 256) {
   long long blocks = (n + per_block - 1) / per_block;
@@ -302,6 +303,7 @@ __global__ void head_softmax_bwd_bf16x8_kernel(const float* __restrict__ dp, con
   }
 }
 extern "C" int ltu_head_softmax_fwd(const void* z, float* p, long long M, int C, int CP, int dtype, ltu_stream_t s) {
+  if (C > 4 && C <= LTU_WIDE_MAXC) return ltu_head_softmax_wide_fwd(z, p, M, C, CP, dtype, s);      // 5 .. 8 classes: manyclass.hip
   if (C > 4 || CP < C) return LTU_E_SHAPE;
   LTU_DISPATCH_T(dtype, {
     if (CP % 4 == 0 && C == 2) hipLaunchKernelGGL((head_softmax_fwd_vec_kernel<T, 2>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
@@ -312,6 +314,7 @@ extern "C" int ltu_head_softmax_fwd(const void* z, float* p, long long M, int C,
 }
 extern "C" int ltu_head_softmax_bwd(const float* dp, const float* p, void* dz, long long M, int C, int CP, int dtype,
                                     ltu_stream_t s) {
+  if (C > 4 && C <= LTU_WIDE_MAXC) return ltu_head_softmax_wide_bwd(dp, p, dz, M, C, CP, dtype, s);
   if (C > 4 || CP < C) return LTU_E_SHAPE;
   if (dtype == LTU_BF16 && CP % 8 == 0 && ((uintptr_t)dz & 15) == 0) {
     if (C == 2) hipLaunchKernelGGL(head_softmax_bwd_bf16x8_kernel<2>, dim3(sgrid(M * (CP / 8))), dim3(256), 0, (hipStream_t)s, dp, p, (uint4*)dz, M, C, CP);
@@ -399,6 +402,7 @@ __global__ void final_softmax_bwd_kernel(const float* __restrict__ dp, const flo
   }
 }
 extern "C" int ltu_final_softmax_fwd(const void* z, float* p, int B, int h, int w, int D, int C, int CP, int dtype, ltu_stream_t s) {
+  if (C > 4 && C <= LTU_WIDE_MAXC) return ltu_final_softmax_wide_fwd(z, p, B, h, w, D, C, CP, dtype, s);      // 5 .. 8 classes: manyclass.hip
   if (C < 1 || C > 4 || CP < 4 * C || CP % 4) return LTU_E_SHAPE;
   LTU_DISPATCH_T(dtype, {
     const dim3 grid(sgrid((long long)B * h * w * D));
@@ -410,6 +414,7 @@ extern "C" int ltu_final_softmax_fwd(const void* z, float* p, int B, int h, int 
 }
 extern "C" int ltu_final_softmax_bwd(const float* dp, const float* p, void* dz, int B, int h, int w, int D, int C, int CP,
                                      int dtype, ltu_stream_t s) {
+  if (C > 4 && C <= LTU_WIDE_MAXC) return ltu_final_softmax_wide_bwd(dp, p, dz, B, h, w, D, C, CP, dtype, s);
   if (C < 1 || C > 4 || CP < 4 * C || CP % 4) return LTU_E_SHAPE;
   LTU_DISPATCH_T(dtype, {
     const dim3 grid(sgrid((long long)B * h * w * D));

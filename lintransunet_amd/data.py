@@ -185,7 +185,8 @@ def augment(img, lab, params):
 def synthetic_patches(batch, size, seed, device, n_classes=2, n_blobs=2):
     """Synthetic CT-like training patches for benchmarks and soak runs: N(0,1) intensities clipped to
     the dataset's normalised HU range [(-91 - 86.9) / 39.4, (250 - 86.9) / 39.4] and a label volume that is a union of `n_blobs`
-    random ellipsoids per patch (nested twice for 3 label values).  Host generators (seeded), uploaded once: a benchmark keeps its
+    random ellipsoids per patch (nested twice for 3 label values; for 4 .. 8 label values one further ellipsoid per class 2 .. k-1, every
+    class 1 .. k-1 present in every patch).  Host generators (seeded), uploaded once: a benchmark keeps its
     inputs resident in HBM.  Returns (x f32 [B,1,H,W,D], label u8 [B,1,H,W,D])."""
     g = torch.Generator().manual_seed(seed)
     H, W, D = size
@@ -202,6 +203,23 @@ def synthetic_patches(batch, size, seed, device, n_classes=2, n_blobs=2):
             lab[b, 0][dist <= 1.0] = 1
             if n_classes == 3:
                 lab[b, 0][dist <= 0.25] = 2
+        if n_classes >= 4 and n_blobs > 0:
+            # 4 .. 8 label values: one more ellipsoid per class 2 .. k-1, painted in class order; then the centre voxel of every
+            # class's ellipsoid (class 1: the last blob's) is set to its own value, so that no later ellipsoid covers a class completely
+            centres = [(1, c)]
+            for k in range(2, n_classes):
+                c = 0.2 + 0.6 * torch.rand(3, generator=g)
+                r = 0.08 + 0.10 * torch.rand(3, generator=g)
+                dist = ((hh - c[0] * H) / (r[0] * H)) ** 2 + ((ww - c[1] * W) / (r[1] * W)) ** 2 + ((dd - c[2] * D) / (r[2] * D)) ** 2
+                lab[b, 0][dist <= 1.0] = k
+                centres.append((k, c))
+            taken = set()
+            for k, c in centres:
+                pos = [min(int(c[a] * n), n - 1) for a, n in enumerate((H, W, D))]
+                while tuple(pos) in taken:                  # two centres in one voxel: the next one along D
+                    pos[2] = (pos[2] + 1) % D
+                taken.add(tuple(pos))
+                lab[b, 0, pos[0], pos[1], pos[2]] = k
     return x.to(device), lab.to(device)
 
 

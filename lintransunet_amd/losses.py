@@ -33,25 +33,31 @@ class LevelCriterion(nn.Module):
     """Weighted sum of the training losses of one decoder level on one prediction, one kernel pass.
 
     spec: {name: weight}.  A spec made only of the names of the original family, {'CrossEntroLoss', 'BalanceDiceLoss',
-    'DiceClassLoss' (class 1), 'DiceClassLoss2' (class 2), 'DiceClassLoss0c' (class 0), 'DiceClassLoss0' (foreground union
-    1 - class 0, multi_criterions.py:30-56)}, runs ops.level_loss (csrc/loss.hip).  A spec with any name of `EXT` runs the
-    whole spec through ops.level_loss_ext (csrc/loss_ext.hip), which also carries the original terms.  params: the parameters
+    'DiceClassLoss' (class 1), 'DiceClassLoss2' .. 'DiceClassLoss7' (classes 2 .. 7, the reference's
+    multi_criterions.DiceClassLoss(class_index)), 'DiceClassLoss0c' (class 0), 'DiceClassLoss0' (foreground union
+    1 - class 0, multi_criterions.py:30-56)}, runs ops.level_loss (csrc/loss.hip) on predictions of up to 4 classes and
+    ops.level_loss_wide (csrc/manyclass.hip) on 5 .. 8.  A spec with any name of `EXT` runs the
+    whole spec through ops.level_loss_ext (csrc/loss_ext.hip), which also carries the original terms but stops at 4 classes.
+    params: the parameters
     of the wider family (ops.LOSS_EXT_PARAMS: gamma, sigma, alpha, alpha2, eps; defaults ops.LOSS_EXT_DEFAULTS).  Returns
     (total, {name: w * value}) with values detached: what the reference scripts log (`criterions_w * l(...)`,
     utils_3D_multi_class.py:85; all weights are 1 in the single-class script).
     """
-    _DICE = {'DiceClassLoss': 1, 'DiceClassLoss2': 2, 'DiceClassLoss0c': 0, 'DiceClassLoss0': 4}      # 4 = foreground union
+    FG = 'fg'           # key of the foreground union in _DICE (every other value is a class index)
+    _DICE = {'DiceClassLoss': 1, 'DiceClassLoss2': 2, 'DiceClassLoss0c': 0, 'DiceClassLoss0': FG,
+             'DiceClassLoss3': 3, 'DiceClassLoss4': 4, 'DiceClassLoss5': 5, 'DiceClassLoss6': 6, 'DiceClassLoss7': 7}
     # every name -> its term of the wider family (ops.LOSS_EXT_TERMS)
     _TERM = {'CrossEntroLoss': 'CE', 'BalanceDiceLoss': 'BAL', 'DiceClassLoss0c': 'DICE0', 'DiceClassLoss': 'DICE1',
-             'DiceClassLoss2': 'DICE2', 'DiceClassLoss0': 'FG'}
+             'DiceClassLoss2': 'DICE2', 'DiceClassLoss3': 'DICE3', 'DiceClassLoss0': 'FG'}
     EXT = {'DiceLoss': 'DICE', 'IOULoss': 'IOU', 'SSLoss': 'SS', 'FocalLoss': 'FOCAL', 'MSELoss': 'MSE', 'ContainLoss': 'CONTAIN',
            'ContainLoss2': 'CONTAIN2', 'BalanceDiceLoss2': 'BAL2', 'CrossEntroLoss0': 'CE0', 'ClassifyLoss': 'CLASSIFY'}
+    EXT_MAXC = 4        # class limit of the wider family (csrc/loss_ext.hip)
 
     def __init__(self, spec: dict, scale: float = 1.0, scale_dev=None, params=None):
         super().__init__()
         if 'DistributionLoss' in spec:
             raise KeyError(_DISTRIBUTION_REFUSED)
-        unknown = set(spec) - set(self._TERM) - set(self.EXT)
+        unknown = set(spec) - set(self._TERM) - set(self._DICE) - set(self.EXT)
         if unknown:
             raise KeyError(f'no HIP kernel for losses {sorted(unknown)}')
         self.spec = dict(spec)
@@ -60,35 +66,55 @@ class LevelCriterion(nn.Module):
         self.params = dict(params or {})
         self.extended = any(name in self.EXT for name in self.spec)
 
+    def _check_classes(self, C):
+        """the Dice names of the spec against the C classes of a prediction; raises before anything is launched.  (Up to 4 classes
+        ltu_loss_fwd takes a weight for each of its 4 class slots and ignores those of absent classes, as it always did.)"""
+        first = C if self.extended or C > 4 else 4
+        absent = [name for name in self.spec if name in self._DICE and self._DICE[name] != self.FG and self._DICE[name] >= first]
+        if absent:
+            raise ValueError(f'{absent}: the Dice of a class the prediction does not have ({C} classes)')
+
+    def dice_weights(self, C):
+        """the Dice weights of the spec as the kernels take them: per class, then the foreground union - 5 entries for C <= 4
+        (ltu_loss_fwd), C + 1 for 5 .. 8 classes (ltu_loss_wide_fwd)"""
+        n = 4 if C <= 4 else C
+        wd = [0.0] * (n + 1)
+        for name, cls in self._DICE.items():
+            if name in self.spec:
+                wd[n if cls == self.FG else cls] += self.spec[name] * self.scale
+        return wd
+
     def forward(self, predict, target, params=None):
+        C = predict.shape[1]
+        self._check_classes(C)
+        if self.extended and C > self.EXT_MAXC:
+            ext = sorted(name for name in self.spec if name in self.EXT)
+            raise ValueError(f'{ext}: the wider loss family has kernels for C <= {self.EXT_MAXC} classes only, the prediction has {C}')
+        if C > ops.LOSS_WIDE_MAXC:
+            raise ValueError(f'the level losses have kernels for C <= {ops.LOSS_WIDE_MAXC} classes, the prediction has {C}')
         p = _channels_last(predict)
-        C = p.shape[-1]
         lab = _labels(target, C)
         sc = self.scale
         if self.extended:
             return self._forward_ext(p, lab, dict(self.params, **(params or {})))
-        wd = [0.0] * 5
-        for name, cls in self._DICE.items():
-            if name in self.spec:
-                wd[cls] += self.spec[name] * sc
-        total, values = ops.level_loss(p, lab, self.spec.get('CrossEntroLoss', 0.0) * sc,
-                                       self.spec.get('BalanceDiceLoss', 0.0) * sc, wd, self.scale_dev)
+        wd = self.dice_weights(C)
+        fn = ops.level_loss if C <= 4 else ops.level_loss_wide
+        total, values = fn(p, lab, self.spec.get('CrossEntroLoss', 0.0) * sc, self.spec.get('BalanceDiceLoss', 0.0) * sc, wd, self.scale_dev)
+        fg = 3 + len(wd) - 1
         named = {}
         for name, w in self.spec.items():
             if name == 'CrossEntroLoss':
                 v = values[1]
             elif name == 'BalanceDiceLoss':
                 v = values[2]
+            elif self._DICE[name] == self.FG:
+                v = values[fg]
             else:
                 v = values[3 + self._DICE[name]]
             named[name] = v if w == 1.0 else v * w
         return total, named
 
     def _forward_ext(self, p, lab, params):
-        C = p.shape[-1]
-        absent = [name for name in self.spec if name in self._DICE and self._DICE[name] < 4 and self._DICE[name] >= C]
-        if absent:
-            raise ValueError(f'{absent}: the Dice of a class the prediction does not have ({C} classes)')
         weights = {}
         for name, w in self.spec.items():
             term = self.EXT.get(name) or self._TERM[name]
@@ -121,9 +147,20 @@ class CrossEntroLoss(_Single):
     NAME = 'CrossEntroLoss'
 
 
+def dice_class_name(class_index: int) -> str:
+    """the spec name of the Dice of class `class_index`: 'DiceClassLoss0c', 'DiceClassLoss', 'DiceClassLoss2' .. 'DiceClassLoss7'"""
+    if not 0 <= int(class_index) < ops.LOSS_WIDE_MAXC:
+        raise ValueError(f'DiceClassLoss: class_index {class_index} outside 0 .. {ops.LOSS_WIDE_MAXC - 1}')
+    return {0: 'DiceClassLoss0c', 1: 'DiceClassLoss'}.get(int(class_index), f'DiceClassLoss{int(class_index)}')
+
+
 class DiceClassLoss(_Single):
-    """loss/criterions.py:35-70 (class 1)"""
+    """loss/criterions.py:35-70 (class 1); loss/multi_criterions.py:58-83 with `class_index`"""
     NAME = 'DiceClassLoss'
+
+    def __init__(self, class_index: int = 1):
+        self.NAME = dice_class_name(class_index)
+        super().__init__()
 
 
 class DiceClassLoss2(_Single):

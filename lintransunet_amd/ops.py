@@ -1524,7 +1524,7 @@ class _HeadSoftmax(torch.autograd.Function):
 
 
 def head_softmax(z, C):
-    """class softmax over the first C of the (padded) channels of z -> fp32 probabilities [..., C]."""
+    """class softmax over the first C <= 8 of the (padded) channels of z -> fp32 probabilities [..., C]."""
     return _HeadSoftmax.apply(z, C)
 
 
@@ -1552,7 +1552,8 @@ class _FinalSoftmax(torch.autograd.Function):
 
 
 def final_softmax(z, C):
-    """window un-embedding + class softmax: z [B,h,w,D,CP >= 4C] (conv output, possibly padded) -> fp32 probabilities [B,2h,2w,D,C]."""
+    """window un-embedding + class softmax: z [B,h,w,D,CP >= 4C] (conv output, possibly padded), C <= 8 -> fp32 probabilities
+    [B,2h,2w,D,C]."""
     return _FinalSoftmax.apply(z, C)
 
 
@@ -1674,10 +1675,56 @@ class _LevelLoss(torch.autograd.Function):
 
 
 def level_loss(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
-    """p fp32 [B,...,C] channels-last probabilities, label uint8 [B,...]: weighted CE + balanced Dice + per-class Dice
-    (w_dice[c], c < 4) + Dice of the foreground union (w_dice[4]).
+    """p fp32 [B,...,C] channels-last probabilities (C <= 4), label uint8 [B,...]: weighted CE + balanced Dice + per-class Dice
+    (w_dice[c], c < 4) + Dice of the foreground union (w_dice[4]).  5 .. 8 classes: level_loss_wide.
     scale_dev: optional 1-element fp32 device tensor multiplying all weights at run time."""
     return _LevelLoss.apply(p, label, w_ce, w_bal, tuple(w_dice), scale_dev)
+
+
+LOSS_WIDE_MAXC = 8      # LTU_WIDE_MAXC of csrc/manyclass.h
+
+
+class _LevelLossWide(torch.autograd.Function):
+    """_LevelLoss for 2 <= C <= 8 (csrc/manyclass.hip); returns (total, values[3 + C + 1]) with values detached."""
+
+    @staticmethod
+    def forward(ctx, p, label, w_ce, w_bal, w_dice, scale_dev):
+        ctx.lc = current()
+        _chk(p, 'p'); _chk(label, 'label')
+        B, C = p.shape[0], p.shape[-1]
+        S = p.numel() // (B * C)
+        dev = p.device
+        if len(w_dice) != C + 1:
+            raise ValueError(f'level_loss_wide: w_dice has {len(w_dice)} entries, {C} classes need {C + 1} (per class, then the foreground union)')
+        sums = torch.empty(_lib.load().ltu_loss_wide_ws_floats(B, S, C), device=dev, dtype=torch.float32)      # partials + sums: no zero fill
+        buf = torch.empty(C + 5, device=dev, dtype=torch.float32)
+        values = buf[:C + 4]             # the report (non-differentiable); buf[C + 4] repeats the total as the differentiable output
+        coef = torch.empty((B, C, 3), device=dev, dtype=torch.float32)
+        wd = (ctypes.c_float * (C + 1))(*[float(w) for w in w_dice])
+        _lib.call('ltu_loss_wide_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(values), _p(coef), B, S, C, float(w_ce), float(w_bal), wd,
+                  _p(scale_dev), _s())
+        ctx.save_for_backward(p, label, coef)
+        ctx.mark_non_differentiable(values)
+        ctx.set_materialize_grads(False)         # no zero-filled gradient tensor for the report output
+        return buf[C + 4], values
+
+    @staticmethod
+    def backward(ctx, g, _gv):
+        p, label, coef = ctx.saved_tensors
+        B, C = p.shape[0], p.shape[-1]
+        S = p.numel() // (B * C)
+        if g is None:
+            return None, None, None, None, None, None
+        g = g.contiguous().to(torch.float32)
+        dp = torch.empty_like(p)
+        _lib.call('ltu_loss_wide_bwd', _p(p), _p(label), _p(coef), _p(g), _p(dp), B, S, C, _s())
+        return dp, None, None, None, None, None
+
+
+def level_loss_wide(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
+    """level_loss for 2 <= C <= 8 classes: w_dice has C + 1 entries (the Dice weight of every class, then that of the foreground
+    union); values = [total, CE, balanced Dice, Dice_0 .. Dice_{C-1}, union Dice] (detached)."""
+    return _LevelLossWide.apply(p, label, w_ce, w_bal, tuple(w_dice), scale_dev)
 
 
 # term and parameter slots of the config array of ltu_loss_ext_fwd / ltu_loss_ext_bwd (the LTU_LOSS_EXT_* enum of include/ltu_hip.h)
@@ -1733,7 +1780,8 @@ class _LevelLossExt(torch.autograd.Function):
 
 
 def level_loss_ext(p, label, weights, params=None, scale_dev=None):
-    """p fp32 [B,...,C] channels-last probabilities (2 <= C <= 4), label uint8 [B,...]: sum_k weights[k] * term_k over the terms of
+    """p fp32 [B,...,C] channels-last probabilities (2 <= C <= 4: the wider family stops there; the original family goes to 8
+    classes through level_loss_wide), label uint8 [B,...]: sum_k weights[k] * term_k over the terms of
     LOSS_EXT_TERMS, with the parameters of LOSS_EXT_PARAMS (defaults LOSS_EXT_DEFAULTS).  Returns (total, values) with
     values[0] = total and values[1 + i] = term LOSS_EXT_TERMS[i] (unweighted, detached); no host synchronisation.
     scale_dev: optional 1-element fp32 device tensor multiplying all weights at run time."""
