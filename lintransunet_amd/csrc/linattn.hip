@@ -824,18 +824,48 @@ __global__ void __launch_bounds__(256) linattn_dctx_combine(const float* __restr
 //   dvT[j][t]  = sum_i dctx[i][j] P[t][i]
 //   dPT[i][t]  = sum_j dctx[i][j] v[t][j]      dk[t][i] = P[t][i] (dPT[i][t] - tvec[i])
 // writes dqkv [B*N][3d] (dq | dk | dv).  Same k-index convention and LDS row format as linattn_apply.
+//
+// bf16 storage: the tile stays the bf16 it was loaded as, [32][4D + 8]: a row is q | k | v | dO of one token (row pitch = 16 bytes
+// modulo 256: the 16 lanes of a ds_read_b128 group cover the 64 banks once).  A lane's dO and v fragments (its token, channels
+// 16 lh + 8 u .. + 7) are single 16-byte reads that go to the matrix cores as they are; k and q are read the same way and unpacked for
+// the two exponentials.  P is needed twice, as the B operand (channels 16 lh + s) and for dk in the accumulator layout (channels
+// 8 g + 4 lh + e): the second copy is the first one exchanged between the wave halves (8 v_permlane32_swap), not a second read and
+// exponential, and q reaches the accumulator layout the same way (4 swaps of packed pairs).  Wave w touches the columns of head w
+// only, so dq, dk and dv go back into the tile in place without a barrier; thread x then reads out exactly the 16-byte pieces of the
+// staging that it overwrites with the next tile, which leaves two barriers per tile: outputs staged | next tile in place.
+// LDS 75.5 KB at d = 256 and 38 KB at d = 128 (fp32 tiles: 132 / 66 KB): two and four workgroups per CU, 4 waves per SIMD, which
+// leaves 128 VGPRs - the body is arranged around that number (see the comments at the phases).  Every D that LA_DISPATCH_D
+// instantiates takes this body for bf16 storage, D = 32 and 64 included (D/8 pieces per third of a row, 16 rows per pass of the 2 D
+// threads, pitch 16 bytes modulo 256 at every D).
+// The staging writes LDS as 8-byte quads and reads the same bytes back as 16-byte pieces and fragments of other types; "older reads"
+// and "in place" below mean program order, so every LDS access of the body goes through a may_alias type (la_lds*): type-based alias
+// analysis may not reorder them.
+typedef uint32_t la_u32x4 __attribute__((ext_vector_type(4)));       // a 16-byte piece of a tile
+typedef la_u32x4 __attribute__((may_alias)) la_lds16;                // ... in LDS
+typedef uint4 __attribute__((may_alias)) la_lds16w;                  // a k or q fragment in LDS, as four packed pairs
+typedef uint2 __attribute__((may_alias)) la_lds8;                    // an output quad in LDS
+typedef bf16x8 __attribute__((may_alias)) la_ldsfrag;                // a dO or v fragment (an MFMA operand) in LDS
+constexpr int LAB_PAD = 8;                       // row padding of the bf16 tiles, in elements
+constexpr int LAB_OCC = 4;                       // waves per SIMD the bf16 body is compiled for: 128 VGPRs, what its LDS footprint admits
+__device__ __forceinline__ void permlane32_swap(uint32_t& a, uint32_t& b) {
+  float fa = __uint_as_float(a), fb = __uint_as_float(b);
+  permlane32_swap(fa, fb);
+  a = __float_as_uint(fa); b = __float_as_uint(fb);
+}
 template <typename T, int D>
-__global__ void __launch_bounds__(2 * D, 2) linattn_bwd_apply(const T* __restrict__ qkv, const T* __restrict__ dout,
+__global__ void __launch_bounds__(2 * D, IsBf16<T>::value ? LAB_OCC : 2) linattn_bwd_apply(const T* __restrict__ qkv, const T* __restrict__ dout,
                                                           const float* __restrict__ ctx, const float* __restrict__ dctx,
                                                           const float* __restrict__ stats, const float* __restrict__ tvec,
                                                           const float* __restrict__ qstat, T* __restrict__ dqkv, int N, int tokb) {
   constexpr int H = D / DK, LD3 = 3 * D + 4, LD1 = D + 4, NTHR = 2 * D, W = GVec<T>::W;
-  extern __shared__ __attribute__((aligned(16))) float smem[];   // [32][LD3] qkv tile (reused for dqkv), [32][LD1] dO, [H][96] stats
+  constexpr int P4 = 4 * D + LAB_PAD;                            // bf16 tile: row pitch in elements
+  // fp32: [32][LD3] qkv tile (reused for dqkv), [32][LD1] dO, [H][96] stats;  bf16: [32][P4] bf16 rows q|k|v|dO, [H][96] stats
+  extern __shared__ __attribute__((aligned(16))) float smem[];
   const int b = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   float* gt = smem + TOK * LD3;
-  float* cs = gt + TOK * LD1 + wave * 96;      // this head's column max | 1/colsum | tvec
+  float* cs = (IsBf16<T>::value ? smem + TOK * P4 / 2 : gt + TOK * LD1) + wave * 96;      // this head's column max | 1/colsum | tvec
   const long long bh = (long long)b * H + wave;
   if (lane < 32) {
     cs[lane] = stats[bh * 64 + lane];
@@ -878,8 +908,6 @@ __global__ void __launch_bounds__(2 * D, 2) linattn_bwd_apply(const T* __restric
 
   const int n_begin = blockIdx.x * tokb;
   const int n_end = min(N, n_begin + tokb);
-  RowTile<T, D, 3 * D, LD3> tq;
-  RowTile<T, D, D, LD1> tg;
   // (row max, scaled inverse sum) of token n0 + li travel with the tile prefetch: loaded after it they would wait for it
   // (unconditional, from a clamped row: a test around the load makes hipcc wait for it - and for the whole tile prefetch issued
   // just before it - where it stands)
@@ -890,52 +918,200 @@ __global__ void __launch_bounds__(2 * D, 2) linattn_bwd_apply(const T* __restric
   // the staging into registers, the NEXT tile goes to LDS (its loads are older than any pending store), and only then are the
   // outputs stored.  vmcnt is one in-order counter and hipcc waits vmcnt(0) at the loop head: stores issued at the end of an
   // iteration had their acknowledgement waited for before every tile, with one wave per SIMD to hide it.
-  tq.load(qb, 3 * D, 0, n_begin, n_end, tid);
-  tg.load(gb, D, 0, n_begin, n_end, tid);
-  float2 qsn = load_qs(n_begin);
-  tq.store(smem, tid);
-  tg.store(gt, tid);
-  __syncthreads();
-  for (int n0 = n_begin; n0 < n_end; n0 += TOK) {
-    const float rmax = qsn.x, rinv = qsn.y;
-    const bool more = n0 + TOK < n_end;
-    if (more) {
-      tq.load(qb, 3 * D, 0, n0 + TOK, n_end, tid);
-      tg.load(gb, D, 0, n0 + TOK, n_end, tid);
-      qsn = load_qs(n0 + TOK);
-    }
-    const float* qrow = &smem[li * LD3 + wave * DK];
-    const float* krow = qrow + D;
-    const float* vrow = qrow + 2 * D;
-    const float* grow = &gt[li * LD1 + wave * DK];
-
-    // B operands with the token on the lane: channels 16*lh + s
-    float gj[16], kk[16], vj[16];
+  if constexpr (IsBf16<T>::value) {
+    uint16_t* sm = reinterpret_cast<uint16_t*>(smem);
+    // Tile traffic: thread x moves the 16-byte piece (row x / (D/8) + 16 h, columns 8 (x % (D/8)) .. + 7) of each third j of the q|k|v
+    // rows and of the dO rows, h = 0, 1: every piece is the thread's first one plus a compile-time offset, in global memory and in
+    // LDS, so one lane offset serves the loads, the LDS writes, the read-out and the stores (an address pair per piece cost 28
+    // registers).  A wave instruction covers whole 2 D-byte thirds of rows.
+    constexpr int VG = D / 8;                                    // pieces per third of a row
+    const int pr = tid / VG, pcol = (tid % VG) * 8;
+    const unsigned go3 = pr * 3 * D + pcol;                        // element offset of the first piece inside a q|k|v tile
+    uint16_t* lq = sm + pr * P4 + pcol;
+    la_u32x4 rq[6], rg[2];
+    // a row behind the run's end repeats its last row: its token's results are not stored
+    auto fetch = [&](int n0) {
+      const uint16_t* tqb = reinterpret_cast<const uint16_t*>(qb) + (long long)n0 * 3 * D;
+      const uint16_t* tgb = reinterpret_cast<const uint16_t*>(gb) + (long long)n0 * D;
+      const int last = n_end - n0 - 1;
 #pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-      const float4 a = *reinterpret_cast<const float4*>(grow + 16 * lh + 4 * q4);
-      const float4 c = *reinterpret_cast<const float4*>(krow + 16 * lh + 4 * q4);
-      const float4 e = *reinterpret_cast<const float4*>(vrow + 16 * lh + 4 * q4);
-      gj[4 * q4] = a.x; gj[4 * q4 + 1] = a.y; gj[4 * q4 + 2] = a.z; gj[4 * q4 + 3] = a.w;
-      kk[4 * q4] = c.x; kk[4 * q4 + 1] = c.y; kk[4 * q4 + 2] = c.z; kk[4 * q4 + 3] = c.w;
-      vj[4 * q4] = e.x; vj[4 * q4 + 1] = e.y; vj[4 * q4 + 2] = e.z; vj[4 * q4 + 3] = e.w;
-    }
-    f32x16 aq, av, ak;
+      for (int h = 0; h < 2; ++h) {
+        const unsigned row = min(pr + 16 * h, last);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { aq[r] = 0.f; av[r] = 0.f; ak[r] = 0.f; }
-    if constexpr (IsBf16<T>::value) {
-#pragma unroll
-      for (int s = 0; s < 16; ++s) kk[s] = __expf(kk[s] - cs[16 * lh + s]) * cs[32 + 16 * lh + s];      // P[t][i=ch]
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        aq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ctxB[u], pack8(gj + 8 * u), aq, 0, 0, 0);
-        av = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dcTB[u], pack8(kk + 8 * u), av, 0, 0, 0);
-        const bf16x8 vb = pack8(vj + 8 * u);
-#pragma unroll
-        for (int pc = 2; pc >= 0; --pc) ak = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dcAB[pc][u], vb, ak, 0, 0, 0);
+        for (int j = 0; j < 3; ++j) rq[3 * h + j] = *reinterpret_cast<const la_u32x4*>(tqb + row * 3 * D + pcol + j * D);
+        rg[h] = *reinterpret_cast<const la_u32x4*>(tgb + row * D + pcol);
       }
-    } else {
+    };
+    auto to_lds = [&]() {
 #pragma unroll
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) *reinterpret_cast<la_lds16*>(lq + 16 * h * P4 + j * D) = rq[3 * h + j];
+        *reinterpret_cast<la_lds16*>(lq + 16 * h * P4 + 3 * D) = rg[h];
+      }
+    };
+    // the row statistics of token n0 + li (clamped to the last row of the run), as load_qs, from a uniform base and a lane offset
+    auto load_qs16 = [&](int n0) {
+      const unsigned o = (unsigned)(min(li, n_end - 1 - n0) * H + wave) * 2;
+      return *reinterpret_cast<const float2*>(qstat + ((long long)b * N + n0) * H * 2 + o);
+    };
+    float2 qsn = load_qs16(n_begin);
+    fetch(n_begin);
+    to_lds();
+    asm volatile("" ::"v"(qsn.x), "v"(qsn.y));   // waited for here, with the tile (see the loop's tail): hipcc sinks the load into the loop otherwise
+    __syncthreads();
+    // 39 operand registers, not 40: the first ctx fragment waits in LDS (a lane-contiguous 16-byte read per tile); with it in a
+    // register hipcc spilled operands to scratch, whose reload waits on vmcnt behind the prefetch just issued
+    la_ldsfrag* ctx0 = reinterpret_cast<la_ldsfrag*>(smem + TOK * P4 / 2 + H * 96) + tid;
+    *ctx0 = ctxB[0];
+    uint16_t* qrow = sm + li * P4 + wave * DK;                 // token li, this head: q (k at + D, v at + 2 D, dO at + 3 D)
+    for (int n0 = n_begin; n0 < n_end; n0 += TOK) {
+      const float rmax = qsn.x, rinv = qsn.y;
+      const bool more = n0 + TOK < n_end;
+      if (more) fetch(n0 + TOK);
+      // Three phases, one accumulator alive at a time (36 operand and 32 prefetch registers are alive throughout, of 128): dq, then
+      // dk, then dv.  The lane reads 16-byte fragments of its token, channels 16 lh + 8 u + e of k-step u.
+      auto unpack = [](uint32_t w, float& lo, float& hi) { lo = __uint_as_float(w << 16); hi = __uint_as_float(w & 0xffff0000u); };
+      auto put_quad = [](uint16_t* dst, float a, float b, float c, float d) {
+        *reinterpret_cast<la_lds8*>(dst) = make_uint2(pack_bf16x2(a, b), pack_bf16x2(c, d));
+      };
+      // The accumulators hold rows (r&3) + 8*(r>>2) + 4*lh of token li: quad g = channels 8 g + 4 lh .. + 3.  The lane has channels
+      // 16 lh .. + 15 of q and of P as quads F0..F3; exchanging (F0, F1) and (F2, F3) between the wave halves (upper half of the
+      // first <-> lower half of the second) leaves quads 0 | 2 and 1 | 3 of the accumulator layout in both halves.
+      {
+        f32x16 aq;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) aq[r] = 0.f;
+#pragma unroll
+        for (int u = 0; u < 2; ++u)                                                                     // dqsT[i][t]
+          aq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u == 0 ? *ctx0 : ctxB[1], *reinterpret_cast<const la_ldsfrag*>(qrow + 3 * D + 16 * lh + 8 * u), aq, 0, 0, 0);
+        uint4 q0 = *reinterpret_cast<const la_lds16w*>(qrow + 16 * lh), q1 = *reinterpret_cast<const la_lds16w*>(qrow + 16 * lh + 8);
+        permlane32_swap(q0.x, q0.z); permlane32_swap(q0.y, q0.w);
+        permlane32_swap(q1.x, q1.z); permlane32_swap(q1.y, q1.w);
+        const uint32_t qq[4][2] = {{q0.x, q0.y}, {q1.x, q1.y}, {q0.z, q0.w}, {q1.z, q1.w}};
+        float dot = 0.f;
+        float qsv[16];
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          float qa[4];
+          unpack(qq[g4][0], qa[0], qa[1]);
+          unpack(qq[g4][1], qa[2], qa[3]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = 4 * g4 + e;
+            qsv[r] = __expf(qa[e] - rmax) * rinv;                 // qs[t][i] = p/sqrt(32)
+            dot += qsv[r] * aq[r];
+          }
+        }
+        dot = xhalf_sum(dot);
+        dot *= 5.65685424949238019521f;                           // sum_i p_i dqs_i = sqrt(32) * sum_i qs_i dqs_i
+        // in place: these columns belong to this wave, whose reads above are older (LDS operations of a wave execute in order)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4)
+          put_quad(qrow + 8 * g4 + 4 * lh, qsv[4 * g4] * (aq[4 * g4] - dot), qsv[4 * g4 + 1] * (aq[4 * g4 + 1] - dot),
+                   qsv[4 * g4 + 2] * (aq[4 * g4 + 2] - dot), qsv[4 * g4 + 3] * (aq[4 * g4 + 3] - dot));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      // the next tile's row statistics, requested once this tile's have been used: with both pairs alive during the dq phase hipcc
+      // ran out of registers and parked a prefetch register in scratch, behind a wait for its load
+      if (more) qsn = load_qs16(n0 + TOK);
+      bf16x8 pb[2];                              // P[t][i = 16 lh + 8 u + e]
+      {
+        f32x16 ak;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ak[r] = 0.f;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {                                                                   // dPT[i][t]
+          const bf16x8 vf = *reinterpret_cast<const la_ldsfrag*>(qrow + 2 * D + 16 * lh + 8 * u);
+#pragma unroll
+          for (int pc = 2; pc >= 0; --pc) ak = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dcAB[pc][u], vf, ak, 0, 0, 0);
+        }
+        // per k-step: 8 values of P as the B operand of the dv product, then exchanged into quads u and u + 2 of the accumulator layout
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const uint4 kw = *reinterpret_cast<const la_lds16w*>(qrow + D + 16 * lh + 8 * u);
+          float kk[8];
+          unpack(kw.x, kk[0], kk[1]);
+          unpack(kw.y, kk[2], kk[3]);
+          unpack(kw.z, kk[4], kk[5]);
+          unpack(kw.w, kk[6], kk[7]);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) kk[e] = __expf(kk[e] - cs[16 * lh + 8 * u + e]) * cs[32 + 16 * lh + 8 * u + e];
+          pb[u] = pack8(kk);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) permlane32_swap(kk[e], kk[4 + e]);
+#pragma unroll
+          for (int g = 0; g < 2; ++g) {
+            const int g4 = u + 2 * g, i0 = 8 * g4 + 4 * lh;
+            const float* pk = kk + 4 * g;
+            put_quad(qrow + D + i0, pk[0] * (ak[4 * g4] - cs[64 + i0]), pk[1] * (ak[4 * g4 + 1] - cs[64 + i0 + 1]),
+                     pk[2] * (ak[4 * g4 + 2] - cs[64 + i0 + 2]), pk[3] * (ak[4 * g4 + 3] - cs[64 + i0 + 3]));
+          }
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      {
+        f32x16 av;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) av[r] = 0.f;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) av = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dcTB[u], pb[u], av, 0, 0, 0);     // dvT[j][t]
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4)
+          put_quad(qrow + 2 * D + 8 * g4 + 4 * lh, av[4 * g4], av[4 * g4 + 1], av[4 * g4 + 2], av[4 * g4 + 3]);
+      }
+      __syncthreads();                       // the outputs are staged; every wave has left the dO tile
+      // a thread reads out the pieces that its own share of the next tile replaces: no barrier in between
+      la_u32x4 ovec[6];
+#pragma unroll
+      for (int p = 0; p < 6; ++p) ovec[p] = *reinterpret_cast<const la_lds16*>(lq + 16 * (p / 3) * P4 + (p % 3) * D);
+      if (more) to_lds();
+      // the statistics are younger than the tile loads just waited for: wait for them here as well, ahead of the stores - the next
+      // dq phase would wait with vmcnt(0), behind the stores and the prefetch issued in front of it
+      asm volatile("" ::"v"(qsn.x), "v"(qsn.y));
+      uint16_t* ot = reinterpret_cast<uint16_t*>(dqkv) + ((long long)b * N + n0) * 3 * D;
+#pragma unroll
+      for (int p = 0; p < 6; ++p)
+        if (pr + 16 * (p / 3) < n_end - n0) *reinterpret_cast<la_u32x4*>(ot + 16 * (p / 3) * 3 * D + (p % 3) * D + go3) = ovec[p];
+      __syncthreads();                       // the next tile is in place
+    }
+  } else {
+    RowTile<T, D, 3 * D, LD3> tq;
+    RowTile<T, D, D, LD1> tg;
+    tq.load(qb, 3 * D, 0, n_begin, n_end, tid);
+    tg.load(gb, D, 0, n_begin, n_end, tid);
+    float2 qsn = load_qs(n_begin);
+    tq.store(smem, tid);
+    tg.store(gt, tid);
+    __syncthreads();
+    for (int n0 = n_begin; n0 < n_end; n0 += TOK) {
+      const float rmax = qsn.x, rinv = qsn.y;
+      const bool more = n0 + TOK < n_end;
+      if (more) {
+        tq.load(qb, 3 * D, 0, n0 + TOK, n_end, tid);
+        tg.load(gb, D, 0, n0 + TOK, n_end, tid);
+        qsn = load_qs(n0 + TOK);
+      }
+      const float* qrow = &smem[li * LD3 + wave * DK];
+      const float* krow = qrow + D;
+      const float* vrow = qrow + 2 * D;
+      const float* grow = &gt[li * LD1 + wave * DK];
+
+      // B operands with the token on the lane: channels 16*lh + s
+      float gj[16], kk[16], vj[16];
+  #pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const float4 a = *reinterpret_cast<const float4*>(grow + 16 * lh + 4 * q4);
+        const float4 c = *reinterpret_cast<const float4*>(krow + 16 * lh + 4 * q4);
+        const float4 e = *reinterpret_cast<const float4*>(vrow + 16 * lh + 4 * q4);
+        gj[4 * q4] = a.x; gj[4 * q4 + 1] = a.y; gj[4 * q4 + 2] = a.z; gj[4 * q4 + 3] = a.w;
+        kk[4 * q4] = c.x; kk[4 * q4 + 1] = c.y; kk[4 * q4 + 2] = c.z; kk[4 * q4 + 3] = c.w;
+        vj[4 * q4] = e.x; vj[4 * q4 + 1] = e.y; vj[4 * q4 + 2] = e.z; vj[4 * q4 + 3] = e.w;
+      }
+      f32x16 aq, av, ak;
+  #pragma unroll
+      for (int r = 0; r < 16; ++r) { aq[r] = 0.f; av[r] = 0.f; ak[r] = 0.f; }
+  #pragma unroll
       for (int s = 0; s < 16; ++s) {
         const int ch = 16 * lh + s;
         const float pk = __expf(kk[s] - cs[ch]) * cs[32 + ch];                  // P[t][i=ch]
@@ -943,62 +1119,62 @@ __global__ void __launch_bounds__(2 * D, 2) linattn_bwd_apply(const T* __restric
         av = __builtin_amdgcn_mfma_f32_32x32x2f32(dcT[s], pk, av, 0, 0, 0);      // dvT[j][t]   (A[row=j][kk=i] = dctx[i][j])
         ak = __builtin_amdgcn_mfma_f32_32x32x2f32(dcA[s], vj[s], ak, 0, 0, 0);   // dPT[i][t]
       }
-    }
-    // registers hold rows idx(r) = (r&3) + 8*(r>>2) + 4*half of token li: 4 groups of 4 contiguous channels
-    float dot = 0.f;
-    float qsv[16], pkv[16];
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      const int i0 = 8 * g4 + 4 * lh;
-      const float4 qv = *reinterpret_cast<const float4*>(qrow + i0);
-      const float4 kv = *reinterpret_cast<const float4*>(krow + i0);
-      const float qa[4] = {qv.x, qv.y, qv.z, qv.w}, ka[4] = {kv.x, kv.y, kv.z, kv.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int r = 4 * g4 + e;
-        qsv[r] = __expf(qa[e] - rmax) * rinv;                 // qs[t][i] = p/sqrt(32)
-        pkv[r] = __expf(ka[e] - cs[i0 + e]) * cs[32 + i0 + e];
-        dot += qsv[r] * aq[r];
+      // registers hold rows idx(r) = (r&3) + 8*(r>>2) + 4*half of token li: 4 groups of 4 contiguous channels
+      float dot = 0.f;
+      float qsv[16], pkv[16];
+  #pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const int i0 = 8 * g4 + 4 * lh;
+        const float4 qv = *reinterpret_cast<const float4*>(qrow + i0);
+        const float4 kv = *reinterpret_cast<const float4*>(krow + i0);
+        const float qa[4] = {qv.x, qv.y, qv.z, qv.w}, ka[4] = {kv.x, kv.y, kv.z, kv.w};
+  #pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r = 4 * g4 + e;
+          qsv[r] = __expf(qa[e] - rmax) * rinv;                 // qs[t][i] = p/sqrt(32)
+          pkv[r] = __expf(ka[e] - cs[i0 + e]) * cs[32 + i0 + e];
+          dot += qsv[r] * aq[r];
+        }
       }
-    }
-    dot = xhalf_sum(dot);
-    dot *= 5.65685424949238019521f;                           // sum_i p_i dqs_i = sqrt(32) * sum_i qs_i dqs_i
-    __syncthreads();   // all waves finished reading the staged tile
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      const int i0 = 8 * g4 + 4 * lh;
-      float4 oq, ok4, ov;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int r = 4 * g4 + e;
-        f4at(oq, e) = qsv[r] * (aq[r] - dot);
-        f4at(ok4, e) = pkv[r] * (ak[r] - cs[64 + i0 + e]);
-        f4at(ov, e) = av[r];
+      dot = xhalf_sum(dot);
+      dot *= 5.65685424949238019521f;                           // sum_i p_i dqs_i = sqrt(32) * sum_i qs_i dqs_i
+      __syncthreads();   // all waves finished reading the staged tile
+  #pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const int i0 = 8 * g4 + 4 * lh;
+        float4 oq, ok4, ov;
+  #pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r = 4 * g4 + e;
+          f4at(oq, e) = qsv[r] * (aq[r] - dot);
+          f4at(ok4, e) = pkv[r] * (ak[r] - cs[64 + i0 + e]);
+          f4at(ov, e) = av[r];
+        }
+        *reinterpret_cast<float4*>(&smem[li * LD3 + wave * DK + i0]) = oq;
+        *reinterpret_cast<float4*>(&smem[li * LD3 + D + wave * DK + i0]) = ok4;
+        *reinterpret_cast<float4*>(&smem[li * LD3 + 2 * D + wave * DK + i0]) = ov;
       }
-      *reinterpret_cast<float4*>(&smem[li * LD3 + wave * DK + i0]) = oq;
-      *reinterpret_cast<float4*>(&smem[li * LD3 + D + wave * DK + i0]) = ok4;
-      *reinterpret_cast<float4*>(&smem[li * LD3 + 2 * D + wave * DK + i0]) = ov;
+      __syncthreads();
+      constexpr int VPR = 3 * D / W, NOUT = (TOK * VPR + NTHR - 1) / NTHR;
+      typename GVec<T>::reg ovec[NOUT];
+  #pragma unroll
+      for (int p = 0; p < NOUT; ++p) {
+        const int idx = min(tid + p * NTHR, TOK * VPR - 1);
+        ovec[p] = GVec<T>::pack_lds(&smem[(idx / VPR) * LD3 + (idx % VPR) * W]);
+      }
+      __syncthreads();                       // the staging has been read: the region takes the next tile
+      if (more) {
+        tq.store(smem, tid);
+        tg.store(gt, tid);
+      }
+  #pragma unroll
+      for (int p = 0; p < NOUT; ++p) {
+        const int idx = tid + p * NTHR;
+        const int t = idx / VPR, c = (idx % VPR) * W;
+        if (idx < TOK * VPR && n0 + t < n_end) GVec<T>::store_g(dqkv + ((long long)b * N + n0 + t) * 3 * D + c, ovec[p]);
+      }
+      __syncthreads();                       // the next tile is in place
     }
-    __syncthreads();
-    constexpr int VPR = 3 * D / W, NOUT = (TOK * VPR + NTHR - 1) / NTHR;
-    typename GVec<T>::reg ovec[NOUT];
-#pragma unroll
-    for (int p = 0; p < NOUT; ++p) {
-      const int idx = min(tid + p * NTHR, TOK * VPR - 1);
-      ovec[p] = GVec<T>::pack_lds(&smem[(idx / VPR) * LD3 + (idx % VPR) * W]);
-    }
-    __syncthreads();                       // the staging has been read: the region takes the next tile
-    if (more) {
-      tq.store(smem, tid);
-      tg.store(gt, tid);
-    }
-#pragma unroll
-    for (int p = 0; p < NOUT; ++p) {
-      const int idx = tid + p * NTHR;
-      const int t = idx / VPR, c = (idx % VPR) * W;
-      if (idx < TOK * VPR && n0 + t < n_end) GVec<T>::store_g(dqkv + ((long long)b * N + n0 + t) * 3 * D + c, ovec[p]);
-    }
-    __syncthreads();                       // the next tile is in place
   }
 }
 
@@ -1020,7 +1196,13 @@ static int pick_splits(int B, int N, int d, int* tokens_per_split) {
 }
 // tokens per workgroup of the per-token kernels: ~512 workgroups, whole tiles
 static int pick_tokb(int B, int N, int d) {
-  // d <= 128: two workgroups fit a CU (66 KB of LDS, <= 256 VGPRs) -> 512 workgroups; d = 256: one (132 KB) -> 256.  Swept 128 .. 1024.
+  // First sweep (fp32 tiles in linattn_bwd_apply: two workgroups per CU at d <= 128, one at d = 256), 128 .. 1024: 512 and 256.
+  // Second sweep, bf16 storage with the bf16-tile linattn_bwd_apply (four and two workgroups per CU), backward us at B = 2 and
+  // N = 57408 (d = 128) | 10752 | 4320 | 512 (d = 256), profiles/linattn_bwd_apply_gen2.txt:
+  //   blocks  128: 62.0 | 35.0 | 24.1 | 13.8     256: 61.6 | 29.4 | 21.7 | 13.8     384: 64.3 | 31.0 | 22.9 | 13.9
+  //           512: 59.5 | 31.0 | 23.1 | 13.9     768: 59.5 | 31.8 | 23.1 | 13.9    1024: 61.5 | 31.8 | 22.9 | 13.9    2048: 62.8 | 31.7 | 22.8 | 13.8
+  // 512 at d <= 128 and 256 at d = 256 remain the best: at d = 256 a second resident workgroup helps more through longer runs (256
+  // workgroups = one wave of them on 256 CUs) than through more of them; the forward column does not move with the knob.
   const int blocks = ltu_knob_pos("LTU_LA_TOKB_BLOCKS", d <= 128 ? 512 : 256);
   long long per = ((long long)B * N + blocks - 1) / blocks;
   int tokb = (int)((per + 31) / 32 * 32);
@@ -1109,7 +1291,8 @@ extern "C" int ltu_linattn_bwd(const void* qkv, const void* dout, const float* c
   const int nsplit = pick_splits(B, N, d, &tps);
   if ((long long)B * nsplit * H * 1024 > ws_floats) return LTU_E_ARG;
   hipStream_t st = (hipStream_t)s;
-  const size_t lds_b = (size_t)(32 * (3 * d + 4) + 32 * (d + 4) + H * 96) * sizeof(float);
+  const size_t lds_b = dtype == LTU_BF16 ? (size_t)TOK * (4 * d + LAB_PAD) * 2 + (size_t)H * 96 * sizeof(float) + (size_t)2 * d * 16
+                                         : (size_t)(32 * (3 * d + 4) + 32 * (d + 4) + H * 96) * sizeof(float);
   const int tokb = pick_tokb(B, N, d);
   LTU_DISPATCH_T(dtype, {
     LA_DISPATCH_D(d, {
