@@ -557,6 +557,42 @@ int ltu_lesion_stats(const float* pred, const uint8_t* target, int* ints, float*
  * decoupled weight decay, bias correction with `step` (>= 1), gradient multiplied by grad_scale on load. */
 int ltu_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
               float weight_decay, long long step, float grad_scale, ltu_stream_t s);
+/* The guarded step (csrc/optim.hip): clipping by the global gradient norm, skipping a step whose gradient is not finite (what
+ * GradScaler.step does in utils/utils_3D_monai.py:103-105) and an exponential moving average of the weights, in
+ * 2 x buckets + 1 launches with no host read and no atomics.  All buffers are 16-byte aligned fp32 unless stated.
+ *   sequence    for each bucket b: ltu_grad_sumsq(g_b, n_b, grad_scale, scratch + off_b, cap - off_b) with off_b = the sum of
+ *               ltu_grad_sumsq_parts(n) over the buckets before b, then ONE ltu_adamw_guard(scratch, sum of all parts, state, ...),
+ *               then for each bucket ltu_adamw_guarded(..., state).
+ *   sumsq       one fp32 partial per workgroup = the sum of (g[i] * grad_scale)^2 over the workgroup's elements.  The number of
+ *               partials, ltu_grad_sumsq_parts(n), depends on n ONLY (no knob, no environment), so the query and the launch
+ *               cannot disagree.  scratch needs 4-byte alignment only (rows of several buckets lie next to each other).
+ *   guard       folds `parts` partials in index order in fp64 and updates the GUARD STATE, LTU_GUARD_STATE_BYTES = 48 bytes that
+ *               the caller zero-fills once and the kernels own from then on.  32-bit words:
+ *                 0  norm     f32  sqrt of the sum: the norm of the scaled gradient before clipping (clip_grad_norm_'s return value)
+ *                 1  coef     f32  grad_scale * min(1, max_norm / (norm + 1e-6)); grad_scale when max_norm <= 0; 0 on a skipped step
+ *                 2  bc1      f32  1 - beta1^applied, computed in double
+ *                 3  bc2      f32  1 - beta2^applied, computed in double
+ *                 4  skip     i32  1 iff skip_nonfinite != 0 and norm is inf or NaN (an inf / NaN anywhere in a bucket, or a
+ *                                  finite gradient whose square overflows fp32, makes the sum non-finite)
+ *                 5  reserved
+ *                 6-7  applied  i64  steps applied so far (the t of the bias corrections); a skipped step leaves it and bc1 / bc2 alone
+ *                 8-9  skipped  i64  steps skipped so far
+ *                 10-11  reserved
+ *               The counters live on the device so that a skipped step does not advance the bias correction and the host never
+ *               has to read the decision back (the sequence can be captured into a graph and replayed).
+ *   guarded     ltu_adamw's arithmetic in the same order with grad_scale = coef and the bias corrections bc1 / bc2 of the state.
+ *               skip = 1: returns without writing anything.  ema (nullable): ema = ema_decay * ema + (1 - ema_decay) * p_new in
+ *               the same pass; ema_decay must be in [0, 1) then.
+ * Two calls on the same buckets give bit-identical results; data-parallel ranks hold identical reduced buckets and so take
+ * identical decisions without communication (like every N > 1 path here this has not run on hardware).
+ * LTU_E_ARG: a scratch shorter than the launch writes, a misaligned or NULL pointer, a NaN max_norm, a bad ema_decay. */
+#define LTU_GUARD_STATE_BYTES 48
+long long ltu_grad_sumsq_parts(long long n);
+int ltu_grad_sumsq(const float* g, long long n, float grad_scale, float* scratch, long long scratch_floats, ltu_stream_t s);
+int ltu_adamw_guard(const float* scratch, long long parts, void* state, float grad_scale, float max_norm /* <= 0: no clipping */,
+                    int skip_nonfinite, float beta1, float beta2, ltu_stream_t s);
+int ltu_adamw_guarded(float* p, const float* g, float* m, float* v, float* ema /* nullable */, long long n, float lr, float beta1,
+                      float beta2, float eps, float weight_decay, float ema_decay, const void* state, ltu_stream_t s);
 
 /* ---- data-parallel gradient exchange (replaces the reduce half of nn.DataParallel, train3D.py:119) -------------------------------
  * Direct RCCL calls: one communicator per process (= per GPU), created from a 128-byte unique id that rank 0 generates and the

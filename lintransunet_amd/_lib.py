@@ -103,6 +103,10 @@ SIGNATURES = {
     'ltu_resample_grid': [P, I, P, I, I, I, L, L, L, P, P, I, I, I, L, L, L, P, I, F, F, F, F, P],
     'ltu_crop_orient': [P, P, P, P, P, I, I, I, I, I, I, I, P],
     'ltu_adamw': [P, P, P, P, L, F, F, F, F, F, L, F, P],
+    'ltu_grad_sumsq_parts': [L],
+    'ltu_grad_sumsq': [P, L, F, P, L, P],
+    'ltu_adamw_guard': [P, L, P, F, F, I, F, F, P],
+    'ltu_adamw_guarded': [P, P, P, P, P, L, F, F, F, F, F, F, P, P],
     'ltu_norm_ws_floats': [],
     'ltu_instnorm_stats': [P, P, P, L, I, L, I, I, P],
     'ltu_instnorm_apply': [P, P, P, P, I, L, I, I, F, F, U, P, I, P],
@@ -173,7 +177,7 @@ def load():
     for name, args in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = args
-        fn.restype = c_longlong if (name.endswith(('_ws_floats', '_ws_elems')) or name == 'ltu_layer_tail_blocks') else c_int
+        fn.restype = c_longlong if (name.endswith(('_ws_floats', '_ws_elems')) or name in ('ltu_layer_tail_blocks', 'ltu_grad_sumsq_parts')) else c_int
     for name, args in EXPERIMENT_SIGNATURES.items():
         fn = getattr(lib, name, None)
         if fn is not None:
