@@ -390,8 +390,8 @@ int ltu_loss_fwd(const float* p, const uint8_t* label, float* sums, long long su
                  float w_ce, float w_bal, const float* w_dice, const float* scale_dev, ltu_stream_t s);
 int ltu_loss_bwd(const float* p, const uint8_t* label, const float* coef, const float* gscale, float* dp, int B,
                  long long S, int C, ltu_stream_t s);
-/* ---- the same losses for 2 <= C <= 8 classes (csrc/manyclass.hip; loss/multi_criterions.py:58-83, DiceClassLoss(class_index)) ----
- * The arithmetic of ltu_loss_fwd with room for 8 classes.  w_dice: C + 1 host floats, the Dice weight of every class, then that
+/* ---- the same losses for 2 <= C <= 8 classes (csrc/loss.hip; loss/multi_criterions.py:58-83, DiceClassLoss(class_index)) ----
+ * The kernels of ltu_loss_fwd with room for 8 classes.  w_dice: C + 1 host floats, the Dice weight of every class, then that
  * of the foreground union.  values (C + 5 floats): [0] = total, [1] = CE, [2] = balanced Dice, [3 + c] = Dice_c, [3 + C] = union
  * Dice, [4 + C] = total again.  sums: scratch of ltu_loss_wide_ws_floats(B, S, C) floats, no initialisation, folded in a fixed
  * order (no floating-point atomics: two calls agree bit for bit).  coef [B][C][3] feeds ltu_loss_wide_bwd (ltu_loss_bwd hands C > 4

@@ -256,6 +256,16 @@ static inline int ltu_check_launch() {
 
 static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
+// voxels per block of the level losses' sums pass (loss.hip, loss_ext.hip): about 1024 blocks over the batch, at least one trip of
+// 256 threads, a multiple of 4 so that every block of the four-voxel kernels starts on a 16-byte boundary
+static inline long long loss_rows(int B, long long S) {
+  long long want = 1024 / (B > 0 ? B : 1);
+  if (want < 1) want = 1;
+  long long rows = (S + want - 1) / want;
+  if (rows < 256) rows = 256;
+  return (rows + 3) / 4 * 4;
+}
+
 // dtype dispatch for host wrappers
 #define LTU_DISPATCH_T(dtype, ...)                           \
   do {                                                       \

@@ -488,14 +488,6 @@ __global__ void __launch_bounds__(256) lx_bwd_kernel(const float* __restrict__ p
   }
 }
 
-static long long lx_rows(int B, long long S) {
-  long long want = 1024 / (B > 0 ? B : 1);
-  if (want < 1) want = 1;
-  long long rows = (S + want - 1) / want;
-  if (rows < 256) rows = 256;
-  return (rows + 3) / 4 * 4;
-}
-
 // 0 = usable; LTU_E_SHAPE / LTU_E_ARG otherwise.  Flags: the sums and derivative terms the nonzero weights need.
 static int lx_check(int B, long long S, int C, const float* cfg, unsigned* fl) {
   if (C < 2 || C > LX_MAXC || B < 1 || S < 1 || (long long)B * lx_row(C) > LX_FIN) return LTU_E_SHAPE;
@@ -515,7 +507,7 @@ static int lx_check(int B, long long S, int C, const float* cfg, unsigned* fl) {
 }
 
 extern "C" long long ltu_loss_ext_ws_floats(int B, long long S, int C) {
-  return (1 + cdiv(S, lx_rows(B, S))) * (long long)B * lx_row(C);
+  return (1 + cdiv(S, loss_rows(B, S))) * (long long)B * lx_row(C);
 }
 
 extern "C" int ltu_loss_ext_fwd(const float* p, const uint8_t* label, float* sums, long long sums_floats, float* values, float* coef, int B,
@@ -523,7 +515,7 @@ extern "C" int ltu_loss_ext_fwd(const float* p, const uint8_t* label, float* sum
   unsigned fl = 0;
   const int rc = lx_check(B, S, C, cfg, &fl);
   if (rc != LTU_OK) return rc;
-  const long long rows = lx_rows(B, S);
+  const long long rows = loss_rows(B, S);
   const int nblk = (int)cdiv(S, rows);
   if (sums == nullptr || (1 + (long long)nblk) * B * lx_row(C) > sums_floats) return LTU_E_ARG;
   LossExtCfg c;

@@ -35,8 +35,8 @@ class LevelCriterion(nn.Module):
     spec: {name: weight}.  A spec made only of the names of the original family, {'CrossEntroLoss', 'BalanceDiceLoss',
     'DiceClassLoss' (class 1), 'DiceClassLoss2' .. 'DiceClassLoss7' (classes 2 .. 7, the reference's
     multi_criterions.DiceClassLoss(class_index)), 'DiceClassLoss0c' (class 0), 'DiceClassLoss0' (foreground union
-    1 - class 0, multi_criterions.py:30-56)}, runs ops.level_loss (csrc/loss.hip) on predictions of up to 4 classes and
-    ops.level_loss_wide (csrc/manyclass.hip) on 5 .. 8.  A spec with any name of `EXT` runs the
+    1 - class 0, multi_criterions.py:30-56)}, runs ops.level_loss on predictions of up to 4 classes and
+    ops.level_loss_wide on 5 .. 8 (both csrc/loss.hip).  A spec with any name of `EXT` runs the
     whole spec through ops.level_loss_ext (csrc/loss_ext.hip), which also carries the original terms but stops at 4 classes.
     params: the parameters
     of the wider family (ops.LOSS_EXT_PARAMS: gamma, sigma, alpha, alpha2, eps; defaults ops.LOSS_EXT_DEFAULTS).  Returns

@@ -1640,91 +1640,62 @@ def attention_gate(skip, up, wx, bx, wg, bg, pw, pb, prep_x=None, prep_g=None):
 # ---------------------------------------------------------------------------------------------- loss
 
 class _LevelLoss(torch.autograd.Function):
-    """Weighted sum of the losses of one decoder level; returns (total, values[1+2+C]) with values detached."""
+    """Weighted sum of the losses of one decoder level through one entry-point family of csrc/loss.hip: `entry` = 'ltu_loss'
+    (w_dice: 5 weights, nv = 9 values) or 'ltu_loss_wide' (C + 1 weights, nv = C + 5).  Returns (total, values[:nv - 1]) with
+    values detached."""
 
     @staticmethod
-    def forward(ctx, p, label, w_ce, w_bal, w_dice, scale_dev):
-        lc = ctx.lc = current()
+    def forward(ctx, p, label, w_ce, w_bal, w_dice, scale_dev, entry, nv):
+        ctx.lc = current()
+        ctx.entry = entry
         _chk(p, 'p'); _chk(label, 'label')
         B, C = p.shape[0], p.shape[-1]
         S = p.numel() // (B * C)
         dev = p.device
-        sums = torch.empty(_lib.load().ltu_loss_ws_floats(B, S, C), device=dev, dtype=torch.float32)      # partials + sums: no zero fill
-        buf = torch.empty(9, device=dev, dtype=torch.float32)
-        values = buf[:8]                 # the report (non-differentiable); buf[8] repeats the total as the differentiable output, so
+        need = getattr(_lib.load(), entry + '_ws_floats')(B, S, C)
+        sums = torch.empty(need, device=dev, dtype=torch.float32)      # partials + sums: no zero fill
+        buf = torch.empty(nv, device=dev, dtype=torch.float32)
+        values = buf[:nv - 1]            # the report (non-differentiable); buf[nv - 1] repeats the total as the differentiable output, so
         coef = torch.empty((B, C, 3), device=dev, dtype=torch.float32)          # no copy kernel is needed to separate the two
-        wd = (ctypes.c_float * 5)(*[float(w_dice[c]) if c < len(w_dice) else 0.0 for c in range(5)])
-        _lib.call('ltu_loss_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(values), _p(coef), B, S, C, float(w_ce), float(w_bal), wd, _p(scale_dev), _s())
+        wd = (ctypes.c_float * len(w_dice))(*w_dice)
+        _lib.call(entry + '_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(values), _p(coef), B, S, C, float(w_ce), float(w_bal), wd,
+                  _p(scale_dev), _s())
         ctx.save_for_backward(p, label, coef)
         ctx.mark_non_differentiable(values)
         ctx.set_materialize_grads(False)         # no zero-filled gradient tensor for the report output
-        return buf[8], values
+        return buf[nv - 1], values
 
     @staticmethod
     def backward(ctx, g, _gv):
-        lc = ctx.lc
         p, label, coef = ctx.saved_tensors
         B, C = p.shape[0], p.shape[-1]
         S = p.numel() // (B * C)
         if g is None:
-            return None, None, None, None, None, None
+            return (None,) * 8
         g = g.contiguous().to(torch.float32)
         dp = torch.empty_like(p)
-        _lib.call('ltu_loss_bwd', _p(p), _p(label), _p(coef), _p(g), _p(dp), B, S, C, _s())
-        return dp, None, None, None, None, None
+        _lib.call(ctx.entry + '_bwd', _p(p), _p(label), _p(coef), _p(g), _p(dp), B, S, C, _s())
+        return (dp,) + (None,) * 7
 
 
 def level_loss(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
     """p fp32 [B,...,C] channels-last probabilities (C <= 4), label uint8 [B,...]: weighted CE + balanced Dice + per-class Dice
     (w_dice[c], c < 4) + Dice of the foreground union (w_dice[4]).  5 .. 8 classes: level_loss_wide.
     scale_dev: optional 1-element fp32 device tensor multiplying all weights at run time."""
-    return _LevelLoss.apply(p, label, w_ce, w_bal, tuple(w_dice), scale_dev)
+    wd = tuple(float(w_dice[c]) if c < len(w_dice) else 0.0 for c in range(5))
+    return _LevelLoss.apply(p, label, w_ce, w_bal, wd, scale_dev, 'ltu_loss', 9)
 
 
 LOSS_WIDE_MAXC = 8      # LTU_WIDE_MAXC of csrc/manyclass.h
 
 
-class _LevelLossWide(torch.autograd.Function):
-    """_LevelLoss for 2 <= C <= 8 (csrc/manyclass.hip); returns (total, values[3 + C + 1]) with values detached."""
-
-    @staticmethod
-    def forward(ctx, p, label, w_ce, w_bal, w_dice, scale_dev):
-        ctx.lc = current()
-        _chk(p, 'p'); _chk(label, 'label')
-        B, C = p.shape[0], p.shape[-1]
-        S = p.numel() // (B * C)
-        dev = p.device
-        if len(w_dice) != C + 1:
-            raise ValueError(f'level_loss_wide: w_dice has {len(w_dice)} entries, {C} classes need {C + 1} (per class, then the foreground union)')
-        sums = torch.empty(_lib.load().ltu_loss_wide_ws_floats(B, S, C), device=dev, dtype=torch.float32)      # partials + sums: no zero fill
-        buf = torch.empty(C + 5, device=dev, dtype=torch.float32)
-        values = buf[:C + 4]             # the report (non-differentiable); buf[C + 4] repeats the total as the differentiable output
-        coef = torch.empty((B, C, 3), device=dev, dtype=torch.float32)
-        wd = (ctypes.c_float * (C + 1))(*[float(w) for w in w_dice])
-        _lib.call('ltu_loss_wide_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(values), _p(coef), B, S, C, float(w_ce), float(w_bal), wd,
-                  _p(scale_dev), _s())
-        ctx.save_for_backward(p, label, coef)
-        ctx.mark_non_differentiable(values)
-        ctx.set_materialize_grads(False)         # no zero-filled gradient tensor for the report output
-        return buf[C + 4], values
-
-    @staticmethod
-    def backward(ctx, g, _gv):
-        p, label, coef = ctx.saved_tensors
-        B, C = p.shape[0], p.shape[-1]
-        S = p.numel() // (B * C)
-        if g is None:
-            return None, None, None, None, None, None
-        g = g.contiguous().to(torch.float32)
-        dp = torch.empty_like(p)
-        _lib.call('ltu_loss_wide_bwd', _p(p), _p(label), _p(coef), _p(g), _p(dp), B, S, C, _s())
-        return dp, None, None, None, None, None
-
-
 def level_loss_wide(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
     """level_loss for 2 <= C <= 8 classes: w_dice has C + 1 entries (the Dice weight of every class, then that of the foreground
     union); values = [total, CE, balanced Dice, Dice_0 .. Dice_{C-1}, union Dice] (detached)."""
-    return _LevelLossWide.apply(p, label, w_ce, w_bal, tuple(w_dice), scale_dev)
+    C = p.shape[-1]
+    if len(w_dice) != C + 1:
+        raise ValueError(f'level_loss_wide: w_dice has {len(w_dice)} entries, {C} classes need {C + 1} (per class, then the foreground union)')
+    return _LevelLoss.apply(p, label, w_ce, w_bal, tuple(float(w) for w in w_dice), scale_dev, 'ltu_loss_wide', C + 5)
 
 
 # term and parameter slots of the config array of ltu_loss_ext_fwd / ltu_loss_ext_bwd (the LTU_LOSS_EXT_* enum of include/ltu_hip.h)

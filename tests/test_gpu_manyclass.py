@@ -1,6 +1,6 @@
-"""GPU tests of the 5 .. 8-class training path (csrc/manyclass.hip and what it plugs into): the wide head kernels and the wide
-level loss against float64 restatements, the final conv and the level-0 / level-1 conv pairs at the new output widths (each kernel
-by name, against float64), the whole model against fixtures generated from the reference with dim_output = 5 and 8
+"""GPU tests of the 5 .. 8-class training path (csrc/manyclass.hip and what it plugs into): the wide head kernels and the level
+loss (csrc/loss.hip, both value layouts) against float64 restatements, the final conv and the level-0 / level-1 conv pairs at the
+new output widths (each kernel by name, against float64), the whole model against fixtures generated from the reference with dim_output = 5 and 8
 (tests/golden/make_golden_manyclass.py), the captured step, the evaluation chain and the refusal of 9 classes.
 
 Shapes are the smallest that reach every path: M = 1031 rows (5 blocks, a tail), the final head on 2 x 3 x 5 x 7 coarse voxels (a grid
@@ -20,6 +20,7 @@ from oracle import seedgen
 from oracle import step as O_step
 from tests import manyclass_common as MC
 from tests import test_gpu_conv_paths as CP
+from tests.test_gpu_ops import _with_knob
 
 pytestmark = pytest.mark.gpu
 
@@ -134,11 +135,24 @@ def test_final_softmax_wide(ops, C, dtype, CP):
 
 def _loss_inputs(C, S, seed, B=2):
     g = G(seed)
-    p = torch.softmax(torch.randn(B, S, C, generator=g) * 1.5, -1)
+    if C == 1:
+        p = 0.01 + 0.98 * torch.rand(B, S, 1, generator=g)          # a one-class softmax row is constant 1: uniform in (0.01, 0.99) instead
+    else:
+        p = torch.softmax(torch.randn(B, S, C, generator=g) * 1.5, -1)
     lab = torch.randint(0, C, (B, S), generator=g).to(torch.uint8)
     lab[0, S // 3] = C + 1                                        # a label value that is no class of the prediction
     w = 0.25 + torch.rand(3 + C, generator=g)                      # w_ce, w_bal, w_dice[0 .. C-1], w_fg: all non-zero
     return p, lab, [float(v) for v in w]
+
+
+def _narrow_dice(w, C):
+    """the 5 Dice weights of ops.level_loss (classes 0 .. 3, union) from the C + 1 of ops.level_loss_wide"""
+    return w[2:2 + C] + [0.0] * (4 - C) + [w[2 + C]]
+
+
+def _narrow_live(C):
+    """slots of the 8-entry report of ops.level_loss that C classes fill, in the order of the wide report"""
+    return [0, 1, 2] + [3 + c for c in range(C)] + [7]
 
 
 def _loss_reference(p, lab, w, scale):
@@ -158,10 +172,8 @@ def _loss_reference(p, lab, w, scale):
     return total.item(), [ce.item(), bal.item()] + [d.item() for d in dice] + [fg.item()], pr.grad
 
 
-@pytest.mark.parametrize('S', [4096, 2052, 1003])
-@pytest.mark.parametrize('C', [5, 8])
-def test_level_loss_wide(ops, C, S):
-    """tolerances of test_gpu_ops.py::test_losses_golden on ltu_loss_fwd / ltu_loss_bwd (values 1e-4, gradient 1e-4 of its max)"""
+def _check_level_loss(ops, C, S, wide):
+    """either layout of the level loss against float64, with and without the device-resident scale; two calls bit-identical"""
     p, lab, w = _loss_inputs(C, S, 300 + C + S)
     for scale in (None, 0.37):
         total_ref, vals_ref, dp_ref = _loss_reference(p, lab, w, 1.0 if scale is None else scale)
@@ -169,13 +181,18 @@ def test_level_loss_wide(ops, C, S):
         runs = []
         for _ in range(2):
             pd = p.to(DEV).requires_grad_(True)
-            tot, values = ops.level_loss_wide(pd, lab.to(DEV), w[0], w[1], w[2:], sc)
+            if wide:
+                tot, values = ops.level_loss_wide(pd, lab.to(DEV), w[0], w[1], w[2:], sc)
+            else:
+                tot, values = ops.level_loss(pd, lab.to(DEV), w[0], w[1], _narrow_dice(w, C), sc)
             tot.backward()
             torch.cuda.synchronize()
-            runs.append((tot.detach().clone(), values.detach().clone(), pd.grad.clone()))
+            assert values.shape == ((C + 4,) if wide else (8,))
+            live = values.detach() if wide else values.detach()[_narrow_live(C)]      # the 8-entry report leaves the slots of absent classes unwritten
+            runs.append((tot.detach().clone(), live.clone(), pd.grad.clone()))
         (t0, v0, g0), (t1, v1, g1) = runs
         assert torch.equal(t0, t1) and torch.equal(v0, v1) and torch.equal(g0, g1), 'two calls must be bit-identical'
-        assert v0.shape == (C + 4,) and t0.item() == v0[0].item()
+        assert t0.item() == v0[0].item()
         assert abs(t0.item() - total_ref) <= 1e-4 * max(1.0, abs(total_ref)), (t0.item(), total_ref)
         got = v0[1:].cpu().tolist()
         assert np.allclose(got, vals_ref, rtol=0, atol=1e-4), (got, vals_ref)
@@ -183,20 +200,44 @@ def test_level_loss_wide(ops, C, S):
 
 
 @pytest.mark.parametrize('S', [4096, 2052, 1003])
-def test_level_loss_wide_equals_narrow_at_4_classes(ops, S):
-    """the same statements in the same order: at C = 4 ltu_loss_wide_fwd / _bwd and ltu_loss_fwd / _bwd agree to the last bit"""
-    C = 4
+@pytest.mark.parametrize('C', [5, 8])
+def test_level_loss_wide(ops, C, S):
+    """tolerances of test_gpu_ops.py::test_losses_golden on ltu_loss_fwd / ltu_loss_bwd (values 1e-4, gradient 1e-4 of its max)"""
+    _check_level_loss(ops, C, S, wide=True)
+
+
+@pytest.mark.parametrize('S', [2052, 1003])
+@pytest.mark.parametrize('C', [1, 2, 3])
+def test_level_loss_narrow(ops, C, S):
+    """the 9-value layout (ops.level_loss) at the class counts the wide test leaves out, same tolerances: the four-voxel path
+    with a short last block (2052; one voxel per thread at C = 1) and the one-voxel path (1003)"""
+    _check_level_loss(ops, C, S, wide=False)
+
+
+WIDE_NARROW = [(C, S, False) for C in (2, 3, 4) for S in (4096, 2052, 1003)] + [(C, 4096, True) for C in (2, 3, 4)]
+
+
+@pytest.mark.parametrize('C,S,scalar', WIDE_NARROW, ids=[f'C{c}-S{s}' + ('-scalar' if k else '') for c, s, k in WIDE_NARROW])
+def test_level_loss_wide_equals_narrow(ops, C, S, scalar):
+    """one implementation behind two layouts: for C = 2 .. 4 ltu_loss_wide_fwd / _bwd and ltu_loss_fwd / _bwd agree to the last bit,
+    on the four-voxel path, its short last block, the one-voxel path and the one-voxel path forced by LTU_LOSS_SCALAR"""
     p, lab, w = _loss_inputs(C, S, 400 + S)
     sc = torch.tensor([0.61], device=DEV)
-    pa, pb = p.to(DEV).requires_grad_(True), p.to(DEV).requires_grad_(True)
-    ta, va = ops.level_loss(pa, lab.to(DEV), w[0], w[1], w[2:], sc)            # 5 Dice weights: classes 0 .. 3, union
-    tb, vb = ops.level_loss_wide(pb, lab.to(DEV), w[0], w[1], w[2:], sc)
-    ta.backward(); tb.backward()
-    torch.cuda.synchronize()
-    assert va.shape == (8,) and vb.shape == (8,)
-    print(f'[C = 4, S = {S}] narrow {va.tolist()} wide {vb.tolist()}')
-    assert torch.equal(ta, tb) and torch.equal(va, vb)
-    assert torch.equal(pa.grad, pb.grad)
+
+    def run(w):
+        pa, pb = p.to(DEV).requires_grad_(True), p.to(DEV).requires_grad_(True)
+        ta, va = ops.level_loss(pa, lab.to(DEV), w[0], w[1], _narrow_dice(w, C), sc)
+        tb, vb = ops.level_loss_wide(pb, lab.to(DEV), w[0], w[1], w[2:], sc)
+        ta.backward(); tb.backward()
+        torch.cuda.synchronize()
+        return ta.detach().clone(), va.clone(), pa.grad, tb.detach().clone(), vb.clone(), pb.grad
+    # all weights, then CE and balanced Dice alone: the total is then its first two terms, whose rounding no further term damps
+    for wk in (w, w[:2] + [0.0] * (C + 1)):
+        ta, va, ga, tb, vb, gb = _with_knob(b'LTU_LOSS_SCALAR', 1, lambda: run(wk)) if scalar else run(wk)
+        assert va.shape == (8,) and vb.shape == (C + 4,)
+        print(f'[C = {C}, S = {S}, scalar {scalar}] narrow {va.tolist()} wide {vb.tolist()}')
+        assert torch.equal(ta, tb) and torch.equal(va[_narrow_live(C)], vb)
+        assert torch.equal(ga, gb)
 
 
 # ---------------------------------------------------------------------------------------------- convs at the new widths
