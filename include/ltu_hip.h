@@ -658,6 +658,29 @@ int ltu_resample_grid(const void* src_img, int src_dtype, const uint8_t* src_lab
 int ltu_crop_orient(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const int* desc, int n, int H, int W,
                     int D, int h, int w, int d, ltu_stream_t s);
 
+/* ---- crop index: crop centres from the label on the device (csrc/crop_index.hip; no reference counterpart - monai keeps np.nonzero
+ * index lists of the whole label on the host).  lab: u8, n_voxels contiguous voxels in raster order of [H][W][D], 16-byte aligned
+ * (else LTU_E_ALIGN).  A voxel belongs to one of 9 bins: its value 0 .. 7, or bin 8 for every value >= 8.
+ *   elems:  the uint32 elements of the index buffer of a label of n_voxels, 9 * (ceil(n_voxels / 4096) + 1); 0 for a size that
+ *           build refuses.
+ *   build:  index = per bin the exclusive prefix of the bin's voxels before every block of 4096 voxels, then its population;
+ *           totals, device u64 [9] = the 9 populations (the caller reads them back once per scan).  Two launches, integer
+ *           arithmetic, no atomics: two builds of one label are byte-identical.
+ *   select: queries, device uint32 [n][2] = (mask, rank): bit b of mask (b = 0 .. 8; higher bits are ignored) puts bin b into
+ *           the set - bit 0 is the background, bits 1 .. 8 together the foreground, one bit one class.  out, device int64 [n] =
+ *           the linear voxel index of the rank-th member (from 0) of the set in ascending raster order, = np.nonzero of the
+ *           set's predicate at [rank]; -1 when rank is not below the set's population.  One wave per query: a 64-way search
+ *           over the blocks' prefixes (3 - 4 rounds of loads), then one block of the label is read.  n = 0 launches nothing.  lab and index are those
+ *           of the build; a label changed since gives -1 or a member of another rank, never an access outside lab.
+ *   Voxels at or beyond n_voxels are neither loaded nor counted.  Nothing is allocated, set or synchronised: capturable.
+ *   Refused before any launch: n_voxels outside 1 .. 2^32 - 1 LTU_E_SHAPE; a NULL pointer, index_elems below elems(n_voxels),
+ *   n < 0 LTU_E_ARG; lab not 16-byte, totals / out not 8-byte, index / queries not 4-byte aligned LTU_E_ALIGN. */
+long long ltu_crop_index_elems(long long n_voxels);
+int ltu_crop_index_build(const uint8_t* lab, long long n_voxels, uint32_t* index, long long index_elems, unsigned long long* totals,
+                         ltu_stream_t s);
+int ltu_crop_index_select(const uint8_t* lab, long long n_voxels, const uint32_t* index, long long index_elems,
+                          const uint32_t* queries, long long* out, int n, ltu_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,9 @@ SIGNATURES = {
     'ltu_crop_flip': [P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_resample_grid': [P, I, P, I, I, I, L, L, L, P, P, I, I, I, L, L, L, P, I, F, F, F, F, P],
     'ltu_crop_orient': [P, P, P, P, P, I, I, I, I, I, I, I, P],
+    'ltu_crop_index_elems': [L],
+    'ltu_crop_index_build': [P, L, P, L, P, P],
+    'ltu_crop_index_select': [P, L, P, L, P, P, I, P],
     'ltu_adamw': [P, P, P, P, L, F, F, F, F, F, L, F, P],
     'ltu_grad_sumsq_parts': [L],
     'ltu_grad_sumsq': [P, L, F, P, L, P],
@@ -177,7 +180,7 @@ def load():
     for name, args in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = args
-        fn.restype = c_longlong if (name.endswith(('_ws_floats', '_ws_elems')) or name in ('ltu_layer_tail_blocks', 'ltu_grad_sumsq_parts')) else c_int
+        fn.restype = c_longlong if (name.endswith(('_ws_floats', '_ws_elems')) or name in ('ltu_layer_tail_blocks', 'ltu_grad_sumsq_parts', 'ltu_crop_index_elems')) else c_int
     for name, args in EXPERIMENT_SIGNATURES.items():
         fn = getattr(lib, name, None)
         if fn is not None:

@@ -3,13 +3,16 @@
 dataset/CT_pancreas_ids.py:143-173: `.npy` scan [D,H,W] -> HU clip [-91, 250] -> (x - 86.9) / 39.4 -> [H,W,D] float32, label uint8;
 then RandCropByPosNegLabeld(pos=0.7, neg=0.3, num_samples) and RandFlipd(prob=0.4, spatial_axis=(0, 1)) of monai 0.7.0.  A scan
 is uploaded once; preprocessing, cropping and flipping are HIP kernels (csrc/data.hip).  Crop centres are drawn on the host from
-the label's foreground / background index lists exactly as monai does (the label comes from disk, so it is host-resident anyway).
+the label's foreground / background index lists exactly as monai does (`crop_centers`), or, without a pass over the label per
+sample, from a `CropIndex` of the device label (csrc/crop_index.hip): the host keeps the draws and needs only the populations.
 `augment` applies the remaining augmentations of the reference (RandRotated, RandAdjustContrastd, RandZoomd, RandFlipd;
 CT_pancreas_ids.py:121-134) to a batch of patches on the device; the random draws stay on the host.
 The third driver's data side (train3D_monai_version.py with dataset/CT_pancreas_monai.py: NIfTI scans of the Medical
 Segmentation Decathlon layout, ScaleIntensityRanged -> Spacingd -> Orientationd('RAS'), then crop + RandFlipd + RandRotate90d) is
 `SpacedScan` / `sample` / `to_native` at the end of this file.
 """
+import warnings
+
 import numpy as np
 import torch
 
@@ -64,6 +67,126 @@ def crop_centers(label, spatial_size, num_samples, pos=0.7, neg=0.3, rand_state=
     return centers
 
 
+FG_MASK, BG_MASK = 0x1fe, 0x001        # bin sets of ltu_crop_index_select: bit b = label value b, bit 8 = every value >= 8
+
+
+def _posneg_queries(n_fg, n_bg, num_samples, pos, neg, rs):
+    """crop_centers' draws from the two populations alone: (bin mask, rank) per sample"""
+    pos_ratio = pos / (pos + neg)
+    if n_fg == 0 and n_bg == 0:
+        raise ValueError('No sampling location available.')
+    if n_fg == 0 or n_bg == 0:
+        pos_ratio = 0 if n_fg == 0 else 1
+    queries = []
+    for _ in range(num_samples):
+        mask, count = (FG_MASK, n_fg) if rs.rand() < pos_ratio else (BG_MASK, n_bg)
+        queries.append((mask, int(rs.randint(count))))
+    return queries
+
+
+def _class_queries(counts, num_samples, ratios, rs):
+    """generate_label_classes_crop_centers' draws from the class populations alone: (bin mask, rank) per sample"""
+    if num_samples < 1:
+        raise ValueError('num_samples must be an int number and greater than 0.')
+    ratios = [1] * len(counts) if ratios is None else list(ratios)
+    if len(ratios) != len(counts):
+        raise ValueError('random crop ratios must match the number of indices of classes.')
+    if any(r < 0 for r in ratios):
+        raise ValueError('ratios should not contain negative number.')
+    for c, count in enumerate(counts):
+        if count == 0:
+            warnings.warn(f'no available indices of class {c} to crop, set the crop ratio of this class to zero.')
+            ratios[c] = 0
+    classes = rs.choice(len(ratios), size=num_samples, p=np.asarray(ratios) / np.sum(ratios))
+    return [(1 << int(c), int(rs.randint(counts[c]))) for c in classes]
+
+
+def _default_num_classes(counts):
+    """the highest populated class bin + 1 (the bin of the values >= 8 is never a class)"""
+    return max([c + 1 for c in range(8) if counts[c] > 0], default=1)
+
+
+def class_crop_centers(label, spatial_size, num_samples, ratios=None, num_classes=None, rand_state=None):
+    """centres of RandCropByLabelClassesd; label: host array [H,W,D] of class ids.  A numpy restatement of monai 0.7.0's
+    map_classes_to_indices + generate_label_classes_crop_centers (recalled, not pinned: monai is absent): the indices of class c
+    < num_classes are np.nonzero((label == c).ravel())[0]; ratios (default: all ones) must be non-negative and one per class, the
+    ratio of an empty class becomes 0 with a warning; classes = rs.choice(len(ratios), size=num_samples, p=ratios / sum), then per
+    sample rs.randint(len(indices[c])), unravel, correct_crop_centers.  num_classes None (monai demands it for a label that is not
+    one-hot) = the highest class 0 .. 7 present + 1."""
+    rs = rand_state or np.random.RandomState()
+    label = np.asarray(label)
+    flat = label.ravel()
+    if num_classes is None:
+        num_classes = _default_num_classes(np.bincount(flat.astype(np.int64), minlength=8))
+    indices = [np.nonzero(flat == c)[0] for c in range(num_classes)]
+    queries = _class_queries([len(i) for i in indices], num_samples, ratios, rs)
+    return [correct_crop_centers(list(np.unravel_index(indices[mask.bit_length() - 1][rank], label.shape)), spatial_size, label.shape)
+            for mask, rank in queries]
+
+
+class CropIndex:
+    """Per-scan crop index of a u8 device label [H, W, D] (csrc/crop_index.hip): built once, it answers "the r-th voxel of this set
+    of label values in raster order" on the device, so drawing a crop centre costs one block of the label instead of np.nonzero
+    passes over all of it.  Construction builds the index and reads the 9 populations back (the one synchronisation per scan):
+    counts[b] = voxels of value b for b < 8, counts[8] = voxels of every value >= 8 (foreground to crop_centers, never a class)."""
+
+    def __init__(self, lab):
+        if not torch.is_tensor(lab) or not lab.is_cuda:
+            raise _lib.LtuError('data.CropIndex is built from the device label (no CPU fallback)')
+        if lab.dtype != torch.uint8 or lab.dim() != 3:
+            raise ValueError(f'CropIndex takes a uint8 label [H, W, D], got {lab.dtype} {tuple(lab.shape)}')
+        self.lab = lab.contiguous()
+        self.shape = tuple(int(n) for n in lab.shape)
+        self.n_voxels = self.lab.numel()
+        elems = _lib.load().ltu_crop_index_elems(self.n_voxels)
+        if elems == 0 and self.n_voxels > 0:
+            raise ValueError(f'CropIndex: a label of {self.n_voxels} voxels is beyond 2^32 - 1')
+        self.index = torch.empty(elems, device=lab.device, dtype=torch.int32)          # uint32 words
+        if self.n_voxels == 0:                       # nothing to build: every draw from it raises as crop_centers does
+            self.counts = (0,) * 9
+        else:
+            totals = torch.empty(9, device=lab.device, dtype=torch.int64)
+            _lib.call('ltu_crop_index_build', _p(self.lab), self.n_voxels, _p(self.index), elems, _p(totals), _s())
+            self.counts = tuple(int(v) for v in totals.cpu().tolist())
+        self.n_background = self.counts[0]
+        self.n_foreground = sum(self.counts[1:])
+
+    def select(self, queries):
+        """queries [(bin mask, rank)] -> int64 numpy [n] of linear voxel indices (-1: rank not below the set's population); one
+        launch and one read-back"""
+        n = len(queries)
+        if n == 0:
+            return np.zeros(0, dtype=np.int64)
+        q = torch.from_numpy(np.asarray(queries, dtype=np.uint32).reshape(n, 2).view(np.int32)).to(self.lab.device)
+        out = torch.empty(n, device=self.lab.device, dtype=torch.int64)
+        _lib.call('ltu_crop_index_select', _p(self.lab), self.n_voxels, _p(self.index), self.index.numel(), _p(q), _p(out), n, _s())
+        return out.cpu().numpy()
+
+    def resolve(self, queries, spatial_size):
+        """the corrected centres [h, w, d] of drawn queries"""
+        idx = self.select(queries)
+        if (idx < 0).any():
+            raise _lib.LtuError('CropIndex: a drawn rank is beyond its population (the label changed after the index was built)')
+        return [correct_crop_centers(list(np.unravel_index(i, self.shape)), spatial_size, self.shape) for i in idx]
+
+    def centers(self, spatial_size, num_samples, pos=0.7, neg=0.3, rand_state=None):
+        """crop_centers(label_host, ...) from the index: the same draws from rand_state in the same order, the same centres"""
+        rs = rand_state or np.random.RandomState()
+        return self.resolve(_posneg_queries(self.n_foreground, self.n_background, num_samples, pos, neg, rs), spatial_size)
+
+    def class_queries(self, num_samples, ratios=None, num_classes=None, rand_state=None):
+        rs = rand_state or np.random.RandomState()
+        if num_classes is None:
+            num_classes = _default_num_classes(self.counts)
+        if not 1 <= num_classes <= 8:
+            raise ValueError(f'CropIndex keeps 8 classes, got num_classes {num_classes}')
+        return _class_queries(list(self.counts[:num_classes]), num_samples, ratios, rs)
+
+    def class_centers(self, spatial_size, num_samples, ratios=None, num_classes=None, rand_state=None):
+        """class_crop_centers(label_host, ...) from the index: the same draws, the same centres; num_classes <= 8"""
+        return self.resolve(self.class_queries(num_samples, ratios, num_classes, rand_state), spatial_size)
+
+
 def crop_flip(img, lab, centers, flips, spatial_size):
     """device patches: ([n,1,h,w,d] f32, [n,1,h,w,d] u8) from img / lab [H,W,D] at the given centres; flips[k] mirrors H and W"""
     H, W, D = img.shape
@@ -78,9 +201,13 @@ def crop_flip(img, lab, centers, flips, spatial_size):
     return oi, ol
 
 
-def sample_patches(img, lab, label_host, spatial_size, num_samples, rand_state, flip_prob=0.4):
-    """one `__getitem__` of IdPosPanCTDataset without the rotate / contrast / zoom augmentations"""
-    centers = crop_centers(label_host, spatial_size, num_samples, rand_state=rand_state)
+def sample_patches(img, lab, label_host, spatial_size, num_samples, rand_state, flip_prob=0.4, index=None):
+    """one `__getitem__` of IdPosPanCTDataset without the rotate / contrast / zoom augmentations; with index, the CropIndex of
+    lab, the centres come from it (the same centres from the same draws) and label_host is not read (it may be None)"""
+    if index is not None:
+        centers = index.centers(spatial_size, num_samples, rand_state=rand_state)
+    else:
+        centers = crop_centers(label_host, spatial_size, num_samples, rand_state=rand_state)
     flips = [rand_state.rand() < flip_prob for _ in range(num_samples)]
     return crop_flip(img, lab, centers, flips, spatial_size)
 
@@ -296,8 +423,9 @@ def resample(src_img, src_lab, matrix, out_shape, imap=(1.0, 0.0, -np.inf, np.in
 class SpacedScan:
     """The deterministic half of the driver's CacheDataset: one NIfTI image (and label) read, uploaded once as stored, and
     resampled on the device to `pixdim` in `axcodes` orientation.  img: f32 [H, W, D]; lab: u8 [H, W, D] (or None);
-    label_host: the resampled label on the host (crop centres are drawn from it); affine: the output's 4x4 affine; matrix: the
-    3x4 float64 pull matrix (RAS voxel -> file voxel); native_shape / native_affine / native: the file's grid and header."""
+    crop_index: the label's CropIndex, built on first use (crop centres are drawn from it); label_host: the resampled label on the
+    host, copied on first use (a scan that is only sampled through the index never copies it); affine: the output's 4x4 affine;
+    matrix: the 3x4 float64 pull matrix (RAS voxel -> file voxel); native_shape / native_affine / native: the file's grid and header."""
 
     def __init__(self, img_path, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda'):
         ni = nifti.load(img_path)
@@ -313,7 +441,19 @@ class SpacedScan:
             lv = nl.data if (nl.slope, nl.inter) == (1.0, 0.0) else nl.scaled()
             rl = torch.as_tensor(np.ascontiguousarray(label_u8(lv))).to(device)
         self.img, self.lab = resample(ri, rl, self.matrix, self.shape, intensity_map(intensity, ni.slope, ni.inter), code)
-        self.label_host = self.lab.cpu().numpy() if self.lab is not None else None
+        self._label_host = self._crop_index = None
+
+    @property
+    def label_host(self):
+        if self._label_host is None and self.lab is not None:
+            self._label_host = self.lab.cpu().numpy()
+        return self._label_host
+
+    @property
+    def crop_index(self):
+        if self._crop_index is None and self.lab is not None:
+            self._crop_index = CropIndex(self.lab)
+        return self._crop_index
 
 
 def orient_desc(flip, k):
@@ -327,12 +467,16 @@ def orient_desc(flip, k):
     return int(a != 0), int(b != 0), k % 2
 
 
-def draw_monai_sample(label_host, spatial_size, rs, flip_prob=0.5, rot90_prob=0.5, max_k=3):
+def draw_monai_sample(label_host, spatial_size, rs, flip_prob=0.5, rot90_prob=0.5, max_k=3, index=None):
     """one sample's draws in the driver's transform order from one RandomState: the crop centre (RandCropByPosNegLabeld,
     num_samples 1), the flip (RandFlipd), then RandRotate90d's k = randint(max_k) + 1 before its probability draw (monai 0.7.0's
     RandRotate90.randomize; recalled, not pinned).  Every draw is made whether or not its transform fires.
-    Returns (centre, flip, k) with k = 0 when the rotation does not fire."""
-    center = crop_centers(label_host, spatial_size, 1, rand_state=rs)[0]
+    Returns (centre, flip, k) with k = 0 when the rotation does not fire.  With index, the label's CropIndex, the centre comes
+    from it and label_host is not read."""
+    if index is not None:
+        center = index.centers(spatial_size, 1, rand_state=rs)[0]
+    else:
+        center = crop_centers(label_host, spatial_size, 1, rand_state=rs)[0]
     flip = rs.rand() < flip_prob
     k = rs.randint(max_k) + 1
     rot = rs.rand() < rot90_prob
@@ -362,13 +506,34 @@ def crop_orient(img, lab, draws, spatial_size):
     return oi, ol
 
 
-def sample(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_prob=0.5):
+def sample(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_prob=0.5, host_centers=False, ratios=None):
     """the random half of the driver's dataset: num_samples patches ([n,1,h,w,d] f32, u8) of a SpacedScan, each with its own
-    crop centre, flip and rot90 drawn by draw_monai_sample"""
-    if scan.label_host is None:
+    crop centre, flip and rot90 in draw_monai_sample's order.  The centres come from scan.crop_index: every host draw of every
+    sample is made first (per sample: centre, flip, k, rotation probability), then one select launch resolves all centres.
+    host_centers=True draws them from scan.label_host instead (np.nonzero passes over the label per sample): the same patches
+    from the same generator.  ratios: one weight per class 0 .. num_classes - 1 switches the centre draw from
+    RandCropByPosNegLabeld to RandCropByLabelClassesd (class_centers / class_crop_centers, num_samples 1 per sample)."""
+    if scan.lab is None:
         raise ValueError('sampling needs a label (RandCropByPosNegLabeld draws centres from it)')
-    draws = [draw_monai_sample(scan.label_host, spatial_size, rand_state, flip_prob, rot90_prob) for _ in range(num_samples)]
-    return crop_orient(scan.img, scan.lab, draws, spatial_size)
+    if host_centers and ratios is None:
+        draws = [draw_monai_sample(scan.label_host, spatial_size, rand_state, flip_prob, rot90_prob) for _ in range(num_samples)]
+        return crop_orient(scan.img, scan.lab, draws, spatial_size)
+    index = None if host_centers else scan.crop_index
+    centres, rest = [], []
+    for _ in range(num_samples):
+        if host_centers:
+            centres.append(class_crop_centers(scan.label_host, spatial_size, 1, ratios, len(ratios), rand_state)[0])
+        elif ratios is not None:
+            centres.extend(index.class_queries(1, ratios, len(ratios), rand_state))
+        else:
+            centres.extend(_posneg_queries(index.n_foreground, index.n_background, 1, 0.7, 0.3, rand_state))
+        flip = rand_state.rand() < flip_prob
+        k = rand_state.randint(3) + 1
+        rot = rand_state.rand() < rot90_prob
+        rest.append((bool(flip), int(k) if rot else 0))
+    if index is not None:
+        centres = index.resolve(centres, spatial_size)
+    return crop_orient(scan.img, scan.lab, [(c, f, k) for c, (f, k) in zip(centres, rest)], spatial_size)
 
 
 def to_native(label_map, scan):
