@@ -315,7 +315,7 @@ int ltu_gelu_dropout_bwd(const void* dh, const void* u, void* du, long long n, f
                          ltu_stream_t s);
 
 /* ---- class-probability heads ---------------------------------------------------------------------
- * mask head softmax (model/Unet_3Dblock.py:1380-1381): logits T [M][CP] (first C valid) -> p f32 [M][C]; C <= 8 in both heads
+ * mask head softmax (model/Unet_3Dblock.py:1380-1381): logits T [M][CP] (first C valid) -> p f32 [M][C]; 1 <= C <= 8 in both heads
  * (else LTU_E_SHAPE); the backward writes the padding columns C .. CP-1 of dz as zero */
 int ltu_head_softmax_fwd(const void* z, float* p, long long M, int C, int CP, int dtype, ltu_stream_t s);
 int ltu_head_softmax_bwd(const float* dp, const float* p, void* dz, long long M, int C, int CP, int dtype, ltu_stream_t s);

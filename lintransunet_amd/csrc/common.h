@@ -8,6 +8,7 @@
 #include "../../include/ltu_hip.h"
 
 #define LTU_WAVE 64
+#define LTU_WIDE_MAXC 8          // most classes of the softmax heads (pointwise.hip) and the level loss (loss.hip)
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -277,5 +278,21 @@ static inline long long loss_rows(int B, long long S) {
       __VA_ARGS__                                            \
     } else {                                                 \
       return LTU_E_DTYPE;                                    \
+    }                                                        \
+  } while (0)
+
+// class-count dispatch for host wrappers: CT is the compile-time class count, 1 .. LTU_WIDE_MAXC
+#define LTU_DISPATCH_C(C, ...)                               \
+  do {                                                       \
+    switch (C) {                                             \
+      case 1: { constexpr int CT = 1; __VA_ARGS__ } break;   \
+      case 2: { constexpr int CT = 2; __VA_ARGS__ } break;   \
+      case 3: { constexpr int CT = 3; __VA_ARGS__ } break;   \
+      case 4: { constexpr int CT = 4; __VA_ARGS__ } break;   \
+      case 5: { constexpr int CT = 5; __VA_ARGS__ } break;   \
+      case 6: { constexpr int CT = 6; __VA_ARGS__ } break;   \
+      case 7: { constexpr int CT = 7; __VA_ARGS__ } break;   \
+      case 8: { constexpr int CT = 8; __VA_ARGS__ } break;   \
+      default: return LTU_E_SHAPE;                           \
     }                                                        \
   } while (0)

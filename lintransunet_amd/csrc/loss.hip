@@ -13,7 +13,7 @@
 // One set of kernels for 1 .. 8 classes behind both entry-point families (ltu_loss_*: C <= 4, nine values; ltu_loss_wide_*:
 // 2 <= C <= 8, C + 5 values).  The class count is a template argument everywhere: per-thread arrays are indexed by unrolled
 // loops only and stay in registers.
-#include "manyclass.h"          // LTU_WIDE_MAXC
+#include "common.h"
 
 // Four voxels per thread and trip (S % 4 == 0, C >= 2): one 4-byte label load and C 16-byte probability loads.  Trips in flight:
 // two up to C = 4, one above (4 C floats a trip: two trips of C = 8 would hold 64 loaded values beside the 32 accumulators).  One
@@ -352,21 +352,6 @@ static void loss_bwd_launch(const float* p, const uint8_t* label, const float* c
   }
 }
 
-#define LOSS_DISPATCH_C(C, ...)                              \
-  do {                                                       \
-    switch (C) {                                             \
-      case 1: { constexpr int CT = 1; __VA_ARGS__ } break;   \
-      case 2: { constexpr int CT = 2; __VA_ARGS__ } break;   \
-      case 3: { constexpr int CT = 3; __VA_ARGS__ } break;   \
-      case 4: { constexpr int CT = 4; __VA_ARGS__ } break;   \
-      case 5: { constexpr int CT = 5; __VA_ARGS__ } break;   \
-      case 6: { constexpr int CT = 6; __VA_ARGS__ } break;   \
-      case 7: { constexpr int CT = 7; __VA_ARGS__ } break;   \
-      case 8: { constexpr int CT = 8; __VA_ARGS__ } break;   \
-      default: return LTU_E_SHAPE;                           \
-    }                                                        \
-  } while (0)
-
 // the four-voxel kernels: S % 4 == 0 and at least two classes
 static bool loss_v4(long long S, int C) { return S % 4 == 0 && C >= 2 && !ltu_knob("LTU_LOSS_SCALAR", 0); }
 
@@ -381,7 +366,7 @@ static int loss_fwd(const float* p, const uint8_t* label, float* sums, long long
   cfg.w_ce = w_ce; cfg.w_bal = w_bal; cfg.w_fg = w_fg;
   for (int c = 0; c < LTU_WIDE_MAXC; ++c) cfg.w_dice[c] = (c < C && w_dice) ? w_dice[c] : 0.f;
   const bool v4 = loss_v4(S, C);
-  LOSS_DISPATCH_C(C, { loss_fwd_launch<CT>(p, label, sums, nblk, rows, values, coef, B, S, cfg, fg_slot, scale_dev, v4, (hipStream_t)s); });
+  LTU_DISPATCH_C(C, { loss_fwd_launch<CT>(p, label, sums, nblk, rows, values, coef, B, S, cfg, fg_slot, scale_dev, v4, (hipStream_t)s); });
   return ltu_check_launch();
 }
 static int loss_bwd(const float* p, const uint8_t* label, const float* coef, const float* gscale, float* dp, int B, long long S, int C,
@@ -393,7 +378,7 @@ static int loss_bwd(const float* p, const uint8_t* label, const float* coef, con
   if (bx > cap) bx = cap;
   if (bx < 1) bx = 1;
   const dim3 grid((unsigned)bx, B);
-  LOSS_DISPATCH_C(C, { loss_bwd_launch<CT>(p, label, coef, gscale, dp, grid, S, v4, (hipStream_t)s); });
+  LTU_DISPATCH_C(C, { loss_bwd_launch<CT>(p, label, coef, gscale, dp, grid, S, v4, (hipStream_t)s); });
   return ltu_check_launch();
 }
 

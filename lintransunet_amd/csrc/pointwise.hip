@@ -2,7 +2,6 @@
 // window (un)embedding, weight repacking, GELU+dropout, class softmax heads, the attention gate,
 // the depthwise positional conv and the nearest-upsampling adjoint.  Channels-last, 4-wide vectors.
 #include "common.h"
-#include "manyclass.h"
 
 static unsigned sgrid(long long n, int per_block = 256) {
   long long blocks = (n + per_block - 1) / per_block;
@@ -234,105 +233,186 @@ extern "C" int ltu_gelu_dropout_bwd(const void* dh, const void* u, void* du, lon
 }
 
 // ------------------------------------------------------------------------------------------------ class softmax heads
-// mask head (model/Unet_3Dblock.py:1380-1381): logits T [M][CP] (CP = padded conv width) -> probs f32 [M][C]
-template <typename T>
-__global__ void head_softmax_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, long long M, int C, int CP) {
-  GRID_STRIDE(m, M) {
-    float v[4];
-    float mx = -INFINITY;
-    for (int c = 0; c < C; ++c) { v[c] = ld1<T>(z + m * CP + c); mx = fmaxf(mx, v[c]); }
-    float sum = 0.f;
-    for (int c = 0; c < C; ++c) { v[c] = expf(v[c] - mx); sum += v[c]; }
-    for (int c = 0; c < C; ++c) p[m * C + c] = v[c] / sum;
+// One kernel family for 1 .. 8 classes.  The class count is a template argument everywhere: per-thread arrays are indexed by unrolled
+// loops only (a run-time class loop over them would put them in scratch memory or serialise the loads: 16 dependent round trips per
+// thread in the final backward), and all loads of a row / coarse voxel are issued before the arithmetic.  A thread holds a row in
+// HEAD_W(C) registers, 4 up to four classes and 8 above; what lies behind the live classes is constant zero.
+#define HEAD_W(C) ((C) <= 4 ? 4 : 8)
+
+// a row of C fp32 values at a stride of 4 C bytes, with the widest access that stride keeps aligned (16 bytes for C = 4, 8; 8 for
+// C = 2, 6; 4 for odd C); v[c >= C] = 0
+template <int C>
+__device__ __forceinline__ void ldrow(const float* __restrict__ q, float (&v)[HEAD_W(C)]) {
+  if constexpr (C % 4 == 0) {
+#pragma unroll
+    for (int k = 0; k < C; k += 4) {
+      const float4 t = *reinterpret_cast<const float4*>(q + k);
+      v[k] = t.x; v[k + 1] = t.y; v[k + 2] = t.z; v[k + 3] = t.w;
+    }
+  } else if constexpr (C % 2 == 0) {
+#pragma unroll
+    for (int k = 0; k < C; k += 2) {
+      const float2 t = *reinterpret_cast<const float2*>(q + k);
+      v[k] = t.x; v[k + 1] = t.y;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < C; ++k) v[k] = q[k];
+  }
+#pragma unroll
+  for (int k = C; k < HEAD_W(C); ++k) v[k] = 0.f;
+}
+// the probabilities e[c] / sum of a row, stored as ldrow loads them.  Division and store of a class stand together: written as C
+// divisions and then C stores, the C = 3 kernels start the next row's exponentials before a row is stored, and the final forward
+// measured 0.9 us (5 %) slower at 2 x 128^3
+template <int C>
+__device__ __forceinline__ void stprobs(float* __restrict__ q, const float (&e)[HEAD_W(C)], float sum) {
+  if constexpr (C % 4 == 0) {
+#pragma unroll
+    for (int k = 0; k < C; k += 4) *reinterpret_cast<float4*>(q + k) = make_float4(e[k] / sum, e[k + 1] / sum, e[k + 2] / sum, e[k + 3] / sum);
+  } else if constexpr (C % 2 == 0) {
+#pragma unroll
+    for (int k = 0; k < C; k += 2) *reinterpret_cast<float2*>(q + k) = make_float2(e[k] / sum, e[k + 1] / sum);
+  } else {
+#pragma unroll
+    for (int k = 0; k < C; ++k) q[k] = e[k] / sum;
   }
 }
-// compile-time class count, CP % 4 == 0: the row's first four logits as ONE vector load (instead of C two-byte loads in a run-time
-// loop), the probabilities as one store for C = 2
+// the first HEAD_W(C) logits of a padded row: one Vec4<T> load up to four classes; above, two 16-byte loads (fp32) or one (bf16)
 template <typename T, int C>
-__global__ void head_softmax_fwd_vec_kernel(const T* __restrict__ z, float* __restrict__ p, long long M, int CP) {
-  GRID_STRIDE(m, M) {
-    const float4 q = Vec4<T>::load(z + m * CP);
-    const float v[4] = {q.x, q.y, q.z, q.w};
-    float mx = -INFINITY, e[C], sum = 0.f;
+__device__ __forceinline__ void ldlogits(const T* __restrict__ q, float (&v)[HEAD_W(C)]) {
+  if constexpr (C > 4 && sizeof(T) == 2) {
+    const uint4 r = *reinterpret_cast<const uint4*>(q);
+    v[0] = __uint_as_float(r.x << 16); v[1] = __uint_as_float(r.x & 0xffff0000u);
+    v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
+    v[4] = __uint_as_float(r.z << 16); v[5] = __uint_as_float(r.z & 0xffff0000u);
+    v[6] = __uint_as_float(r.w << 16); v[7] = __uint_as_float(r.w & 0xffff0000u);
+  } else {
 #pragma unroll
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, v[c]);
-#pragma unroll
-    for (int c = 0; c < C; ++c) { e[c] = expf(v[c] - mx); sum += e[c]; }
-    if constexpr (C == 2) *reinterpret_cast<float2*>(p + m * 2) = make_float2(e[0] / sum, e[1] / sum);
-    else {
-#pragma unroll
-      for (int c = 0; c < C; ++c) p[m * C + c] = e[c] / sum;
+    for (int k = 0; k < HEAD_W(C); k += 4) {
+      const float4 t = Vec4<T>::load(q + k);
+      v[k] = t.x; v[k + 1] = t.y; v[k + 2] = t.z; v[k + 3] = t.w;
     }
   }
 }
-template <typename T>
-__global__ void head_softmax_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz,
-                                        long long M, int C, int CP) {
+// rows of CP elements of `elt` bytes, the first at `base`, all start on a multiple of `unit` bytes
+static bool rows_aligned(const void* base, int CP, int elt, int unit) { return CP * elt % unit == 0 && (uintptr_t)base % unit == 0; }
+
+// mask head (model/Unet_3Dblock.py:1380-1381): logits T [M][CP] (CP = padded conv width, first C live) -> probs f32 [M][C].
+// VEC: ldlogits may read the row (see the launcher); otherwise C scalar loads
+template <typename T, int C, bool VEC>
+__global__ void __launch_bounds__(256) head_softmax_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, long long M, int CP) {
+  constexpr int W = HEAD_W(C);
   GRID_STRIDE(m, M) {
-    float dot = 0.f;
-    for (int c = 0; c < C; ++c) dot += dp[m * C + c] * p[m * C + c];
-    for (int c = 0; c < CP; ++c) st1<T>(dz + m * CP + c, c < C ? p[m * C + c] * (dp[m * C + c] - dot) : 0.f);
+    float v[W];
+    if constexpr (VEC) ldlogits<T, C>(z + m * CP, v);
+    else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) v[c] = ld1<T>(z + m * CP + c);
+    }
+    float mx = -INFINITY, sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) mx = fmaxf(mx, v[c]);
+#pragma unroll
+    for (int c = 0; c < C; ++c) { v[c] = expf(v[c] - mx); sum += v[c]; }
+    stprobs<C>(p + m * C, v, sum);
   }
 }
-// bf16 rows of CP = 8k padded logits: one 16-byte store per 8 channels (the fused conv pairs pad the heads to 16 / 32 columns)
-template <int CT>
-__global__ void head_softmax_bwd_bf16x8_kernel(const float* __restrict__ dp, const float* __restrict__ p, uint4* __restrict__ dz,
-                                               long long M, int C_rt, int CP) {
-  const int C = CT > 0 ? CT : C_rt;
+// g[c] = p_c (dp_c - sum_k dp_k p_k) for c < C, 0 behind.  The rounding of the sum is written out, not left to -ffp-contract=fast (which
+// fuses or packs the products differently from one instantiation to the next), and is the one the results at C = 2, 3 have always
+// carried: an fma chain in the row kernels (FUSED; what the loop over a run-time C compiled to, and what the final head does), every
+// product rounded before it is added - fmaf(x, y, 0) - in the 16-byte-store kernel (what its packed multiplies gave)
+template <int C, bool FUSED>
+__device__ __forceinline__ void head_grad(const float* __restrict__ dp, const float* __restrict__ p, long long m, float (&g)[HEAD_W(C)]) {
+  constexpr int W = HEAD_W(C);
+  float a[W], b[W];
+  ldrow<C>(dp + m * C, a);
+  ldrow<C>(p + m * C, b);
+  float dot = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) dot = FUSED ? fmaf(a[c], b[c], dot) : dot + fmaf(a[c], b[c], 0.f);
+#pragma unroll
+  for (int c = 0; c < W; ++c) g[c] = c < C ? b[c] * (a[c] - dot) : 0.f;
+}
+// bf16 rows of CP = 8k padded logits: one thread and one 16-byte store per 8 columns (the fused conv pairs pad the heads to 16 / 32
+// columns); the first group holds the C gradients, every other word is a constant zero
+template <int C>
+__global__ void __launch_bounds__(256) head_softmax_bwd_bf16x8_kernel(const float* __restrict__ dp, const float* __restrict__ p,
+                                                                      uint4* __restrict__ dz, long long M, int CP) {
   const int v8 = CP / 8;
   GRID_STRIDE(i, M * v8) {
     const long long m = i / v8;
     uint4 o = make_uint4(0u, 0u, 0u, 0u);
     if (i - m * v8 == 0) {
-      float dot = 0.f, g[4] = {0.f, 0.f, 0.f, 0.f}, a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (CT == 2) {
-        const float2 av = *reinterpret_cast<const float2*>(dp + m * 2), bv = *reinterpret_cast<const float2*>(p + m * 2);
-        a[0] = av.x; a[1] = av.y; b[0] = bv.x; b[1] = bv.y;
-      } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) if (c < C) { a[c] = dp[m * C + c]; b[c] = p[m * C + c]; }
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (c < C) dot += a[c] * b[c];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (c < C) g[c] = b[c] * (a[c] - dot);
+      float g[HEAD_W(C)];
+      head_grad<C, false>(dp, p, m, g);
       o.x = pack_bf16x2(g[0], g[1]);
       o.y = pack_bf16x2(g[2], g[3]);
+      if constexpr (C > 4) {
+        o.z = pack_bf16x2(g[4], g[5]);
+        o.w = pack_bf16x2(g[6], g[7]);
+      }
     }
     dz[i] = o;
   }
 }
+// one thread per row.  VEC: every row starts on a Vec4<T> boundary and CP % 4 == 0: 4-wide stores, zeros behind the first HEAD_W(C)
+// columns; otherwise scalar stores
+template <typename T, int C, bool VEC>
+__global__ void __launch_bounds__(256) head_softmax_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz,
+                                                               long long M, int CP) {
+  constexpr int W = HEAD_W(C);
+  GRID_STRIDE(m, M) {
+    float g[W];
+    head_grad<C, true>(dp, p, m, g);
+    T* o = dz + m * CP;
+    if constexpr (VEC) {
+#pragma unroll
+      for (int k = 0; k < W; k += 4) Vec4<T>::store(o + k, make_float4(g[k], g[k + 1], g[k + 2], g[k + 3]));
+      for (int k = W; k < CP; k += 4) Vec4<T>::store(o + k, make_float4(0.f, 0.f, 0.f, 0.f));
+    } else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) st1<T>(o + c, g[c]);
+      for (int c = C; c < CP; ++c) st1<T>(o + c, 0.f);
+    }
+  }
+}
 extern "C" int ltu_head_softmax_fwd(const void* z, float* p, long long M, int C, int CP, int dtype, ltu_stream_t s) {
-  if (C > 4 && C <= LTU_WIDE_MAXC) return ltu_head_softmax_wide_fwd(z, p, M, C, CP, dtype, s);      // 5 .. 8 classes: manyclass.hip
-  if (C > 4 || CP < C) return LTU_E_SHAPE;
+  if (C < 1 || C > LTU_WIDE_MAXC || CP < C) return LTU_E_SHAPE;
   LTU_DISPATCH_T(dtype, {
-    if (CP % 4 == 0 && C == 2) hipLaunchKernelGGL((head_softmax_fwd_vec_kernel<T, 2>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
-    else if (CP % 4 == 0 && C == 3) hipLaunchKernelGGL((head_softmax_fwd_vec_kernel<T, 3>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
-    else hipLaunchKernelGGL((head_softmax_fwd_kernel<T>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, C, CP);
+    LTU_DISPATCH_C(C, {
+      // ldlogits reads HEAD_W(C) logits in units of a Vec4<T> (C <= 4) or of 16 bytes; a multiple of the unit that holds C logits holds those
+      if (rows_aligned(z, CP, sizeof(T), CT <= 4 ? 4 * sizeof(T) : 16))
+        hipLaunchKernelGGL((head_softmax_fwd_kernel<T, CT, true>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
+      else hipLaunchKernelGGL((head_softmax_fwd_kernel<T, CT, false>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
+    });
   });
   return ltu_check_launch();
 }
 extern "C" int ltu_head_softmax_bwd(const float* dp, const float* p, void* dz, long long M, int C, int CP, int dtype,
                                     ltu_stream_t s) {
-  if (C > 4 && C <= LTU_WIDE_MAXC) return ltu_head_softmax_wide_bwd(dp, p, dz, M, C, CP, dtype, s);
-  if (C > 4 || CP < C) return LTU_E_SHAPE;
-  if (dtype == LTU_BF16 && CP % 8 == 0 && ((uintptr_t)dz & 15) == 0) {
-    if (C == 2) hipLaunchKernelGGL(head_softmax_bwd_bf16x8_kernel<2>, dim3(sgrid(M * (CP / 8))), dim3(256), 0, (hipStream_t)s, dp, p, (uint4*)dz, M, C, CP);
-    else if (C == 3) hipLaunchKernelGGL(head_softmax_bwd_bf16x8_kernel<3>, dim3(sgrid(M * (CP / 8))), dim3(256), 0, (hipStream_t)s, dp, p, (uint4*)dz, M, C, CP);
-    else hipLaunchKernelGGL(head_softmax_bwd_bf16x8_kernel<0>, dim3(sgrid(M * (CP / 8))), dim3(256), 0, (hipStream_t)s, dp, p, (uint4*)dz, M, C, CP);
+  if (C < 1 || C > LTU_WIDE_MAXC || CP < C) return LTU_E_SHAPE;
+  if (dtype == LTU_BF16 && rows_aligned(dz, CP, 2, 16)) {
+    LTU_DISPATCH_C(C, {
+      hipLaunchKernelGGL(head_softmax_bwd_bf16x8_kernel<CT>, dim3(sgrid(M * (CP / 8))), dim3(256), 0, (hipStream_t)s, dp, p, (uint4*)dz, M, CP);
+    });
     return ltu_check_launch();
   }
-  LTU_DISPATCH_T(dtype, { hipLaunchKernelGGL((head_softmax_bwd_kernel<T>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, M, C, CP); });
+  LTU_DISPATCH_T(dtype, {
+    const bool vec = rows_aligned(dz, CP, sizeof(T), 4 * sizeof(T));      // CP % 4 == 0 and CP >= C make CP >= HEAD_W(C)
+    LTU_DISPATCH_C(C, {
+      if (vec) hipLaunchKernelGGL((head_softmax_bwd_kernel<T, CT, true>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, M, CP);
+      else hipLaunchKernelGGL((head_softmax_bwd_kernel<T, CT, false>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, M, CP);
+    });
+  });
   return ltu_check_launch();
 }
 
-// final head (model/Unet_3Dblock.py:1392-1394): z T [B,h,w,D,4C] -> window un-embedding + softmax over classes
-// -> probs f32 [B,2h,2w,D,C];  channel c*4 + kh*2 + kw of voxel (h,w) is class c of voxel (2h+kh, 2w+kw).
-// CT: compile-time class count (0 = run-time C).  With a run-time C the class loops stay loops: one scalar load per trip, each
-// waited for where it stands (16 dependent round trips per thread in the backward kernel).
-template <typename T, int CT>
-__global__ void final_softmax_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, int B, int h, int w, int D, int C_rt, int CP) {
-  const int C = CT > 0 ? CT : C_rt;
+// final head (model/Unet_3Dblock.py:1392-1394): z T [B,h,w,D,CP >= 4C] -> window un-embedding + softmax over classes
+// -> probs f32 [B,2h,2w,D,C];  channel c*4 + kh*2 + kw of coarse voxel (h,w) is class c of fine voxel (2h+kh, 2w+kw), so the 4-wide
+// load at channel 4c is class c of the four fine voxels.  One thread per coarse voxel.
+template <typename T, int C>
+__global__ void __launch_bounds__(256) final_softmax_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, int B, int h, int w, int D, int CP) {
   const long long n = (long long)B * h * w * D;
   GRID_STRIDE(i, n) {
     const int d = (int)(i % D);
@@ -340,34 +420,27 @@ __global__ void final_softmax_fwd_kernel(const T* __restrict__ z, float* __restr
     const int ww = (int)(t % w); t /= w;
     const int hh = (int)(t % h);
     const int b = (int)(t / h);
-    float v[16];
+    float v[4 * C];
 #pragma unroll
-    for (int k = 0; k < 16; k += 4) {
-      if (k < 4 * C) {
-        const float4 q = Vec4<T>::load(z + i * CP + k);
-        v[k] = q.x; v[k + 1] = q.y; v[k + 2] = q.z; v[k + 3] = q.w;
-      }
+    for (int c = 0; c < C; ++c) {
+      const float4 t4 = Vec4<T>::load(z + i * CP + 4 * c);
+      v[4 * c] = t4.x; v[4 * c + 1] = t4.y; v[4 * c + 2] = t4.z; v[4 * c + 3] = t4.w;
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float mx = -INFINITY, e[4], sum = 0.f;
+      float mx = -INFINITY, sum = 0.f, e[HEAD_W(C)];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) if (c < C) mx = fmaxf(mx, v[c * 4 + q]);
+      for (int c = 0; c < C; ++c) mx = fmaxf(mx, v[4 * c + q]);
 #pragma unroll
-      for (int c = 0; c < 4; ++c) if (c < C) { e[c] = expf(v[c * 4 + q] - mx); sum += e[c]; }
-      float* o = p + ((((long long)b * 2 * h + 2 * hh + (q >> 1)) * 2 * w + 2 * ww + (q & 1)) * D + d) * C;
-      if constexpr (CT == 2) *reinterpret_cast<float2*>(o) = make_float2(e[0] / sum, e[1] / sum);
-      else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) if (c < C) o[c] = e[c] / sum;
-      }
+      for (int c = 0; c < C; ++c) { e[c] = expf(v[4 * c + q] - mx); sum += e[c]; }
+      stprobs<C>(p + ((((long long)b * 2 * h + 2 * hh + (q >> 1)) * 2 * w + 2 * ww + (q & 1)) * D + d) * C, e, sum);
     }
   }
 }
-template <typename T, int CT>
-__global__ void final_softmax_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz, int B,
-                                         int h, int w, int D, int C_rt, int CP) {
-  const int C = CT > 0 ? CT : C_rt;
+template <typename T, int C>
+__global__ void __launch_bounds__(256) final_softmax_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz,
+                                                                int B, int h, int w, int D, int CP) {
+  constexpr int W = HEAD_W(C);
   const long long n = (long long)B * h * w * D;
   GRID_STRIDE(i, n) {
     const int d = (int)(i % D);
@@ -375,52 +448,41 @@ __global__ void final_softmax_bwd_kernel(const float* __restrict__ dp, const flo
     const int ww = (int)(t % w); t /= w;
     const int hh = (int)(t % h);
     const int b = (int)(t / h);
-    float v[16], gv[4][4], pv[4][4];
+    float gv[4][W], pv[4][W];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                 // all loads of the four fine voxels first
       const long long o = ((((long long)b * 2 * h + 2 * hh + (q >> 1)) * 2 * w + 2 * ww + (q & 1)) * D + d) * C;
-      if constexpr (CT == 2) {
-        const float2 a = *reinterpret_cast<const float2*>(dp + o), c2 = *reinterpret_cast<const float2*>(p + o);
-        gv[q][0] = a.x; gv[q][1] = a.y; pv[q][0] = c2.x; pv[q][1] = c2.y;
-      } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) if (c < C) { gv[q][c] = dp[o + c]; pv[q][c] = p[o + c]; }
-      }
+      ldrow<C>(dp + o, gv[q]);
+      ldrow<C>(p + o, pv[q]);
     }
+    float dot[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float dot = 0.f;
+      dot[q] = 0.f;
 #pragma unroll
-      for (int c = 0; c < 4; ++c) if (c < C) dot += gv[q][c] * pv[q][c];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (c < C) v[c * 4 + q] = pv[q][c] * (gv[q][c] - dot);
+      for (int c = 0; c < C; ++c) dot[q] = fmaf(gv[q][c], pv[q][c], dot[q]);      // the chain -ffp-contract=fast has always made of it, written out
     }
 #pragma unroll
-    for (int k = 0; k < 16; k += 4)
-      if (k < 4 * C) Vec4<T>::store(dz + i * CP + k, make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]));
+    for (int c = 0; c < C; ++c)
+      Vec4<T>::store(dz + i * CP + 4 * c, make_float4(pv[0][c] * (gv[0][c] - dot[0]), pv[1][c] * (gv[1][c] - dot[1]),
+                                                      pv[2][c] * (gv[2][c] - dot[2]), pv[3][c] * (gv[3][c] - dot[3])));
     for (int k = 4 * C; k < CP; k += 4) Vec4<T>::store(dz + i * CP + k, make_float4(0.f, 0.f, 0.f, 0.f));      // padded conv columns
   }
 }
 extern "C" int ltu_final_softmax_fwd(const void* z, float* p, int B, int h, int w, int D, int C, int CP, int dtype, ltu_stream_t s) {
-  if (C > 4 && C <= LTU_WIDE_MAXC) return ltu_final_softmax_wide_fwd(z, p, B, h, w, D, C, CP, dtype, s);      // 5 .. 8 classes: manyclass.hip
-  if (C < 1 || C > 4 || CP < 4 * C || CP % 4) return LTU_E_SHAPE;
+  if (C < 1 || C > LTU_WIDE_MAXC || CP < 4 * C || CP % 4) return LTU_E_SHAPE;
   LTU_DISPATCH_T(dtype, {
     const dim3 grid(sgrid((long long)B * h * w * D));
-    if (C == 2) hipLaunchKernelGGL((final_softmax_fwd_kernel<T, 2>), grid, dim3(256), 0, (hipStream_t)s, (const T*)z, p, B, h, w, D, C, CP);
-    else if (C == 3) hipLaunchKernelGGL((final_softmax_fwd_kernel<T, 3>), grid, dim3(256), 0, (hipStream_t)s, (const T*)z, p, B, h, w, D, C, CP);
-    else hipLaunchKernelGGL((final_softmax_fwd_kernel<T, 0>), grid, dim3(256), 0, (hipStream_t)s, (const T*)z, p, B, h, w, D, C, CP);
+    LTU_DISPATCH_C(C, { hipLaunchKernelGGL((final_softmax_fwd_kernel<T, CT>), grid, dim3(256), 0, (hipStream_t)s, (const T*)z, p, B, h, w, D, CP); });
   });
   return ltu_check_launch();
 }
 extern "C" int ltu_final_softmax_bwd(const float* dp, const float* p, void* dz, int B, int h, int w, int D, int C, int CP,
                                      int dtype, ltu_stream_t s) {
-  if (C > 4 && C <= LTU_WIDE_MAXC) return ltu_final_softmax_wide_bwd(dp, p, dz, B, h, w, D, C, CP, dtype, s);
-  if (C < 1 || C > 4 || CP < 4 * C || CP % 4) return LTU_E_SHAPE;
+  if (C < 1 || C > LTU_WIDE_MAXC || CP < 4 * C || CP % 4) return LTU_E_SHAPE;
   LTU_DISPATCH_T(dtype, {
     const dim3 grid(sgrid((long long)B * h * w * D));
-    if (C == 2) hipLaunchKernelGGL((final_softmax_bwd_kernel<T, 2>), grid, dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, B, h, w, D, C, CP);
-    else if (C == 3) hipLaunchKernelGGL((final_softmax_bwd_kernel<T, 3>), grid, dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, B, h, w, D, C, CP);
-    else hipLaunchKernelGGL((final_softmax_bwd_kernel<T, 0>), grid, dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, B, h, w, D, C, CP);
+    LTU_DISPATCH_C(C, { hipLaunchKernelGGL((final_softmax_bwd_kernel<T, CT>), grid, dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, B, h, w, D, CP); });
   });
   return ltu_check_launch();
 }

@@ -1686,7 +1686,7 @@ def level_loss(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
     return _LevelLoss.apply(p, label, w_ce, w_bal, wd, scale_dev, 'ltu_loss', 9)
 
 
-LOSS_WIDE_MAXC = 8      # LTU_WIDE_MAXC of csrc/manyclass.h
+LOSS_WIDE_MAXC = 8      # LTU_WIDE_MAXC of csrc/common.h
 
 
 def level_loss_wide(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):

@@ -55,11 +55,15 @@ def test_contract_errors_return_before_any_launch():
     assert fwd(ws=need - 1) == -4                                               # short scratch: LTU_E_ARG
     assert fwd(sums=None) == -4 and bwd(dp=None) == -4                          # NULL
     assert lib.ltu_loss_wide_fwd(fake, fake, fake, need, fake, fake, B, S, C, 1.0, 1.0, None, None, None) == -4
-    # the refusals of the narrower entries stay: 9 classes in the heads, 5 in ltu_loss_fwd
+    # the refusals of the narrower entries stay: 9 and 0 classes in the heads, 5 in ltu_loss_fwd
     assert lib.ltu_head_softmax_fwd(fake, fake, 16, 9, 16, 0, None) == -2
     assert lib.ltu_head_softmax_bwd(fake, fake, fake, 16, 9, 16, 0, None) == -2
     assert lib.ltu_final_softmax_fwd(fake, fake, 1, 2, 2, 2, 9, 36, 0, None) == -2
     assert lib.ltu_final_softmax_bwd(fake, fake, fake, 1, 2, 2, 2, 9, 36, 0, None) == -2
+    assert lib.ltu_head_softmax_fwd(fake, fake, 16, 0, 16, 0, None) == -2
+    assert lib.ltu_head_softmax_bwd(fake, fake, fake, 16, 0, 16, 0, None) == -2
+    assert lib.ltu_final_softmax_fwd(fake, fake, 1, 2, 2, 2, 0, 8, 0, None) == -2
+    assert lib.ltu_final_softmax_bwd(fake, fake, fake, 1, 2, 2, 2, 0, 8, 0, None) == -2
     assert lib.ltu_final_softmax_fwd(fake, fake, 1, 2, 2, 2, 8, 28, 0, None) == -2      # CP < 4 C
     assert lib.ltu_head_softmax_fwd(fake, fake, 16, 8, 7, 0, None) == -2                # CP < C
     wd5 = (ctypes.c_float * 5)(*([1.0] * 5))
