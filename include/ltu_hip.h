@@ -15,7 +15,7 @@
  *     (one process per GPU is the intended use).  The only process-global data are (a) the tuning
  *     knob table of ltu_config_set (mutex-protected; knobs are looked up per call: override, then
  *     the environment variable of the same name, then the default) and (b) per-device "dynamic
- *     LDS limit raised" latches for four kernels (atomic bit masks).
+ *     LDS limit raised" latches for five kernels (atomic bit masks).
  *   - Dropout: (p, seed) select a counter-based hash mask (a murmur3 finalizer + a linear expansion to 64 bits per
  *     4-element group, csrc/common.h); the backward entry points regenerate
  *     the mask from the same (p, seed) instead of reading a stored one.  Independence: the four keep decisions of a group are
@@ -680,6 +680,41 @@ int ltu_crop_index_build(const uint8_t* lab, long long n_voxels, uint32_t* index
                          ltu_stream_t s);
 int ltu_crop_index_select(const uint8_t* lab, long long n_voxels, const uint32_t* index, long long index_elems,
                           const uint32_t* queries, long long* out, int n, ltu_stream_t s);
+
+/* ---- augmentation of the NIfTI pipeline's patches (csrc/augment.hip; no reference counterpart: the monai driver crops, flips and
+ * rot90s only).
+ * sample_affine: patches [n][h][w][d] (f32 and / or u8, either pair NULL, not both) gathered from the scan [H][W][D] (the layout of
+ *   SpacedScan.img / .lab) through one float64 3x4 pull matrix per patch, mats a HOST array [n][12]: patch voxel (x, y, z) reads the
+ *   scan coordinate c = M (x, y, z, 1).  n <= LTU_SAMPLE_AFFINE_MAX (matrices, sigmas and seeds travel as kernel arguments).
+ *   image: trilinear, out = sum of w * (tap inside the scan ? voxel : fill) over the 8 taps; a tap outside is never loaded; a matrix
+ *          of integer coordinates reproduces the source voxels exactly (bit for bit, except that a source -0.0 comes out as +0.0).
+ *   label: the voxel at the round-half-even coordinate, 0 when that voxel is outside the scan.
+ *   The patch need not lie inside the scan.  Coordinates: an fp64 origin per workgroup tile (at most 256 voxel steps wide), split into
+ *   integer and fraction, fp32 increments inside the tile (within ~2e-5 voxel of fp64), clamped to [-2, S + 1] before the float -> int
+ *   conversion, which is therefore defined for every finite matrix.  When every matrix of the call has the form
+ *   [[a, b, 0, .], [c, e, 0, .], [0, 0, g, .]] (rotation about D only) a z-decoupled kernel runs: in-plane taps once per D column.
+ *   noise: noise_sigma (HOST float [n], NULL = none) and seeds (HOST uint64 [n], required with noise_sigma): with sigma_k > 0 the
+ *          image store adds sigma_k * z, z ~ N(0, 1) from the counter-based generator defined in csrc/augment.hip's header comment,
+ *          keyed by (seed_k, linear voxel index in the patch); sigma_k == 0 or NULL gives the bits of a call without noise.
+ *   Refused before any launch: NULL mats, unpaired pointers, n outside 0 .. LTU_SAMPLE_AFFINE_MAX, noise_sigma without seeds, a
+ *   non-finite matrix entry or fill, a negative or non-finite sigma LTU_E_ARG; a size < 1, a scan extent > 2^22, h > 65535, a patch of
+ *   2^32 voxels or more LTU_E_SHAPE; d % 4 == 0 with out_img not 16-byte or out_lab not 4-byte aligned LTU_E_ALIGN.
+ * gauss_blur3: out [n][H][W][D] f32 = mul_k * (3-D Gaussian blur of x [n][H][W][D]), out of place, one launch.  weights: HOST float
+ *   [n][3][LTU_BLUR_MAX_RADIUS + 1], the half tables w[0 .. r] of the axes H, W, D (normalised so that w[0] + 2 sum w[t] = 1; entries
+ *   beyond r are ignored); radii: HOST int [n][3], 0 = that axis untouched; mul: HOST float [n] or NULL (= 1), applied in the store.
+ *   Boundaries reflect (d c b a | a b c d | d c b a), the semantics of scipy.ndimage.gaussian_filter(mode='reflect').  A patch with
+ *   three radii 0 is copied as x * mul (mul == 1: bit-exact).  The three passes run inside a workgroup (pass D from memory into LDS,
+ *   pass W LDS to LDS, pass H LDS to memory): no intermediate volume, no workspace.  n <= LTU_BLUR_MAX_N.
+ *   Refused before any launch: NULL x / out / weights / radii, x == out, n outside 0 .. LTU_BLUR_MAX_N, a negative radius, a
+ *   non-finite weight or mul LTU_E_ARG; a radius above LTU_BLUR_MAX_RADIUS or >= that axis's extent, a size < 1 LTU_E_SHAPE. */
+#define LTU_SAMPLE_AFFINE_MAX 32
+#define LTU_BLUR_MAX_N 16
+#define LTU_BLUR_MAX_RADIUS 8
+int ltu_sample_affine(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats,
+                      const float* noise_sigma, const unsigned long long* seeds, int n, int H, int W, int D, int h, int w, int d,
+                      float fill, ltu_stream_t s);
+int ltu_gauss_blur3(const float* x, float* out, const float* weights, const int* radii, const float* mul, int n, int H, int W, int D,
+                    ltu_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,424 @@
+// Augmentation of the NIfTI pipeline's patches on the device (no reference counterpart: the monai driver crops, flips and rot90s
+// only).  Two kernels: ltu_sample_affine cuts rotated / zoomed / flipped patches straight from the scan in one gather (and adds
+// Gaussian noise in the store), ltu_gauss_blur3 blurs a batch of patches in one launch (three 1-D passes inside a workgroup).
+//
+// ---- the noise generator (restated in numpy by lintransunet_amd/data.py::noise_reference) ------------------------------------
+// Stateless like the dropout masks: the normal deviate of voxel i (the linear index (x * w + y) * d + z inside its patch, < 2^32)
+// of a patch with the 64-bit seed (lo = low 32 bits, hi = high 32 bits) is, with fmix32 of common.h and uint32 arithmetic,
+//   ka = fmix32(lo ^ 0x243F6A88) + fmix32(hi ^ 0x85A308D3) * 0x9E3779B1
+//   kb = fmix32(hi ^ 0x13198A2E) + fmix32(lo ^ 0x03707344) * 0x9E3779B1
+//   j  = i >> 1                                       (one Box-Muller pair per two voxels)
+//   w1 = fmix32(j ^ ka),  w2 = fmix32((j + 0x9E3779B9) ^ kb)
+//   u1 = ((w1 >> 9) + 0.5) * 2^-23,  u2 = ((w2 >> 9) + 0.5) * 2^-23        (exact in fp32, in (0, 1))
+//   r  = sqrt(-2 ln u1),  z[2j] = r cos(2 pi u2),  z[2j + 1] = r sin(2 pi u2)
+// in fp32 with logf / sqrtf / sincospif.  |z| <= sqrt(48 ln 2) = 5.77.
+#include "common.h"
+
+struct NoiseKey { uint32_t ka, kb; };
+__device__ __forceinline__ NoiseKey noise_key(unsigned long long seed) {
+  const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
+  NoiseKey k;
+  k.ka = fmix32(lo ^ 0x243F6A88u) + fmix32(hi ^ 0x85A308D3u) * 0x9E3779B1u;
+  k.kb = fmix32(hi ^ 0x13198A2Eu) + fmix32(lo ^ 0x03707344u) * 0x9E3779B1u;
+  return k;
+}
+// the two deviates of pair j
+__device__ __forceinline__ void noise_pair(const NoiseKey& k, uint32_t j, float* z0, float* z1) {
+  const uint32_t w1 = fmix32(j ^ k.ka), w2 = fmix32((j + 0x9E3779B9u) ^ k.kb);
+  const float u1 = ((float)(w1 >> 9) + 0.5f) * 1.1920928955078125e-7f, u2 = ((float)(w2 >> 9) + 0.5f) * 1.1920928955078125e-7f;
+  const float r = sqrtf(-2.f * logf(u1));
+  float sn, cs;
+  sincospif(2.f * u2, &sn, &cs);
+  *z0 = r * cs;
+  *z1 = r * sn;
+}
+
+// ---- ltu_sample_affine ---------------------------------------------------------------------------------------------------------
+// A workgroup takes TX consecutive x (patch H index), TY consecutive y and ZL * VEC consecutive z of one patch: ZL lanes along z,
+// then TY along y, then TX along x, powers of two chosen on the host from d and w so that ZL * TY * TX = 256 (a shallow, narrow
+// patch folds several x into a block instead of leaving lanes idle).  A row's origin o = M (x, y0, z0, 1) is fp64 and is split per
+// axis into an integer base and a fraction in [0, 1); inside the row tile the coordinate is base + (fr + m1 * yl + m2 * zl) with the
+// bracket in fp32: at most 256 steps of a tile keep it within ~2e-5 of the fp64 coordinate, floors, weights and tap indices are
+// fp32 / int32, and a matrix with integer entries gives exact integers: the weights are then 1 and 0 and the sum of w * v returns
+// the source voxel's value (its bits, except that a source -0.0 comes out as +0.0: 0.f + -0.f, and adding the 0 * v terms).  The bracket is clamped to [-2 - base, S + 1 - base] before the conversion (base itself
+// is clamped to +-2^22, beyond every scan the entry point accepts), so the conversion is defined for every finite matrix.
+struct SampleAffineArgs {
+  double mat[LTU_SAMPLE_AFFINE_MAX][12];
+  unsigned long long seed[LTU_SAMPLE_AFFINE_MAX];
+  float sigma[LTU_SAMPLE_AFFINE_MAX];
+};
+
+struct SaAxis { int base; float fr, lo, hi; };
+__device__ __forceinline__ SaAxis sa_axis(double o, int S) {
+  const double b = fmin(fmax(floor(o), -4194304.0), 4194304.0);
+  SaAxis a;
+  a.base = (int)b;
+  a.fr = (float)fmin(fmax(o - b, -3.0e7), 3.0e7);       // [0, 1) unless base was clamped: then far out on the right side
+  a.lo = (float)(-2.0 - b);
+  a.hi = (float)((double)S + 1.0 - b);                  // exact in fp32: |.| <= 2^23 + 2
+  return a;
+}
+// in-tile coordinate -> (index of the lower tap, weight of the upper tap)
+__device__ __forceinline__ void sa_split(const SaAxis& a, float l, int* i0, float* t) {
+  l = fminf(fmaxf(l, a.lo), a.hi);
+  const float f = floorf(l);
+  *t = l - f;
+  *i0 = a.base + (int)f;
+}
+// round half to even of base + l
+__device__ __forceinline__ int sa_round(int i0, float t) { return i0 + ((t > 0.5f || (t == 0.5f && (i0 & 1))) ? 1 : 0); }
+
+// ZDEC: every matrix of the launch has the form [[a, b, 0, .], [c, e, 0, .], [0, 0, g, .]] (rotation about D only): the in-plane
+// taps, weights and the label's in-plane voxel are computed once per lane, the VEC depth voxels are 1-D lerps on the four rows.
+template <bool ZDEC, int VEC, typename IDX>
+__global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lab,
+                                                            float* __restrict__ oimg, uint8_t* __restrict__ olab, SampleAffineArgs c,
+                                                            int H, int W, int D, int h, int w, int d, int zl_log2, int ty_log2, float fill) {
+  const int k = blockIdx.z;
+  const int zl = 1 << zl_log2, ty = 1 << ty_log2;
+  const int x = (int)(blockIdx.y << (8 - zl_log2 - ty_log2)) + (int)(threadIdx.x >> (zl_log2 + ty_log2));
+  const int ztiles = (d + zl * VEC - 1) / (zl * VEC);
+  const int tile_y = blockIdx.x / ztiles, tile_z = blockIdx.x - tile_y * ztiles;
+  const int y0 = tile_y * ty, z0 = tile_z * zl * VEC;
+  const int yl = (threadIdx.x >> zl_log2) & (ty - 1), zq = (threadIdx.x & (zl - 1)) * VEC;
+  const int y = y0 + yl, z = z0 + zq;
+  if (x >= h || y >= w || z >= d) return;
+  const double* m = c.mat[k];
+  SaAxis ax[3];
+  float my[3], mz[3];
+  const int S[3] = {H, W, D};
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    ax[s] = sa_axis(fma(m[4 * s], (double)x, fma(m[4 * s + 1], (double)y0, fma(m[4 * s + 2], (double)z0, m[4 * s + 3]))), S[s]);
+    my[s] = (float)m[4 * s + 1];
+    mz[s] = (float)m[4 * s + 2];
+  }
+  float vi[VEC];
+  uint8_t vl[VEC];
+  if (ZDEC) {
+    int i0[2];
+    float t[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) sa_split(ax[s], fmaf(my[s], (float)yl, ax[s].fr), &i0[s], &t[s]);
+    IDX row[4];                        // offset of the row's first voxel; 0 for a row outside the scan (never loaded through)
+    bool in[4];
+    float wxy[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int xi = i0[0] + (r >> 1), yi = i0[1] + (r & 1);
+      in[r] = (unsigned)xi < (unsigned)H && (unsigned)yi < (unsigned)W;
+      row[r] = in[r] ? ((IDX)xi * W + yi) * D : (IDX)0;
+      wxy[r] = ((r >> 1) ? t[0] : 1.f - t[0]) * ((r & 1) ? t[1] : 1.f - t[1]);
+    }
+    const int xr = sa_round(i0[0], t[0]), yr = sa_round(i0[1], t[1]);
+    const bool lin = (unsigned)xr < (unsigned)H && (unsigned)yr < (unsigned)W;
+    const IDX lrow = lin ? ((IDX)xr * W + yr) * D : (IDX)0;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      int iz;
+      float tz;
+      sa_split(ax[2], fmaf(mz[2], (float)(zq + j), ax[2].fr), &iz, &tz);
+      if (img != nullptr) {
+        float p[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const int zi = iz + e;
+          const bool zin = (unsigned)zi < (unsigned)D;
+          float acc = 0.f;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc += wxy[r] * ((in[r] && zin) ? img[row[r] + zi] : fill);
+          p[e] = acc;
+        }
+        vi[j] = (1.f - tz) * p[0] + tz * p[1];
+      }
+      if (lab != nullptr) {
+        const int zr = sa_round(iz, tz);
+        vl[j] = (lin && (unsigned)zr < (unsigned)D) ? lab[lrow + zr] : (uint8_t)0;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      int i0[3];
+      float t[3];
+#pragma unroll
+      for (int s = 0; s < 3; ++s) sa_split(ax[s], fmaf(my[s], (float)yl, fmaf(mz[s], (float)(zq + j), ax[s].fr)), &i0[s], &t[s]);
+      if (img != nullptr) {
+        float acc = 0.f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          const int bx = r >> 2, by = (r >> 1) & 1, bz = r & 1;
+          const int xi = i0[0] + bx, yi = i0[1] + by, zi = i0[2] + bz;
+          const bool in = (unsigned)xi < (unsigned)H && (unsigned)yi < (unsigned)W && (unsigned)zi < (unsigned)D;
+          const float wt = (bx ? t[0] : 1.f - t[0]) * (by ? t[1] : 1.f - t[1]) * (bz ? t[2] : 1.f - t[2]);
+          float v = fill;
+          if (in) v = img[((IDX)xi * W + yi) * D + zi];          // the offset exists only for a tap inside the scan
+          acc += wt * v;
+        }
+        vi[j] = acc;
+      }
+      if (lab != nullptr) {
+        const int xr = sa_round(i0[0], t[0]), yr = sa_round(i0[1], t[1]), zr = sa_round(i0[2], t[2]);
+        const bool in = (unsigned)xr < (unsigned)H && (unsigned)yr < (unsigned)W && (unsigned)zr < (unsigned)D;
+        uint8_t lv = 0;
+        if (in) lv = lab[((IDX)xr * W + yr) * D + zr];
+        vl[j] = lv;
+      }
+    }
+  }
+  const uint32_t vox = ((uint32_t)x * (uint32_t)w + (uint32_t)y) * (uint32_t)d + (uint32_t)z;       // < 2^32 (checked on the host)
+  const long long dst = (long long)k * h * w * d + vox;
+  if (img != nullptr) {
+    const float sg = c.sigma[k];
+    if (sg > 0.f) {
+      const NoiseKey key = noise_key(c.seed[k]);
+      if (VEC == 4) {                     // vox % 4 == 0: two whole pairs
+        float n[4];
+        noise_pair(key, vox >> 1, &n[0], &n[1]);
+        noise_pair(key, (vox >> 1) + 1, &n[2], &n[3]);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) vi[j] = fmaf(sg, n[j], vi[j]);
+      } else {
+        float n0, n1;
+        noise_pair(key, vox >> 1, &n0, &n1);
+        vi[0] = fmaf(sg, (vox & 1) ? n1 : n0, vi[0]);
+      }
+    }
+    if (VEC == 4) *reinterpret_cast<float4*>(oimg + dst) = make_float4(vi[0], vi[1], vi[2], vi[3]);
+    else oimg[dst] = vi[0];
+  }
+  if (lab != nullptr) {
+    if (VEC == 4)
+      *reinterpret_cast<uint32_t*>(olab + dst) = (uint32_t)vl[0] | ((uint32_t)vl[1] << 8) | ((uint32_t)vl[2] << 16) | ((uint32_t)vl[3] << 24);
+    else olab[dst] = vl[0];
+  }
+}
+
+template <bool ZDEC, int VEC, typename IDX>
+static void sample_affine_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SampleAffineArgs& c, int n, int H,
+                                 int W, int D, int h, int w, int d, float fill, hipStream_t st) {
+  const int per_lane = (d + VEC - 1) / VEC;
+  int zl_log2 = 0;
+  while ((1 << zl_log2) < per_lane && zl_log2 < (VEC == 4 ? 4 : 6)) ++zl_log2;
+  int ty_log2 = 0;
+  while ((1 << ty_log2) < w && zl_log2 + ty_log2 < 8) ++ty_log2;
+  const int zl = 1 << zl_log2, ty = 1 << ty_log2, tx = 256 >> (zl_log2 + ty_log2);
+  const unsigned tiles = cdiv(w, ty) * cdiv(d, zl * VEC);
+  hipLaunchKernelGGL((sample_affine_kernel<ZDEC, VEC, IDX>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c, H, W,
+                     D, h, w, d, zl_log2, ty_log2, fill);
+}
+
+extern "C" int ltu_sample_affine(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats,
+                                 const float* noise_sigma, const unsigned long long* seeds, int n, int H, int W, int D, int h, int w,
+                                 int d, float fill, ltu_stream_t s) {
+  if (mats == nullptr || (img == nullptr) != (out_img == nullptr) || (lab == nullptr) != (out_lab == nullptr) ||
+      (img == nullptr && lab == nullptr) || n < 0 || n > LTU_SAMPLE_AFFINE_MAX || (noise_sigma != nullptr && seeds == nullptr) ||
+      !(fill - fill == 0.f))
+    return LTU_E_ARG;
+  if (n == 0) return LTU_OK;
+  const int smax = 1 << 22;
+  if (H < 1 || W < 1 || D < 1 || H > smax || W > smax || D > smax || h < 1 || w < 1 || d < 1 || h > 65535 ||
+      (long long)h * w * d >= (1LL << 32) || (long long)cdiv(w, 4) * cdiv(d, 4) >= (1LL << 31))
+    return LTU_E_SHAPE;
+  SampleAffineArgs c;
+  bool zdec = true;
+  for (int k = 0; k < n; ++k) {
+    for (int j = 0; j < 12; ++j) {
+      const double v = mats[12 * k + j];
+      if (!(v - v == 0.0)) return LTU_E_ARG;             // NaN or infinite
+      c.mat[k][j] = v;
+    }
+    const double* m = mats + 12 * k;
+    zdec = zdec && m[2] == 0.0 && m[6] == 0.0 && m[8] == 0.0 && m[9] == 0.0;
+    const float sg = noise_sigma != nullptr ? noise_sigma[k] : 0.f;
+    if (!(sg >= 0.f) || !(sg - sg == 0.f)) return LTU_E_ARG;
+    c.sigma[k] = img != nullptr ? sg : 0.f;
+    c.seed[k] = seeds != nullptr ? seeds[k] : 0ull;
+  }
+  const int vec = (d % 4 == 0) ? 4 : 1;
+  if (vec == 4 && (((uintptr_t)out_img & 15) != 0 || ((uintptr_t)out_lab & 3) != 0)) return LTU_E_ALIGN;
+  const bool small = (long long)H * W * D < (1LL << 31);
+  const hipStream_t st = (hipStream_t)s;
+#define SA_GO(Z, V)                                                                                                       \
+  do {                                                                                                                    \
+    if (small) sample_affine_launch<Z, V, int>(img, lab, out_img, out_lab, c, n, H, W, D, h, w, d, fill, st);             \
+    else sample_affine_launch<Z, V, long long>(img, lab, out_img, out_lab, c, n, H, W, D, h, w, d, fill, st);             \
+  } while (0)
+  if (zdec && vec == 4) SA_GO(true, 4);
+  else if (zdec) SA_GO(true, 1);
+  else if (vec == 4) SA_GO(false, 4);
+  else SA_GO(false, 1);
+#undef SA_GO
+  return ltu_check_launch();
+}
+
+// ---- ltu_gauss_blur3 -----------------------------------------------------------------------------------------------------------
+// One workgroup blurs a TH x TW x 32 tile of one patch.  Pass D reads the input rows of the tile and of its (rh, rw) halo in H and W
+// from memory - 4 outputs per lane from 4 + 2 rd consecutive voxels, reflected at the patch's ends - and writes LDS buffer B
+// [TH + 2 rh][TW + 2 rw][32]; pass W reads B and writes C [TH + 2 rh][TW][32]; pass H reads C and stores mul * value.  The halos are
+// the call's largest radius per axis (the host knows them), so a call that blurs in plane only carries no halo it does not need.
+// LDS rows are 32 floats with the lanes along D in every pass: the 32 lanes of a half wave fall on 32 different banks in the W and
+// the H pass as they stand, no padding needed.  Every voxel of the tile is read from memory once per pass-D row it appears in (the
+// halo rows of neighbouring tiles overlap), written once, and nothing intermediate leaves the CU.
+#define GB_TD 32
+#define GB_TH 16
+#define GB_TAPS (LTU_BLUR_MAX_RADIUS + 1)
+static_assert(GB_TD == 32, "the blur's index arithmetic (rows of 8 quads / 32 lanes) is written for 32");
+struct BlurArgs {
+  float wt[LTU_BLUR_MAX_N][3][GB_TAPS];       // wt[k][axis][t], t = 0 .. radius; 0 beyond
+  int rad[LTU_BLUR_MAX_N][3];
+  float mul[LTU_BLUR_MAX_N];
+};
+
+// scipy's 'reflect' (d c b a | a b c d | d c b a) for any i
+__device__ __forceinline__ int reflect_idx(int i, int n) {
+  int mth = i % (2 * n);
+  if (mth < 0) mth += 2 * n;
+  return mth < n ? mth : 2 * n - 1 - mth;
+}
+
+// 4 outputs from the window v[0 .. 4 + 2 R): out[i] = w[0] v[R + i] + sum_t w[t] (v[R + i - t] + v[R + i + t])
+template <int RMAX>
+__device__ __forceinline__ void blur4(const float (&v)[4 + 2 * RMAX], const float* __restrict__ wt, int r, float (&o)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float acc = wt[0] * v[RMAX + i];
+#pragma unroll
+    for (int t = 1; t <= RMAX; ++t)
+      if (t <= r) acc = fmaf(wt[t], v[RMAX + i - t] + v[RMAX + i + t], acc);
+    o[i] = r == 0 ? v[RMAX + i] : acc;
+  }
+}
+
+template <int RMAX>
+__global__ void __launch_bounds__(512) gauss_blur3_kernel(const float* __restrict__ x, float* __restrict__ out, BlurArgs c, int H, int W,
+                                                          int D, int TW, int rh, int rw) {
+  extern __shared__ float gb_lds[];
+  const int k = blockIdx.y;
+  const int tilesD = (D + GB_TD - 1) / GB_TD, tilesW = (W + TW - 1) / TW;
+  int b = blockIdx.x;
+  const int td = b % tilesD; b /= tilesD;
+  const int tw = b % tilesW;
+  const int th = b / tilesW;
+  const int h0 = th * GB_TH, w0 = tw * TW, d0 = td * GB_TD;
+  const int BH = GB_TH + 2 * rh, BW = TW + 2 * rw;
+  float* B = gb_lds;                              // [BH][BW][32]
+  float* C = gb_lds + BH * BW * GB_TD;            // [BH][TW][32]
+  const long long per = (long long)H * W * D;
+  const float* xk = x + k * per;
+  float* ok = out + k * per;
+  const int rhk = c.rad[k][0], rwk = c.rad[k][1], rdk = c.rad[k][2];
+  const float* wh = c.wt[k][0];
+  const float* ww = c.wt[k][1];
+  const float* wd = c.wt[k][2];
+
+  // pass D: memory -> B
+  for (int it = threadIdx.x; it < BH * BW * (GB_TD / 4); it += blockDim.x) {
+    const int q = it & 7, rowi = it >> 3;
+    const int wwi = rowi % BW, hhi = rowi / BW;
+    const int dq = d0 + 4 * q;
+    if (dq >= D) continue;
+    const int gh = reflect_idx(h0 - rh + hhi, H), gw = reflect_idx(w0 - rw + wwi, W);
+    const float* row = xk + ((long long)gh * W + gw) * D;
+    float v[4 + 2 * RMAX];
+    const bool interior = dq - rdk >= 0 && dq + 3 + rdk < D;
+#pragma unroll
+    for (int j = 0; j < 4 + 2 * RMAX; ++j) {
+      const int off = j - RMAX;                   // window position relative to dq
+      v[j] = 0.f;
+      if (off >= -rdk && off < 4 + rdk) v[j] = row[interior ? dq + off : reflect_idx(dq + off, D)];
+    }
+    float o[4];
+    blur4<RMAX>(v, wd, rdk, o);
+    *reinterpret_cast<float4*>(B + (hhi * BW + wwi) * GB_TD + 4 * q) = make_float4(o[0], o[1], o[2], o[3]);
+  }
+  __syncthreads();
+  // pass W: B -> C, 4 consecutive w per lane, lanes along d
+  for (int it = threadIdx.x; it < BH * (TW / 4) * GB_TD; it += blockDim.x) {
+    const int dl = it & 31, r2 = it >> 5;
+    const int wq = r2 % (TW / 4), hhi = r2 / (TW / 4);
+    const float* brow = B + (hhi * BW + rw + 4 * wq) * GB_TD + dl;       // window position 0 of this lane
+    float v[4 + 2 * RMAX];
+#pragma unroll
+    for (int j = 0; j < 4 + 2 * RMAX; ++j) {
+      const int off = j - RMAX;
+      v[j] = 0.f;
+      if (off >= -rwk && off < 4 + rwk) v[j] = brow[off * GB_TD];
+    }
+    float o[4];
+    blur4<RMAX>(v, ww, rwk, o);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) C[(hhi * TW + 4 * wq + i) * GB_TD + dl] = o[i];
+  }
+  __syncthreads();
+  // pass H: C -> memory, 4 consecutive h per lane, lanes along d
+  const float mul = c.mul[k];
+  for (int it = threadIdx.x; it < (GB_TH / 4) * TW * GB_TD; it += blockDim.x) {
+    const int dl = it & 31, r2 = it >> 5;
+    const int wl = r2 % TW, hq = r2 / TW;
+    const int gw = w0 + wl, gd = d0 + dl;
+    if (gw >= W || gd >= D || h0 + 4 * hq >= H) continue;
+    const float* crow = C + ((rh + 4 * hq) * TW + wl) * GB_TD + dl;
+    float v[4 + 2 * RMAX];
+#pragma unroll
+    for (int j = 0; j < 4 + 2 * RMAX; ++j) {
+      const int off = j - RMAX;
+      v[j] = 0.f;
+      if (off >= -rhk && off < 4 + rhk) v[j] = crow[off * TW * GB_TD];
+    }
+    float o[4];
+    blur4<RMAX>(v, wh, rhk, o);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int gh = h0 + 4 * hq + i;
+      if (gh < H) ok[((long long)gh * W + gw) * D + gd] = mul == 1.f ? o[i] : o[i] * mul;
+    }
+  }
+}
+
+extern "C" int ltu_gauss_blur3(const float* x, float* out, const float* weights, const int* radii, const float* mul, int n, int H,
+                               int W, int D, ltu_stream_t s) {
+  if (x == nullptr || out == nullptr || x == out || weights == nullptr || radii == nullptr || n < 0 || n > LTU_BLUR_MAX_N)
+    return LTU_E_ARG;
+  if (n == 0) return LTU_OK;
+  if (H < 1 || W < 1 || D < 1 || H > (1 << 22) || W > (1 << 22) || D > (1 << 22)) return LTU_E_SHAPE;
+  BlurArgs c;
+  int rmax[3] = {0, 0, 0};
+  const int ext[3] = {H, W, D};
+  for (int k = 0; k < n; ++k) {
+    for (int a = 0; a < 3; ++a) {
+      const int r = radii[3 * k + a];
+      if (r < 0) return LTU_E_ARG;
+      if (r > LTU_BLUR_MAX_RADIUS || (r > 0 && r >= ext[a])) return LTU_E_SHAPE;
+      c.rad[k][a] = r;
+      if (r > rmax[a]) rmax[a] = r;
+      for (int t = 0; t < GB_TAPS; ++t) {
+        const float wv = t <= r ? weights[(3 * k + a) * GB_TAPS + t] : 0.f;
+        if (!(wv - wv == 0.f)) return LTU_E_ARG;
+        c.wt[k][a][t] = wv;
+      }
+    }
+    const float m = mul != nullptr ? mul[k] : 1.f;
+    if (!(m - m == 0.f)) return LTU_E_ARG;
+    c.mul[k] = m;
+  }
+  // the widest tile whose two buffers fit the CU's 160 KiB
+  const int rh = rmax[0], rw = rmax[1];
+  int TW = 16;
+  auto lds_bytes = [&](int tw) { return ((GB_TH + 2 * rh) * (tw + 2 * rw) + (GB_TH + 2 * rh) * tw) * GB_TD * (int)sizeof(float); };
+  if (lds_bytes(TW) > 160 * 1024) TW = 8;
+  const int smem = lds_bytes(TW);
+  const long long tiles = (long long)cdiv(H, GB_TH) * cdiv(W, TW) * cdiv(D, GB_TD);
+  if (tiles >= (1LL << 31)) return LTU_E_SHAPE;
+  const bool wide = rmax[0] > 4 || rmax[1] > 4 || rmax[2] > 4;
+  static LtuDevOnce attr_once;
+  if (attr_once.first()) {
+    ltu_dyn_lds(&gauss_blur3_kernel<4>, 160 * 1024);
+    ltu_dyn_lds(&gauss_blur3_kernel<8>, 160 * 1024);
+  }
+  if (wide)
+    hipLaunchKernelGGL(gauss_blur3_kernel<8>, dim3((unsigned)tiles, n), dim3(512), smem, (hipStream_t)s, x, out, c, H, W, D, TW, rh, rw);
+  else
+    hipLaunchKernelGGL(gauss_blur3_kernel<4>, dim3((unsigned)tiles, n), dim3(512), smem, (hipStream_t)s, x, out, c, H, W, D, TW, rh, rw);
+  return ltu_check_launch();
+}

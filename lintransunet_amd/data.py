@@ -441,6 +441,7 @@ class SpacedScan:
             lv = nl.data if (nl.slope, nl.inter) == (1.0, 0.0) else nl.scaled()
             rl = torch.as_tensor(np.ascontiguousarray(label_u8(lv))).to(device)
         self.img, self.lab = resample(ri, rl, self.matrix, self.shape, intensity_map(intensity, ni.slope, ni.inter), code)
+        self.pixdim, self.intensity = tuple(float(p) for p in pixdim), intensity      # sample(augment=) rotates in mm, fills with the window's floor
         self._label_host = self._crop_index = None
 
     @property
@@ -506,34 +507,243 @@ def crop_orient(img, lab, draws, spatial_size):
     return oi, ol
 
 
-def sample(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_prob=0.5, host_centers=False, ratios=None):
+# ---- augmentation of the NIfTI pipeline (csrc/augment.hip; no reference counterpart) --------------------------------------------
+# Rotation, zoom, flip, rot90 and the crop are ONE gather from the scan (a rotated patch shows the anatomy around it, not replicated
+# borders), with Gaussian noise added in the store; blur and brightness are one launch over the patches; gamma is adjust_contrast.
+
+def patch_matrix(start, size, flip, k, angles=(0.0, 0.0, 0.0), zoom=1.0, spacing=(1.0, 1.0, 1.0)):
+    """3x4 float64 pull matrix (patch voxel -> scan voxel) of a patch of `size` whose unrotated crop begins at `start`:
+    M = T(start + (size-1)/2) S^-1 Rx Ry Rz (1/zoom) S P T(-(size-1)/2), S = diag(spacing) (the rotation happens in millimetres),
+    P the signed permutation of orient_desc(flip, k), angles in radians about H, W, D in rotate_matrix's convention, zoom > 1
+    magnifies.  With zero angles and zoom 1 the entries are integers and the matrix selects the voxels crop_orient selects."""
+    size = np.asarray(size, dtype=np.float64)
+    c = (size - 1) / 2
+    fh, fw, swap = orient_desc(flip, k)
+    if swap and size[0] != size[1]:
+        raise ValueError(f'rot90 by an odd k of a non-square patch ({int(size[0])} x {int(size[1])}) is not supported')
+    sa, sb = (-1.0 if fh else 1.0), (-1.0 if fw else 1.0)
+    P = np.eye(4)
+    P[:2, :2] = [[0.0, sa], [sb, 0.0]] if swap else [[sa, 0.0], [0.0, sb]]
+    t0, t1 = np.eye(4), np.eye(4)
+    t0[:3, 3], t1[:3, 3] = -c, np.asarray(start, dtype=np.float64) + c
+    if not any(float(a) != 0.0 for a in angles) and float(zoom) == 1.0:
+        return (t1 @ P @ t0)[:3]                         # exact integers (and halves that cancel)
+    ax, ay, az = (float(a) for a in angles)
+    rx = np.array([[1, 0, 0, 0], [0, np.cos(ax), -np.sin(ax), 0], [0, np.sin(ax), np.cos(ax), 0], [0, 0, 0, 1]], dtype=np.float64)
+    ry = np.array([[np.cos(ay), 0, np.sin(ay), 0], [0, 1, 0, 0], [-np.sin(ay), 0, np.cos(ay), 0], [0, 0, 0, 1]], dtype=np.float64)
+    rz = np.array([[np.cos(az), -np.sin(az), 0, 0], [np.sin(az), np.cos(az), 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=np.float64)
+    sp = np.asarray(spacing, dtype=np.float64)
+    S, Si = np.diag([*sp, 1.0]), np.diag([*(1.0 / sp), 1.0])
+    Z = np.diag([1.0 / float(zoom)] * 3 + [1.0])
+    return (t1 @ Si @ rx @ ry @ rz @ Z @ S @ P @ t0)[:3]
+
+
+def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None):
+    """ltu_sample_affine: device patches ([n,1,h,w,d] f32 or None, [n,1,h,w,d] u8 or None) gathered from img / lab [H,W,D] through
+    mats [n,3,4] (float64 pull matrices, patch voxel -> scan voxel): image trilinear with `fill` outside the scan, label nearest
+    (round half even) with 0 outside.  noise_sigma [n] with seeds [n] (uint64) adds sigma_k * N(0, 1) to patch k in the store
+    (noise_reference restates the generator)."""
+    vol = img if img is not None else lab
+    if vol is None or not vol.is_cuda:
+        raise _lib.LtuError('data.sample_affine runs on the GPU only (no CPU fallback)')
+    if img is not None and lab is not None and img.shape != lab.shape:
+        raise ValueError(f'image {tuple(img.shape)} and label {tuple(lab.shape)} differ in shape')
+    if (img is not None and (img.dtype != torch.float32 or not img.is_contiguous())) or \
+            (lab is not None and (lab.dtype != torch.uint8 or not lab.is_contiguous())):
+        raise ValueError('sample_affine takes a contiguous float32 image and uint8 label')
+    H, W, D = vol.shape
+    h, w, d = (int(s) for s in size)
+    m = np.ascontiguousarray(np.asarray(mats, dtype=np.float64).reshape(-1, 12))
+    n = m.shape[0]
+    sg = sd = None
+    if noise_sigma is not None:
+        if seeds is None:
+            raise ValueError('noise_sigma needs seeds')
+        sg = np.ascontiguousarray(np.asarray(noise_sigma, dtype=np.float32).reshape(n))
+        sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(n))
+    oi = torch.empty((n, 1, h, w, d), device=vol.device, dtype=torch.float32) if img is not None else None
+    ol = torch.empty((n, 1, h, w, d), device=vol.device, dtype=torch.uint8) if lab is not None else None
+    for s in range(0, n, _lib.SAMPLE_AFFINE_MAX):
+        e = min(n, s + _lib.SAMPLE_AFFINE_MAX)
+        _lib.call('ltu_sample_affine', _p(img), _p(lab), _p(oi[s:e]) if oi is not None else 0, _p(ol[s:e]) if ol is not None else 0,
+                  m[s:e].ctypes.data, sg[s:e].ctypes.data if sg is not None else 0, sd[s:e].ctypes.data if sd is not None else 0,
+                  e - s, H, W, D, h, w, d, float(fill), _s())
+    return oi, ol
+
+
+def blur_weights(sigma):
+    """the 1-D table of scipy.ndimage.gaussian_filter1d(truncate=4.0): float64 [2 r + 1], r = int(4 sigma + 0.5), exp(-k^2 / (2
+    sigma^2)) normalised to sum 1; sigma 0 is the unit impulse"""
+    sigma = float(sigma)
+    r = int(4.0 * sigma + 0.5)
+    if r == 0:
+        return np.ones(1)
+    k = np.arange(-r, r + 1, dtype=np.float64)
+    wt = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+    return wt / wt.sum()
+
+
+def gaussian_blur(x, sigmas, mul=None):
+    """ltu_gauss_blur3: x [n,(1,)H,W,D] f32 -> mul_k * gaussian_filter(x_k, sigma_k, mode='reflect', truncate=4.0), out of place, one
+    launch per LTU_BLUR_MAX_N patches.  sigmas: [n] or [n][3] (per axis H, W, D) in voxels, 0 leaves an axis untouched; a radius
+    int(4 sigma + 0.5) above 8 or not below the axis's extent is refused."""
+    v = _vol4(x)
+    if v.dtype != torch.float32:
+        raise ValueError(f'gaussian_blur takes float32 patches, got {v.dtype}')
+    n, H, W, D = v.shape
+    sg = np.asarray(sigmas, dtype=np.float64)
+    sg = np.repeat(sg.reshape(n, 1), 3, 1) if sg.ndim <= 1 else sg.reshape(n, 3)
+    taps = _lib.BLUR_MAX_RADIUS + 1
+    wts = np.zeros((n, 3, taps), dtype=np.float32)
+    rad = np.zeros((n, 3), dtype=np.int32)
+    for k in range(n):
+        for a in range(3):
+            t = blur_weights(sg[k, a])
+            r = len(t) // 2
+            rad[k, a] = r
+            if r < taps:                                  # a larger radius is refused by the call
+                wts[k, a, :r + 1] = t[r:]
+    ml = np.ascontiguousarray(np.asarray(mul, dtype=np.float32).reshape(n)) if mul is not None else None
+    out = torch.empty_like(v)
+    for s in range(0, n, _lib.BLUR_MAX_N):
+        e = min(n, s + _lib.BLUR_MAX_N)
+        _lib.call('ltu_gauss_blur3', _p(v[s:e]), _p(out[s:e]), wts[s:e].ctypes.data, rad[s:e].ctypes.data,
+                  ml[s:e].ctypes.data if ml is not None else 0, e - s, H, W, D, _s())
+    return out.view(x.shape)
+
+
+def _fmix32(h):
+    h = h ^ (h >> np.uint32(16))
+    h = h * np.uint32(0x85EBCA6B)
+    h = h ^ (h >> np.uint32(13))
+    h = h * np.uint32(0xC2B2AE35)
+    return h ^ (h >> np.uint32(16))
+
+
+def noise_reference(seed, count):
+    """the N(0, 1) deviates ltu_sample_affine adds (times sigma) to voxels 0 .. count-1 (linear index in the patch) of a patch with
+    this seed: the generator of csrc/augment.hip's header comment on the same 32-bit words, Box-Muller in float64"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    with np.errstate(over='ignore'):
+        lo, hi = np.uint32(seed & 0xFFFFFFFF), np.uint32(seed >> 32)
+        g = np.uint32(0x9E3779B1)
+        ka = _fmix32(lo ^ np.uint32(0x243F6A88)) + _fmix32(hi ^ np.uint32(0x85A308D3)) * g
+        kb = _fmix32(hi ^ np.uint32(0x13198A2E)) + _fmix32(lo ^ np.uint32(0x03707344)) * g
+        j = np.arange((int(count) + 1) // 2, dtype=np.uint32)
+        w1 = _fmix32(j ^ ka)
+        w2 = _fmix32((j + np.uint32(0x9E3779B9)) ^ kb)
+    u1 = ((w1 >> np.uint32(9)).astype(np.float64) + 0.5) * 2.0 ** -23
+    u2 = ((w2 >> np.uint32(9)).astype(np.float64) + 0.5) * 2.0 ** -23
+    r = np.sqrt(-2.0 * np.log(u1))
+    z = np.stack([r * np.cos(2 * np.pi * u2), r * np.sin(2 * np.pi * u2)], 1).ravel()
+    return z[:int(count)]
+
+
+class Augmentation:
+    """The random augmentations of data.sample(..., augment=): a plain record of probabilities and ranges.  rot_range: the largest
+    |angle| in radians about H, W, D (the default rotates about D only: slices are 2 mm against 0.5 mm in plane); zoom > 1
+    magnifies; noise_std, blur_sigma (voxels), brightness and gamma are uniform ranges; fill: the image value outside the scan, None =
+    the lower bound of the scan's intensity window (0.0 when it has none)."""
+
+    def __init__(self, rot_prob=0.2, rot_range=(0.0, 0.0, np.pi), zoom_prob=0.2, zoom_range=(0.7, 1.4), noise_prob=0.1,
+                 noise_std=(0.0, 0.1), blur_prob=0.2, blur_sigma=(0.5, 1.0), brightness_prob=0.15, brightness=(0.75, 1.25),
+                 gamma_prob=0.3, gamma=(0.7, 1.5), fill=None):
+        self.rot_prob, self.rot_range = rot_prob, tuple(rot_range)
+        self.zoom_prob, self.zoom_range = zoom_prob, tuple(zoom_range)
+        self.noise_prob, self.noise_std = noise_prob, tuple(noise_std)
+        self.blur_prob, self.blur_sigma = blur_prob, tuple(blur_sigma)
+        self.brightness_prob, self.brightness = brightness_prob, tuple(brightness)
+        self.gamma_prob, self.gamma = gamma_prob, tuple(gamma)
+        self.fill = fill
+
+    def draw(self, rs):
+        """one sample's draws in their fixed order; every draw is made whether or not its transform fires (draw_augmentation's
+        convention)"""
+        p = {}
+        p['rotate'] = rs.rand() < self.rot_prob
+        p['angles'] = [rs.uniform(-r, r) for r in self.rot_range]
+        p['zoom'] = rs.rand() < self.zoom_prob
+        p['zoom_factor'] = rs.uniform(*self.zoom_range)
+        p['noise'] = rs.rand() < self.noise_prob
+        p['noise_std'] = rs.uniform(*self.noise_std)
+        p['seed'] = (int(rs.randint(2 ** 31)) << 31) | int(rs.randint(2 ** 31))
+        p['blur'] = rs.rand() < self.blur_prob
+        p['sigma'] = rs.uniform(*self.blur_sigma)
+        p['bright'] = rs.rand() < self.brightness_prob
+        p['mul'] = rs.uniform(*self.brightness)
+        p['contrast'] = rs.rand() < self.gamma_prob
+        p['gamma'] = rs.uniform(*self.gamma)
+        return p
+
+
+def _augmented(scan, draws, params, spatial_size, augment, spacing):
+    """the patches of draws [(centre, flip, k)] under params (one Augmentation.draw per patch): one sample_affine, then one
+    gaussian_blur if a patch blurs or brightens, then adjust_contrast if a patch fires gamma"""
+    size = tuple(int(s) for s in spatial_size)
+    fill = augment.fill
+    if fill is None:
+        lo = intensity_map(getattr(scan, 'intensity', None))[2]
+        fill = float(lo) if np.isfinite(lo) else 0.0
+    mats = [patch_matrix([max(c[a] - size[a] // 2, 0) for a in range(3)], size, f, k,
+                         p['angles'] if p['rotate'] else (0.0, 0.0, 0.0), p['zoom_factor'] if p['zoom'] else 1.0, spacing)
+            for (c, f, k), p in zip(draws, params)]
+    noisy = any(p['noise'] for p in params)
+    img, lab = sample_affine(scan.img, scan.lab, np.stack(mats), size, fill,
+                             [p['noise_std'] if p['noise'] else 0.0 for p in params] if noisy else None,
+                             [p['seed'] for p in params] if noisy else None)
+    if any(p['blur'] or p['bright'] for p in params):
+        img = gaussian_blur(img, [p['sigma'] if p['blur'] else 0.0 for p in params], [p['mul'] if p['bright'] else 1.0 for p in params])
+    if any(p['contrast'] for p in params):
+        img = adjust_contrast(img, [p['gamma'] if p['contrast'] else -1.0 for p in params])
+    return img, lab
+
+
+def sample_draws(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_prob=0.5, host_centers=False, ratios=None,
+                 augment=None):
+    """every host draw of one data.sample call: ([(centre, flip, k)], [Augmentation.draw dict] or None).  The four draws of every
+    sample come first, exactly as without augment (so the crops, flips and rot90s of an augmented call are those of the plain
+    call from the same generator); the augmentation draws of sample 0, 1, ... follow."""
+    if host_centers and ratios is None:
+        draws = [draw_monai_sample(scan.label_host, spatial_size, rand_state, flip_prob, rot90_prob) for _ in range(num_samples)]
+    else:
+        index = None if host_centers else scan.crop_index
+        centres, rest = [], []
+        for _ in range(num_samples):
+            if host_centers:
+                centres.append(class_crop_centers(scan.label_host, spatial_size, 1, ratios, len(ratios), rand_state)[0])
+            elif ratios is not None:
+                centres.extend(index.class_queries(1, ratios, len(ratios), rand_state))
+            else:
+                centres.extend(_posneg_queries(index.n_foreground, index.n_background, 1, 0.7, 0.3, rand_state))
+            flip = rand_state.rand() < flip_prob
+            k = rand_state.randint(3) + 1
+            rot = rand_state.rand() < rot90_prob
+            rest.append((bool(flip), int(k) if rot else 0))
+        if index is not None:
+            centres = index.resolve(centres, spatial_size)
+        draws = [(c, f, k) for c, (f, k) in zip(centres, rest)]
+    return draws, ([augment.draw(rand_state) for _ in range(num_samples)] if augment is not None else None)
+
+
+def sample(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_prob=0.5, host_centers=False, ratios=None,
+           augment=None):
     """the random half of the driver's dataset: num_samples patches ([n,1,h,w,d] f32, u8) of a SpacedScan, each with its own
     crop centre, flip and rot90 in draw_monai_sample's order.  The centres come from scan.crop_index: every host draw of every
     sample is made first (per sample: centre, flip, k, rotation probability), then one select launch resolves all centres.
     host_centers=True draws them from scan.label_host instead (np.nonzero passes over the label per sample): the same patches
     from the same generator.  ratios: one weight per class 0 .. num_classes - 1 switches the centre draw from
-    RandCropByPosNegLabeld to RandCropByLabelClassesd (class_centers / class_crop_centers, num_samples 1 per sample)."""
+    RandCropByPosNegLabeld to RandCropByLabelClassesd (class_centers / class_crop_centers, num_samples 1 per sample).
+    augment: an Augmentation.  The draws above keep their place; behind them come, per sample, Augmentation.draw's (rotation fire,
+    three angles; zoom fire, factor; noise fire, std, two seed words; blur fire, sigma; brightness fire, multiplier; gamma fire,
+    gamma).  The patches are then gathered through patch_matrix by one sample_affine (rotation in millimetres of scan.pixdim,
+    noise in the store), blurred / brightened by one gaussian_blur and gamma-adjusted by adjust_contrast.  None changes nothing:
+    the same draws, patches and generator state."""
     if scan.lab is None:
         raise ValueError('sampling needs a label (RandCropByPosNegLabeld draws centres from it)')
-    if host_centers and ratios is None:
-        draws = [draw_monai_sample(scan.label_host, spatial_size, rand_state, flip_prob, rot90_prob) for _ in range(num_samples)]
+    draws, params = sample_draws(scan, spatial_size, rand_state, num_samples, flip_prob, rot90_prob, host_centers, ratios, augment)
+    if augment is None:
         return crop_orient(scan.img, scan.lab, draws, spatial_size)
-    index = None if host_centers else scan.crop_index
-    centres, rest = [], []
-    for _ in range(num_samples):
-        if host_centers:
-            centres.append(class_crop_centers(scan.label_host, spatial_size, 1, ratios, len(ratios), rand_state)[0])
-        elif ratios is not None:
-            centres.extend(index.class_queries(1, ratios, len(ratios), rand_state))
-        else:
-            centres.extend(_posneg_queries(index.n_foreground, index.n_background, 1, 0.7, 0.3, rand_state))
-        flip = rand_state.rand() < flip_prob
-        k = rand_state.randint(3) + 1
-        rot = rand_state.rand() < rot90_prob
-        rest.append((bool(flip), int(k) if rot else 0))
-    if index is not None:
-        centres = index.resolve(centres, spatial_size)
-    return crop_orient(scan.img, scan.lab, [(c, f, k) for c, (f, k) in zip(centres, rest)], spatial_size)
+    return _augmented(scan, draws, params, spatial_size, augment, getattr(scan, 'pixdim', (1.0, 1.0, 1.0)))
 
 
 def to_native(label_map, scan):
