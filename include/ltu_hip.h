@@ -699,6 +699,21 @@ int ltu_crop_index_select(const uint8_t* lab, long long n_voxels, const uint32_t
  *   Refused before any launch: NULL mats, unpaired pointers, n outside 0 .. LTU_SAMPLE_AFFINE_MAX, noise_sigma without seeds, a
  *   non-finite matrix entry or fill, a negative or non-finite sigma LTU_E_ARG; a size < 1, a scan extent > 2^22, h > 65535, a patch of
  *   2^32 voxels or more LTU_E_SHAPE; d % 4 == 0 with out_img not 16-byte or out_lab not 4-byte aligned LTU_E_ALIGN.
+ * sample_elastic: sample_affine with a uniform cubic B-spline free-form deformation applied in patch space ahead of M.  phi: a DEVICE
+ *   array [n][3][gh][gw][gd] f32 (at most 6 KB per patch: too large for kernel arguments at n = 32), the control lattice of patch k:
+ *   displacements in PATCH voxels along the patch axes H, W, D, 4 <= gh, gw, gd <= LTU_ELASTIC_MAX_GRID.  For the patch voxel
+ *   p = (x, y, z) and, per axis a with patch coordinate t and patch extent n_a,
+ *     s = t * (g_a - 3) / (n_a - 1)   (s = 0 when n_a == 1),   i = min(floor(s), g_a - 4),   f = s - i,
+ *     B(f) = ((1-f)^3, 3f^3 - 6f^2 + 4, -3f^3 + 3f^2 + 3f + 1, f^3) / 6,
+ *     u_c(p) = sum_{l,m,n in 0..3} B_l(fx) B_m(fy) B_n(fz) * phi[c][ix+l][iy+m][iz+n],   scan coordinate c = M (p + u(p), 1):
+ *   C2-smooth, exactly 0 for a zero lattice (the output then has sample_affine's bits), and the crop, flip, rot90, rotation and zoom
+ *   of M keep their meaning.  Each component of u is clamped to +-LTU_ELASTIC_MAX_DISP voxels (a NaN to -LTU_ELASTIC_MAX_DISP), so
+ *   any lattice content gives defined coordinates; M[:, :3] u is added in fp32 inside sample_affine's coordinate bracket.  The
+ *   lattice enters LDS once per workgroup, contracted with the tile's x weights; a lane contracts its y weights into the few
+ *   lattice columns along z that its run of voxels needs, then 4 multiply-adds per voxel and component.  Image, label, fill, noise,
+ *   mats, n as in sample_affine; no atomics, no workspace, no synchronisation: capturable.
+ *   Refused before any launch: everything sample_affine refuses, with its codes; NULL phi LTU_E_ARG; a lattice extent outside
+ *   4 .. LTU_ELASTIC_MAX_GRID LTU_E_SHAPE; phi not 4-byte aligned LTU_E_ALIGN.
  * gauss_blur3: out [n][H][W][D] f32 = mul_k * (3-D Gaussian blur of x [n][H][W][D]), out of place, one launch.  weights: HOST float
  *   [n][3][LTU_BLUR_MAX_RADIUS + 1], the half tables w[0 .. r] of the axes H, W, D (normalised so that w[0] + 2 sum w[t] = 1; entries
  *   beyond r are ignored); radii: HOST int [n][3], 0 = that axis untouched; mul: HOST float [n] or NULL (= 1), applied in the store.
@@ -708,11 +723,16 @@ int ltu_crop_index_select(const uint8_t* lab, long long n_voxels, const uint32_t
  *   Refused before any launch: NULL x / out / weights / radii, x == out, n outside 0 .. LTU_BLUR_MAX_N, a negative radius, a
  *   non-finite weight or mul LTU_E_ARG; a radius above LTU_BLUR_MAX_RADIUS or >= that axis's extent, a size < 1 LTU_E_SHAPE. */
 #define LTU_SAMPLE_AFFINE_MAX 32
+#define LTU_ELASTIC_MAX_GRID 8
+#define LTU_ELASTIC_MAX_DISP 64
 #define LTU_BLUR_MAX_N 16
 #define LTU_BLUR_MAX_RADIUS 8
 int ltu_sample_affine(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats,
                       const float* noise_sigma, const unsigned long long* seeds, int n, int H, int W, int D, int h, int w, int d,
                       float fill, ltu_stream_t s);
+int ltu_sample_elastic(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats, const float* phi,
+                       int gh, int gw, int gd, const float* noise_sigma, const unsigned long long* seeds, int n, int H, int W, int D,
+                       int h, int w, int d, float fill, ltu_stream_t s);
 int ltu_gauss_blur3(const float* x, float* out, const float* weights, const int* radii, const float* mul, int n, int H, int W, int D,
                     ltu_stream_t s);
 

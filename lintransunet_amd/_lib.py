@@ -30,6 +30,7 @@ WGRAD_GROUP_MAX = 32      # LTU_WGRAD_GROUP_MAX of include/ltu_hip.h
 CROP_ORIENT_MAX = 64      # LTU_CROP_ORIENT_MAX of include/ltu_hip.h
 BLEND_ITEMS_MAX = 32      # LTU_BLEND_ITEMS_MAX of include/ltu_hip.h
 SAMPLE_AFFINE_MAX = 32    # LTU_SAMPLE_AFFINE_MAX of include/ltu_hip.h
+ELASTIC_MAX_GRID, ELASTIC_MAX_DISP = 8, 64      # LTU_ELASTIC_MAX_GRID / LTU_ELASTIC_MAX_DISP of include/ltu_hip.h
 BLUR_MAX_N, BLUR_MAX_RADIUS = 16, 8      # LTU_BLUR_MAX_N / LTU_BLUR_MAX_RADIUS of include/ltu_hip.h
 U8, I16 = 2, 3            # LTU_U8 / LTU_I16 source dtypes of ltu_resample_grid (LTU_F32 = 0)
 
@@ -108,6 +109,7 @@ SIGNATURES = {
     'ltu_crop_index_build': [P, L, P, L, P, P],
     'ltu_crop_index_select': [P, L, P, L, P, P, I, P],
     'ltu_sample_affine': [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
+    'ltu_sample_elastic': [P, P, P, P, P, P, I, I, I, P, P, I, I, I, I, I, I, I, F, P],
     'ltu_gauss_blur3': [P, P, P, P, P, I, I, I, I, P],
     'ltu_adamw': [P, P, P, P, L, F, F, F, F, F, L, F, P],
     'ltu_grad_sumsq_parts': [L],

@@ -1,6 +1,7 @@
 // Augmentation of the NIfTI pipeline's patches on the device (no reference counterpart: the monai driver crops, flips and rot90s
-// only).  Two kernels: ltu_sample_affine cuts rotated / zoomed / flipped patches straight from the scan in one gather (and adds
-// Gaussian noise in the store), ltu_gauss_blur3 blurs a batch of patches in one launch (three 1-D passes inside a workgroup).
+// only).  Three kernels: ltu_sample_affine cuts rotated / zoomed / flipped patches straight from the scan in one gather (and adds
+// Gaussian noise in the store), ltu_sample_elastic is that gather with a B-spline free-form deformation folded in, ltu_gauss_blur3
+// blurs a batch of patches in one launch (three 1-D passes inside a workgroup).
 //
 // ---- the noise generator (restated in numpy by lintransunet_amd/data.py::noise_reference) ------------------------------------
 // Stateless like the dropout masks: the normal deviate of voxel i (the linear index (x * w + y) * d + z inside its patch, < 2^32)
@@ -249,6 +250,255 @@ extern "C" int ltu_sample_affine(const float* img, const uint8_t* lab, float* ou
   else if (vec == 4) SA_GO(false, 4);
   else SA_GO(false, 1);
 #undef SA_GO
+  return ltu_check_launch();
+}
+
+// ---- ltu_sample_elastic --------------------------------------------------------------------------------------------------------
+// ltu_sample_affine's gather with a cubic B-spline free-form deformation folded in ahead of the pull matrix (restated in numpy by
+// lintransunet_amd/data.py::elastic_displacement).  A patch of size (h, w, d) carries a control lattice phi[3][gh][gw][gd] of
+// displacements in PATCH voxels along the patch axes H, W, D, 4 <= g_a <= LTU_ELASTIC_MAX_GRID.  For the patch voxel p = (x, y, z)
+// and, per axis a with patch coordinate t and patch extent n_a,
+//   s = t * (g_a - 3) / (n_a - 1)        (s = 0 when n_a == 1)
+//   i = min(floor(s), g_a - 4),  f = s - i
+//   B(f) = ((1-f)^3, 3f^3 - 6f^2 + 4, -3f^3 + 3f^2 + 3f + 1, f^3) / 6
+//   u_c(p) = sum_{l,m,n in 0..3} B_l(fx) B_m(fy) B_n(fz) * phi[c][ix+l][iy+m][iz+n]
+//   source coordinate = M * (p + u(p), 1)
+// the uniform cubic B-spline FFD: C2-smooth, exactly 0 for a zero lattice (the B are >= 0 and every product is +0), applied in patch
+// space so that the crop, flip, rot90, rotation and zoom of M keep their meaning.  Image, label, fill and noise as in sample_affine.
+//
+// The tile of a workgroup is sample_affine's (ZL lanes of VEC voxels along z, TY along y, TX along x) with TX capped at SE_TX_MAX.
+// The spline is contracted axis by axis, each stage where its inputs are shared widest:
+//   x  once per workgroup: the lattice is loaded from memory once and enters LDS already contracted with the B(fx) of each of the
+//      tile's TX rows, A[xl][c][gw][gd] (at most 8 * 3 * 64 floats = 6 KiB; a 512 x 512 x 32 patch has TX = 1: 768 B);
+//   y  once per lane: the 4 rows iy .. iy+3 of A into the NC lattice columns c0 .. c0+NC-1 along z that the lane's run of VEC voxels
+//      touches (c0 = iz of its first voxel): 4 * NC LDS reads and FMAs per component, the lanes of a wave reading few distinct
+//      addresses (iy and c0 change every (n - 1) / (g - 3) voxels);
+//   z  per voxel: 4 FMAs per component on the columns at off = iz - c0, picked by compile-time-indexed selects (no register array is
+//      indexed at run time).  A run that crosses a lattice cell boundary has off > 0 in its later voxels; the far-end clamp
+//      i = min(floor(s), g - 4) gives f = 1 there.
+// NC: 4 for VEC == 1; for VEC == 4, 5 when the run spans at most two cells (3 (gd - 3) <= 0.99 (d - 1), the host decides) and 8
+// otherwise (off <= gd - 4 <= 4).  Columns at or beyond gd are read at gd - 1 and never selected.
+// Each component of u is clamped to +-LTU_ELASTIC_MAX_DISP with fmaxf / fminf (NaN -> -LTU_ELASTIC_MAX_DISP), so every lattice
+// content gives a defined coordinate, and M[:, :3] u joins sample_affine's fp32 bracket: at most 64 |M| more on a bracket of at
+// most 256 |M|, its error stays well inside the label's 1e-4 tie band.  With a zero lattice the bracket is sample_affine's plus
+// +-0: the same bits.  There is no z-decoupled variant: a deformed row's in-plane taps change with z.
+#define SE_TX_MAX 8
+#define SE_PLANE (LTU_ELASTIC_MAX_GRID * LTU_ELASTIC_MAX_GRID)
+
+// s >= 0 -> (index of the first of the 4 control points, their weights)
+__device__ __forceinline__ void se_basis(float s, int g, int* i, float (&b)[4]) {
+  const int ii = min(max((int)floorf(s), 0), g - 4);
+  const float f = s - (float)ii, f2 = f * f, f3 = f2 * f, om = 1.f - f;
+  const float sixth = 1.f / 6.f;
+  b[0] = om * om * om * sixth;
+  b[1] = (3.f * f3 - 6.f * f2 + 4.f) * sixth;
+  b[2] = (-3.f * f3 + 3.f * f2 + 3.f * f + 1.f) * sixth;
+  b[3] = f3 * sixth;
+  *i = ii;
+}
+
+template <int VEC, int NC, typename IDX>
+__global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lab,
+                                                             float* __restrict__ oimg, uint8_t* __restrict__ olab, SampleAffineArgs c,
+                                                             const float* __restrict__ phi, int gh, int gw, int gd, float sx, float sy,
+                                                             float sz, int H, int W, int D, int h, int w, int d, int zl_log2,
+                                                             int ty_log2, int tx_log2, float fill) {
+  static_assert(NC >= 4 && NC <= LTU_ELASTIC_MAX_GRID && (VEC == 4 || NC == 4), "NC columns cover a run of VEC voxels");
+  __shared__ float A[SE_TX_MAX * 3 * SE_PLANE];
+  const int k = blockIdx.z;
+  const int zl = 1 << zl_log2, ty = 1 << ty_log2, tx = 1 << tx_log2;
+  const int x0 = (int)(blockIdx.y << tx_log2);
+  const int plane = gw * gd;
+  const float* pk = phi + (long long)k * 3 * gh * plane;
+  for (int e = threadIdx.x; e < tx * 3 * plane; e += 256) {          // e = (xl * 3 + component) * plane + (j * gd + q)
+    const int xl = e / (3 * plane), r = e - xl * 3 * plane, cc = r / plane, jq = r - cc * plane;
+    float v = 0.f;
+    if (x0 + xl < h) {
+      int ix;
+      float bx[4];
+      se_basis((float)(x0 + xl) * sx, gh, &ix, bx);
+      const float* p = pk + (cc * gh + ix) * plane + jq;             // rows ix .. ix + 3 <= gh - 1
+      v = bx[0] * p[0] + bx[1] * p[plane] + bx[2] * p[2 * plane] + bx[3] * p[3 * plane];
+    }
+    A[e] = v;
+  }
+  __syncthreads();
+  const int xl = (int)(threadIdx.x >> (zl_log2 + ty_log2));
+  const int x = x0 + xl;
+  const int ztiles = (d + zl * VEC - 1) / (zl * VEC);
+  const int tile_y = blockIdx.x / ztiles, tile_z = blockIdx.x - tile_y * ztiles;
+  const int y0 = tile_y * ty, z0 = tile_z * zl * VEC;
+  const int yl = (threadIdx.x >> zl_log2) & (ty - 1), zq = (threadIdx.x & (zl - 1)) * VEC;
+  const int y = y0 + yl, z = z0 + zq;
+  if (xl >= tx || x >= h || y >= w || z >= d) return;
+  const double* m = c.mat[k];
+  SaAxis ax[3];
+  float mx[3], my[3], mz[3];
+  const int S[3] = {H, W, D};
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    ax[s] = sa_axis(fma(m[4 * s], (double)x, fma(m[4 * s + 1], (double)y0, fma(m[4 * s + 2], (double)z0, m[4 * s + 3]))), S[s]);
+    mx[s] = (float)m[4 * s];
+    my[s] = (float)m[4 * s + 1];
+    mz[s] = (float)m[4 * s + 2];
+  }
+  int iy, c0;
+  float by[4], bz[4];
+  se_basis((float)y * sy, gw, &iy, by);
+  se_basis((float)z * sz, gd, &c0, bz);
+  float col[3][NC];
+  {
+    const float* a = A + xl * 3 * plane + iy * gd;                   // rows iy .. iy + 3 <= gw - 1
+#pragma unroll
+    for (int q = 0; q < NC; ++q) {
+      const int qi = min(c0 + q, gd - 1);
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc) {
+        const float* p = a + cc * plane + qi;
+        col[cc][q] = by[0] * p[0] + by[1] * p[gd] + by[2] * p[2 * gd] + by[3] * p[3 * gd];
+      }
+    }
+  }
+  float vi[VEC];
+  uint8_t vl[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    int off = 0;
+    if (j > 0) {
+      int iz;
+      se_basis((float)(z + j) * sz, gd, &iz, bz);
+      off = min(max(iz - c0, 0), NC - 4);
+    }
+    float u[3];
+#pragma unroll
+    for (int cc = 0; cc < 3; ++cc) {
+      float acc = 0.f;
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        float v = col[cc][n];
+#pragma unroll
+        for (int o = 1; o <= NC - 4; ++o) v = off == o ? col[cc][n + o] : v;
+        acc += bz[n] * v;
+      }
+      u[cc] = fminf(fmaxf(acc, -(float)LTU_ELASTIC_MAX_DISP), (float)LTU_ELASTIC_MAX_DISP);
+    }
+    int i0[3];
+    float t[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+      sa_split(ax[s], fmaf(my[s], (float)yl, fmaf(mz[s], (float)(zq + j), ax[s].fr)) + (mx[s] * u[0] + my[s] * u[1] + mz[s] * u[2]),
+               &i0[s], &t[s]);
+    if (img != nullptr) {
+      float acc = 0.f;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int bx = r >> 2, by2 = (r >> 1) & 1, bz2 = r & 1;
+        const int xi = i0[0] + bx, yi = i0[1] + by2, zi = i0[2] + bz2;
+        const bool in = (unsigned)xi < (unsigned)H && (unsigned)yi < (unsigned)W && (unsigned)zi < (unsigned)D;
+        const float wt = (bx ? t[0] : 1.f - t[0]) * (by2 ? t[1] : 1.f - t[1]) * (bz2 ? t[2] : 1.f - t[2]);
+        float v = fill;
+        if (in) v = img[((IDX)xi * W + yi) * D + zi];          // the offset exists only for a tap inside the scan
+        acc += wt * v;
+      }
+      vi[j] = acc;
+    }
+    if (lab != nullptr) {
+      const int xr = sa_round(i0[0], t[0]), yr = sa_round(i0[1], t[1]), zr = sa_round(i0[2], t[2]);
+      const bool in = (unsigned)xr < (unsigned)H && (unsigned)yr < (unsigned)W && (unsigned)zr < (unsigned)D;
+      uint8_t lv = 0;
+      if (in) lv = lab[((IDX)xr * W + yr) * D + zr];
+      vl[j] = lv;
+    }
+  }
+  const uint32_t vox = ((uint32_t)x * (uint32_t)w + (uint32_t)y) * (uint32_t)d + (uint32_t)z;       // < 2^32 (checked on the host)
+  const long long dst = (long long)k * h * w * d + vox;
+  if (img != nullptr) {
+    const float sg = c.sigma[k];
+    if (sg > 0.f) {
+      const NoiseKey key = noise_key(c.seed[k]);
+      if (VEC == 4) {                     // vox % 4 == 0: two whole pairs
+        float n[4];
+        noise_pair(key, vox >> 1, &n[0], &n[1]);
+        noise_pair(key, (vox >> 1) + 1, &n[2], &n[3]);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) vi[j] = fmaf(sg, n[j], vi[j]);
+      } else {
+        float n0, n1;
+        noise_pair(key, vox >> 1, &n0, &n1);
+        vi[0] = fmaf(sg, (vox & 1) ? n1 : n0, vi[0]);
+      }
+    }
+    if (VEC == 4) *reinterpret_cast<float4*>(oimg + dst) = make_float4(vi[0], vi[1], vi[2], vi[3]);
+    else oimg[dst] = vi[0];
+  }
+  if (lab != nullptr) {
+    if (VEC == 4)
+      *reinterpret_cast<uint32_t*>(olab + dst) = (uint32_t)vl[0] | ((uint32_t)vl[1] << 8) | ((uint32_t)vl[2] << 16) | ((uint32_t)vl[3] << 24);
+    else olab[dst] = vl[0];
+  }
+}
+
+template <int VEC, int NC, typename IDX>
+static void sample_elastic_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SampleAffineArgs& c,
+                                  const float* phi, int gh, int gw, int gd, int n, int H, int W, int D, int h, int w, int d, float fill,
+                                  hipStream_t st) {
+  const int per_lane = (d + VEC - 1) / VEC;
+  int zl_log2 = 0;
+  while ((1 << zl_log2) < per_lane && zl_log2 < (VEC == 4 ? 4 : 6)) ++zl_log2;
+  int ty_log2 = 0;
+  while ((1 << ty_log2) < w && zl_log2 + ty_log2 < 8) ++ty_log2;
+  int tx_log2 = 8 - zl_log2 - ty_log2;                 // a tile narrower than 256 / SE_TX_MAX lanes leaves the rest of them idle
+  if ((1 << tx_log2) > SE_TX_MAX) tx_log2 = 3;
+  static_assert(SE_TX_MAX == 8, "tx_log2 is capped at 3");
+  const int zl = 1 << zl_log2, ty = 1 << ty_log2, tx = 1 << tx_log2;
+  const unsigned tiles = cdiv(w, ty) * cdiv(d, zl * VEC);
+  const float sx = h > 1 ? (float)((double)(gh - 3) / (double)(h - 1)) : 0.f;
+  const float sy = w > 1 ? (float)((double)(gw - 3) / (double)(w - 1)) : 0.f;
+  const float sz = d > 1 ? (float)((double)(gd - 3) / (double)(d - 1)) : 0.f;
+  hipLaunchKernelGGL((sample_elastic_kernel<VEC, NC, IDX>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c, phi, gh,
+                     gw, gd, sx, sy, sz, H, W, D, h, w, d, zl_log2, ty_log2, tx_log2, fill);
+}
+
+extern "C" int ltu_sample_elastic(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats,
+                                  const float* phi, int gh, int gw, int gd, const float* noise_sigma, const unsigned long long* seeds,
+                                  int n, int H, int W, int D, int h, int w, int d, float fill, ltu_stream_t s) {
+  if (mats == nullptr || phi == nullptr || (img == nullptr) != (out_img == nullptr) || (lab == nullptr) != (out_lab == nullptr) ||
+      (img == nullptr && lab == nullptr) || n < 0 || n > LTU_SAMPLE_AFFINE_MAX || (noise_sigma != nullptr && seeds == nullptr) ||
+      !(fill - fill == 0.f))
+    return LTU_E_ARG;
+  if (gh < 4 || gw < 4 || gd < 4 || gh > LTU_ELASTIC_MAX_GRID || gw > LTU_ELASTIC_MAX_GRID || gd > LTU_ELASTIC_MAX_GRID)
+    return LTU_E_SHAPE;
+  if (n == 0) return LTU_OK;
+  const int smax = 1 << 22;
+  if (H < 1 || W < 1 || D < 1 || H > smax || W > smax || D > smax || h < 1 || w < 1 || d < 1 || h > 65535 ||
+      (long long)h * w * d >= (1LL << 32) || (long long)cdiv(w, 4) * cdiv(d, 4) >= (1LL << 31))
+    return LTU_E_SHAPE;
+  SampleAffineArgs c;
+  for (int k = 0; k < n; ++k) {
+    for (int j = 0; j < 12; ++j) {
+      const double v = mats[12 * k + j];
+      if (!(v - v == 0.0)) return LTU_E_ARG;             // NaN or infinite
+      c.mat[k][j] = v;
+    }
+    const float sg = noise_sigma != nullptr ? noise_sigma[k] : 0.f;
+    if (!(sg >= 0.f) || !(sg - sg == 0.f)) return LTU_E_ARG;
+    c.sigma[k] = img != nullptr ? sg : 0.f;
+    c.seed[k] = seeds != nullptr ? seeds[k] : 0ull;
+  }
+  const int vec = (d % 4 == 0) ? 4 : 1;
+  if (((uintptr_t)phi & 3) != 0 || (vec == 4 && (((uintptr_t)out_img & 15) != 0 || ((uintptr_t)out_lab & 3) != 0))) return LTU_E_ALIGN;
+  const bool small = (long long)H * W * D < (1LL << 31);
+  const bool two_cells = 3.0 * (gd - 3) <= 0.99 * (d - 1);       // a run of 4 voxels along z spans at most two lattice cells
+  const hipStream_t st = (hipStream_t)s;
+#define SE_GO(V, NCOL)                                                                                                              \
+  do {                                                                                                                              \
+    if (small) sample_elastic_launch<V, NCOL, int>(img, lab, out_img, out_lab, c, phi, gh, gw, gd, n, H, W, D, h, w, d, fill, st);   \
+    else sample_elastic_launch<V, NCOL, long long>(img, lab, out_img, out_lab, c, phi, gh, gw, gd, n, H, W, D, h, w, d, fill, st);   \
+  } while (0)
+  if (vec == 1) SE_GO(1, 4);
+  else if (two_cells) SE_GO(4, 5);
+  else SE_GO(4, LTU_ELASTIC_MAX_GRID);
+#undef SE_GO
   return ltu_check_launch();
 }
 

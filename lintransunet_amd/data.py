@@ -538,11 +538,55 @@ def patch_matrix(start, size, flip, k, angles=(0.0, 0.0, 0.0), zoom=1.0, spacing
     return (t1 @ Si @ rx @ ry @ rz @ Z @ S @ P @ t0)[:3]
 
 
-def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None):
+def elastic_displacement(phi, size):
+    """the displacement field of ltu_sample_elastic in float64 numpy (no GPU): phi [3, gh, gw, gd], the control lattice of one patch
+    (displacements in patch voxels along the patch axes H, W, D), size (h, w, d) -> u [3, h, w, d], the uniform cubic B-spline
+    free-form deformation of csrc/augment.hip's header comment.  Per axis a with patch coordinate t and extent n_a:
+    s = t (g_a - 3) / (n_a - 1) (0 when n_a == 1), i = min(floor(s), g_a - 4), f = s - i,
+    B(f) = ((1-f)^3, 3f^3 - 6f^2 + 4, -3f^3 + 3f^2 + 3f + 1, f^3) / 6, u_c(p) = sum_lmn B_l(fx) B_m(fy) B_n(fz) phi[c][ix+l][iy+m][iz+n];
+    patch voxel p reads the scan at M (p + u(p), 1)."""
+    phi = np.asarray(phi, dtype=np.float64)
+    if phi.ndim != 4 or phi.shape[0] != 3 or min(phi.shape[1:]) < 4:
+        raise ValueError(f'a control lattice is [3, gh, gw, gd] with extents >= 4, got {phi.shape}')
+    wts = []
+    for n, g in zip((int(v) for v in size), phi.shape[1:]):
+        t = np.arange(n, dtype=np.float64)
+        sc = t * (g - 3) / (n - 1) if n > 1 else np.zeros(n)
+        i = np.minimum(np.floor(sc), g - 4).astype(np.int64)
+        f = sc - i
+        B = np.stack([(1 - f) ** 3, 3 * f ** 3 - 6 * f ** 2 + 4, -3 * f ** 3 + 3 * f ** 2 + 3 * f + 1, f ** 3], 1) / 6
+        wa = np.zeros((n, g))
+        for l in range(4):
+            wa[np.arange(n), i + l] += B[:, l]
+        wts.append(wa)
+    return np.einsum('xl,ym,zn,clmn->cxyz', *wts, phi)
+
+
+def _check_lattice(elastic):
+    """sample_affine's elastic argument, checked on the host: [n, 3, gh, gw, gd] float32 (ndarray or tensor as given), extents 4 ..
+    LTU_ELASTIC_MAX_GRID, finite, |phi| <= LTU_ELASTIC_MAX_DISP"""
+    if torch.is_tensor(elastic):
+        lat = elastic.to(torch.float32).contiguous()
+        ok = bool((lat.abs() <= _lib.ELASTIC_MAX_DISP).all())
+    else:
+        lat = np.ascontiguousarray(np.asarray(elastic, dtype=np.float32))
+        ok = bool((np.abs(lat) <= _lib.ELASTIC_MAX_DISP).all())          # False for a NaN
+    if lat.ndim != 5 or lat.shape[1] != 3 or not all(4 <= int(g) <= _lib.ELASTIC_MAX_GRID for g in lat.shape[2:]):
+        raise ValueError(f'elastic is [n, 3, gh, gw, gd] with lattice extents 4 .. {_lib.ELASTIC_MAX_GRID}, got {tuple(lat.shape)}')
+    if not ok:
+        raise ValueError(f'elastic must be finite with |phi| <= {_lib.ELASTIC_MAX_DISP} patch voxels')
+    return lat
+
+
+def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, elastic=None):
     """ltu_sample_affine: device patches ([n,1,h,w,d] f32 or None, [n,1,h,w,d] u8 or None) gathered from img / lab [H,W,D] through
     mats [n,3,4] (float64 pull matrices, patch voxel -> scan voxel): image trilinear with `fill` outside the scan, label nearest
     (round half even) with 0 outside.  noise_sigma [n] with seeds [n] (uint64) adds sigma_k * N(0, 1) to patch k in the store
-    (noise_reference restates the generator)."""
+    (noise_reference restates the generator).  elastic: [n, 3, gh, gw, gd] (ndarray or device tensor), one B-spline control lattice
+    per patch in patch voxels; patch voxel p then reads the scan at M (p + u(p), 1), u = elastic_displacement (ltu_sample_elastic).
+    The lattice is checked on the host (extents 4 .. 8, finite, |phi| <= 64: ValueError) and uploaded once."""
+    if elastic is not None:
+        elastic = _check_lattice(elastic)
     vol = img if img is not None else lab
     if vol is None or not vol.is_cuda:
         raise _lib.LtuError('data.sample_affine runs on the GPU only (no CPU fallback)')
@@ -563,8 +607,18 @@ def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None):
         sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(n))
     oi = torch.empty((n, 1, h, w, d), device=vol.device, dtype=torch.float32) if img is not None else None
     ol = torch.empty((n, 1, h, w, d), device=vol.device, dtype=torch.uint8) if lab is not None else None
+    if elastic is not None:
+        if elastic.shape[0] != n:
+            raise ValueError(f'elastic holds {elastic.shape[0]} lattices for {n} matrices')
+        lat = (elastic if torch.is_tensor(elastic) else torch.from_numpy(elastic)).to(vol.device)
+        g = tuple(int(v) for v in lat.shape[2:])
     for s in range(0, n, _lib.SAMPLE_AFFINE_MAX):
         e = min(n, s + _lib.SAMPLE_AFFINE_MAX)
+        if elastic is not None:
+            _lib.call('ltu_sample_elastic', _p(img), _p(lab), _p(oi[s:e]) if oi is not None else 0, _p(ol[s:e]) if ol is not None else 0,
+                      m[s:e].ctypes.data, _p(lat[s:e]), *g, sg[s:e].ctypes.data if sg is not None else 0,
+                      sd[s:e].ctypes.data if sd is not None else 0, e - s, H, W, D, h, w, d, float(fill), _s())
+            continue
         _lib.call('ltu_sample_affine', _p(img), _p(lab), _p(oi[s:e]) if oi is not None else 0, _p(ol[s:e]) if ol is not None else 0,
                   m[s:e].ctypes.data, sg[s:e].ctypes.data if sg is not None else 0, sd[s:e].ctypes.data if sd is not None else 0,
                   e - s, H, W, D, h, w, d, float(fill), _s())
@@ -643,11 +697,17 @@ class Augmentation:
     """The random augmentations of data.sample(..., augment=): a plain record of probabilities and ranges.  rot_range: the largest
     |angle| in radians about H, W, D (the default rotates about D only: slices are 2 mm against 0.5 mm in plane); zoom > 1
     magnifies; noise_std, blur_sigma (voxels), brightness and gamma are uniform ranges; fill: the image value outside the scan, None =
-    the lower bound of the scan's intensity window (0.0 when it has none)."""
+    the lower bound of the scan's intensity window (0.0 when it has none).  elastic_prob > 0 adds a B-spline free-form deformation
+    (elastic_displacement): a control lattice of elastic_grid points per patch axis, uniform in +-elastic_mm millimetres of the scan
+    with elastic_mm drawn from its range; 0 (the default) makes no draw for it."""
 
     def __init__(self, rot_prob=0.2, rot_range=(0.0, 0.0, np.pi), zoom_prob=0.2, zoom_range=(0.7, 1.4), noise_prob=0.1,
                  noise_std=(0.0, 0.1), blur_prob=0.2, blur_sigma=(0.5, 1.0), brightness_prob=0.15, brightness=(0.75, 1.25),
-                 gamma_prob=0.3, gamma=(0.7, 1.5), fill=None):
+                 gamma_prob=0.3, gamma=(0.7, 1.5), fill=None, elastic_prob=0.0, elastic_mm=(0.0, 4.0), elastic_grid=(6, 6, 4)):
+        self.elastic_prob, self.elastic_mm = elastic_prob, tuple(float(v) for v in elastic_mm)
+        self.elastic_grid = tuple(int(g) for g in elastic_grid)
+        if len(self.elastic_grid) != 3 or not all(4 <= g <= _lib.ELASTIC_MAX_GRID for g in self.elastic_grid):
+            raise ValueError(f'elastic_grid is three lattice extents 4 .. {_lib.ELASTIC_MAX_GRID}, got {elastic_grid}')
         self.rot_prob, self.rot_range = rot_prob, tuple(rot_range)
         self.zoom_prob, self.zoom_range = zoom_prob, tuple(zoom_range)
         self.noise_prob, self.noise_std = noise_prob, tuple(noise_std)
@@ -673,7 +733,30 @@ class Augmentation:
         p['mul'] = rs.uniform(*self.brightness)
         p['contrast'] = rs.rand() < self.gamma_prob
         p['gamma'] = rs.uniform(*self.gamma)
+        if self.elastic_prob > 0:
+            p['elastic'] = rs.rand() < self.elastic_prob
+            p['elastic_mm'] = rs.uniform(*self.elastic_mm)
+            p['phi'] = rs.uniform(-1, 1, (3, *self.elastic_grid))
         return p
+
+    def check_fold(self, spatial_size, pixdim, swap=True):
+        """ValueError unless the largest control displacement this record can draw stays within 0.4 lattice cells on every patch
+        axis: max(elastic_mm) * max(zoom_range) / pixdim_a <= 0.4 (size_a - 1) / (g_a - 3).  0.4 cells is the known injectivity
+        bound of the cubic B-spline free-form deformation (Choi and Lee: 1 / 2.48), so the deformed patch cannot fold.  swap: a
+        rot90 by an odd k may map patch axis H onto scan axis W and W onto H, the finer of the two in-plane spacings then counts
+        for both.  Nothing is checked while elastic_prob == 0."""
+        if not self.elastic_prob > 0:
+            return
+        pix = [float(v) for v in pixdim]
+        if swap:
+            pix[0] = pix[1] = min(pix[0], pix[1])
+        for a in range(3):
+            vox = max(self.elastic_mm) * max(self.zoom_range) / pix[a]
+            cap = 0.4 * (int(spatial_size[a]) - 1) / (self.elastic_grid[a] - 3)
+            if not vox <= cap:
+                raise ValueError(f'elastic deformation may fold along patch axis {a}: up to {vox:.3g} voxels (elastic_mm '
+                                 f'{max(self.elastic_mm):g} mm x zoom {max(self.zoom_range):g} / {pix[a]:g} mm) against 0.4 lattice cells '
+                                 f'= {cap:.3g} voxels (size {int(spatial_size[a])}, lattice {self.elastic_grid[a]})')
 
 
 def _augmented(scan, draws, params, spatial_size, augment, spacing):
@@ -688,9 +771,20 @@ def _augmented(scan, draws, params, spatial_size, augment, spacing):
                          p['angles'] if p['rotate'] else (0.0, 0.0, 0.0), p['zoom_factor'] if p['zoom'] else 1.0, spacing)
             for (c, f, k), p in zip(draws, params)]
     noisy = any(p['noise'] for p in params)
+    lattice = None
+    if any(p.get('elastic') for p in params):
+        # millimetres of the scan -> patch voxels: patch axis c runs along scan axis axis(c) (an odd k swaps H and W), and a patch
+        # voxel covers pixdim / zoom of it; a patch that does not fire keeps a zero lattice (the bits of sample_affine's general kernel)
+        lattice = np.zeros((len(params), 3, *augment.elastic_grid), dtype=np.float32)
+        for i, ((_, f, k), p) in enumerate(zip(draws, params)):
+            if p['elastic']:
+                swap = orient_desc(f, k)[2]
+                zf = p['zoom_factor'] if p['zoom'] else 1.0
+                for c, a in enumerate((1, 0, 2) if swap else (0, 1, 2)):
+                    lattice[i, c] = p['phi'][c] * (p['elastic_mm'] * zf / float(spacing[a]))
     img, lab = sample_affine(scan.img, scan.lab, np.stack(mats), size, fill,
                              [p['noise_std'] if p['noise'] else 0.0 for p in params] if noisy else None,
-                             [p['seed'] for p in params] if noisy else None)
+                             [p['seed'] for p in params] if noisy else None, elastic=lattice)
     if any(p['blur'] or p['bright'] for p in params):
         img = gaussian_blur(img, [p['sigma'] if p['blur'] else 0.0 for p in params], [p['mul'] if p['bright'] else 1.0 for p in params])
     if any(p['contrast'] for p in params):
@@ -702,7 +796,10 @@ def sample_draws(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, r
                  augment=None):
     """every host draw of one data.sample call: ([(centre, flip, k)], [Augmentation.draw dict] or None).  The four draws of every
     sample come first, exactly as without augment (so the crops, flips and rot90s of an augmented call are those of the plain
-    call from the same generator); the augmentation draws of sample 0, 1, ... follow."""
+    call from the same generator); the augmentation draws of sample 0, 1, ... follow.  An augment that deforms is checked against
+    folding first (Augmentation.check_fold: ValueError before any draw is consumed)."""
+    if augment is not None:
+        augment.check_fold(spatial_size, getattr(scan, 'pixdim', (1.0, 1.0, 1.0)), swap=rot90_prob > 0)
     if host_centers and ratios is None:
         draws = [draw_monai_sample(scan.label_host, spatial_size, rand_state, flip_prob, rot90_prob) for _ in range(num_samples)]
     else:
@@ -735,9 +832,10 @@ def sample(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_p
     RandCropByPosNegLabeld to RandCropByLabelClassesd (class_centers / class_crop_centers, num_samples 1 per sample).
     augment: an Augmentation.  The draws above keep their place; behind them come, per sample, Augmentation.draw's (rotation fire,
     three angles; zoom fire, factor; noise fire, std, two seed words; blur fire, sigma; brightness fire, multiplier; gamma fire,
-    gamma).  The patches are then gathered through patch_matrix by one sample_affine (rotation in millimetres of scan.pixdim,
-    noise in the store), blurred / brightened by one gaussian_blur and gamma-adjusted by adjust_contrast.  None changes nothing:
-    the same draws, patches and generator state."""
+    gamma; with elastic_prob > 0 also: deformation fire, its amplitude in millimetres, the control lattice).  The patches are then
+    gathered through patch_matrix by one sample_affine (rotation in millimetres of scan.pixdim, the B-spline deformation of the
+    patches that fire it folded into the same gather, noise in the store), blurred / brightened by one gaussian_blur and
+    gamma-adjusted by adjust_contrast.  None changes nothing: the same draws, patches and generator state."""
     if scan.lab is None:
         raise ValueError('sampling needs a label (RandCropByPosNegLabeld draws centres from it)')
     draws, params = sample_draws(scan, spatial_size, rand_state, num_samples, flip_prob, rot90_prob, host_centers, ratios, augment)

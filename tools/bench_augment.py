@@ -7,7 +7,10 @@ batch of 12 patches of 512x512x32.  Four ways to get the batch alternate in one 
   (d) crop_orient followed by data.rotate + data.zoom on image and label: what a user had to do before, on cut patches.
 Then the kernels alone on fixed matrices (identity; 0.5 rad about D at zoom 1.2; the same matrices pushed through the general
 instantiation by a 1e-9 rad tilt; oblique (0.2, -0.3, 0.5) at zoom 1.2; the in-plane case with noise), and ltu_gauss_blur3 on the 12
-patches at sigma 1.0 and 2.0.  Algorithmic bytes of a gather: 5 per patch voxel written + 5 per source voxel touched (patch voxels
+patches at sigma 1.0 and 2.0, and the deformed gather (ltu_sample_elastic, lattice (6, 6, 4) of +-11.2 voxels in plane and +-2.8 along D, given as a host array
+as data.sample gives it: checked and uploaded in the call) beside ltu_sample_affine's general instantiation on the same matrices, in
+plane and oblique, with their ratio; a zero lattice on the device shows the kernel without the upload and with the undeformed
+access pattern.  (e) is data.sample with the deformation firing on every patch beside rotation and zoom.  Algorithmic bytes of a gather: 5 per patch voxel written + 5 per source voxel touched (patch voxels
 / zoom^3); of a blur: 8 per voxel.  One JSON line.
 usage: bench_augment.py [repeats]"""
 import json
@@ -73,7 +76,8 @@ def only(**kw):
 
 inplane = only(rot_prob=1.0, zoom_prob=1.0)
 oblique = only(rot_prob=1.0, zoom_prob=1.0, rot_range=(0.3, 0.3, np.pi))
-rs = {k: np.random.RandomState(1) for k in 'abcd'}
+elastic = only(rot_prob=1.0, zoom_prob=1.0, elastic_prob=1.0)
+rs = {k: np.random.RandomState(1) for k in 'abcde'}
 
 
 def old_way():
@@ -91,6 +95,7 @@ ts = alternate({
     'b_sample_inplane_us': lambda: data.sample(scan, SIZE, rs['b'], num_samples=N, augment=inplane),
     'c_sample_oblique_us': lambda: data.sample(scan, SIZE, rs['c'], num_samples=N, augment=oblique),
     'd_crop_rotate_zoom_us': old_way,
+    'e_sample_elastic_us': lambda: data.sample(scan, SIZE, rs['e'], num_samples=N, augment=elastic),
 })
 res.update({k: spread(v) for k, v in ts.items()})
 
@@ -115,6 +120,23 @@ ts = alternate({k: (lambda m=m, sg=sg: data.sample_affine(scan.img, scan.lab, m,
 for k, (_, zoom, _) in kern.items():
     nbytes = 5 * vox * (1 + 1 / zoom ** 3)
     res['affine_' + k] = dict(spread(ts[k]), gb=round(nbytes / 1e9, 3), tbps=round(nbytes / statistics.median(ts[k]) / 1e6, 2))
+
+GRID = (6, 6, 4)
+amp = np.array([4.0 * 1.4 / sp for sp in SPACING]).reshape(1, 3, 1, 1, 1)      # Augmentation's largest: 4 mm at zoom 1.4, in voxels
+phi = (np.random.RandomState(11).uniform(-1, 1, (N, 3, *GRID)) * amp).astype(np.float32)
+zero = torch.zeros((N, 3, *GRID), device=dev)
+pairs = {'inplane': kern['inplane_general'][0], 'oblique': kern['oblique'][0]}
+fns = {}
+for k, m in pairs.items():
+    fns['elastic_' + k] = lambda m=m: data.sample_affine(scan.img, scan.lab, m, SIZE, -2.3, elastic=phi)
+    fns['elastic_zero_' + k] = lambda m=m: data.sample_affine(scan.img, scan.lab, m, SIZE, -2.3, elastic=zero)
+    fns['general_' + k] = lambda m=m: data.sample_affine(scan.img, scan.lab, m, SIZE, -2.3)
+ts = alternate(fns)
+for k in pairs:
+    for name in ('elastic_', 'elastic_zero_', 'general_'):
+        res[name + k + '_us'] = spread(ts[name + k])
+    res['elastic_over_general_' + k] = round(statistics.median(ts['elastic_' + k]) / statistics.median(ts['general_' + k]), 3)
+    res['elastic_zero_over_general_' + k] = round(statistics.median(ts['elastic_zero_' + k]) / statistics.median(ts['general_' + k]), 3)
 
 patches, _ = data.sample_affine(scan.img, None, kern['identity'][0], SIZE)
 ts = alternate({'blur_sigma1_us': lambda: data.gaussian_blur(patches, [1.0] * N, [1.1] * N),
