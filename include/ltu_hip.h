@@ -425,6 +425,35 @@ int ltu_loss_ext_fwd(const float* p, const uint8_t* label, float* sums, long lon
                      int C, const float* cfg, const float* scale_dev, ltu_stream_t s);
 int ltu_loss_ext_bwd(const float* p, const uint8_t* label, const float* coef, const float* cfg, const float* gscale, float* dp, int B,
                      long long S, int C, ltu_stream_t s);
+/* ---- boundary loss of one level (Kervadec et al., "Boundary loss for highly unbalanced segmentation"; no reference counterpart;
+ *      csrc/distmap.hip, csrc/loss_boundary.hip) ---------------------------------------------------------------------------
+ * distmap_signed: label u8 [B][H][W][D], classes a HOST array of K distinct ids in 0 .. 255 (1 <= K <= 8; a repeated id is
+ * LTU_E_ARG) -> phi f32 [B][K][H][W][D], the signed Euclidean distance map of G = {label == classes[k]} inside the patch with
+ * spacing (sh, sw, sd) > 0: phi(x) = dist(x, G) outside G, -(dist(x, not G) - 1) inside G (the 1 is not scaled by the spacing:
+ * Kervadec's one_hot2dist), and phi = 0 everywhere when G is empty or fills the patch, decided on the device.  Squared distances
+ * are formed in double and kept as fp32 between the three line passes (exact integers with unit spacing); the passes keep their
+ * envelopes in LDS.  scratch: ltu_distmap_scratch_elems(B, K, H, W, D) 4-byte elements, no initialisation.  One call serves all
+ * B K volumes and both polarities on stream s (capturable), no atomics, no host read: two calls agree bit for bit.
+ * LTU_E_SHAPE: an axis outside 1 .. 512, K outside 1 .. 8, B K > 65535; LTU_E_ARG: a bad class id, a non-finite or non-positive
+ * spacing, a NULL pointer, short scratch; all before anything is launched.
+ * loss_boundary: p f32 [B][S][C] probabilities (2 <= C <= 8), phi f32 [B][K][S], classes / w HOST arrays of the K terms (a class
+ * >= C or a non-finite weight is LTU_E_ARG).  values (1 + K floats): [1 + k] = value_k = (1 / (B S)) sum_b sum_s p[b][s][c_k]
+ * phi[b][k][s] (unweighted), [0] = (base_total ? base_total[0] : 0) + scale sum_k w_k value_k with scale = scale_dev[0] *
+ * term_scale_dev[0] (each NULL = 1; device-resident, read at run time, as in ltu_loss_fwd).  sums: scratch of
+ * ltu_loss_boundary_sums_floats(B, S, K) floats on an 8-byte boundary, no initialisation, folded in a fixed order (no atomics:
+ * bit-reproducible); shorter is LTU_E_ARG.  bwd: dp [B][S][C] gets gscale[0] scale w_k phi[b][k][s] / (B S) in channel c_k:
+ * added to what ltu_loss_bwd / ltu_loss_wide_bwd / ltu_loss_ext_bwd has just written there when accumulate != 0, else written
+ * with zeros in every other channel.  Argument errors return before anything is launched. */
+long long ltu_distmap_scratch_elems(int B, int K, int H, int W, int D);
+int ltu_distmap_signed(const uint8_t* label, const int* classes, int K, float* phi, void* scratch, long long scratch_elems, int B, int H,
+                       int W, int D, float sh, float sw, float sd, ltu_stream_t s);
+long long ltu_loss_boundary_sums_floats(int B, long long S, int K);
+int ltu_loss_boundary_fwd(const float* p, const float* phi, const int* classes, const float* w, int K, float* sums, long long sums_floats,
+                          float* values, const float* base_total, const float* scale_dev, const float* term_scale_dev, int B,
+                          long long S, int C, ltu_stream_t s);
+int ltu_loss_boundary_bwd(const float* phi, const int* classes, const float* w, int K, const float* scale_dev,
+                          const float* term_scale_dev, const float* gscale, float* dp, int accumulate, int B, long long S, int C,
+                          ltu_stream_t s);
 /* label pyramid (utils/utils_3D_embed_full.py:64,73-76): u8 [B,H,W,D] -> max over (2,2,kd) windows */
 int ltu_label_maxpool(const uint8_t* x, uint8_t* y, int B, int H, int W, int D, int kd, ltu_stream_t s);
 

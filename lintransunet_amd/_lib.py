@@ -150,6 +150,11 @@ SIGNATURES = {
     'ltu_loss_ext_ws_floats': [I, L, I],
     'ltu_loss_ext_fwd': [P, P, P, L, P, P, I, L, I, P, P, P],
     'ltu_loss_ext_bwd': [P, P, P, P, P, P, I, L, I, P],
+    'ltu_distmap_scratch_elems': [I, I, I, I, I],
+    'ltu_distmap_signed': [P, P, I, P, P, L, I, I, I, I, F, F, F, P],
+    'ltu_loss_boundary_sums_floats': [I, L, I],
+    'ltu_loss_boundary_fwd': [P, P, P, P, I, P, L, P, P, P, P, I, L, I, P],
+    'ltu_loss_boundary_bwd': [P, P, P, I, P, P, P, P, I, I, L, I, P],
     'ltu_label_maxpool': [P, P, I, I, I, I, I, P],
     'ltu_comm_load': [ctypes.c_char_p],
     'ltu_comm_unique_id': [P],
@@ -186,7 +191,8 @@ def load():
     for name, args in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = args
-        fn.restype = c_longlong if (name.endswith(('_ws_floats', '_ws_elems')) or name in ('ltu_layer_tail_blocks', 'ltu_grad_sumsq_parts', 'ltu_crop_index_elems')) else c_int
+        fn.restype = c_longlong if (name.endswith(('_ws_floats', '_ws_elems')) or name in ('ltu_layer_tail_blocks', 'ltu_grad_sumsq_parts', 'ltu_crop_index_elems', 'ltu_distmap_scratch_elems',
+                                                                                           'ltu_loss_boundary_sums_floats')) else c_int
     for name, args in EXPERIMENT_SIGNATURES.items():
         fn = getattr(lib, name, None)
         if fn is not None:

@@ -38,6 +38,11 @@ class LevelCriterion(nn.Module):
     1 - class 0, multi_criterions.py:30-56)}, runs ops.level_loss on predictions of up to 4 classes and
     ops.level_loss_wide on 5 .. 8 (both csrc/loss.hip).  A spec with any name of `EXT` runs the
     whole spec through ops.level_loss_ext (csrc/loss_ext.hip), which also carries the original terms but stops at 4 classes.
+    The boundary names 'BoundaryLoss' (class 1), 'BoundaryLoss2' .. 'BoundaryLoss7' and 'BoundaryLoss0c' (class 0) add Kervadec's
+    boundary term w * mean(p_c * phi_c) on the signed distance maps of the label (ops.signed_distance_maps with `spacing`, or the
+    `phi` given to forward: [B,K,...] in the order of `boundary_classes`) to whichever family the rest of the spec runs through
+    (ops.level_loss_boundary; up to 8 classes, or 4 beside a name of `EXT`); `term_scale_dev` (1-element fp32 device tensor) scales
+    the boundary terms alone at run time.  A spec without boundary names takes the path it always took.
     params: the parameters
     of the wider family (ops.LOSS_EXT_PARAMS: gamma, sigma, alpha, alpha2, eps; defaults ops.LOSS_EXT_DEFAULTS).  Returns
     (total, {name: w * value}) with values detached: what the reference scripts log (`criterions_w * l(...)`,
@@ -52,12 +57,14 @@ class LevelCriterion(nn.Module):
     EXT = {'DiceLoss': 'DICE', 'IOULoss': 'IOU', 'SSLoss': 'SS', 'FocalLoss': 'FOCAL', 'MSELoss': 'MSE', 'ContainLoss': 'CONTAIN',
            'ContainLoss2': 'CONTAIN2', 'BalanceDiceLoss2': 'BAL2', 'CrossEntroLoss0': 'CE0', 'ClassifyLoss': 'CLASSIFY'}
     EXT_MAXC = 4        # class limit of the wider family (csrc/loss_ext.hip)
+    BOUNDARY = {'BoundaryLoss': 1, 'BoundaryLoss2': 2, 'BoundaryLoss0c': 0, 'BoundaryLoss3': 3, 'BoundaryLoss4': 4, 'BoundaryLoss5': 5,
+                'BoundaryLoss6': 6, 'BoundaryLoss7': 7}      # boundary term (csrc/loss_boundary.hip) of class ...
 
-    def __init__(self, spec: dict, scale: float = 1.0, scale_dev=None, params=None):
+    def __init__(self, spec: dict, scale: float = 1.0, scale_dev=None, params=None, spacing=(1.0, 1.0, 1.0), term_scale_dev=None):
         super().__init__()
         if 'DistributionLoss' in spec:
             raise KeyError(_DISTRIBUTION_REFUSED)
-        unknown = set(spec) - set(self._TERM) - set(self._DICE) - set(self.EXT)
+        unknown = set(spec) - set(self._TERM) - set(self._DICE) - set(self.EXT) - set(self.BOUNDARY)
         if unknown:
             raise KeyError(f'no HIP kernel for losses {sorted(unknown)}')
         self.spec = dict(spec)
@@ -65,6 +72,14 @@ class LevelCriterion(nn.Module):
         self.scale_dev = scale_dev          # 1-element fp32 device tensor: run-time factor on top of `scale` (captured graphs)
         self.params = dict(params or {})
         self.extended = any(name in self.EXT for name in self.spec)
+        self.boundary = [name for name in self.spec if name in self.BOUNDARY]
+        self.spacing = tuple(float(v) for v in spacing)      # of the label's voxels (H, W, D): the maps' unit of length
+        self.term_scale_dev = term_scale_dev      # 1-element fp32 device tensor: run-time factor of the boundary terms alone
+
+    @property
+    def boundary_classes(self):
+        """the classes of the spec's boundary names, in the order of the maps (`phi`) that forward builds or takes"""
+        return tuple(self.BOUNDARY[name] for name in self.boundary)
 
     def _check_classes(self, C):
         """the Dice names of the spec against the C classes of a prediction; raises before anything is launched.  (Up to 4 classes
@@ -73,6 +88,9 @@ class LevelCriterion(nn.Module):
         absent = [name for name in self.spec if name in self._DICE and self._DICE[name] != self.FG and self._DICE[name] >= first]
         if absent:
             raise ValueError(f'{absent}: the Dice of a class the prediction does not have ({C} classes)')
+        absent = [name for name in self.boundary if self.BOUNDARY[name] >= C]
+        if absent or (self.boundary and C < 2):
+            raise ValueError(f'{absent or self.boundary}: the boundary term of a class the prediction does not have ({C} classes)')
 
     def dice_weights(self, C):
         """the Dice weights of the spec as the kernels take them: per class, then the foreground union - 5 entries for C <= 4
@@ -84,7 +102,7 @@ class LevelCriterion(nn.Module):
                 wd[n if cls == self.FG else cls] += self.spec[name] * self.scale
         return wd
 
-    def forward(self, predict, target, params=None):
+    def forward(self, predict, target, params=None, phi=None):
         C = predict.shape[1]
         self._check_classes(C)
         if self.extended and C > self.EXT_MAXC:
@@ -94,15 +112,25 @@ class LevelCriterion(nn.Module):
             raise ValueError(f'the level losses have kernels for C <= {ops.LOSS_WIDE_MAXC} classes, the prediction has {C}')
         p = _channels_last(predict)
         lab = _labels(target, C)
-        sc = self.scale
+        if self.boundary:
+            return self._forward_boundary(p, lab, C, dict(self.params, **(params or {})), phi)
         if self.extended:
             return self._forward_ext(p, lab, dict(self.params, **(params or {})))
         wd = self.dice_weights(C)
         fn = ops.level_loss if C <= 4 else ops.level_loss_wide
-        total, values = fn(p, lab, self.spec.get('CrossEntroLoss', 0.0) * sc, self.spec.get('BalanceDiceLoss', 0.0) * sc, wd, self.scale_dev)
-        fg = 3 + len(wd) - 1
+        total, values = fn(p, lab, *self._ce_bal(), wd, self.scale_dev)
+        return total, self._named_orig(values, len(wd))
+
+    def _ce_bal(self):
+        return self.spec.get('CrossEntroLoss', 0.0) * self.scale, self.spec.get('BalanceDiceLoss', 0.0) * self.scale
+
+    def _named_orig(self, values, n_wd):
+        """{name: w * value} of the original family's names from the values of ltu_loss_fwd / ltu_loss_wide_fwd"""
+        fg = 3 + n_wd - 1
         named = {}
         for name, w in self.spec.items():
+            if name in self.BOUNDARY:
+                continue
             if name == 'CrossEntroLoss':
                 v = values[1]
             elif name == 'BalanceDiceLoss':
@@ -112,19 +140,53 @@ class LevelCriterion(nn.Module):
             else:
                 v = values[3 + self._DICE[name]]
             named[name] = v if w == 1.0 else v * w
-        return total, named
+        return named
 
-    def _forward_ext(self, p, lab, params):
+    def _ext_weights(self):
         weights = {}
         for name, w in self.spec.items():
+            if name in self.BOUNDARY:
+                continue
             term = self.EXT.get(name) or self._TERM[name]
             weights[term] = weights.get(term, 0.0) + w * self.scale
-        total, values = ops.level_loss_ext(p, lab, weights, params, self.scale_dev)
+        return weights
+
+    def _named_ext(self, values):
         named = {}
         for name, w in self.spec.items():
+            if name in self.BOUNDARY:
+                continue
             v = values[1 + ops.LOSS_EXT_TERMS.index(self.EXT.get(name) or self._TERM[name])]
             named[name] = v if w == 1.0 else v * w
-        return total, named
+        return named
+
+    def _forward_ext(self, p, lab, params):
+        total, values = ops.level_loss_ext(p, lab, self._ext_weights(), params, self.scale_dev)
+        return total, self._named_ext(values)
+
+    def _forward_boundary(self, p, lab, C, params, phi):
+        """the rest of the spec through its own family's entry, then the boundary terms on top of it (ops.level_loss_boundary)"""
+        classes = self.boundary_classes
+        if phi is None:
+            if lab.dim() != 4:
+                raise ValueError('the boundary term builds its distance maps from 3-D label patches [B,1,H,W,D]; pass `phi` otherwise')
+            phi = ops.signed_distance_maps(lab, classes, self.spacing)
+        n_wd = 0
+        if len(self.boundary) == len(self.spec):
+            base = None
+        elif self.extended:
+            base = ('ltu_loss_ext', ops.loss_ext_cfg(self._ext_weights(), params))
+        else:
+            wd = self.dice_weights(C)
+            n_wd = len(wd)
+            base = ('ltu_loss' if C <= 4 else 'ltu_loss_wide', (*self._ce_bal(), tuple(float(w) for w in wd)))
+        total, base_values, values = ops.level_loss_boundary(p, lab, phi, classes, [self.spec[name] * self.scale for name in self.boundary],
+                                                             base, self.scale_dev, self.term_scale_dev)
+        named = {} if base is None else self._named_ext(base_values) if self.extended else self._named_orig(base_values, n_wd)
+        for k, name in enumerate(self.boundary):
+            w = self.spec[name]
+            named[name] = values[k] if w == 1.0 else values[k] * w
+        return total, {name: named[name] for name in self.spec}
 
 
 _DISTRIBUTION_REFUSED = ('no HIP kernel for DistributionLoss: the reference module (loss/criterions.py:119-176) raises a shape '
@@ -277,6 +339,26 @@ class ClassifyLoss(_Single):
         super().__init__(eps=eps)
 
 
+def boundary_name(class_index: int) -> str:
+    """the spec name of the boundary term of class `class_index`: 'BoundaryLoss0c', 'BoundaryLoss', 'BoundaryLoss2' .. 'BoundaryLoss7'"""
+    if not 0 <= int(class_index) < ops.LOSS_WIDE_MAXC:
+        raise ValueError(f'BoundaryLoss: class_index {class_index} outside 0 .. {ops.LOSS_WIDE_MAXC - 1}')
+    return {0: 'BoundaryLoss0c', 1: 'BoundaryLoss'}.get(int(class_index), f'BoundaryLoss{int(class_index)}')
+
+
+class BoundaryLoss(nn.Module):
+    """Kervadec et al., "Boundary loss for highly unbalanced segmentation" (no reference counterpart): mean over (b, s) of
+    p[b, class_index, s] * phi[b, s], phi the signed distance map of {target == class_index} built on the GPU from the label patch
+    with `spacing` (ops.signed_distance_maps); forward(predict, target, phi=None) takes maps built elsewhere as [B,1,...]"""
+
+    def __init__(self, class_index: int = 1, spacing=(1.0, 1.0, 1.0)):
+        super().__init__()
+        self.impl = LevelCriterion({boundary_name(class_index): 1.0}, spacing=spacing)
+
+    def forward(self, predict, target, phi=None):
+        return self.impl(predict, target, phi=phi)[0]
+
+
 class _EvalMetric(nn.Module):
     """the evaluation losses train3D.py:143 requests besides the Dice losses (`eval_list`): computed on the un-thresholded class
     probabilities by the metric kernels of the inference driver (csrc/infer.hip); evaluation only, no gradient"""
@@ -333,6 +415,7 @@ Loss_Dict = {
     'BalanceDiceLoss2': BalanceDiceLoss2,
     'CrossEntroLoss0': CrossEntroLoss0,
     'ClassifyLoss': ClassifyLoss,
+    'BoundaryLoss': BoundaryLoss,
     'Recall': Recall,
     'Precision': Precision,
 }
@@ -340,7 +423,8 @@ Loss_Dict = {
 
 def get_criterions(name_list):
     """loss/criterions.py:773-782, and the training losses of loss/multi_criterions.py that a `--criterion_list` can name
-    (BalanceDiceLoss2, CrossEntroLoss0, ClassifyLoss, DiceClassLoss0, DiceClassLoss2).  DistributionLoss is refused."""
+    (BalanceDiceLoss2, CrossEntroLoss0, ClassifyLoss, DiceClassLoss0, DiceClassLoss2), and BoundaryLoss (class 1, unit spacing).
+    DistributionLoss is refused."""
     if 'DistributionLoss' in name_list:
         raise KeyError(_DISTRIBUTION_REFUSED)
     return {name: Loss_Dict[name]() for name in name_list}
@@ -399,6 +483,7 @@ Multi_Loss_Dict = {
     'DiceClassLoss0': DiceClassLoss0,
     'DiceClassLoss': DiceClassLoss,
     'DiceClassLoss2': DiceClassLoss2,
+    'BoundaryLoss': BoundaryLoss,
     'Recall': MultiRecall,
     'Precision': MultiPrecision,
     'Recall2': MultiRecall2,
@@ -411,7 +496,8 @@ Multi_Loss_Dict = {
 
 def get_multi_criterions(name_list):
     """loss/multi_criterions.py:704-714 for the names the multi-class scripts request: CrossEntroLoss and DiceClassLoss0 /
-    DiceClassLoss / DiceClassLoss2 are the differentiable modules above (train3D_multi_class.py trains with them); Recall,
+    DiceClassLoss / DiceClassLoss2 are the differentiable modules above (train3D_multi_class.py trains with them), as is
+    BoundaryLoss; Recall,
     Precision, Recall2, Precision2, RecallLoss, PrecisionLoss and the multi-class LocalizationLoss are evaluation-only modules
     over csrc/class_metrics.hip.  Any other name raises KeyError."""
     unknown = [name for name in name_list if name not in Multi_Loss_Dict]

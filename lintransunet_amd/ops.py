@@ -1757,3 +1757,116 @@ def level_loss_ext(p, label, weights, params=None, scale_dev=None):
     values[0] = total and values[1 + i] = term LOSS_EXT_TERMS[i] (unweighted, detached); no host synchronisation.
     scale_dev: optional 1-element fp32 device tensor multiplying all weights at run time."""
     return _LevelLossExt.apply(p, label, loss_ext_cfg(weights, params), scale_dev)
+
+
+# ---------------------------------------------------------------------------------------------- boundary loss
+
+DISTMAP_MAX_AXIS = 512      # DM_MAX_AXIS of csrc/distmap.hip: the largest training patch edge
+BOUNDARY_MAX_TERMS = 8      # most classes of one ltu_distmap_signed / ltu_loss_boundary_* call
+
+
+def _int_array(values):
+    return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def signed_distance_maps(label, classes, spacing=(1.0, 1.0, 1.0)):
+    """label uint8 [B,H,W,D], classes: K distinct class ids (1 <= K <= 8) -> fp32 [B,K,H,W,D], the signed Euclidean distance map
+    of G_k = {label == classes[k]} inside the patch (csrc/distmap.hip): dist(x, G) outside G, -(dist(x, not G) - 1) inside (the 1
+    is not scaled by the spacing: Kervadec's one_hot2dist), 0 everywhere when G is empty or fills the patch.  spacing: (s_H, s_W,
+    s_D) > 0 of the patch's voxels.  Every axis at most DISTMAP_MAX_AXIS.  One call for all B K volumes on the current stream, no
+    host read; two calls agree bit for bit."""
+    _chk(label, 'label')
+    if label.dtype != torch.uint8 or label.dim() != 4:
+        raise TypeError('signed_distance_maps: label must be uint8 [B,H,W,D]')
+    B, H, W, D = label.shape
+    K = len(classes)
+    sh, sw, sd = (float(v) for v in spacing)
+    phi = torch.empty((B, K, H, W, D), device=label.device, dtype=torch.float32)
+    scratch = torch.empty(max(1, _lib.load().ltu_distmap_scratch_elems(B, K, H, W, D)), device=label.device, dtype=torch.int32)
+    _lib.call('ltu_distmap_signed', _p(label), _int_array(classes), K, _p(phi), _p(scratch), _n(scratch), B, H, W, D, sh, sw, sd, _s())
+    return phi
+
+
+def _base_loss_fwd(base, p, label, B, S, C, scale_dev):
+    """the forward of a level's existing loss entry, unchanged: base = (entry, args).  Returns (values buffer, coef)"""
+    entry, args = base
+    dev = p.device
+    sums = torch.empty(getattr(_lib.load(), entry + '_ws_floats')(B, S, C), device=dev, dtype=torch.float32)
+    if entry == 'ltu_loss_ext':
+        buf = torch.empty(len(LOSS_EXT_TERMS) + 2, device=dev, dtype=torch.float32)
+        coef = torch.empty((B, C, 8), device=dev, dtype=torch.float32)
+        _lib.call('ltu_loss_ext_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(buf), _p(coef), B, S, C, args, _p(scale_dev), _s())
+    else:
+        w_ce, w_bal, w_dice = args
+        buf = torch.empty(len(w_dice) + 4, device=dev, dtype=torch.float32)
+        coef = torch.empty((B, C, 3), device=dev, dtype=torch.float32)
+        wd = (ctypes.c_float * len(w_dice))(*w_dice)
+        _lib.call(entry + '_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(buf), _p(coef), B, S, C, float(w_ce), float(w_bal), wd,
+                  _p(scale_dev), _s())
+    return buf, coef
+
+
+class _LevelLossBoundary(torch.autograd.Function):
+    """A level's existing loss entry (`base` = (entry, args) with entry 'ltu_loss' / 'ltu_loss_wide' / 'ltu_loss_ext', or None)
+    followed by the boundary term of csrc/loss_boundary.hip on the maps phi [B,K,...].  The boundary forward adds the base total
+    and the boundary backward adds into the dp the base backward has just written: no torch arithmetic joins the two.  Returns
+    (total, base values or None, boundary values [K]) with the values detached."""
+
+    @staticmethod
+    def forward(ctx, p, label, phi, base, classes, weights, scale_dev, term_scale_dev):
+        _chk(p, 'p'); _chk(label, 'label'); _chk(phi, 'phi')
+        B, C = p.shape[0], p.shape[-1]
+        S = p.numel() // (B * C)
+        K = len(classes)
+        if phi.dtype != torch.float32 or phi.numel() != B * K * S:
+            raise ValueError(f'boundary loss: phi must be fp32 [B, {K}, ...] over the voxels of p')
+        dev = p.device
+        base_buf = coef = None
+        if base is not None:
+            base_buf, coef = _base_loss_fwd(base, p, label, B, S, C, scale_dev)
+        ctx.cls, ctx.w = _int_array(classes), (ctypes.c_float * K)(*[float(w) for w in weights])
+        need = _lib.load().ltu_loss_boundary_sums_floats(B, S, K)
+        sums = torch.empty((need + 1) // 2, device=dev, dtype=torch.float64).view(torch.float32)      # doubles: 8-byte aligned, no zero fill
+        buf = torch.empty(K + 1, device=dev, dtype=torch.float32)
+        _lib.call('ltu_loss_boundary_fwd', _p(p), _p(phi), ctx.cls, ctx.w, K, _p(sums), _n(sums), _p(buf), _p(base_buf), _p(scale_dev),
+                  _p(term_scale_dev), B, S, C, _s())
+        ctx.base, ctx.K = base, K
+        ctx.scales = (scale_dev, term_scale_dev)
+        ctx.save_for_backward(p, label, phi, coef)
+        total, values = buf[0], buf[1:]         # two views of one buffer: the differentiable total and the report
+        base_values = None if base_buf is None else base_buf[:-1]
+        ctx.mark_non_differentiable(*(v for v in (values, base_values) if v is not None))
+        ctx.set_materialize_grads(False)
+        return total, base_values, values
+
+    @staticmethod
+    def backward(ctx, g, _gb, _gv):
+        p, label, phi, coef = ctx.saved_tensors
+        if g is None:
+            return (None,) * 8
+        B, C = p.shape[0], p.shape[-1]
+        S = p.numel() // (B * C)
+        g = g.contiguous().to(torch.float32)
+        dp = torch.empty_like(p)
+        if ctx.base is not None:
+            entry, args = ctx.base
+            if entry == 'ltu_loss_ext':
+                _lib.call('ltu_loss_ext_bwd', _p(p), _p(label), _p(coef), args, _p(g), _p(dp), B, S, C, _s())
+            else:
+                _lib.call(entry + '_bwd', _p(p), _p(label), _p(coef), _p(g), _p(dp), B, S, C, _s())
+        scale_dev, term_scale_dev = ctx.scales
+        _lib.call('ltu_loss_boundary_bwd', _p(phi), ctx.cls, ctx.w, ctx.K, _p(scale_dev), _p(term_scale_dev), _p(g), _p(dp),
+                  0 if ctx.base is None else 1, B, S, C, _s())
+        return (dp,) + (None,) * 7
+
+
+def level_loss_boundary(p, label, phi, classes, weights, base=None, scale_dev=None, term_scale_dev=None):
+    """p fp32 [B,...,C] channels-last probabilities (2 <= C <= 8), label uint8 [B,...], phi fp32 [B,K,...] (signed_distance_maps):
+    the level's existing loss `base` - ('ltu_loss' | 'ltu_loss_wide', (w_ce, w_bal, w_dice)) or ('ltu_loss_ext', loss_ext_cfg(..))
+    as level_loss / level_loss_wide / level_loss_ext would launch it, or None - plus scale * sum_k weights[k] * value_k with value_k =
+    mean over (b, s) of p[b, s, classes[k]] * phi[b, k, s] and scale = scale_dev[0] * term_scale_dev[0] (1-element fp32 device
+    tensors read at run time, None = 1).  Returns (total, base values or None, boundary values [K]), values detached; no host
+    synchronisation."""
+    if len(classes) != len(weights) or not 1 <= len(classes) <= BOUNDARY_MAX_TERMS:
+        raise ValueError(f'level_loss_boundary: 1 .. {BOUNDARY_MAX_TERMS} classes, one weight each')
+    return _LevelLossBoundary.apply(p, label, phi, base, tuple(classes), tuple(weights), scale_dev, term_scale_dev)

@@ -62,41 +62,80 @@ def label_pyramid(label, n_levels=5):
     return out
 
 
-def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0, level_scale=None, pyr=None):
+def boundary_maps(pyr, specs, spacing=(1.0, 1.0, 1.0)):
+    """signed distance maps for the levels whose spec has a boundary name (losses.LevelCriterion.BOUNDARY), from the pyramid's
+    labels: a list over levels of fp32 [B,K,h,w,d] or None.  The voxels of level l are `spacing` * (H_0 / H_l, W_0 / W_l,
+    D_0 / D_l) apart."""
+    n = len(pyr)
+    full = pyr[0].shape[1:]
+    phis = []
+    for lvl in range(n):
+        classes = LevelCriterion(specs[-lvl - 1]).boundary_classes
+        if not classes:
+            phis.append(None)
+            continue
+        sp = tuple(float(s) * f / c for s, f, c in zip(spacing, full, pyr[lvl].shape[1:]))
+        phis.append(ops.signed_distance_maps(pyr[lvl], classes, sp))
+    return phis
+
+
+def has_boundary(specs):
+    return any(name in LevelCriterion.BOUNDARY for spec in specs for name in spec)
+
+
+def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0, level_scale=None, pyr=None, spacing=(1.0, 1.0, 1.0),
+                          boundary_scale=None, phis=None):
     """Per-level fused losses (utils/utils_3D_embed_full.py:66-82).  Returns (list of weighted level totals,
     list of {name: value}); `sum(totals)` is the reference's total_loss * scale.
     level_scale: optional fp32 device tensor [n_levels] that REPLACES `weights[lvl] * scale` at run time (a captured graph
-    then follows the per-epoch weights of train3D.py:122-137 and the accumulation count without re-capture)."""
+    then follows the per-epoch weights of train3D.py:122-137 and the accumulation count without re-capture).
+    spacing: millimetres of the patch's voxels, for the boundary names of a spec; boundary_scale: optional 1-element fp32 device
+    tensor multiplying the boundary terms alone at run time (Kervadec's alpha schedule); phis: the levels' distance maps, already
+    built (boundary_maps).  A spec list without boundary names uses none of the three."""
     n = len(weights)
     specs = specs or level_specs(n)
     pyr = pyr or label_pyramid(label, n)      # pyr: the pyramid, already built (train_step builds it beside the encoder)
+    if phis is None and has_boundary(specs):
+        phis = boundary_maps(pyr, specs, spacing)
     totals, named = [], []
     for lvl in range(n):
         pred = predict if lvl == 0 else masks[-lvl]
         if level_scale is not None:
-            crit = LevelCriterion(specs[-lvl - 1], scale=1.0, scale_dev=level_scale[lvl:lvl + 1])
+            crit = LevelCriterion(specs[-lvl - 1], scale=1.0, scale_dev=level_scale[lvl:lvl + 1], term_scale_dev=boundary_scale)
         else:
-            crit = LevelCriterion(specs[-lvl - 1], scale=weights[lvl] * scale)
-        tot, vals = crit(pred, pyr[lvl].unsqueeze(1))
+            crit = LevelCriterion(specs[-lvl - 1], scale=weights[lvl] * scale, term_scale_dev=boundary_scale)
+        if crit.boundary:
+            tot, vals = crit(pred, pyr[lvl].unsqueeze(1), phi=phis[lvl])
+        else:
+            tot, vals = crit(pred, pyr[lvl].unsqueeze(1))
         totals.append(tot)
         named.append(vals)
     return totals, named
 
 
-def train_step(model, images, labels, weights, step_times=1, specs=None, reducer=None, ctx=None, level_scale=None, reduce=True):
+def train_step(model, images, labels, weights, step_times=1, specs=None, reducer=None, ctx=None, level_scale=None, reduce=True,
+               spacing=(1.0, 1.0, 1.0), boundary_scale=None):
     """forward + 5-level loss + backward for one batch of patches (one `j` of utils_3D_embed_full.py:55-86).
     Returns the list of weighted level losses (device scalars, no host sync).
     Gradient accumulation (utils_3D_embed_full.py:85-91): call `step_times` times with reduce=False except on the last
-    micro-step; the caller zeroes the gradients before the first one."""
+    micro-step; the caller zeroes the gradients before the first one.
+    spacing, boundary_scale: see deep_supervision_loss; the distance maps of the levels with a boundary name are built behind the
+    label pyramid on the side stream."""
     lc = ctx or ops.current()
     with ops.use(lc):
         lc.begin_step(images.device)
-        pyr = []
-        lc.side_run(lambda: pyr.extend(label_pyramid(labels, len(weights))))     # beside the encoder (joined inside the model's forward)
+        pyr, phis = [], []
+        boundary = specs is not None and has_boundary(specs)
+
+        def side():
+            pyr.extend(label_pyramid(labels, len(weights)))
+            if boundary:
+                phis.extend(boundary_maps(pyr, specs, spacing))
+        lc.side_run(side)                    # beside the encoder (joined inside the model's forward)
         predict, masks = model(images)
         lc.side_join()
         totals, named = deep_supervision_loss(predict, masks, labels, weights, specs, scale=1.0 / step_times, level_scale=level_scale,
-                                              pyr=pyr)
+                                              pyr=pyr, spacing=spacing, boundary_scale=boundary_scale, phis=phis if boundary else None)
         if reducer is not None:
             reducer.prepare(lc, reduce=reduce)
         one = lc.one(images.device)
@@ -301,14 +340,17 @@ class GraphedStep:
       zeroes the buckets only for j == 0 and reduces only for j == step_times - 1; each (zero, reduce) combination in use is its
       own captured graph (they share one memory pool).
     * per-epoch level weights (train3D.py:122-137) live in a device tensor read by the loss kernels: `set_weights(w)` updates
-      it in place, no re-capture.
+      it in place, no re-capture.  The factor of the boundary terms (specs with a 'BoundaryLoss..' name; `spacing` = millimetres of
+      the patch's voxels) lives in another: `set_boundary_scale(a)`.
     * every replay first checks that parameter and gradient storage is where it was at capture time (e.g. an optimizer built
       afterwards that re-homes `p.data`); if not, the step is captured again.
     * the step owns its `ops.Context` (scratch arena frozen after capture), so other graphs / eager steps cannot move it.
     """
 
-    def __init__(self, model, images, labels, weights, reducer, step_times=1, specs=None, warmup=2, overlap=None):
+    def __init__(self, model, images, labels, weights, reducer, step_times=1, specs=None, warmup=2, overlap=None,
+                 spacing=(1.0, 1.0, 1.0), boundary_scale=1.0):
         self.model, self.reducer = model, reducer
+        self.spacing = tuple(float(v) for v in spacing)
         self.step_times, self.specs, self.warmup = int(step_times), specs, warmup
         self.n_levels = len(weights)
         dev = images.device
@@ -322,6 +364,11 @@ class GraphedStep:
         self.ctx.set_step_counter(self.counter)
         self.level_scale = torch.empty(self.n_levels, device=dev, dtype=torch.float32)
         self.set_weights(weights)
+        # factor of the boundary terms (Kervadec's alpha), read by their kernels at run time; only a spec with a boundary name has one
+        self.boundary_scale = None
+        if specs is not None and has_boundary(specs):
+            self.boundary_scale = torch.empty(1, device=dev, dtype=torch.float32)
+            self.set_boundary_scale(boundary_scale)
         # weight-gradient queue (ops.Context.wq_install): with the step replayed as linear segments, the weight gradients of each
         # transformer / decoder level are captured as linear graphs of their own and replayed on a side stream beside the
         # data-gradient chain of the coarser, latency-bound levels (LTU_WQ=0: everything in line)
@@ -345,6 +392,12 @@ class GraphedStep:
         self.weights = tuple(float(w) for w in weights)
         self.level_scale.copy_(torch.tensor([w / self.step_times for w in self.weights], dtype=torch.float32))
 
+    def set_boundary_scale(self, a):
+        """factor of the boundary terms of every level from the next replay on (in place, no re-capture)"""
+        if self.boundary_scale is None:
+            raise ValueError('no level of this step has a boundary term')
+        self.boundary_scale.fill_(float(a))
+
     def _body(self, zero, reduce, on_flush=None, on_join=None):
         self.counter.add_(1)
         # weight gradients in batches on a side stream / as graphs of their own, at SIDE_BLOCKS workgroups per launch
@@ -356,7 +409,8 @@ class GraphedStep:
                 self.ctx.side_run(self.reducer.zero_grad)
             return train_step(self.model, self.x, self.lab, self.weights, step_times=self.step_times, specs=self.specs,
                               reducer=self.reducer, ctx=self.ctx, level_scale=self.level_scale,
-                              reduce=reduce and self.overlap in ('graph', 'segments'))
+                              reduce=reduce and self.overlap in ('graph', 'segments'), spacing=self.spacing,
+                              boundary_scale=self.boundary_scale)
         finally:
             self.ctx.wq_install(None)
 
