@@ -454,6 +454,30 @@ int ltu_loss_boundary_fwd(const float* p, const float* phi, const int* classes, 
 int ltu_loss_boundary_bwd(const float* phi, const int* classes, const float* w, int K, const float* scale_dev,
                           const float* term_scale_dev, const float* gscale, float* dp, int accumulate, int B, long long S, int C,
                           ltu_stream_t s);
+/* ---- top-k cross-entropy of one level (nnU-Net's TopKLoss; no reference counterpart; csrc/loss_topk.hip) -------------------------
+ * p f32 [B][S][C] probabilities (2 <= C <= 8), label u8 [B][S], N = B S.  Per voxel l = -log(max(p[label], 1e-6)) in fp32 (0 and
+ * no gradient where label >= C; such voxels still count in N).  k = min(max(floor((double)frac N), 1), N) with frac the host
+ * argument or, when frac_dev != NULL, frac_dev[0] read on the device at run time (out of range: clamped to k = 1 / k = N;
+ * non-finite: k = N).  tau = the k-th largest l over the whole batch, n_gt = #{l > tau}, n_eq = #{l == tau}:
+ *   value = (sum_{l > tau} l + (k - n_gt) tau) / k          (k = N: the plain mean)
+ *   values[0] = (base_total ? base_total[0] : 0) + scale_dev[0] w value (scale_dev NULL = 1), values[1] = value, values[2] = tau.
+ * bwd: dp[b][s][label] gets gscale[0] scale_dev[0] w weight (-1 / p) where p >= 1e-6, with weight = 1 / k where l > tau, 0 where
+ * l < tau and (k - n_gt) / (n_eq k) where l == tau (tied voxels share what is left of the k: the symmetric subgradient, which
+ * makes the result a function of the input where torch.topk picks arbitrarily); added to what a level's base backward has just
+ * written when accumulate != 0, else written with zeros in every other channel.
+ * tau is found by an exact radix select on the bits of l with integer histograms (integer LDS / global atomics only, no
+ * floating-point atomics; partial sums folded in a fixed order): two calls agree bit for bit; no host read, capturable.
+ * scratch: ltu_loss_topk_scratch_elems(B, S) 4-byte elements on a 16-byte boundary (else LTU_E_ALIGN), no initialisation; it
+ * keeps l and the selection record, and the backward reads the scratch its forward wrote.
+ * LTU_E_SHAPE: C outside 2 .. 8, B S outside 1 .. 2^31 - 1; LTU_E_ARG: a NULL pointer, short scratch, non-finite w, host frac
+ * outside (0, 1] when frac_dev is NULL; all before anything is launched. */
+long long ltu_loss_topk_scratch_elems(int B, long long S);
+int ltu_loss_topk_fwd(const float* p, const uint8_t* label, void* scratch, long long scratch_elems, float* values /* 3 */,
+                      const float* base_total, float w, float frac, const float* frac_dev, const float* scale_dev, int B,
+                      long long S, int C, ltu_stream_t s);
+int ltu_loss_topk_bwd(const float* p, const uint8_t* label, const void* scratch, long long scratch_elems, float w,
+                      const float* scale_dev, const float* gscale, float* dp, int accumulate, int B, long long S, int C,
+                      ltu_stream_t s);
 /* label pyramid (utils/utils_3D_embed_full.py:64,73-76): u8 [B,H,W,D] -> max over (2,2,kd) windows */
 int ltu_label_maxpool(const uint8_t* x, uint8_t* y, int B, int H, int W, int D, int kd, ltu_stream_t s);
 

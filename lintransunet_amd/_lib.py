@@ -155,6 +155,9 @@ SIGNATURES = {
     'ltu_loss_boundary_sums_floats': [I, L, I],
     'ltu_loss_boundary_fwd': [P, P, P, P, I, P, L, P, P, P, P, I, L, I, P],
     'ltu_loss_boundary_bwd': [P, P, P, I, P, P, P, P, I, I, L, I, P],
+    'ltu_loss_topk_scratch_elems': [I, L],
+    'ltu_loss_topk_fwd': [P, P, P, L, P, P, F, F, P, P, I, L, I, P],
+    'ltu_loss_topk_bwd': [P, P, P, L, F, P, P, P, I, I, L, I, P],
     'ltu_label_maxpool': [P, P, I, I, I, I, I, P],
     'ltu_comm_load': [ctypes.c_char_p],
     'ltu_comm_unique_id': [P],
@@ -192,7 +195,7 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = args
         fn.restype = c_longlong if (name.endswith(('_ws_floats', '_ws_elems')) or name in ('ltu_layer_tail_blocks', 'ltu_grad_sumsq_parts', 'ltu_crop_index_elems', 'ltu_distmap_scratch_elems',
-                                                                                           'ltu_loss_boundary_sums_floats')) else c_int
+                                                                                           'ltu_loss_boundary_sums_floats', 'ltu_loss_topk_scratch_elems')) else c_int
     for name, args in EXPERIMENT_SIGNATURES.items():
         fn = getattr(lib, name, None)
         if fn is not None:

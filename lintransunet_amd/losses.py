@@ -43,6 +43,10 @@ class LevelCriterion(nn.Module):
     `phi` given to forward: [B,K,...] in the order of `boundary_classes`) to whichever family the rest of the spec runs through
     (ops.level_loss_boundary; up to 8 classes, or 4 beside a name of `EXT`); `term_scale_dev` (1-element fp32 device tensor) scales
     the boundary terms alone at run time.  A spec without boundary names takes the path it always took.
+    'TopKCELoss' adds nnU-Net's top-k cross-entropy (ops.level_loss_topk, csrc/loss_topk.hip): the mean of -log(max(p[label], 1e-6))
+    over the hardest `topk_fraction` of the voxels of the whole batch, behind whichever family the rest of the spec runs through
+    and behind its boundary terms (up to 8 classes, or 4 beside a name of `EXT`); `topk_fraction_dev` (1-element fp32 device
+    tensor) replaces the fraction at run time.  Voxels tied at the threshold share the remaining weight (see ops.level_loss_topk).
     params: the parameters
     of the wider family (ops.LOSS_EXT_PARAMS: gamma, sigma, alpha, alpha2, eps; defaults ops.LOSS_EXT_DEFAULTS).  Returns
     (total, {name: w * value}) with values detached: what the reference scripts log (`criterions_w * l(...)`,
@@ -59,12 +63,14 @@ class LevelCriterion(nn.Module):
     EXT_MAXC = 4        # class limit of the wider family (csrc/loss_ext.hip)
     BOUNDARY = {'BoundaryLoss': 1, 'BoundaryLoss2': 2, 'BoundaryLoss0c': 0, 'BoundaryLoss3': 3, 'BoundaryLoss4': 4, 'BoundaryLoss5': 5,
                 'BoundaryLoss6': 6, 'BoundaryLoss7': 7}      # boundary term (csrc/loss_boundary.hip) of class ...
+    TOPK = 'TopKCELoss'     # top-k cross-entropy (csrc/loss_topk.hip)
 
-    def __init__(self, spec: dict, scale: float = 1.0, scale_dev=None, params=None, spacing=(1.0, 1.0, 1.0), term_scale_dev=None):
+    def __init__(self, spec: dict, scale: float = 1.0, scale_dev=None, params=None, spacing=(1.0, 1.0, 1.0), term_scale_dev=None,
+                 topk_fraction: float = 0.1, topk_fraction_dev=None):
         super().__init__()
         if 'DistributionLoss' in spec:
             raise KeyError(_DISTRIBUTION_REFUSED)
-        unknown = set(spec) - set(self._TERM) - set(self._DICE) - set(self.EXT) - set(self.BOUNDARY)
+        unknown = set(spec) - set(self._TERM) - set(self._DICE) - set(self.EXT) - set(self.BOUNDARY) - {self.TOPK}
         if unknown:
             raise KeyError(f'no HIP kernel for losses {sorted(unknown)}')
         self.spec = dict(spec)
@@ -75,6 +81,11 @@ class LevelCriterion(nn.Module):
         self.boundary = [name for name in self.spec if name in self.BOUNDARY]
         self.spacing = tuple(float(v) for v in spacing)      # of the label's voxels (H, W, D): the maps' unit of length
         self.term_scale_dev = term_scale_dev      # 1-element fp32 device tensor: run-time factor of the boundary terms alone
+        self.topk = self.TOPK in self.spec
+        self.topk_fraction = float(topk_fraction)
+        if self.topk and topk_fraction_dev is None and not 0.0 < self.topk_fraction <= 1.0:
+            raise ValueError(f'topk_fraction {topk_fraction} outside (0, 1]')
+        self.topk_fraction_dev = topk_fraction_dev      # 1-element fp32 device tensor: the fraction, read at run time
 
     @property
     def boundary_classes(self):
@@ -91,6 +102,8 @@ class LevelCriterion(nn.Module):
         absent = [name for name in self.boundary if self.BOUNDARY[name] >= C]
         if absent or (self.boundary and C < 2):
             raise ValueError(f'{absent or self.boundary}: the boundary term of a class the prediction does not have ({C} classes)')
+        if self.topk and C < 2:
+            raise ValueError(f'{self.TOPK}: needs a prediction of at least 2 classes')
 
     def dice_weights(self, C):
         """the Dice weights of the spec as the kernels take them: per class, then the foreground union - 5 entries for C <= 4
@@ -112,6 +125,8 @@ class LevelCriterion(nn.Module):
             raise ValueError(f'the level losses have kernels for C <= {ops.LOSS_WIDE_MAXC} classes, the prediction has {C}')
         p = _channels_last(predict)
         lab = _labels(target, C)
+        if self.topk:
+            return self._forward_topk(p, lab, C, dict(self.params, **(params or {})), phi)
         if self.boundary:
             return self._forward_boundary(p, lab, C, dict(self.params, **(params or {})), phi)
         if self.extended:
@@ -129,7 +144,7 @@ class LevelCriterion(nn.Module):
         fg = 3 + n_wd - 1
         named = {}
         for name, w in self.spec.items():
-            if name in self.BOUNDARY:
+            if name in self.BOUNDARY or name == self.TOPK:
                 continue
             if name == 'CrossEntroLoss':
                 v = values[1]
@@ -145,7 +160,7 @@ class LevelCriterion(nn.Module):
     def _ext_weights(self):
         weights = {}
         for name, w in self.spec.items():
-            if name in self.BOUNDARY:
+            if name in self.BOUNDARY or name == self.TOPK:
                 continue
             term = self.EXT.get(name) or self._TERM[name]
             weights[term] = weights.get(term, 0.0) + w * self.scale
@@ -154,7 +169,7 @@ class LevelCriterion(nn.Module):
     def _named_ext(self, values):
         named = {}
         for name, w in self.spec.items():
-            if name in self.BOUNDARY:
+            if name in self.BOUNDARY or name == self.TOPK:
                 continue
             v = values[1 + ops.LOSS_EXT_TERMS.index(self.EXT.get(name) or self._TERM[name])]
             named[name] = v if w == 1.0 else v * w
@@ -164,22 +179,46 @@ class LevelCriterion(nn.Module):
         total, values = ops.level_loss_ext(p, lab, self._ext_weights(), params, self.scale_dev)
         return total, self._named_ext(values)
 
-    def _forward_boundary(self, p, lab, C, params, phi):
-        """the rest of the spec through its own family's entry, then the boundary terms on top of it (ops.level_loss_boundary)"""
-        classes = self.boundary_classes
+    def _base_entry(self, C, params):
+        """the spec's names other than the boundary and top-k ones as the `base` of ops.level_loss_boundary / ops.level_loss_topk
+        (None without any), and the number of Dice weights of an original-family base"""
+        if len(self.boundary) + int(self.topk) == len(self.spec):
+            return None, 0
+        if self.extended:
+            return ('ltu_loss_ext', ops.loss_ext_cfg(self._ext_weights(), params)), 0
+        wd = self.dice_weights(C)
+        return ('ltu_loss' if C <= 4 else 'ltu_loss_wide', (*self._ce_bal(), tuple(float(w) for w in wd))), len(wd)
+
+    def _boundary_phi(self, lab, phi):
         if phi is None:
             if lab.dim() != 4:
                 raise ValueError('the boundary term builds its distance maps from 3-D label patches [B,1,H,W,D]; pass `phi` otherwise')
-            phi = ops.signed_distance_maps(lab, classes, self.spacing)
-        n_wd = 0
-        if len(self.boundary) == len(self.spec):
-            base = None
-        elif self.extended:
-            base = ('ltu_loss_ext', ops.loss_ext_cfg(self._ext_weights(), params))
-        else:
-            wd = self.dice_weights(C)
-            n_wd = len(wd)
-            base = ('ltu_loss' if C <= 4 else 'ltu_loss_wide', (*self._ce_bal(), tuple(float(w) for w in wd)))
+            phi = ops.signed_distance_maps(lab, self.boundary_classes, self.spacing)
+        return phi
+
+    def _forward_topk(self, p, lab, C, params, phi):
+        """the rest of the spec through its own family's entry, its boundary terms, then the top-k cross-entropy on top of both
+        (ops.level_loss_topk)"""
+        base, n_wd = self._base_entry(C, params)
+        boundary = None
+        if self.boundary:
+            boundary = (self._boundary_phi(lab, phi), self.boundary_classes, [self.spec[name] * self.scale for name in self.boundary],
+                        self.term_scale_dev)
+        w = self.spec[self.TOPK]
+        out = ops.level_loss_topk(p, lab, w * self.scale, self.topk_fraction, self.topk_fraction_dev, base, self.scale_dev, boundary)
+        total, base_values, values = out[:3]
+        named = {} if base is None else self._named_ext(base_values) if self.extended else self._named_orig(base_values, n_wd)
+        for k, name in enumerate(self.boundary):
+            wb = self.spec[name]
+            named[name] = out[3][k] if wb == 1.0 else out[3][k] * wb
+        named[self.TOPK] = values[0] if w == 1.0 else values[0] * w
+        return total, {name: named[name] for name in self.spec}
+
+    def _forward_boundary(self, p, lab, C, params, phi):
+        """the rest of the spec through its own family's entry, then the boundary terms on top of it (ops.level_loss_boundary)"""
+        classes = self.boundary_classes
+        phi = self._boundary_phi(lab, phi)
+        base, n_wd = self._base_entry(C, params)
         total, base_values, values = ops.level_loss_boundary(p, lab, phi, classes, [self.spec[name] * self.scale for name in self.boundary],
                                                              base, self.scale_dev, self.term_scale_dev)
         named = {} if base is None else self._named_ext(base_values) if self.extended else self._named_orig(base_values, n_wd)
@@ -359,6 +398,18 @@ class BoundaryLoss(nn.Module):
         return self.impl(predict, target, phi=phi)[0]
 
 
+class TopKCELoss(nn.Module):
+    """nnU-Net's TopKLoss (no reference counterpart): the cross-entropy -log(max(p[label], 1e-6)) averaged over the hardest `k`
+    percent of the voxels of the whole batch; voxels tied at the threshold share the remaining weight (ops.level_loss_topk)"""
+
+    def __init__(self, k: float = 10.0):
+        super().__init__()
+        self.impl = LevelCriterion({'TopKCELoss': 1.0}, topk_fraction=float(k) / 100.0)
+
+    def forward(self, predict, target):
+        return self.impl(predict, target)[0]
+
+
 class _EvalMetric(nn.Module):
     """the evaluation losses train3D.py:143 requests besides the Dice losses (`eval_list`): computed on the un-thresholded class
     probabilities by the metric kernels of the inference driver (csrc/infer.hip); evaluation only, no gradient"""
@@ -416,6 +467,7 @@ Loss_Dict = {
     'CrossEntroLoss0': CrossEntroLoss0,
     'ClassifyLoss': ClassifyLoss,
     'BoundaryLoss': BoundaryLoss,
+    'TopKCELoss': TopKCELoss,
     'Recall': Recall,
     'Precision': Precision,
 }
@@ -423,8 +475,8 @@ Loss_Dict = {
 
 def get_criterions(name_list):
     """loss/criterions.py:773-782, and the training losses of loss/multi_criterions.py that a `--criterion_list` can name
-    (BalanceDiceLoss2, CrossEntroLoss0, ClassifyLoss, DiceClassLoss0, DiceClassLoss2), and BoundaryLoss (class 1, unit spacing).
-    DistributionLoss is refused."""
+    (BalanceDiceLoss2, CrossEntroLoss0, ClassifyLoss, DiceClassLoss0, DiceClassLoss2), and BoundaryLoss (class 1, unit spacing) and
+    TopKCELoss (k = 10 percent).  DistributionLoss is refused."""
     if 'DistributionLoss' in name_list:
         raise KeyError(_DISTRIBUTION_REFUSED)
     return {name: Loss_Dict[name]() for name in name_list}
@@ -484,6 +536,7 @@ Multi_Loss_Dict = {
     'DiceClassLoss': DiceClassLoss,
     'DiceClassLoss2': DiceClassLoss2,
     'BoundaryLoss': BoundaryLoss,
+    'TopKCELoss': TopKCELoss,
     'Recall': MultiRecall,
     'Precision': MultiPrecision,
     'Recall2': MultiRecall2,
@@ -496,8 +549,8 @@ Multi_Loss_Dict = {
 
 def get_multi_criterions(name_list):
     """loss/multi_criterions.py:704-714 for the names the multi-class scripts request: CrossEntroLoss and DiceClassLoss0 /
-    DiceClassLoss / DiceClassLoss2 are the differentiable modules above (train3D_multi_class.py trains with them), as is
-    BoundaryLoss; Recall,
+    DiceClassLoss / DiceClassLoss2 are the differentiable modules above (train3D_multi_class.py trains with them), as are
+    BoundaryLoss and TopKCELoss; Recall,
     Precision, Recall2, Precision2, RecallLoss, PrecisionLoss and the multi-class LocalizationLoss are evaluation-only modules
     over csrc/class_metrics.hip.  Any other name raises KeyError."""
     unknown = [name for name in name_list if name not in Multi_Loss_Dict]

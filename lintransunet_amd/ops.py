@@ -21,6 +21,7 @@ thread-local) is remembered by the autograd node and used by its backward, which
 """
 import contextlib
 import ctypes
+import math
 import threading
 
 import torch
@@ -1870,3 +1871,114 @@ def level_loss_boundary(p, label, phi, classes, weights, base=None, scale_dev=No
     if len(classes) != len(weights) or not 1 <= len(classes) <= BOUNDARY_MAX_TERMS:
         raise ValueError(f'level_loss_boundary: 1 .. {BOUNDARY_MAX_TERMS} classes, one weight each')
     return _LevelLossBoundary.apply(p, label, phi, base, tuple(classes), tuple(weights), scale_dev, term_scale_dev)
+
+
+# ---------------------------------------------------------------------------------------------- top-k cross-entropy
+
+def topk_count(frac, N):
+    """k of the top-k cross-entropy (csrc/loss_topk.hip): min(max(floor(frac * N), 1), N) with frac taken as fp32 and the product
+    formed in double, as the kernel forms it.  Out of range clamps (k = 1 below, k = N above); a non-finite frac gives N."""
+    N = int(N)
+    f = ctypes.c_float(float(frac)).value
+    if not math.isfinite(f):
+        return N
+    return min(max(int(math.floor(f * N)), 1), N)
+
+
+class _LevelLossTopK(torch.autograd.Function):
+    """A level's existing loss entry (`base`, as in _LevelLossBoundary, or None), then the boundary term when `boundary` =
+    (classes, weights, term_scale_dev) comes with maps `phi`, then the top-k cross-entropy of csrc/loss_topk.hip: each forward
+    takes the total before it as its base total, each backward adds into the dp the one before it wrote, and no torch arithmetic
+    joins them.  Returns (total, base values or None, boundary values or None, top-k values [2] = (value, tau)), values detached."""
+
+    @staticmethod
+    def forward(ctx, p, label, phi, weight, frac, frac_dev, base, scale_dev, boundary):
+        _chk(p, 'p'); _chk(label, 'label')
+        B, C = p.shape[0], p.shape[-1]
+        S = p.numel() // (B * C)
+        dev = p.device
+        if frac_dev is not None and (frac_dev.dtype != torch.float32 or frac_dev.numel() != 1 or not frac_dev.is_cuda):
+            raise ValueError('top-k loss: frac_dev must be a 1-element fp32 device tensor')
+        base_buf = coef = bnd_buf = None
+        if base is not None:
+            base_buf, coef = _base_loss_fwd(base, p, label, B, S, C, scale_dev)
+        before = base_buf
+        ctx.bnd = None
+        if boundary is not None:
+            classes, weights, term_scale_dev = boundary
+            _chk(phi, 'phi')
+            K = len(classes)
+            if phi.dtype != torch.float32 or phi.numel() != B * K * S:
+                raise ValueError(f'boundary loss: phi must be fp32 [B, {K}, ...] over the voxels of p')
+            cls, wv = _int_array(classes), (ctypes.c_float * K)(*[float(w) for w in weights])
+            need = _lib.load().ltu_loss_boundary_sums_floats(B, S, K)
+            sums = torch.empty((need + 1) // 2, device=dev, dtype=torch.float64).view(torch.float32)
+            bnd_buf = torch.empty(K + 1, device=dev, dtype=torch.float32)
+            _lib.call('ltu_loss_boundary_fwd', _p(p), _p(phi), cls, wv, K, _p(sums), _n(sums), _p(bnd_buf), _p(before), _p(scale_dev),
+                      _p(term_scale_dev), B, S, C, _s())
+            ctx.bnd = (cls, wv, K, term_scale_dev)
+            before = bnd_buf
+        need = _lib.load().ltu_loss_topk_scratch_elems(B, S)
+        if need <= 0:
+            raise _lib.LtuError('ltu_loss_topk_scratch_elems: 2 <= C <= 8 classes and 1 .. 2^31 - 1 voxels in the batch')
+        scratch = torch.empty(need, device=dev, dtype=torch.int32)      # histograms, record and the per-voxel losses: no fill
+        buf = torch.empty(3, device=dev, dtype=torch.float32)
+        _lib.call('ltu_loss_topk_fwd', _p(p), _p(label), _p(scratch), _n(scratch), _p(buf), _p(before), float(weight), float(frac),
+                  _p(frac_dev), _p(scale_dev), B, S, C, _s())
+        ctx.base, ctx.weight, ctx.scale_dev = base, float(weight), scale_dev
+        ctx.save_for_backward(p, label, phi, coef, scratch)
+        total, values = buf[0], buf[1:]
+        base_values = None if base_buf is None else base_buf[:-1]
+        bnd_values = None if bnd_buf is None else bnd_buf[1:]
+        ctx.mark_non_differentiable(*(v for v in (values, base_values, bnd_values) if v is not None))
+        ctx.set_materialize_grads(False)
+        return total, base_values, bnd_values, values
+
+    @staticmethod
+    def backward(ctx, g, _gb, _gn, _gv):
+        p, label, phi, coef, scratch = ctx.saved_tensors
+        if g is None:
+            return (None,) * 9
+        B, C = p.shape[0], p.shape[-1]
+        S = p.numel() // (B * C)
+        g = g.contiguous().to(torch.float32)
+        dp = torch.empty_like(p)
+        written = 0
+        if ctx.base is not None:
+            entry, args = ctx.base
+            if entry == 'ltu_loss_ext':
+                _lib.call('ltu_loss_ext_bwd', _p(p), _p(label), _p(coef), args, _p(g), _p(dp), B, S, C, _s())
+            else:
+                _lib.call(entry + '_bwd', _p(p), _p(label), _p(coef), _p(g), _p(dp), B, S, C, _s())
+            written = 1
+        if ctx.bnd is not None:
+            cls, wv, K, term_scale_dev = ctx.bnd
+            _lib.call('ltu_loss_boundary_bwd', _p(phi), cls, wv, K, _p(ctx.scale_dev), _p(term_scale_dev), _p(g), _p(dp), written,
+                      B, S, C, _s())
+            written = 1
+        _lib.call('ltu_loss_topk_bwd', _p(p), _p(label), _p(scratch), _n(scratch), ctx.weight, _p(ctx.scale_dev), _p(g), _p(dp), written,
+                  B, S, C, _s())
+        return (dp,) + (None,) * 8
+
+
+def level_loss_topk(p, label, weight, frac=0.1, frac_dev=None, base=None, scale_dev=None, boundary=None):
+    """p fp32 [B,...,C] channels-last probabilities (2 <= C <= 8), label uint8 [B,...]: the level's existing loss `base` (as
+    level_loss_boundary takes it, or None) plus scale_dev[0] * weight * value, value = the cross-entropy -log(max(p[label], 1e-6))
+    averaged over the hardest k = topk_count(frac, N) of the N voxels of the whole batch (nnU-Net's TopKLoss; voxels with label >=
+    C have loss 0, no gradient, and count in N).  frac_dev: 1-element fp32 device tensor that replaces `frac` and is read at run
+    time (a captured graph follows it).  Voxels tied at the k-th largest loss share the remaining weight equally (the symmetric
+    subgradient), so the result does not depend on an arbitrary choice among them and two calls agree bit for bit.
+    Returns (total, base values or None, (value, tau)), values detached; no host synchronisation.
+    boundary = (phi, classes, weights, term_scale_dev) puts the boundary terms of level_loss_boundary between the two; their values
+    are then returned as a fourth entry."""
+    if frac_dev is None and not 0.0 < float(frac) <= 1.0:
+        raise ValueError(f'level_loss_topk: frac {frac} outside (0, 1]')
+    if boundary is None:
+        total, base_values, _, values = _LevelLossTopK.apply(p, label, None, weight, frac, frac_dev, base, scale_dev, None)
+        return total, base_values, values
+    phi, classes, weights, term_scale_dev = boundary
+    if len(classes) != len(weights) or not 1 <= len(classes) <= BOUNDARY_MAX_TERMS:
+        raise ValueError(f'level_loss_topk: 1 .. {BOUNDARY_MAX_TERMS} boundary classes, one weight each')
+    total, base_values, bnd_values, values = _LevelLossTopK.apply(p, label, phi, weight, frac, frac_dev, base, scale_dev,
+                                                                  (tuple(classes), tuple(weights), term_scale_dev))
+    return total, base_values, values, bnd_values

@@ -83,27 +83,35 @@ def has_boundary(specs):
     return any(name in LevelCriterion.BOUNDARY for spec in specs for name in spec)
 
 
+def has_topk(specs):
+    return any(LevelCriterion.TOPK in spec for spec in specs)
+
+
 def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0, level_scale=None, pyr=None, spacing=(1.0, 1.0, 1.0),
-                          boundary_scale=None, phis=None):
+                          boundary_scale=None, phis=None, topk_fraction=0.1):
     """Per-level fused losses (utils/utils_3D_embed_full.py:66-82).  Returns (list of weighted level totals,
     list of {name: value}); `sum(totals)` is the reference's total_loss * scale.
     level_scale: optional fp32 device tensor [n_levels] that REPLACES `weights[lvl] * scale` at run time (a captured graph
     then follows the per-epoch weights of train3D.py:122-137 and the accumulation count without re-capture).
     spacing: millimetres of the patch's voxels, for the boundary names of a spec; boundary_scale: optional 1-element fp32 device
     tensor multiplying the boundary terms alone at run time (Kervadec's alpha schedule); phis: the levels' distance maps, already
-    built (boundary_maps).  A spec list without boundary names uses none of the three."""
+    built (boundary_maps).  A spec list without boundary names uses none of the three.
+    topk_fraction: the fraction of the hardest voxels that 'TopKCELoss' averages over, the same at every level: a number, or a
+    1-element fp32 device tensor read at run time."""
     n = len(weights)
     specs = specs or level_specs(n)
     pyr = pyr or label_pyramid(label, n)      # pyr: the pyramid, already built (train_step builds it beside the encoder)
     if phis is None and has_boundary(specs):
         phis = boundary_maps(pyr, specs, spacing)
+    topk = {'topk_fraction_dev': topk_fraction} if torch.is_tensor(topk_fraction) else {'topk_fraction': topk_fraction}
     totals, named = [], []
     for lvl in range(n):
         pred = predict if lvl == 0 else masks[-lvl]
         if level_scale is not None:
-            crit = LevelCriterion(specs[-lvl - 1], scale=1.0, scale_dev=level_scale[lvl:lvl + 1], term_scale_dev=boundary_scale)
+            crit = LevelCriterion(specs[-lvl - 1], scale=1.0, scale_dev=level_scale[lvl:lvl + 1], term_scale_dev=boundary_scale,
+                                  **topk)
         else:
-            crit = LevelCriterion(specs[-lvl - 1], scale=weights[lvl] * scale, term_scale_dev=boundary_scale)
+            crit = LevelCriterion(specs[-lvl - 1], scale=weights[lvl] * scale, term_scale_dev=boundary_scale, **topk)
         if crit.boundary:
             tot, vals = crit(pred, pyr[lvl].unsqueeze(1), phi=phis[lvl])
         else:
@@ -114,13 +122,13 @@ def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0,
 
 
 def train_step(model, images, labels, weights, step_times=1, specs=None, reducer=None, ctx=None, level_scale=None, reduce=True,
-               spacing=(1.0, 1.0, 1.0), boundary_scale=None):
+               spacing=(1.0, 1.0, 1.0), boundary_scale=None, topk_fraction=0.1):
     """forward + 5-level loss + backward for one batch of patches (one `j` of utils_3D_embed_full.py:55-86).
     Returns the list of weighted level losses (device scalars, no host sync).
     Gradient accumulation (utils_3D_embed_full.py:85-91): call `step_times` times with reduce=False except on the last
     micro-step; the caller zeroes the gradients before the first one.
     spacing, boundary_scale: see deep_supervision_loss; the distance maps of the levels with a boundary name are built behind the
-    label pyramid on the side stream."""
+    label pyramid on the side stream.  topk_fraction: see deep_supervision_loss."""
     lc = ctx or ops.current()
     with ops.use(lc):
         lc.begin_step(images.device)
@@ -135,7 +143,8 @@ def train_step(model, images, labels, weights, step_times=1, specs=None, reducer
         predict, masks = model(images)
         lc.side_join()
         totals, named = deep_supervision_loss(predict, masks, labels, weights, specs, scale=1.0 / step_times, level_scale=level_scale,
-                                              pyr=pyr, spacing=spacing, boundary_scale=boundary_scale, phis=phis if boundary else None)
+                                              pyr=pyr, spacing=spacing, boundary_scale=boundary_scale, phis=phis if boundary else None,
+                                              topk_fraction=topk_fraction)
         if reducer is not None:
             reducer.prepare(lc, reduce=reduce)
         one = lc.one(images.device)
@@ -341,14 +350,15 @@ class GraphedStep:
       own captured graph (they share one memory pool).
     * per-epoch level weights (train3D.py:122-137) live in a device tensor read by the loss kernels: `set_weights(w)` updates
       it in place, no re-capture.  The factor of the boundary terms (specs with a 'BoundaryLoss..' name; `spacing` = millimetres of
-      the patch's voxels) lives in another: `set_boundary_scale(a)`.
+      the patch's voxels) lives in another: `set_boundary_scale(a)`.  The fraction of 'TopKCELoss' (the same at all levels) lives in
+      a third: `set_topk_fraction(f)`, e.g. annealed from 1.0 (plain cross-entropy) down to 0.1.
     * every replay first checks that parameter and gradient storage is where it was at capture time (e.g. an optimizer built
       afterwards that re-homes `p.data`); if not, the step is captured again.
     * the step owns its `ops.Context` (scratch arena frozen after capture), so other graphs / eager steps cannot move it.
     """
 
     def __init__(self, model, images, labels, weights, reducer, step_times=1, specs=None, warmup=2, overlap=None,
-                 spacing=(1.0, 1.0, 1.0), boundary_scale=1.0):
+                 spacing=(1.0, 1.0, 1.0), boundary_scale=1.0, topk_fraction=0.1):
         self.model, self.reducer = model, reducer
         self.spacing = tuple(float(v) for v in spacing)
         self.step_times, self.specs, self.warmup = int(step_times), specs, warmup
@@ -369,6 +379,11 @@ class GraphedStep:
         if specs is not None and has_boundary(specs):
             self.boundary_scale = torch.empty(1, device=dev, dtype=torch.float32)
             self.set_boundary_scale(boundary_scale)
+        # fraction of the top-k cross-entropy, read by its kernels at run time; only a spec with 'TopKCELoss' has one
+        self.topk_fraction = None
+        if specs is not None and has_topk(specs):
+            self.topk_fraction = torch.empty(1, device=dev, dtype=torch.float32)
+            self.set_topk_fraction(topk_fraction)
         # weight-gradient queue (ops.Context.wq_install): with the step replayed as linear segments, the weight gradients of each
         # transformer / decoder level are captured as linear graphs of their own and replayed on a side stream beside the
         # data-gradient chain of the coarser, latency-bound levels (LTU_WQ=0: everything in line)
@@ -398,6 +413,15 @@ class GraphedStep:
             raise ValueError('no level of this step has a boundary term')
         self.boundary_scale.fill_(float(a))
 
+    def set_topk_fraction(self, f):
+        """fraction of the hardest voxels in the top-k cross-entropy of every level from the next replay on (in place, no
+        re-capture)"""
+        if self.topk_fraction is None:
+            raise ValueError('no level of this step has a top-k term')
+        if not 0.0 < float(f) <= 1.0:
+            raise ValueError(f'topk fraction {f} outside (0, 1]')
+        self.topk_fraction.fill_(float(f))
+
     def _body(self, zero, reduce, on_flush=None, on_join=None):
         self.counter.add_(1)
         # weight gradients in batches on a side stream / as graphs of their own, at SIDE_BLOCKS workgroups per launch
@@ -410,7 +434,8 @@ class GraphedStep:
             return train_step(self.model, self.x, self.lab, self.weights, step_times=self.step_times, specs=self.specs,
                               reducer=self.reducer, ctx=self.ctx, level_scale=self.level_scale,
                               reduce=reduce and self.overlap in ('graph', 'segments'), spacing=self.spacing,
-                              boundary_scale=self.boundary_scale)
+                              boundary_scale=self.boundary_scale,
+                              topk_fraction=0.1 if self.topk_fraction is None else self.topk_fraction)
         finally:
             self.ctx.wq_install(None)
 
