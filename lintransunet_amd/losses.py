@@ -32,21 +32,20 @@ def _labels(target, n_class):
 class LevelCriterion(nn.Module):
     """Weighted sum of the training losses of one decoder level on one prediction, one kernel pass.
 
-    spec: {name: weight}.  A spec made only of the names of the original family, {'CrossEntroLoss', 'BalanceDiceLoss',
-    'DiceClassLoss' (class 1), 'DiceClassLoss2' .. 'DiceClassLoss7' (classes 2 .. 7, the reference's
-    multi_criterions.DiceClassLoss(class_index)), 'DiceClassLoss0c' (class 0), 'DiceClassLoss0' (foreground union
-    1 - class 0, multi_criterions.py:30-56)}, runs ops.level_loss on predictions of up to 4 classes and
-    ops.level_loss_wide on 5 .. 8 (both csrc/loss.hip).  A spec with any name of `EXT` runs the
-    whole spec through ops.level_loss_ext (csrc/loss_ext.hip), which also carries the original terms but stops at 4 classes.
+    spec: {name: weight}.  Every spec runs through ops.level_loss_chain, one autograd node of up to three stages.  The base stage
+    carries the names of the original family, {'CrossEntroLoss', 'BalanceDiceLoss', 'DiceClassLoss' (class 1), 'DiceClassLoss2' ..
+    'DiceClassLoss7' (classes 2 .. 7, the reference's multi_criterions.DiceClassLoss(class_index)), 'DiceClassLoss0c' (class 0),
+    'DiceClassLoss0' (foreground union 1 - class 0, multi_criterions.py:30-56)}: ltu_loss on predictions of up to 4 classes and
+    ltu_loss_wide on 5 .. 8 (both csrc/loss.hip), or, with any name of `EXT`, ltu_loss_ext (csrc/loss_ext.hip), which also carries the
+    original terms but stops at 4 classes.  It is absent only from a spec made of boundary and top-k names alone.
     The boundary names 'BoundaryLoss' (class 1), 'BoundaryLoss2' .. 'BoundaryLoss7' and 'BoundaryLoss0c' (class 0) add Kervadec's
     boundary term w * mean(p_c * phi_c) on the signed distance maps of the label (ops.signed_distance_maps with `spacing`, or the
-    `phi` given to forward: [B,K,...] in the order of `boundary_classes`) to whichever family the rest of the spec runs through
-    (ops.level_loss_boundary; up to 8 classes, or 4 beside a name of `EXT`); `term_scale_dev` (1-element fp32 device tensor) scales
-    the boundary terms alone at run time.  A spec without boundary names takes the path it always took.
-    'TopKCELoss' adds nnU-Net's top-k cross-entropy (ops.level_loss_topk, csrc/loss_topk.hip): the mean of -log(max(p[label], 1e-6))
-    over the hardest `topk_fraction` of the voxels of the whole batch, behind whichever family the rest of the spec runs through
-    and behind its boundary terms (up to 8 classes, or 4 beside a name of `EXT`); `topk_fraction_dev` (1-element fp32 device
-    tensor) replaces the fraction at run time.  Voxels tied at the threshold share the remaining weight (see ops.level_loss_topk).
+    `phi` given to forward: [B,K,...] in the order of `boundary_classes`) as the second stage (csrc/loss_boundary.hip; up to 8
+    classes, or 4 beside a name of `EXT`); `term_scale_dev` (1-element fp32 device tensor) scales the boundary terms alone at run
+    time.  'TopKCELoss' adds nnU-Net's top-k cross-entropy as the third stage (csrc/loss_topk.hip): the mean of
+    -log(max(p[label], 1e-6)) over the hardest `topk_fraction` of the voxels of the whole batch (up to 8 classes, or 4 beside a name
+    of `EXT`); `topk_fraction_dev` (1-element fp32 device tensor) replaces the fraction at run time.  Voxels tied at the threshold
+    share the remaining weight (see ops.level_loss_topk).  A spec without boundary and top-k names launches what it always launched.
     params: the parameters
     of the wider family (ops.LOSS_EXT_PARAMS: gamma, sigma, alpha, alpha2, eps; defaults ops.LOSS_EXT_DEFAULTS).  Returns
     (total, {name: w * value}) with values detached: what the reference scripts log (`criterions_w * l(...)`,
@@ -79,6 +78,7 @@ class LevelCriterion(nn.Module):
         self.params = dict(params or {})
         self.extended = any(name in self.EXT for name in self.spec)
         self.boundary = [name for name in self.spec if name in self.BOUNDARY]
+        self.base_names = [name for name in self.spec if name not in self.BOUNDARY and name != self.TOPK]      # what the base entry runs
         self.spacing = tuple(float(v) for v in spacing)      # of the label's voxels (H, W, D): the maps' unit of length
         self.term_scale_dev = term_scale_dev      # 1-element fp32 device tensor: run-time factor of the boundary terms alone
         self.topk = self.TOPK in self.spec
@@ -125,107 +125,48 @@ class LevelCriterion(nn.Module):
             raise ValueError(f'the level losses have kernels for C <= {ops.LOSS_WIDE_MAXC} classes, the prediction has {C}')
         p = _channels_last(predict)
         lab = _labels(target, C)
-        if self.topk:
-            return self._forward_topk(p, lab, C, dict(self.params, **(params or {})), phi)
+        base = boundary = topk = None
+        if self.base_names or not (self.boundary or self.topk):
+            base = self._base_entry(C, dict(self.params, **(params or {})))
         if self.boundary:
-            return self._forward_boundary(p, lab, C, dict(self.params, **(params or {})), phi)
-        if self.extended:
-            return self._forward_ext(p, lab, dict(self.params, **(params or {})))
-        wd = self.dice_weights(C)
-        fn = ops.level_loss if C <= 4 else ops.level_loss_wide
-        total, values = fn(p, lab, *self._ce_bal(), wd, self.scale_dev)
-        return total, self._named_orig(values, len(wd))
+            if phi is None:
+                if lab.dim() != 4:
+                    raise ValueError('the boundary term builds its distance maps from 3-D label patches [B,1,H,W,D]; pass `phi` otherwise')
+                phi = ops.signed_distance_maps(lab, self.boundary_classes, self.spacing)
+            boundary = (phi, self.boundary_classes, [self.spec[name] * self.scale for name in self.boundary], self.term_scale_dev)
+        if self.topk:
+            topk = (self.spec[self.TOPK] * self.scale, self.topk_fraction, self.topk_fraction_dev)
+        total, base_values, boundary_values, topk_values = ops.level_loss_chain(p, lab, base, boundary, topk, self.scale_dev)
+        value = {name: base_values[self._value_index(name, C)] for name in self.base_names}
+        value.update((name, boundary_values[k]) for k, name in enumerate(self.boundary))
+        if self.topk:
+            value[self.TOPK] = topk_values[0]
+        return total, {name: value[name] if w == 1.0 else value[name] * w for name, w in self.spec.items()}
 
-    def _ce_bal(self):
-        return self.spec.get('CrossEntroLoss', 0.0) * self.scale, self.spec.get('BalanceDiceLoss', 0.0) * self.scale
-
-    def _named_orig(self, values, n_wd):
-        """{name: w * value} of the original family's names from the values of ltu_loss_fwd / ltu_loss_wide_fwd"""
-        fg = 3 + n_wd - 1
-        named = {}
-        for name, w in self.spec.items():
-            if name in self.BOUNDARY or name == self.TOPK:
-                continue
-            if name == 'CrossEntroLoss':
-                v = values[1]
-            elif name == 'BalanceDiceLoss':
-                v = values[2]
-            elif self._DICE[name] == self.FG:
-                v = values[fg]
-            else:
-                v = values[3 + self._DICE[name]]
-            named[name] = v if w == 1.0 else v * w
-        return named
-
-    def _ext_weights(self):
-        weights = {}
-        for name, w in self.spec.items():
-            if name in self.BOUNDARY or name == self.TOPK:
-                continue
-            term = self.EXT.get(name) or self._TERM[name]
-            weights[term] = weights.get(term, 0.0) + w * self.scale
-        return weights
-
-    def _named_ext(self, values):
-        named = {}
-        for name, w in self.spec.items():
-            if name in self.BOUNDARY or name == self.TOPK:
-                continue
-            v = values[1 + ops.LOSS_EXT_TERMS.index(self.EXT.get(name) or self._TERM[name])]
-            named[name] = v if w == 1.0 else v * w
-        return named
-
-    def _forward_ext(self, p, lab, params):
-        total, values = ops.level_loss_ext(p, lab, self._ext_weights(), params, self.scale_dev)
-        return total, self._named_ext(values)
+    def _term(self, name):
+        """the term of the wider family (ops.LOSS_EXT_TERMS) behind a base name"""
+        return self.EXT.get(name) or self._TERM[name]
 
     def _base_entry(self, C, params):
-        """the spec's names other than the boundary and top-k ones as the `base` of ops.level_loss_boundary / ops.level_loss_topk
-        (None without any), and the number of Dice weights of an original-family base"""
-        if len(self.boundary) + int(self.topk) == len(self.spec):
-            return None, 0
+        """the spec's base names as the `base` of ops.level_loss_chain: the wider family beside any name of `EXT`, else the original
+        one (ltu_loss up to 4 classes, ltu_loss_wide for 5 .. 8)"""
         if self.extended:
-            return ('ltu_loss_ext', ops.loss_ext_cfg(self._ext_weights(), params)), 0
-        wd = self.dice_weights(C)
-        return ('ltu_loss' if C <= 4 else 'ltu_loss_wide', (*self._ce_bal(), tuple(float(w) for w in wd))), len(wd)
+            weights = {}
+            for name in self.base_names:
+                weights[self._term(name)] = weights.get(self._term(name), 0.0) + self.spec[name] * self.scale
+            return 'ltu_loss_ext', ops.loss_ext_cfg(weights, params)
+        w_ce, w_bal = self.spec.get('CrossEntroLoss', 0.0) * self.scale, self.spec.get('BalanceDiceLoss', 0.0) * self.scale
+        return 'ltu_loss' if C <= 4 else 'ltu_loss_wide', (w_ce, w_bal, tuple(float(w) for w in self.dice_weights(C)))
 
-    def _boundary_phi(self, lab, phi):
-        if phi is None:
-            if lab.dim() != 4:
-                raise ValueError('the boundary term builds its distance maps from 3-D label patches [B,1,H,W,D]; pass `phi` otherwise')
-            phi = ops.signed_distance_maps(lab, self.boundary_classes, self.spacing)
-        return phi
-
-    def _forward_topk(self, p, lab, C, params, phi):
-        """the rest of the spec through its own family's entry, its boundary terms, then the top-k cross-entropy on top of both
-        (ops.level_loss_topk)"""
-        base, n_wd = self._base_entry(C, params)
-        boundary = None
-        if self.boundary:
-            boundary = (self._boundary_phi(lab, phi), self.boundary_classes, [self.spec[name] * self.scale for name in self.boundary],
-                        self.term_scale_dev)
-        w = self.spec[self.TOPK]
-        out = ops.level_loss_topk(p, lab, w * self.scale, self.topk_fraction, self.topk_fraction_dev, base, self.scale_dev, boundary)
-        total, base_values, values = out[:3]
-        named = {} if base is None else self._named_ext(base_values) if self.extended else self._named_orig(base_values, n_wd)
-        for k, name in enumerate(self.boundary):
-            wb = self.spec[name]
-            named[name] = out[3][k] if wb == 1.0 else out[3][k] * wb
-        named[self.TOPK] = values[0] if w == 1.0 else values[0] * w
-        return total, {name: named[name] for name in self.spec}
-
-    def _forward_boundary(self, p, lab, C, params, phi):
-        """the rest of the spec through its own family's entry, then the boundary terms on top of it (ops.level_loss_boundary)"""
-        classes = self.boundary_classes
-        phi = self._boundary_phi(lab, phi)
-        base, n_wd = self._base_entry(C, params)
-        total, base_values, values = ops.level_loss_boundary(p, lab, phi, classes, [self.spec[name] * self.scale for name in self.boundary],
-                                                             base, self.scale_dev, self.term_scale_dev)
-        named = {} if base is None else self._named_ext(base_values) if self.extended else self._named_orig(base_values, n_wd)
-        for k, name in enumerate(self.boundary):
-            w = self.spec[name]
-            named[name] = values[k] if w == 1.0 else values[k] * w
-        return total, {name: named[name] for name in self.spec}
+    def _value_index(self, name, C):
+        """where the base entry's report holds the value of a base name: [total, CE, balanced Dice, Dice per class .., union Dice]
+        of the original family, [total, terms of ops.LOSS_EXT_TERMS ..] of the wider one"""
+        if self.extended:
+            return 1 + ops.LOSS_EXT_TERMS.index(self._term(name))
+        if name not in self._DICE:
+            return 1 if name == 'CrossEntroLoss' else 2
+        cls = self._DICE[name]
+        return 3 + ((4 if C <= 4 else C) if cls == self.FG else cls)
 
 
 _DISTRIBUTION_REFUSED = ('no HIP kernel for DistributionLoss: the reference module (loss/criterions.py:119-176) raises a shape '
@@ -248,11 +189,15 @@ class CrossEntroLoss(_Single):
     NAME = 'CrossEntroLoss'
 
 
+def _class_name(stem, class_index):
+    if not 0 <= int(class_index) < ops.LOSS_WIDE_MAXC:
+        raise ValueError(f'{stem}: class_index {class_index} outside 0 .. {ops.LOSS_WIDE_MAXC - 1}')
+    return {0: stem + '0c', 1: stem}.get(int(class_index), f'{stem}{int(class_index)}')
+
+
 def dice_class_name(class_index: int) -> str:
     """the spec name of the Dice of class `class_index`: 'DiceClassLoss0c', 'DiceClassLoss', 'DiceClassLoss2' .. 'DiceClassLoss7'"""
-    if not 0 <= int(class_index) < ops.LOSS_WIDE_MAXC:
-        raise ValueError(f'DiceClassLoss: class_index {class_index} outside 0 .. {ops.LOSS_WIDE_MAXC - 1}')
-    return {0: 'DiceClassLoss0c', 1: 'DiceClassLoss'}.get(int(class_index), f'DiceClassLoss{int(class_index)}')
+    return _class_name('DiceClassLoss', class_index)
 
 
 class DiceClassLoss(_Single):
@@ -380,9 +325,7 @@ class ClassifyLoss(_Single):
 
 def boundary_name(class_index: int) -> str:
     """the spec name of the boundary term of class `class_index`: 'BoundaryLoss0c', 'BoundaryLoss', 'BoundaryLoss2' .. 'BoundaryLoss7'"""
-    if not 0 <= int(class_index) < ops.LOSS_WIDE_MAXC:
-        raise ValueError(f'BoundaryLoss: class_index {class_index} outside 0 .. {ops.LOSS_WIDE_MAXC - 1}')
-    return {0: 'BoundaryLoss0c', 1: 'BoundaryLoss'}.get(int(class_index), f'BoundaryLoss{int(class_index)}')
+    return _class_name('BoundaryLoss', class_index)
 
 
 class BoundaryLoss(nn.Module):

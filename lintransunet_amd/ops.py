@@ -1640,70 +1640,16 @@ def attention_gate(skip, up, wx, bx, wg, bg, pw, pb, prep_x=None, prep_g=None):
 
 # ---------------------------------------------------------------------------------------------- loss
 
-class _LevelLoss(torch.autograd.Function):
-    """Weighted sum of the losses of one decoder level through one entry-point family of csrc/loss.hip: `entry` = 'ltu_loss'
-    (w_dice: 5 weights, nv = 9 values) or 'ltu_loss_wide' (C + 1 weights, nv = C + 5).  Returns (total, values[:nv - 1]) with
-    values detached."""
-
-    @staticmethod
-    def forward(ctx, p, label, w_ce, w_bal, w_dice, scale_dev, entry, nv):
-        ctx.lc = current()
-        ctx.entry = entry
-        _chk(p, 'p'); _chk(label, 'label')
-        B, C = p.shape[0], p.shape[-1]
-        S = p.numel() // (B * C)
-        dev = p.device
-        need = getattr(_lib.load(), entry + '_ws_floats')(B, S, C)
-        sums = torch.empty(need, device=dev, dtype=torch.float32)      # partials + sums: no zero fill
-        buf = torch.empty(nv, device=dev, dtype=torch.float32)
-        values = buf[:nv - 1]            # the report (non-differentiable); buf[nv - 1] repeats the total as the differentiable output, so
-        coef = torch.empty((B, C, 3), device=dev, dtype=torch.float32)          # no copy kernel is needed to separate the two
-        wd = (ctypes.c_float * len(w_dice))(*w_dice)
-        _lib.call(entry + '_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(values), _p(coef), B, S, C, float(w_ce), float(w_bal), wd,
-                  _p(scale_dev), _s())
-        ctx.save_for_backward(p, label, coef)
-        ctx.mark_non_differentiable(values)
-        ctx.set_materialize_grads(False)         # no zero-filled gradient tensor for the report output
-        return buf[nv - 1], values
-
-    @staticmethod
-    def backward(ctx, g, _gv):
-        p, label, coef = ctx.saved_tensors
-        B, C = p.shape[0], p.shape[-1]
-        S = p.numel() // (B * C)
-        if g is None:
-            return (None,) * 8
-        g = g.contiguous().to(torch.float32)
-        dp = torch.empty_like(p)
-        _lib.call(ctx.entry + '_bwd', _p(p), _p(label), _p(coef), _p(g), _p(dp), B, S, C, _s())
-        return (dp,) + (None,) * 7
-
-
-def level_loss(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
-    """p fp32 [B,...,C] channels-last probabilities (C <= 4), label uint8 [B,...]: weighted CE + balanced Dice + per-class Dice
-    (w_dice[c], c < 4) + Dice of the foreground union (w_dice[4]).  5 .. 8 classes: level_loss_wide.
-    scale_dev: optional 1-element fp32 device tensor multiplying all weights at run time."""
-    wd = tuple(float(w_dice[c]) if c < len(w_dice) else 0.0 for c in range(5))
-    return _LevelLoss.apply(p, label, w_ce, w_bal, wd, scale_dev, 'ltu_loss', 9)
-
-
 LOSS_WIDE_MAXC = 8      # LTU_WIDE_MAXC of csrc/common.h
-
-
-def level_loss_wide(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
-    """level_loss for 2 <= C <= 8 classes: w_dice has C + 1 entries (the Dice weight of every class, then that of the foreground
-    union); values = [total, CE, balanced Dice, Dice_0 .. Dice_{C-1}, union Dice] (detached)."""
-    C = p.shape[-1]
-    if len(w_dice) != C + 1:
-        raise ValueError(f'level_loss_wide: w_dice has {len(w_dice)} entries, {C} classes need {C + 1} (per class, then the foreground union)')
-    return _LevelLoss.apply(p, label, w_ce, w_bal, tuple(float(w) for w in w_dice), scale_dev, 'ltu_loss_wide', C + 5)
-
 
 # term and parameter slots of the config array of ltu_loss_ext_fwd / ltu_loss_ext_bwd (the LTU_LOSS_EXT_* enum of include/ltu_hip.h)
 LOSS_EXT_TERMS = ('CE', 'BAL', 'DICE0', 'DICE1', 'DICE2', 'DICE3', 'FG', 'DICE', 'IOU', 'SS', 'FOCAL', 'MSE', 'CONTAIN', 'CONTAIN2',
                   'BAL2', 'CE0', 'CLASSIFY')
 LOSS_EXT_PARAMS = ('gamma', 'sigma', 'alpha', 'alpha2', 'eps')
 LOSS_EXT_DEFAULTS = {'gamma': 2.0, 'sigma': 0.05, 'alpha': 0.4, 'alpha2': 0.3, 'eps': 1e-5}
+
+DISTMAP_MAX_AXIS = 512      # DM_MAX_AXIS of csrc/distmap.hip: the largest training patch edge
+BOUNDARY_MAX_TERMS = 8      # most classes of one ltu_distmap_signed / ltu_loss_boundary_* call
 
 
 def loss_ext_cfg(weights, params=None):
@@ -1716,39 +1662,168 @@ def loss_ext_cfg(weights, params=None):
     return (ctypes.c_float * len(vals))(*vals)
 
 
-class _LevelLossExt(torch.autograd.Function):
-    """The wider loss family of one decoder level; returns (total, values[1 + NTERM]) with values detached."""
+def _int_array(values):
+    return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+# The stages of a level's loss, in the order they chain.  Every forward takes `before`, the buffer whose slot 0 holds the total of the
+# stages before it (None for the first), and returns its own buffer with the new total in slot 0; every backward but the base's
+# takes `written`: 0 writes dp, 1 adds into it.
+
+def _base_fwd(base, p, label, scale_dev, B, S, C):
+    """base = (entry, args): 'ltu_loss' (C <= 4) / 'ltu_loss_wide' (C <= 8) of csrc/loss.hip with args = (w_ce, w_bal, w_dice: 5 /
+    C + 1 weights), or 'ltu_loss_ext' of csrc/loss_ext.hip with args = loss_ext_cfg(..).  Always the first stage.  Returns (buf,
+    coef): buf[:-1] is the report [total, terms ..] and buf[-1] repeats the total as the differentiable output, so no copy kernel
+    is needed to separate the two"""
+    entry, args = base
+    ext = entry == 'ltu_loss_ext'
+    if ext:
+        nv, weights = len(LOSS_EXT_TERMS) + 2, (args,)
+    else:
+        w_ce, w_bal, w_dice = args
+        nv, weights = len(w_dice) + 4, (float(w_ce), float(w_bal), (ctypes.c_float * len(w_dice))(*w_dice))
+    sums = torch.empty(getattr(_lib.load(), entry + '_ws_floats')(B, S, C), device=p.device, dtype=torch.float32)      # partials + sums: no zero fill
+    buf = torch.empty(nv, device=p.device, dtype=torch.float32)
+    coef = torch.empty((B, C, 8 if ext else 3), device=p.device, dtype=torch.float32)
+    _lib.call(entry + '_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(buf), _p(coef), B, S, C, *weights, _p(scale_dev), _s())
+    return buf, coef
+
+
+def _base_bwd(base, coef, p, label, g, dp, B, S, C):
+    entry, args = base
+    cfg = (args,) if entry == 'ltu_loss_ext' else ()
+    _lib.call(entry + '_bwd', _p(p), _p(label), _p(coef), *cfg, _p(g), _p(dp), B, S, C, _s())
+
+
+def _boundary_fwd(boundary, p, phi, before, scale_dev, B, S, C):
+    """boundary = (classes int array, weights float array, K, term_scale_dev) on the maps phi [B,K,...] (csrc/loss_boundary.hip).
+    Returns buf = [total, value_0 .. value_{K-1}]"""
+    cls, wv, K, term_scale_dev = boundary
+    need = _lib.load().ltu_loss_boundary_sums_floats(B, S, K)
+    sums = torch.empty((need + 1) // 2, device=p.device, dtype=torch.float64).view(torch.float32)      # doubles: 8-byte aligned, no zero fill
+    buf = torch.empty(K + 1, device=p.device, dtype=torch.float32)
+    _lib.call('ltu_loss_boundary_fwd', _p(p), _p(phi), cls, wv, K, _p(sums), _n(sums), _p(buf), _p(before), _p(scale_dev),
+              _p(term_scale_dev), B, S, C, _s())
+    return buf
+
+
+def _boundary_bwd(boundary, phi, g, dp, written, scale_dev, B, S, C):
+    cls, wv, K, term_scale_dev = boundary
+    _lib.call('ltu_loss_boundary_bwd', _p(phi), cls, wv, K, _p(scale_dev), _p(term_scale_dev), _p(g), _p(dp), written, B, S, C, _s())
+
+
+def _topk_fwd(topk, p, label, before, scale_dev, B, S, C):
+    """topk = (weight, frac, frac_dev) (csrc/loss_topk.hip).  Returns (buf = [total, value, tau], scratch)"""
+    weight, frac, frac_dev = topk
+    need = _lib.load().ltu_loss_topk_scratch_elems(B, S)
+    if need <= 0:
+        raise _lib.LtuError('ltu_loss_topk_scratch_elems: 2 <= C <= 8 classes and 1 .. 2^31 - 1 voxels in the batch')
+    scratch = torch.empty(need, device=p.device, dtype=torch.int32)      # histograms, record and the per-voxel losses: no fill
+    buf = torch.empty(3, device=p.device, dtype=torch.float32)
+    _lib.call('ltu_loss_topk_fwd', _p(p), _p(label), _p(scratch), _n(scratch), _p(buf), _p(before), float(weight), float(frac),
+              _p(frac_dev), _p(scale_dev), B, S, C, _s())
+    return buf, scratch
+
+
+def _topk_bwd(topk, scratch, p, label, g, dp, written, scale_dev, B, S, C):
+    _lib.call('ltu_loss_topk_bwd', _p(p), _p(label), _p(scratch), _n(scratch), float(topk[0]), _p(scale_dev), _p(g), _p(dp), written,
+              B, S, C, _s())
+
+
+class _LevelLossChain(torch.autograd.Function):
+    """The loss of one decoder level as a chain of optional stages (None = absent): `base`, then `boundary` on the maps `phi`, then
+    `topk`, each as its _*_fwd above takes it.  Each forward adds the total before it and each backward adds into the dp the one
+    before it wrote: no torch arithmetic and no copy joins them.  Returns (total, base report, boundary values [K], top-k values
+    [2] = (value, tau)), None for an absent stage: views of the stages' buffers, the reports detached."""
 
     @staticmethod
-    def forward(ctx, p, label, cfg, scale_dev):
-        ctx.lc = current()
-        _chk(p, 'p'); _chk(label, 'label')
+    def forward(ctx, p, label, phi, base, boundary, topk, scale_dev):
         B, C = p.shape[0], p.shape[-1]
         S = p.numel() // (B * C)
-        dev = p.device
-        nt = len(LOSS_EXT_TERMS)
-        sums = torch.empty(_lib.load().ltu_loss_ext_ws_floats(B, S, C), device=dev, dtype=torch.float32)      # no zero fill
-        buf = torch.empty(nt + 2, device=dev, dtype=torch.float32)
-        values = buf[:nt + 1]            # the report; buf[nt + 1] repeats the total as the differentiable output
-        coef = torch.empty((B, C, 8), device=dev, dtype=torch.float32)
-        _lib.call('ltu_loss_ext_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(values), _p(coef), B, S, C, cfg, _p(scale_dev), _s())
-        ctx.cfg = cfg
-        ctx.save_for_backward(p, label, coef)
-        ctx.mark_non_differentiable(values)
-        ctx.set_materialize_grads(False)
-        return buf[nt + 1], values
+        before = coef = scratch = None
+        reports = [None, None, None]
+        if base is not None:
+            before, coef = _base_fwd(base, p, label, scale_dev, B, S, C)
+            reports[0] = before[:-1]
+        if boundary is not None:
+            before = _boundary_fwd(boundary, p, phi, before, scale_dev, B, S, C)
+            reports[1] = before[1:]
+        if topk is not None:
+            before, scratch = _topk_fwd(topk, p, label, before, scale_dev, B, S, C)
+            reports[2] = before[1:]
+        total = before[-1] if boundary is None and topk is None else before[0]      # of the last stage's buffer
+        ctx.stages, ctx.scale_dev = (base, boundary, topk), scale_dev
+        ctx.save_for_backward(p, label, phi, coef, scratch)
+        ctx.mark_non_differentiable(*(r for r in reports if r is not None))
+        ctx.set_materialize_grads(False)         # no zero-filled gradient tensor for the report outputs
+        return (total, *reports)
 
     @staticmethod
-    def backward(ctx, g, _gv):
-        p, label, coef = ctx.saved_tensors
-        B, C = p.shape[0], p.shape[-1]
-        S = p.numel() // (B * C)
+    def backward(ctx, g, *_reports):
         if g is None:
-            return None, None, None, None
+            return (None,) * 7
+        p, label, phi, coef, scratch = ctx.saved_tensors
+        base, boundary, topk = ctx.stages
+        B, C = p.shape[0], p.shape[-1]
+        S = p.numel() // (B * C)
         g = g.contiguous().to(torch.float32)
         dp = torch.empty_like(p)
-        _lib.call('ltu_loss_ext_bwd', _p(p), _p(label), _p(coef), ctx.cfg, _p(g), _p(dp), B, S, C, _s())
-        return dp, None, None, None
+        written = 0
+        if base is not None:
+            _base_bwd(base, coef, p, label, g, dp, B, S, C)
+            written = 1
+        if boundary is not None:
+            _boundary_bwd(boundary, phi, g, dp, written, ctx.scale_dev, B, S, C)
+            written = 1
+        if topk is not None:
+            _topk_bwd(topk, scratch, p, label, g, dp, written, ctx.scale_dev, B, S, C)
+        return (dp,) + (None,) * 6
+
+
+def level_loss_chain(p, label, base=None, boundary=None, topk=None, scale_dev=None):
+    """p fp32 [B,...,C] channels-last probabilities, label uint8 [B,...]: the sum of the given stages, at least one, in one autograd
+    node.  base = ('ltu_loss' | 'ltu_loss_wide', (w_ce, w_bal, w_dice)) or ('ltu_loss_ext', loss_ext_cfg(..)), as level_loss /
+    level_loss_wide / level_loss_ext launch it; boundary = (phi, classes, weights, term_scale_dev), see level_loss_boundary; topk =
+    (weight, frac, frac_dev), see level_loss_topk.  scale_dev: optional 1-element fp32 device tensor multiplying all weights at run
+    time.  Returns (total, base values, boundary values, top-k values), None for a stage not given, values detached; every check
+    is made before the first launch and there is no host synchronisation."""
+    if base is None and boundary is None and topk is None:
+        raise ValueError('level_loss_chain: at least one of base, boundary and topk')
+    _chk(p, 'p'); _chk(label, 'label')
+    phi = None
+    if boundary is not None:
+        phi, classes, weights, term_scale_dev = boundary
+        K = len(classes)
+        if len(weights) != K or not 1 <= K <= BOUNDARY_MAX_TERMS:
+            raise ValueError(f'level_loss_chain: 1 .. {BOUNDARY_MAX_TERMS} boundary classes, one weight each')
+        _chk(phi, 'phi')
+        if phi.dtype != torch.float32 or phi.numel() * p.shape[-1] != K * p.numel():
+            raise ValueError(f'boundary loss: phi must be fp32 [B, {K}, ...] over the voxels of p')
+        boundary = (_int_array(classes), (ctypes.c_float * K)(*[float(w) for w in weights]), K, term_scale_dev)
+    if topk is not None:
+        _, frac, frac_dev = topk
+        if frac_dev is None and not 0.0 < float(frac) <= 1.0:
+            raise ValueError(f'level_loss_chain: frac {frac} outside (0, 1]')
+        if frac_dev is not None and (frac_dev.dtype != torch.float32 or frac_dev.numel() != 1 or not frac_dev.is_cuda):
+            raise ValueError('top-k loss: frac_dev must be a 1-element fp32 device tensor')
+    return _LevelLossChain.apply(p, label, phi, base, boundary, topk, scale_dev)
+
+
+def level_loss(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
+    """p fp32 [B,...,C] channels-last probabilities (C <= 4), label uint8 [B,...]: weighted CE + balanced Dice + per-class Dice
+    (w_dice[c], c < 4) + Dice of the foreground union (w_dice[4]).  5 .. 8 classes: level_loss_wide.
+    scale_dev: optional 1-element fp32 device tensor multiplying all weights at run time."""
+    wd = tuple(float(w_dice[c]) if c < len(w_dice) else 0.0 for c in range(5))
+    return level_loss_chain(p, label, ('ltu_loss', (w_ce, w_bal, wd)), scale_dev=scale_dev)[:2]
+
+
+def level_loss_wide(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
+    """level_loss for 2 <= C <= 8 classes: w_dice has C + 1 entries (the Dice weight of every class, then that of the foreground
+    union); values = [total, CE, balanced Dice, Dice_0 .. Dice_{C-1}, union Dice] (detached)."""
+    C = p.shape[-1]
+    if len(w_dice) != C + 1:
+        raise ValueError(f'level_loss_wide: w_dice has {len(w_dice)} entries, {C} classes need {C + 1} (per class, then the foreground union)')
+    return level_loss_chain(p, label, ('ltu_loss_wide', (w_ce, w_bal, tuple(float(w) for w in w_dice))), scale_dev=scale_dev)[:2]
 
 
 def level_loss_ext(p, label, weights, params=None, scale_dev=None):
@@ -1757,17 +1832,7 @@ def level_loss_ext(p, label, weights, params=None, scale_dev=None):
     LOSS_EXT_TERMS, with the parameters of LOSS_EXT_PARAMS (defaults LOSS_EXT_DEFAULTS).  Returns (total, values) with
     values[0] = total and values[1 + i] = term LOSS_EXT_TERMS[i] (unweighted, detached); no host synchronisation.
     scale_dev: optional 1-element fp32 device tensor multiplying all weights at run time."""
-    return _LevelLossExt.apply(p, label, loss_ext_cfg(weights, params), scale_dev)
-
-
-# ---------------------------------------------------------------------------------------------- boundary loss
-
-DISTMAP_MAX_AXIS = 512      # DM_MAX_AXIS of csrc/distmap.hip: the largest training patch edge
-BOUNDARY_MAX_TERMS = 8      # most classes of one ltu_distmap_signed / ltu_loss_boundary_* call
-
-
-def _int_array(values):
-    return (ctypes.c_int * len(values))(*[int(v) for v in values])
+    return level_loss_chain(p, label, ('ltu_loss_ext', loss_ext_cfg(weights, params)), scale_dev=scale_dev)[:2]
 
 
 def signed_distance_maps(label, classes, spacing=(1.0, 1.0, 1.0)):
@@ -1788,79 +1853,6 @@ def signed_distance_maps(label, classes, spacing=(1.0, 1.0, 1.0)):
     return phi
 
 
-def _base_loss_fwd(base, p, label, B, S, C, scale_dev):
-    """the forward of a level's existing loss entry, unchanged: base = (entry, args).  Returns (values buffer, coef)"""
-    entry, args = base
-    dev = p.device
-    sums = torch.empty(getattr(_lib.load(), entry + '_ws_floats')(B, S, C), device=dev, dtype=torch.float32)
-    if entry == 'ltu_loss_ext':
-        buf = torch.empty(len(LOSS_EXT_TERMS) + 2, device=dev, dtype=torch.float32)
-        coef = torch.empty((B, C, 8), device=dev, dtype=torch.float32)
-        _lib.call('ltu_loss_ext_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(buf), _p(coef), B, S, C, args, _p(scale_dev), _s())
-    else:
-        w_ce, w_bal, w_dice = args
-        buf = torch.empty(len(w_dice) + 4, device=dev, dtype=torch.float32)
-        coef = torch.empty((B, C, 3), device=dev, dtype=torch.float32)
-        wd = (ctypes.c_float * len(w_dice))(*w_dice)
-        _lib.call(entry + '_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(buf), _p(coef), B, S, C, float(w_ce), float(w_bal), wd,
-                  _p(scale_dev), _s())
-    return buf, coef
-
-
-class _LevelLossBoundary(torch.autograd.Function):
-    """A level's existing loss entry (`base` = (entry, args) with entry 'ltu_loss' / 'ltu_loss_wide' / 'ltu_loss_ext', or None)
-    followed by the boundary term of csrc/loss_boundary.hip on the maps phi [B,K,...].  The boundary forward adds the base total
-    and the boundary backward adds into the dp the base backward has just written: no torch arithmetic joins the two.  Returns
-    (total, base values or None, boundary values [K]) with the values detached."""
-
-    @staticmethod
-    def forward(ctx, p, label, phi, base, classes, weights, scale_dev, term_scale_dev):
-        _chk(p, 'p'); _chk(label, 'label'); _chk(phi, 'phi')
-        B, C = p.shape[0], p.shape[-1]
-        S = p.numel() // (B * C)
-        K = len(classes)
-        if phi.dtype != torch.float32 or phi.numel() != B * K * S:
-            raise ValueError(f'boundary loss: phi must be fp32 [B, {K}, ...] over the voxels of p')
-        dev = p.device
-        base_buf = coef = None
-        if base is not None:
-            base_buf, coef = _base_loss_fwd(base, p, label, B, S, C, scale_dev)
-        ctx.cls, ctx.w = _int_array(classes), (ctypes.c_float * K)(*[float(w) for w in weights])
-        need = _lib.load().ltu_loss_boundary_sums_floats(B, S, K)
-        sums = torch.empty((need + 1) // 2, device=dev, dtype=torch.float64).view(torch.float32)      # doubles: 8-byte aligned, no zero fill
-        buf = torch.empty(K + 1, device=dev, dtype=torch.float32)
-        _lib.call('ltu_loss_boundary_fwd', _p(p), _p(phi), ctx.cls, ctx.w, K, _p(sums), _n(sums), _p(buf), _p(base_buf), _p(scale_dev),
-                  _p(term_scale_dev), B, S, C, _s())
-        ctx.base, ctx.K = base, K
-        ctx.scales = (scale_dev, term_scale_dev)
-        ctx.save_for_backward(p, label, phi, coef)
-        total, values = buf[0], buf[1:]         # two views of one buffer: the differentiable total and the report
-        base_values = None if base_buf is None else base_buf[:-1]
-        ctx.mark_non_differentiable(*(v for v in (values, base_values) if v is not None))
-        ctx.set_materialize_grads(False)
-        return total, base_values, values
-
-    @staticmethod
-    def backward(ctx, g, _gb, _gv):
-        p, label, phi, coef = ctx.saved_tensors
-        if g is None:
-            return (None,) * 8
-        B, C = p.shape[0], p.shape[-1]
-        S = p.numel() // (B * C)
-        g = g.contiguous().to(torch.float32)
-        dp = torch.empty_like(p)
-        if ctx.base is not None:
-            entry, args = ctx.base
-            if entry == 'ltu_loss_ext':
-                _lib.call('ltu_loss_ext_bwd', _p(p), _p(label), _p(coef), args, _p(g), _p(dp), B, S, C, _s())
-            else:
-                _lib.call(entry + '_bwd', _p(p), _p(label), _p(coef), _p(g), _p(dp), B, S, C, _s())
-        scale_dev, term_scale_dev = ctx.scales
-        _lib.call('ltu_loss_boundary_bwd', _p(phi), ctx.cls, ctx.w, ctx.K, _p(scale_dev), _p(term_scale_dev), _p(g), _p(dp),
-                  0 if ctx.base is None else 1, B, S, C, _s())
-        return (dp,) + (None,) * 7
-
-
 def level_loss_boundary(p, label, phi, classes, weights, base=None, scale_dev=None, term_scale_dev=None):
     """p fp32 [B,...,C] channels-last probabilities (2 <= C <= 8), label uint8 [B,...], phi fp32 [B,K,...] (signed_distance_maps):
     the level's existing loss `base` - ('ltu_loss' | 'ltu_loss_wide', (w_ce, w_bal, w_dice)) or ('ltu_loss_ext', loss_ext_cfg(..))
@@ -1870,10 +1862,8 @@ def level_loss_boundary(p, label, phi, classes, weights, base=None, scale_dev=No
     synchronisation."""
     if len(classes) != len(weights) or not 1 <= len(classes) <= BOUNDARY_MAX_TERMS:
         raise ValueError(f'level_loss_boundary: 1 .. {BOUNDARY_MAX_TERMS} classes, one weight each')
-    return _LevelLossBoundary.apply(p, label, phi, base, tuple(classes), tuple(weights), scale_dev, term_scale_dev)
+    return level_loss_chain(p, label, base, (phi, classes, weights, term_scale_dev), scale_dev=scale_dev)[:3]
 
-
-# ---------------------------------------------------------------------------------------------- top-k cross-entropy
 
 def topk_count(frac, N):
     """k of the top-k cross-entropy (csrc/loss_topk.hip): min(max(floor(frac * N), 1), N) with frac taken as fp32 and the product
@@ -1883,82 +1873,6 @@ def topk_count(frac, N):
     if not math.isfinite(f):
         return N
     return min(max(int(math.floor(f * N)), 1), N)
-
-
-class _LevelLossTopK(torch.autograd.Function):
-    """A level's existing loss entry (`base`, as in _LevelLossBoundary, or None), then the boundary term when `boundary` =
-    (classes, weights, term_scale_dev) comes with maps `phi`, then the top-k cross-entropy of csrc/loss_topk.hip: each forward
-    takes the total before it as its base total, each backward adds into the dp the one before it wrote, and no torch arithmetic
-    joins them.  Returns (total, base values or None, boundary values or None, top-k values [2] = (value, tau)), values detached."""
-
-    @staticmethod
-    def forward(ctx, p, label, phi, weight, frac, frac_dev, base, scale_dev, boundary):
-        _chk(p, 'p'); _chk(label, 'label')
-        B, C = p.shape[0], p.shape[-1]
-        S = p.numel() // (B * C)
-        dev = p.device
-        if frac_dev is not None and (frac_dev.dtype != torch.float32 or frac_dev.numel() != 1 or not frac_dev.is_cuda):
-            raise ValueError('top-k loss: frac_dev must be a 1-element fp32 device tensor')
-        base_buf = coef = bnd_buf = None
-        if base is not None:
-            base_buf, coef = _base_loss_fwd(base, p, label, B, S, C, scale_dev)
-        before = base_buf
-        ctx.bnd = None
-        if boundary is not None:
-            classes, weights, term_scale_dev = boundary
-            _chk(phi, 'phi')
-            K = len(classes)
-            if phi.dtype != torch.float32 or phi.numel() != B * K * S:
-                raise ValueError(f'boundary loss: phi must be fp32 [B, {K}, ...] over the voxels of p')
-            cls, wv = _int_array(classes), (ctypes.c_float * K)(*[float(w) for w in weights])
-            need = _lib.load().ltu_loss_boundary_sums_floats(B, S, K)
-            sums = torch.empty((need + 1) // 2, device=dev, dtype=torch.float64).view(torch.float32)
-            bnd_buf = torch.empty(K + 1, device=dev, dtype=torch.float32)
-            _lib.call('ltu_loss_boundary_fwd', _p(p), _p(phi), cls, wv, K, _p(sums), _n(sums), _p(bnd_buf), _p(before), _p(scale_dev),
-                      _p(term_scale_dev), B, S, C, _s())
-            ctx.bnd = (cls, wv, K, term_scale_dev)
-            before = bnd_buf
-        need = _lib.load().ltu_loss_topk_scratch_elems(B, S)
-        if need <= 0:
-            raise _lib.LtuError('ltu_loss_topk_scratch_elems: 2 <= C <= 8 classes and 1 .. 2^31 - 1 voxels in the batch')
-        scratch = torch.empty(need, device=dev, dtype=torch.int32)      # histograms, record and the per-voxel losses: no fill
-        buf = torch.empty(3, device=dev, dtype=torch.float32)
-        _lib.call('ltu_loss_topk_fwd', _p(p), _p(label), _p(scratch), _n(scratch), _p(buf), _p(before), float(weight), float(frac),
-                  _p(frac_dev), _p(scale_dev), B, S, C, _s())
-        ctx.base, ctx.weight, ctx.scale_dev = base, float(weight), scale_dev
-        ctx.save_for_backward(p, label, phi, coef, scratch)
-        total, values = buf[0], buf[1:]
-        base_values = None if base_buf is None else base_buf[:-1]
-        bnd_values = None if bnd_buf is None else bnd_buf[1:]
-        ctx.mark_non_differentiable(*(v for v in (values, base_values, bnd_values) if v is not None))
-        ctx.set_materialize_grads(False)
-        return total, base_values, bnd_values, values
-
-    @staticmethod
-    def backward(ctx, g, _gb, _gn, _gv):
-        p, label, phi, coef, scratch = ctx.saved_tensors
-        if g is None:
-            return (None,) * 9
-        B, C = p.shape[0], p.shape[-1]
-        S = p.numel() // (B * C)
-        g = g.contiguous().to(torch.float32)
-        dp = torch.empty_like(p)
-        written = 0
-        if ctx.base is not None:
-            entry, args = ctx.base
-            if entry == 'ltu_loss_ext':
-                _lib.call('ltu_loss_ext_bwd', _p(p), _p(label), _p(coef), args, _p(g), _p(dp), B, S, C, _s())
-            else:
-                _lib.call(entry + '_bwd', _p(p), _p(label), _p(coef), _p(g), _p(dp), B, S, C, _s())
-            written = 1
-        if ctx.bnd is not None:
-            cls, wv, K, term_scale_dev = ctx.bnd
-            _lib.call('ltu_loss_boundary_bwd', _p(phi), cls, wv, K, _p(ctx.scale_dev), _p(term_scale_dev), _p(g), _p(dp), written,
-                      B, S, C, _s())
-            written = 1
-        _lib.call('ltu_loss_topk_bwd', _p(p), _p(label), _p(scratch), _n(scratch), ctx.weight, _p(ctx.scale_dev), _p(g), _p(dp), written,
-                  B, S, C, _s())
-        return (dp,) + (None,) * 8
 
 
 def level_loss_topk(p, label, weight, frac=0.1, frac_dev=None, base=None, scale_dev=None, boundary=None):
@@ -1973,12 +1887,7 @@ def level_loss_topk(p, label, weight, frac=0.1, frac_dev=None, base=None, scale_
     are then returned as a fourth entry."""
     if frac_dev is None and not 0.0 < float(frac) <= 1.0:
         raise ValueError(f'level_loss_topk: frac {frac} outside (0, 1]')
-    if boundary is None:
-        total, base_values, _, values = _LevelLossTopK.apply(p, label, None, weight, frac, frac_dev, base, scale_dev, None)
-        return total, base_values, values
-    phi, classes, weights, term_scale_dev = boundary
-    if len(classes) != len(weights) or not 1 <= len(classes) <= BOUNDARY_MAX_TERMS:
+    if boundary is not None and (len(boundary[1]) != len(boundary[2]) or not 1 <= len(boundary[1]) <= BOUNDARY_MAX_TERMS):
         raise ValueError(f'level_loss_topk: 1 .. {BOUNDARY_MAX_TERMS} boundary classes, one weight each')
-    total, base_values, bnd_values, values = _LevelLossTopK.apply(p, label, phi, weight, frac, frac_dev, base, scale_dev,
-                                                                  (tuple(classes), tuple(weights), term_scale_dev))
-    return total, base_values, values, bnd_values
+    total, base_values, bnd_values, values = level_loss_chain(p, label, base, boundary, (weight, frac, frac_dev), scale_dev)
+    return (total, base_values, values) if boundary is None else (total, base_values, values, bnd_values)
