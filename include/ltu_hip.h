@@ -701,6 +701,21 @@ enum { LTU_U8 = 2, LTU_I16 = 3 };
 int ltu_resample_grid(const void* src_img, int src_dtype, const uint8_t* src_lab, int S0, int S1, int S2, long long ss0, long long ss1,
                       long long ss2, float* out_img, uint8_t* out_lab, int O0, int O1, int O2, long long os0, long long os1,
                       long long os2, const double* mat, int lane_axis, float alpha, float beta, float lo, float hi, ltu_stream_t s);
+/* resample_argmax: the way back of a prediction.  probs: C planar f32 channels (channel c at probs + c * cs) of one volume of shape
+ *   S0 x S1 x S2 (element strides ss0..2), C = 2 .. 8.  Every output voxel p gets the coordinate, the clamp, the taps and the
+ *   weights of resample_grid once; class c's value there is the trilinear sum of channel c, bit for bit what resample_grid gives
+ *   for that channel as an LTU_F32 source with alpha 1, beta 0, lo -inf, hi +inf.  out_lab (u8, shape O0 x O1 x O2, strides
+ *   os0..2) = the first maximal class (strict > scanning c = 0 .. C-1: torch.argmax, class_metrics_pass's label map).
+ *   class_mask: bit c set stores class c's resampled value too, into plane j of out_prob (f32, plane stride ocs, each plane laid
+ *   out as out_lab), j = the number of set bits below c; 0 stores labels only (out_prob and ocs are then ignored).
+ *   lane_axis and the 64 x 64 tile as for resample_grid; both outputs go through LDS when lane_axis is not the output's fastest
+ *   axis.  Tap offsets inside a channel are 32-bit while (S - 1) . ss < 2^31, the channel base is a 64-bit pointer offset.
+ *   No workspace, no atomics: two calls give the same bytes.  LTU_E_ARG: NULL probs, mat or out_lab, lane_axis outside 0..2,
+ *   class_mask negative or with a bit >= C, class_mask != 0 with NULL out_prob; LTU_E_SHAPE: C outside 2..8, a size or stride < 1
+ *   (cs always, ocs when class_mask != 0). */
+int ltu_resample_argmax(const float* probs, int C, long long cs, int S0, int S1, int S2, long long ss0, long long ss1, long long ss2,
+                        uint8_t* out_lab, float* out_prob, int class_mask, long long ocs, int O0, int O1, int O2, long long os0,
+                        long long os1, long long os2, const double* mat, int lane_axis, ltu_stream_t s);
 /* crop_orient: patches [n][h][w][d] (f32 and / or u8, either pair NULL, not both) cut from vol [H][W][D] at desc, a HOST int32 array
  * [n][6] = (h0, w0, d0, flip_h, flip_w, swap_hw): out[k][x][y][z] = vol[h0 + a][w0 + b][d0 + z] with (u, v) = swap_hw ? (y, x) :
  * (x, y), a = flip_h ? h-1-u : u, b = flip_w ? w-1-v : v - a signed permutation of the (h, w) plane, which expresses "flip along

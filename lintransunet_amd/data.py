@@ -9,7 +9,7 @@ sample, from a `CropIndex` of the device label (csrc/crop_index.hip): the host k
 CT_pancreas_ids.py:121-134) to a batch of patches on the device; the random draws stay on the host.
 The third driver's data side (train3D_monai_version.py with dataset/CT_pancreas_monai.py: NIfTI scans of the Medical
 Segmentation Decathlon layout, ScaleIntensityRanged -> Spacingd -> Orientationd('RAS'), then crop + RandFlipd + RandRotate90d) is
-`SpacedScan` / `sample` / `to_native` at the end of this file.
+`SpacedScan` / `sample` / `to_native` / `to_native_probs` at the end of this file.
 """
 import warnings
 
@@ -418,6 +418,42 @@ def resample(src_img, src_lab, matrix, out_shape, imap=(1.0, 0.0, -np.inf, np.in
     _lib.call('ltu_resample_grid', _p(src_img), int(src_dtype), _p(src_lab), *S, *(int(s) for s in src_strides), _p(oi), _p(ol),
               *O, *(int(s) for s in out_strides), _p(mat), lane, *(float(v) for v in imap), _s())
     return oi, ol
+
+
+def resample_argmax(probs, matrix, out_shape, src_strides=None, out_strides=None, lane_axis=None, classes=()):
+    """ltu_resample_argmax: probs f32 [C, ...] on the device, C = 2 .. 8 channels of one volume of shape (S0, S1, S2) read through
+    `src_strides` (default: x fastest, i.e. every channel a [S2][S1][S0] array), pulled through the 3x4 float64 matrix onto out_shape
+    (layouts and the lane axis as data.resample) with the arg-max taken there: the first maximal class wins, as torch.argmax.
+    Every channel is resampled bit for bit as data.resample resamples it alone; the coordinates and taps are formed once for all.
+    classes: class ids whose resampled probabilities are returned too, in ascending order.
+    Returns (label u8, probabilities f32 [K, ...] or None)."""
+    if not torch.is_tensor(probs) or not probs.is_cuda:
+        raise _lib.LtuError('data.resample_argmax runs on the GPU only (no CPU fallback)')
+    if probs.dim() != 4 or probs.dtype != torch.float32 or not 2 <= probs.shape[0] <= 8:
+        raise ValueError(f'resample_argmax takes float32 probabilities [C, S0, S1, S2] with C = 2 .. 8, got {probs.dtype} {tuple(probs.shape)}')
+    C = int(probs.shape[0])
+    ks = sorted({int(k) for k in classes})
+    if ks and not (0 <= ks[0] and ks[-1] < C):
+        raise ValueError(f'classes {tuple(classes)} are not all in 0 .. {C - 1}')
+    probs = probs.contiguous()
+    if src_strides is None:
+        S = tuple(int(n) for n in probs.shape[:0:-1])
+        src_strides = (1, S[0], S[0] * S[1])
+    else:
+        S = tuple(int(n) for n in probs.shape[1:])
+    O = tuple(int(n) for n in out_shape)
+    if out_strides is None:
+        out_strides, alloc = (O[1] * O[2], O[2], 1), O
+    else:
+        alloc = tuple(O[a] for a in np.argsort(out_strides)[::-1])
+    m = np.asarray(matrix, dtype=np.float64).reshape(3, 4)
+    mat = torch.as_tensor(m.ravel().copy()).to(probs.device)
+    lane = geometry.lane_axis(m, src_strides) if lane_axis is None else lane_axis
+    ol = torch.empty(alloc, device=probs.device, dtype=torch.uint8)
+    op = torch.empty((len(ks),) + alloc, device=probs.device, dtype=torch.float32) if ks else None
+    _lib.call('ltu_resample_argmax', _p(probs), C, probs.stride(0), *S, *(int(s) for s in src_strides), _p(ol), _p(op),
+              sum(1 << k for k in ks), O[0] * O[1] * O[2], *O, *(int(s) for s in out_strides), _p(mat), lane, _s())
+    return ol, op
 
 
 class SpacedScan:
@@ -856,3 +892,21 @@ def to_native(label_map, scan):
     X, Y, Z = scan.native_shape
     _, out = resample(None, lm, geometry.invert(scan.matrix), (X, Y, Z), src_strides=(W * D, D, 1), out_strides=(1, X, X * Y))
     return out
+
+
+def to_native_probs(probs, scan, classes=()):
+    """the arg-max on the file's grid: RAS f32 probabilities [C, H, W, D] (a leading size-1 batch axis allowed, e.g.
+    infer_volume(..., probs=True)[0:1]) are pulled back through the inverse pull matrix with trilinear sampling and the arg-max is
+    taken there (nnU-Net's export order; to_native resamples a ready-made label map with nearest sampling instead).
+    Returns (u8 label [Z][Y][X] on the device, ready for nifti.save(..., scan.native_affine, like=scan.native), f32 [K][Z][Y][X]
+    probabilities of `classes` on that grid or None)."""
+    if probs.dim() == 5 and probs.shape[0] == 1:
+        probs = probs[0]
+    if probs.dim() != 4 or tuple(probs.shape[1:]) != tuple(scan.shape):
+        raise ValueError(f'to_native_probs takes probabilities [C, {", ".join(str(n) for n in scan.shape)}], got {tuple(probs.shape)}')
+    if probs.dtype != torch.float32:
+        raise ValueError(f'to_native_probs takes float32 probabilities, got {probs.dtype}')
+    H, W, D = scan.shape
+    X, Y, Z = scan.native_shape
+    return resample_argmax(probs, geometry.invert(scan.matrix), (X, Y, Z), src_strides=(W * D, D, 1), out_strides=(1, X, X * Y),
+                           classes=classes)

@@ -13,7 +13,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, data, ops
 from .ops import _p, _s
 
 
@@ -582,3 +582,24 @@ def infer_volume(model, images, depth_size=32, roi_xy=512, sw_batch_size=4, over
                                             mode=mode, sigma_scale=sigma_scale, mirror_axes=mirror_axes)
     finally:
         model.train(was_training)
+
+
+def segment_scan(models, scan, classes=(), **infer_volume_kwargs):
+    """a data.SpacedScan to its prediction on the file's grid: infer_volume(model, scan.img[None, None], probs=True, ...) per
+    member of `models` (one model or a sequence: the folds or checkpoints of an ensemble), the members' softmaxes summed in fp32 in
+    member order, then one data.to_native_probs.  Defaults here: mode='gaussian', mirror_axes=(0, 1); every other default is
+    infer_volume's.  The sum is not divided for the label (the arg-max does not change under a positive scale); with `classes` it is
+    scaled by 1 / len(models) first, so the returned probabilities are the members' mean.
+    Returns to_native_probs' pair (u8 label [Z][Y][X], f32 [K][Z][Y][X] or None)."""
+    members = [models] if isinstance(models, torch.nn.Module) else list(models)
+    if not members:
+        raise ValueError('segment_scan needs at least one model')
+    kw = dict(mode='gaussian', mirror_axes=(0, 1))
+    kw.update(infer_volume_kwargs)
+    total = None
+    for model in members:
+        p = infer_volume(model, scan.img[None, None], probs=True, **kw)
+        total = p if total is None else total.add_(p)
+    if classes and len(members) > 1:
+        total.mul_(1.0 / len(members))
+    return data.to_native_probs(total, scan, classes)
