@@ -13,134 +13,36 @@
 // One set of kernels for 1 .. 8 classes behind both entry-point families (ltu_loss_*: C <= 4, nine values; ltu_loss_wide_*:
 // 2 <= C <= 8, C + 5 values).  The class count is a template argument everywhere: per-thread arrays are indexed by unrolled
 // loops only and stay in registers.
-#include "common.h"
+#include "loss_stream.h"
 
-// Four voxels per thread and trip (S % 4 == 0, C >= 2): one 4-byte label load and C 16-byte probability loads.  Trips in flight:
-// two up to C = 4, one above (4 C floats a trip: two trips of C = 8 would hold 64 loaded values beside the 32 accumulators).  One
-// voxel at a time (a 1-byte and C 4-byte loads per trip, 16 dependent trips per thread) the level-0 pass ran at 2.2 TB/s.
+// One voxel into {P, T, I, E} of each class.  The rounding is written out, not left to -ffp-contract=fast (see the finalize kernel):
+// t (1 - p) is exact (t is 0 or 1) and meets the E sum in one fused multiply-add with the log.  Left alone, the compiler fuses most
+// of these and rounds the product on its own where it has paired it with the product of I into a packed add: which voxels of a
+// thread those are changes with the class count and with any edit.  p t is exact, so I is the same number either way; as a fused
+// multiply-add it keeps the four-voxel kernel of C = 2 at 62 VGPRs (97, one wave per SIMD less, with p * t and a separate add).
 template <int C>
-__global__ void __launch_bounds__(256) loss_sums_v4_kernel(const float* __restrict__ p, const uint8_t* __restrict__ label, float* __restrict__ sums,
-                                                           long long S, int rows_per_block) {
-  __shared__ float red[4][C * 4];
-  const int b = blockIdx.y;
-  float acc[C][4];
+__device__ __forceinline__ void loss_add(int lab, const float* f, float (&acc)[C * 4]) {
 #pragma unroll
-  for (int c = 0; c < C; ++c)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[c][k] = 0.f;
-  const long long s0 = (long long)blockIdx.x * rows_per_block;
-  long long s1 = s0 + rows_per_block;
-  if (s1 > S) s1 = S;
-  auto fetch = [&](long long s, uint32_t& labs, float (&f)[4 * C]) {
-    labs = *reinterpret_cast<const uint32_t*>(label + (long long)b * S + s);
-    const float* pv = p + ((long long)b * S + s) * C;
-#pragma unroll
-    for (int q = 0; q < C; ++q) {
-      const float4 t = *reinterpret_cast<const float4*>(pv + 4 * q);
-      f[4 * q] = t.x; f[4 * q + 1] = t.y; f[4 * q + 2] = t.z; f[4 * q + 3] = t.w;
-    }
-  };
-  auto add = [&](uint32_t labs, const float (&f)[4 * C]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int lab = (int)((labs >> (8 * j)) & 255u);
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        const float pc = f[j * C + c];
-        const float t = lab == c ? 1.f : 0.f;
-        acc[c][0] += pc;
-        acc[c][1] += t;
-        acc[c][2] += pc * t;
-        acc[c][3] += t * (1.f - pc) * logf(fmaxf(pc, 1e-6f));
-      }
-    }
-  };
-  long long s = s0 + (long long)threadIdx.x * 4;
-  if constexpr (C <= 4) {
-    for (; s + 1024 < s1; s += 2048) {
-      uint32_t l0, l1;
-      float f0[4 * C], f1[4 * C];
-      fetch(s, l0, f0);
-      fetch(s + 1024, l1, f1);
-      add(l0, f0);
-      add(l1, f1);
-    }
-    if (s < s1) {
-      uint32_t l0;
-      float f0[4 * C];
-      fetch(s, l0, f0);
-      add(l0, f0);
-    }
-  } else {
-    for (; s < s1; s += 1024) {
-      uint32_t l0;
-      float f0[4 * C];
-      fetch(s, l0, f0);
-      add(l0, f0);
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < C; ++c)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float v = wave_sum(acc[c][k]);
-      if (lane == 0) red[wave][c * 4 + k] = v;
-    }
-  __syncthreads();
-  if (threadIdx.x < C * 4) {
-    float v = 0.f;
-    for (int w = 0; w < 4; ++w) v += red[w][threadIdx.x];
-    // per-block partial [block][b][C*4] behind the final sums, folded by the finalize kernel in a fixed order (no fp32 atomics:
-    // their order, and with it the last bit of every loss coefficient, changed from run to run - bf16 rounding downstream turns
-    // that bit into 1e-2 of some gradients)
-    sums[((long long)(1 + blockIdx.x) * gridDim.y + b) * C * 4 + threadIdx.x] = v;
+  for (int c = 0; c < C; ++c) {
+    const float pc = f[c];
+    const float t = lab == c ? 1.f : 0.f;
+    acc[c * 4 + 0] += pc;
+    acc[c * 4 + 1] += t;
+    acc[c * 4 + 2] = fmaf(pc, t, acc[c * 4 + 2]);
+    acc[c * 4 + 3] = fmaf(lab == c ? 1.f - pc : 0.f, logf(fmaxf(pc, 1e-6f)), acc[c * 4 + 3]);
   }
 }
-// any S and C: one voxel per thread and trip.  p f32 [B][S][C], label u8 [B][S]; sums [1 + block][B][C][4] = {P,T,I,E}
-template <int C>
+
+// p f32 [B][S][C], label u8 [B][S]; sums [1 + block][B][C][4] = {P,T,I,E}.  V4: four voxels per thread and trip, two trips in flight
+// up to C = 4 (loss_stream.h)
+template <int C, bool V4>
 __global__ void __launch_bounds__(256) loss_sums_kernel(const float* __restrict__ p, const uint8_t* __restrict__ label, float* __restrict__ sums,
                                                         long long S, int rows_per_block) {
-  __shared__ float red[4][C * 4];
-  const int b = blockIdx.y;
-  float acc[C][4];
+  float acc[C * 4];
 #pragma unroll
-  for (int c = 0; c < C; ++c)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[c][k] = 0.f;
-  const long long s0 = (long long)blockIdx.x * rows_per_block;
-  long long s1 = s0 + rows_per_block;
-  if (s1 > S) s1 = S;
-  for (long long s = s0 + threadIdx.x; s < s1; s += 256) {
-    const int lab = label[(long long)b * S + s];
-    const float* pv = p + ((long long)b * S + s) * C;
-    float f[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) f[c] = pv[c];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const float pc = f[c];
-      const float t = lab == c ? 1.f : 0.f;
-      acc[c][0] += pc;
-      acc[c][1] += t;
-      acc[c][2] += pc * t;
-      acc[c][3] += t * (1.f - pc) * logf(fmaxf(pc, 1e-6f));
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < C; ++c)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float v = wave_sum(acc[c][k]);
-      if (lane == 0) red[wave][c * 4 + k] = v;
-    }
-  __syncthreads();
-  if (threadIdx.x < C * 4) {
-    float v = 0.f;
-    for (int w = 0; w < 4; ++w) v += red[w][threadIdx.x];
-    sums[((long long)(1 + blockIdx.x) * gridDim.y + b) * C * 4 + threadIdx.x] = v;
-  }
+  for (int k = 0; k < C * 4; ++k) acc[k] = 0.f;
+  ls_walk_block<C, V4, (C <= 4)>(p, label, S, rows_per_block, [&](int lab, const float* f) { loss_add<C>(lab, f, acc); });
+  ls_store_partial<C * 4>(acc, sums);
 }
 
 // weights: w_ce, w_bal, w_dice[c] (standard per-class Dice on class c), w_fg.  values out: [0] = total, [1] = ce, [2] = bal,
@@ -161,35 +63,7 @@ template <int C>
 __global__ void __launch_bounds__(256) loss_finalize_kernel(float* __restrict__ sums, int nblk, float* __restrict__ values, float* __restrict__ coef,
                                                             int B, long long S, LossCfg cfg, int fg_slot, const float* __restrict__ scale_dev) {
 #pragma clang fp contract(off)
-  {
-    // fold the per-block partials in a fixed order: output o = tid % nout is shared by the 256 / nout thread groups (each sums
-    // every ngrp-th block, 8 loads in flight), which meet in LDS
-    __shared__ float fold[256];
-    const int nout = B * C * 4;                          // <= 256
-    const int ngrp = 256 / nout;
-    const int o = threadIdx.x % nout, grp = threadIdx.x / nout;
-    float a0 = 0.f, a1 = 0.f;
-    if (grp < ngrp) {
-      const float* pp = sums + nout + o;
-      int z = grp;
-      for (; z + 7 * ngrp < nblk; z += 8 * ngrp) {
-        const float v0 = pp[(long long)z * nout], v1 = pp[(long long)(z + ngrp) * nout], v2 = pp[(long long)(z + 2 * ngrp) * nout],
-                    v3 = pp[(long long)(z + 3 * ngrp) * nout], v4 = pp[(long long)(z + 4 * ngrp) * nout],
-                    v5 = pp[(long long)(z + 5 * ngrp) * nout], v6 = pp[(long long)(z + 6 * ngrp) * nout],
-                    v7 = pp[(long long)(z + 7 * ngrp) * nout];
-        a0 += (v0 + v1) + (v2 + v3); a1 += (v4 + v5) + (v6 + v7);
-      }
-      for (; z < nblk; z += ngrp) a0 += pp[(long long)z * nout];
-    }
-    fold[threadIdx.x] = a0 + a1;
-    __syncthreads();
-    if ((int)threadIdx.x < nout) {
-      float t = 0.f;
-      for (int g = 0; g < ngrp; ++g) t += fold[g * nout + threadIdx.x];
-      sums[threadIdx.x] = t;
-    }
-    __syncthreads();
-  }
+  ls_fold(sums, nblk, B * C * 4, sums);      // B * C * 4 <= 256 partial rows into sums[0 ..)
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   if (scale_dev != nullptr) {
     const float sc = scale_dev[0];
@@ -269,92 +143,28 @@ __global__ void __launch_bounds__(256) loss_finalize_kernel(float* __restrict__ 
   values[fg_slot + 1] = total;      // a second copy: the autograd wrapper exposes it as the differentiable scalar and the rest as the report
 }
 
-// dp[s,c] = gscale * (alpha + t (beta + gamma f'(p))); four voxels per thread (S % 4 == 0): 16-byte loads and stores
-template <int C>
-__global__ void __launch_bounds__(256) loss_bwd_v4_kernel(const float* __restrict__ p, const uint8_t* __restrict__ label, const float* __restrict__ coef,
-                                                          const float* __restrict__ gscale, float* __restrict__ dp, long long S) {
-  const int b = blockIdx.y;
-  const float gs = gscale[0];
-  float k0[C], k1[C], k2[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const float* k = coef + ((long long)b * C + c) * 3;
-    k0[c] = k[0]; k1[c] = k[1]; k2[c] = k[2];
-  }
-  for (long long s = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; s < S; s += (long long)gridDim.x * 1024) {
-    const long long i = (long long)b * S + s;
-    const uint32_t labs = *reinterpret_cast<const uint32_t*>(label + i);
-    float f[4 * C], o[4 * C];
-#pragma unroll
-    for (int q = 0; q < C; ++q) {
-      const float4 t = *reinterpret_cast<const float4*>(p + i * C + 4 * q);
-      f[4 * q] = t.x; f[4 * q + 1] = t.y; f[4 * q + 2] = t.z; f[4 * q + 3] = t.w;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int lab = (int)((labs >> (8 * j)) & 255u);
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        const float pc = f[j * C + c];
-        const float fp = -logf(fmaxf(pc, 1e-6f)) + (pc > 1e-6f ? (1.f - pc) / pc : 0.f);
-        o[j * C + c] = gs * (lab == c ? k0[c] + (k1[c] + k2[c] * fp) : k0[c]);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < C; ++q) *reinterpret_cast<float4*>(dp + i * C + 4 * q) = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-  }
-}
-// any S: one voxel per thread and trip
-template <int C>
+// dp[s,c] = gscale * (alpha + t (beta + gamma f'(p))), beta + gamma f' in one fused multiply-add.  V4: four voxels per thread
+template <int C, bool V4>
 __global__ void __launch_bounds__(256) loss_bwd_kernel(const float* __restrict__ p, const uint8_t* __restrict__ label, const float* __restrict__ coef,
                                                        const float* __restrict__ gscale, float* __restrict__ dp, long long S) {
-  const int b = blockIdx.y;
   const float gs = gscale[0];
   float k0[C], k1[C], k2[C];
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    const float* k = coef + ((long long)b * C + c) * 3;
+    const float* k = coef + ((long long)blockIdx.y * C + c) * 3;
     k0[c] = k[0]; k1[c] = k[1]; k2[c] = k[2];
   }
-  for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < S; s += (long long)gridDim.x * 256) {
-    const long long i = (long long)b * S + s;
-    const int lab = label[i];
-    float f[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) f[c] = p[i * C + c];
+  ls_walk_grid<C, V4>(p, label, dp, S, [&](int lab, const float* f, float* o) {
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const float pc = f[c];
       const float fp = -logf(fmaxf(pc, 1e-6f)) + (pc > 1e-6f ? (1.f - pc) / pc : 0.f);
-      dp[i * C + c] = gs * (lab == c ? k0[c] + (k1[c] + k2[c] * fp) : k0[c]);
+      o[c] = gs * (lab == c ? k0[c] + fmaf(k2[c], fp, k1[c]) : k0[c]);
     }
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-template <int C>
-static void loss_fwd_launch(const float* p, const uint8_t* label, float* sums, int nblk, long long rows, float* values, float* coef, int B, long long S,
-                            const LossCfg& cfg, int fg_slot, const float* scale_dev, bool v4, hipStream_t s) {
-  if (v4) {          // implies C >= 2: no four-voxel kernel is instantiated for one class
-    if constexpr (C >= 2) hipLaunchKernelGGL(loss_sums_v4_kernel<C>, dim3(nblk, B), dim3(256), 0, s, p, label, sums, S, (int)rows);
-  } else {
-    hipLaunchKernelGGL(loss_sums_kernel<C>, dim3(nblk, B), dim3(256), 0, s, p, label, sums, S, (int)rows);
-  }
-  hipLaunchKernelGGL(loss_finalize_kernel<C>, dim3(1), dim3(256), 0, s, sums, nblk, values, coef, B, S, cfg, fg_slot, scale_dev);
-}
-template <int C>
-static void loss_bwd_launch(const float* p, const uint8_t* label, const float* coef, const float* gscale, float* dp, dim3 grid, long long S, bool v4,
-                            hipStream_t s) {
-  if (v4) {
-    if constexpr (C >= 2) hipLaunchKernelGGL(loss_bwd_v4_kernel<C>, grid, dim3(256), 0, s, p, label, coef, gscale, dp, S);
-  } else {
-    hipLaunchKernelGGL(loss_bwd_kernel<C>, grid, dim3(256), 0, s, p, label, coef, gscale, dp, S);
-  }
-}
-
-// the four-voxel kernels: S % 4 == 0 and at least two classes
-static bool loss_v4(long long S, int C) { return S % 4 == 0 && C >= 2 && !ltu_knob("LTU_LOSS_SCALAR", 0); }
-
 // Both entry-point families end here.  w_dice: C Dice weights (NULL: all zero); fg_slot: where the values hold the union Dice (the
 // second total follows it).
 static int loss_fwd(const float* p, const uint8_t* label, float* sums, long long sums_floats, float* values, float* coef, int B, long long S, int C,
@@ -366,21 +176,32 @@ static int loss_fwd(const float* p, const uint8_t* label, float* sums, long long
   cfg.w_ce = w_ce; cfg.w_bal = w_bal; cfg.w_fg = w_fg;
   for (int c = 0; c < LTU_WIDE_MAXC; ++c) cfg.w_dice[c] = (c < C && w_dice) ? w_dice[c] : 0.f;
   const bool v4 = loss_v4(S, C);
-  LTU_DISPATCH_C(C, { loss_fwd_launch<CT>(p, label, sums, nblk, rows, values, coef, B, S, cfg, fg_slot, scale_dev, v4, (hipStream_t)s); });
+  hipStream_t st = (hipStream_t)s;
+  LTU_DISPATCH_C(C, {
+    if (v4) {          // implies C >= 2: no four-voxel kernel is instantiated for one class
+      if constexpr (CT >= 2) hipLaunchKernelGGL((loss_sums_kernel<CT, true>), dim3(nblk, B), dim3(256), 0, st, p, label, sums, S, (int)rows);
+    } else {
+      hipLaunchKernelGGL((loss_sums_kernel<CT, false>), dim3(nblk, B), dim3(256), 0, st, p, label, sums, S, (int)rows);
+    }
+    hipLaunchKernelGGL(loss_finalize_kernel<CT>, dim3(1), dim3(256), 0, st, sums, nblk, values, coef, B, S, cfg, fg_slot, scale_dev);
+  });
   return ltu_check_launch();
 }
 static int loss_bwd(const float* p, const uint8_t* label, const float* coef, const float* gscale, float* dp, int B, long long S, int C,
                     ltu_stream_t s) {
   const bool v4 = loss_v4(S, C);
-  const int nb = B > 0 ? B : 1;
-  long long bx = (S / (v4 ? 4 : 1) + 255) / 256;
-  const long long cap = 4096 / nb > 1 ? 4096 / nb : 1;
-  if (bx > cap) bx = cap;
-  if (bx < 1) bx = 1;
-  const dim3 grid((unsigned)bx, B);
-  LTU_DISPATCH_C(C, { loss_bwd_launch<CT>(p, label, coef, gscale, dp, grid, S, v4, (hipStream_t)s); });
+  const dim3 grid = loss_bwd_grid(B, S, v4);
+  hipStream_t st = (hipStream_t)s;
+  LTU_DISPATCH_C(C, {
+    if (v4) {
+      if constexpr (CT >= 2) hipLaunchKernelGGL((loss_bwd_kernel<CT, true>), grid, dim3(256), 0, st, p, label, coef, gscale, dp, S);
+    } else {
+      hipLaunchKernelGGL((loss_bwd_kernel<CT, false>), grid, dim3(256), 0, st, p, label, coef, gscale, dp, S);
+    }
+  });
   return ltu_check_launch();
 }
+
 
 // 1 <= C <= 4: five Dice weights (classes 0 .. 3, union; NULL: all zero), nine values (union Dice at [7], second total at [8])
 extern "C" long long ltu_loss_ws_floats(int B, long long S, int C) { return (1 + cdiv(S, loss_rows(B, S))) * (long long)B * C * 4; }

@@ -15,7 +15,7 @@
 //     f(p) = (1-p) log max(p, 1e-6),  h(p) = (1-p)^gamma log p,  g(p) = p log max(1-p, 1e-6)
 // with the eight per-(b, c) coefficients written by the finalize kernel.  Sums and derivative terms the spec does not use are
 // switched off by a wave-uniform flag word.
-#include "common.h"
+#include "loss_stream.h"
 
 #define LX_MAXC 4
 #define LX_NS 7               // per-(b, c) sums: P T I E Q R F
@@ -31,142 +31,73 @@ struct LossExtCfg {
   float v[LTU_LOSS_EXT_NCFG];
 };
 
-// One voxel into the running sums.  pl = probability of the labelled class (1 when the label is outside 0 .. C-1: E and F then
-// add nothing); the logs of E and F are taken once per voxel and routed to the labelled class by selects.
+// y = sum_c c p_c, a chain of fused multiply-adds from class 1 up
 template <int C>
-__device__ __forceinline__ void lx_add(int lab, const float* f, float (&acc)[C][LX_NS], float (&ex)[LX_NX], unsigned fl, float gam) {
+__device__ __forceinline__ float lx_mean_class(const float* f) {
+  float y = 0.f;
+#pragma unroll
+  for (int c = 1; c < C; ++c) y = fmaf((float)c, f[c], y);
+  return y;
+}
+
+// One voxel into the running sums a[c * LX_NS + k] (per class) and a[LX_NS * C + k] (per sample).  pl = probability of the labelled
+// class (1 when the label is outside 0 .. C-1: E and F then add nothing); the logs of E and F are taken once per voxel and routed to
+// the labelled class by selects.  Where a product meets a sum the rounding is written out, not left to -ffp-contract=fast (see the
+// finalize kernel of loss.hip): p^2 is rounded on its own and added to Q and R (the bits the results of the four-voxel kernels have
+// always carried), the class-index mean y is a chain of fused multiply-adds.  The other products meet their sum behind a select and
+// cannot be fused.
+template <int C>
+__device__ __forceinline__ void lx_add(int lab, const float* f, float (&a)[LX_NS * C + LX_NX], unsigned fl, float gam) {
   float pl = 1.f;
 #pragma unroll
   for (int c = 0; c < C; ++c) {
+    float* acc = a + c * LX_NS;
     const float pc = f[c];
     const bool t = lab == c;
-    acc[c][0] += pc;
-    acc[c][1] += t ? 1.f : 0.f;
-    acc[c][2] += t ? pc : 0.f;
+    acc[0] += pc;
+    acc[1] += t ? 1.f : 0.f;
+    acc[2] += t ? pc : 0.f;
     if (fl & FL_Q) {
-      const float q = pc * pc;
-      acc[c][4] += q;
-      acc[c][5] += t ? q : 0.f;
+      const float q = ls_rounded(pc * pc);
+      acc[4] += q;
+      acc[5] += t ? q : 0.f;
     }
     pl = t ? pc : pl;
   }
   if (fl & FL_E) {
     const float e = (1.f - pl) * logf(fmaxf(pl, 1e-6f));
 #pragma unroll
-    for (int c = 0; c < C; ++c) acc[c][3] += lab == c ? e : 0.f;
+    for (int c = 0; c < C; ++c) a[c * LX_NS + 3] += lab == c ? e : 0.f;
   }
   if (fl & FL_F) {
     // voxels with t = 0 add exactly 0 (the reference's 0 * log 0 there is NaN when p == 0)
     const float om = 1.f - pl;
     const float h = ((fl & FL_F2) ? om * om : powf(om, gam)) * logf(pl);
 #pragma unroll
-    for (int c = 0; c < C; ++c) acc[c][6] += lab == c ? h : 0.f;
+    for (int c = 0; c < C; ++c) a[c * LX_NS + 6] += lab == c ? h : 0.f;
   }
+  float* ex = a + LX_NS * C;
   if (fl & FL_E0B) {
     const float p0 = f[0];
     ex[0] += lab == 0 ? 0.f : p0 * logf(fmaxf(1.f - p0, 1e-6f));
   }
   if (fl & FL_CLS) {
-    float y = 0.f;
-#pragma unroll
-    for (int c = 1; c < C; ++c) y += (float)c * f[c];
-    const float d = y - (float)lab;
+    const float d = lx_mean_class<C>(f) - (float)lab;
     ex[1] += lab != 0 ? 1.f : 0.f;
     ex[2] += lab != 0 ? d * d : 0.f;
   }
 }
 
-// block partial of the (7 C + 3) sums of sample b -> sums[(1 + block) * B + b][...]
-template <int C>
-__device__ __forceinline__ void lx_store_partial(float (&acc)[C][LX_NS], float (&ex)[LX_NX], float* __restrict__ sums, int b) {
-  __shared__ float red[4][LX_NS * LX_MAXC + LX_NX];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr int W = LX_NS * C + LX_NX;
-#pragma unroll
-  for (int c = 0; c < C; ++c)
-#pragma unroll
-    for (int k = 0; k < LX_NS; ++k) {
-      const float v = wave_sum(acc[c][k]);
-      if (lane == 0) red[wave][c * LX_NS + k] = v;
-    }
-#pragma unroll
-  for (int k = 0; k < LX_NX; ++k) {
-    const float v = wave_sum(ex[k]);
-    if (lane == 0) red[wave][LX_NS * C + k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < W) {
-    float v = 0.f;
-    for (int w = 0; w < 4; ++w) v += red[w][threadIdx.x];
-    sums[((long long)(1 + blockIdx.x) * gridDim.y + b) * W + threadIdx.x] = v;
-  }
-}
-
-// S % 4 == 0: four voxels per thread and trip, one 4-byte label load and C 16-byte probability loads, two trips in flight
-template <int C>
-__global__ void __launch_bounds__(256) lx_sums_v4_kernel(const float* __restrict__ p, const uint8_t* __restrict__ label, float* __restrict__ sums,
-                                                         long long S, int rows_per_block, unsigned fl, float gam) {
-  const int b = blockIdx.y;
-  float acc[C][LX_NS], ex[LX_NX] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < C; ++c)
-#pragma unroll
-    for (int k = 0; k < LX_NS; ++k) acc[c][k] = 0.f;
-  const long long s0 = (long long)blockIdx.x * rows_per_block;
-  long long s1 = s0 + rows_per_block;
-  if (s1 > S) s1 = S;
-  auto fetch = [&](long long s, uint32_t& labs, float (&f)[4 * C]) {
-    labs = *reinterpret_cast<const uint32_t*>(label + (long long)b * S + s);
-    const float* pv = p + ((long long)b * S + s) * C;
-#pragma unroll
-    for (int q = 0; q < C; ++q) {
-      const float4 t = *reinterpret_cast<const float4*>(pv + 4 * q);
-      f[4 * q] = t.x; f[4 * q + 1] = t.y; f[4 * q + 2] = t.z; f[4 * q + 3] = t.w;
-    }
-  };
-  auto add = [&](uint32_t labs, const float (&f)[4 * C]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) lx_add<C>((int)((labs >> (8 * j)) & 255u), f + j * C, acc, ex, fl, gam);
-  };
-  long long s = s0 + (long long)threadIdx.x * 4;
-  for (; s + 1024 < s1; s += 2048) {
-    uint32_t l0, l1;
-    float f0[4 * C], f1[4 * C];
-    fetch(s, l0, f0);
-    fetch(s + 1024, l1, f1);
-    add(l0, f0);
-    add(l1, f1);
-  }
-  if (s < s1) {
-    uint32_t l0;
-    float f0[4 * C];
-    fetch(s, l0, f0);
-    add(l0, f0);
-  }
-  lx_store_partial<C>(acc, ex, sums, b);
-}
-
-// any S: one voxel per thread and trip
-template <int C>
+// p f32 [B][S][C], label u8 [B][S]; sums [1 + block][B][7 C + 3].  V4 (S % 4 == 0): four voxels per thread and trip, two trips in
+// flight (loss_stream.h)
+template <int C, bool V4>
 __global__ void __launch_bounds__(256) lx_sums_kernel(const float* __restrict__ p, const uint8_t* __restrict__ label, float* __restrict__ sums,
                                                       long long S, int rows_per_block, unsigned fl, float gam) {
-  const int b = blockIdx.y;
-  float acc[C][LX_NS], ex[LX_NX] = {0.f, 0.f, 0.f};
+  float a[LX_NS * C + LX_NX];
 #pragma unroll
-  for (int c = 0; c < C; ++c)
-#pragma unroll
-    for (int k = 0; k < LX_NS; ++k) acc[c][k] = 0.f;
-  const long long s0 = (long long)blockIdx.x * rows_per_block;
-  long long s1 = s0 + rows_per_block;
-  if (s1 > S) s1 = S;
-  for (long long s = s0 + threadIdx.x; s < s1; s += blockDim.x) {
-    float f[C];
-    const float* pv = p + ((long long)b * S + s) * C;
-#pragma unroll
-    for (int c = 0; c < C; ++c) f[c] = pv[c];
-    lx_add<C>(label[(long long)b * S + s], f, acc, ex, fl, gam);
-  }
-  lx_store_partial<C>(acc, ex, sums, b);
+  for (int k = 0; k < LX_NS * C + LX_NX; ++k) a[k] = 0.f;
+  ls_walk_block<C, V4, true>(p, label, S, rows_per_block, [&](int lab, const float* f) { lx_add<C>(lab, f, a, fl, gam); });
+  ls_store_partial<LX_NS * C + LX_NX>(a, sums);
 }
 
 // One block of LX_FIN threads.  (1) The per-block partials fold in a fixed order (as in loss.hip: no fp32 atomics, the loss and its
@@ -176,38 +107,13 @@ __global__ void __launch_bounds__(256) lx_sums_kernel(const float* __restrict__ 
 __global__ void __launch_bounds__(LX_FIN) lx_finalize_kernel(const float* __restrict__ sums, int nblk, float* __restrict__ values,
                                                              float* __restrict__ coef, int B, long long S, int C, LossExtCfg cfg,
                                                              const float* __restrict__ scale_dev) {
-  __shared__ float fold[LX_FIN];
   __shared__ float sm[LX_FIN];
   __shared__ float per_b[LX_FIN / (2 * LX_NS + LX_NX) + 1][8];        // B <= 15 (C = 2)
   __shared__ float share[LX_FIN / (LX_NS + 1)][LTU_LOSS_EXT_NTERM];
   __shared__ float val[LTU_LOSS_EXT_NTERM];
   const int W = lx_row(C);
   const int nout = B * W;                                  // <= LX_FIN
-  {
-    const int ngrp = LX_FIN / nout;
-    const int o = threadIdx.x % nout, grp = threadIdx.x / nout;
-    float a0 = 0.f, a1 = 0.f;
-    if (grp < ngrp) {
-      const float* pp = sums + nout + o;
-      int z = grp;
-      for (; z + 7 * ngrp < nblk; z += 8 * ngrp) {
-        const float v0 = pp[(long long)z * nout], v1 = pp[(long long)(z + ngrp) * nout], v2 = pp[(long long)(z + 2 * ngrp) * nout],
-                    v3 = pp[(long long)(z + 3 * ngrp) * nout], v4 = pp[(long long)(z + 4 * ngrp) * nout],
-                    v5 = pp[(long long)(z + 5 * ngrp) * nout], v6 = pp[(long long)(z + 6 * ngrp) * nout],
-                    v7 = pp[(long long)(z + 7 * ngrp) * nout];
-        a0 += (v0 + v1) + (v2 + v3); a1 += (v4 + v5) + (v6 + v7);
-      }
-      for (; z < nblk; z += ngrp) a0 += pp[(long long)z * nout];
-    }
-    fold[threadIdx.x] = a0 + a1;
-    __syncthreads();
-    if ((int)threadIdx.x < nout) {
-      float t = 0.f;
-      for (int g = 0; g < ngrp; ++g) t += fold[g * nout + threadIdx.x];
-      sm[threadIdx.x] = t;
-    }
-    __syncthreads();
-  }
+  ls_fold(sums, nblk, nout, sm);
   const float sc = scale_dev != nullptr ? scale_dev[0] : 1.f;
   float w[LTU_LOSS_EXT_NTERM];
 #pragma unroll
@@ -400,11 +306,13 @@ __device__ __forceinline__ float lx_dce(float p) { return -logf(fmaxf(p, 1e-6f))
 // At p == 1 exactly (log p == 0) the first term of h' is its limit 0, also for gamma < 1 where (1-p)^(gamma-1) is inf there.
 __device__ __forceinline__ float lx_dfocal(float p, unsigned fl, float gam) {
   const float om = 1.f - p, lp = logf(p);
-  if (fl & FL_F2) return -2.f * om * lp + om * om / p;
+  if (fl & FL_F2) return fmaf(-2.f * om, lp, om * om / p);
   return (lp != 0.f ? -gam * powf(om, gam - 1.f) * lp : 0.f) + powf(om, gam) / p;
 }
 
-// gradient of one voxel: f[C] probabilities, k[C][8] coefficients (scaled by gs on the way out)
+// gradient of one voxel: f[C] probabilities, k[C][8] coefficients (scaled by gs on the way out).  Every product that meets a sum
+// does so in a fused multiply-add, written out: the four-voxel and the one-voxel kernel then do the same arithmetic for a voxel
+// (left to the compiler they did not)
 template <int C>
 __device__ __forceinline__ void lx_grad(int lab, const float* f, const float (&k)[C][LX_NK], float* o, unsigned fl, float gam, float gs) {
   float pl = 1.f;
@@ -412,25 +320,19 @@ __device__ __forceinline__ void lx_grad(int lab, const float* f, const float (&k
   for (int c = 0; c < C; ++c) pl = lab == c ? f[c] : pl;
   const float dce = (fl & FL_E) ? lx_dce(pl) : 0.f;
   const float dfo = (fl & FL_F) ? lx_dfocal(pl, fl, gam) : 0.f;
-  float md = 0.f;
-  if (fl & FL_CLS) {
-    float y = 0.f;
-#pragma unroll
-    for (int c = 1; c < C; ++c) y += (float)c * f[c];
-    md = lab != 0 ? y - (float)lab : 0.f;
-  }
+  const float md = (fl & FL_CLS) && lab != 0 ? lx_mean_class<C>(f) - (float)lab : 0.f;
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     const float pc = f[c];
     const bool t = lab == c;
-    float g = k[c][0] + k[c][1] * pc;
-    if (t) g += k[c][2] + k[c][3] * pc + k[c][4] * dce + k[c][5] * dfo;
+    float g = fmaf(k[c][1], pc, k[c][0]);
+    if (t) g += fmaf(k[c][5], dfo, fmaf(k[c][4], dce, fmaf(k[c][3], pc, k[c][2])));
     if (c == 0 && (fl & FL_E0B) && !t) {
       // g'(p) of g = p log max(1-p, 1e-6)
       const float q = 1.f - pc;
-      g += k[0][6] * (logf(fmaxf(q, 1e-6f)) - (q > 1e-6f ? pc / q : 0.f));
+      g = fmaf(k[0][6], logf(fmaxf(q, 1e-6f)) - (q > 1e-6f ? pc / q : 0.f), g);
     }
-    g += k[c][7] * md;
+    g = fmaf(k[c][7], md, g);
     o[c] = gs * g;
   }
 }
@@ -446,46 +348,14 @@ __device__ __forceinline__ void lx_load_coef(const float* __restrict__ coef, int
   }
 }
 
-// four voxels per thread (S % 4 == 0): 16-byte loads and stores
-template <int C>
-__global__ void __launch_bounds__(256) lx_bwd_v4_kernel(const float* __restrict__ p, const uint8_t* __restrict__ label, const float* __restrict__ coef,
-                                                        const float* __restrict__ gscale, float* __restrict__ dp, long long S, unsigned fl, float gam) {
-  const int b = blockIdx.y;
-  const float gs = gscale[0];
-  float k[C][LX_NK];
-  lx_load_coef<C>(coef, b, k);
-  for (long long s = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; s < S; s += (long long)gridDim.x * 1024) {
-    const long long i = (long long)b * S + s;
-    const uint32_t labs = *reinterpret_cast<const uint32_t*>(label + i);
-    float f[4 * C], o[4 * C];
-#pragma unroll
-    for (int q = 0; q < C; ++q) {
-      const float4 t = *reinterpret_cast<const float4*>(p + i * C + 4 * q);
-      f[4 * q] = t.x; f[4 * q + 1] = t.y; f[4 * q + 2] = t.z; f[4 * q + 3] = t.w;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) lx_grad<C>((int)((labs >> (8 * j)) & 255u), f + j * C, k, o + j * C, fl, gam, gs);
-#pragma unroll
-    for (int q = 0; q < C; ++q) *reinterpret_cast<float4*>(dp + i * C + 4 * q) = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-  }
-}
-
-template <int C>
+// V4 (S % 4 == 0): four voxels per thread, 16-byte loads and stores (loss_stream.h)
+template <int C, bool V4>
 __global__ void __launch_bounds__(256) lx_bwd_kernel(const float* __restrict__ p, const uint8_t* __restrict__ label, const float* __restrict__ coef,
                                                      const float* __restrict__ gscale, float* __restrict__ dp, long long S, unsigned fl, float gam) {
-  const int b = blockIdx.y;
   const float gs = gscale[0];
   float k[C][LX_NK];
-  lx_load_coef<C>(coef, b, k);
-  for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < S; s += (long long)gridDim.x * 256) {
-    const long long i = (long long)b * S + s;
-    float f[C], o[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) f[c] = p[i * C + c];
-    lx_grad<C>(label[i], f, k, o, fl, gam, gs);
-#pragma unroll
-    for (int c = 0; c < C; ++c) dp[i * C + c] = o[c];
-  }
+  lx_load_coef<C>(coef, blockIdx.y, k);
+  ls_walk_grid<C, V4>(p, label, dp, S, [&](int lab, const float* f, float* o) { lx_grad<C>(lab, f, k, o, fl, gam, gs); });
 }
 
 // 0 = usable; LTU_E_SHAPE / LTU_E_ARG otherwise.  Flags: the sums and derivative terms the nonzero weights need.
@@ -521,15 +391,15 @@ extern "C" int ltu_loss_ext_fwd(const float* p, const uint8_t* label, float* sum
   LossExtCfg c;
   for (int k = 0; k < LTU_LOSS_EXT_NCFG; ++k) c.v[k] = cfg[k];
   const float gam = c.v[LTU_LOSS_EXT_GAMMA];
-  const bool v4 = S % 4 == 0 && !ltu_knob("LTU_LOSS_SCALAR", 0);
+  const bool v4 = loss_v4(S, C);
   const dim3 grid(nblk, B);
   hipStream_t st = (hipStream_t)s;
-  if (v4 && C == 2) hipLaunchKernelGGL(lx_sums_v4_kernel<2>, grid, dim3(256), 0, st, p, label, sums, S, (int)rows, fl, gam);
-  else if (v4 && C == 3) hipLaunchKernelGGL(lx_sums_v4_kernel<3>, grid, dim3(256), 0, st, p, label, sums, S, (int)rows, fl, gam);
-  else if (v4) hipLaunchKernelGGL(lx_sums_v4_kernel<4>, grid, dim3(256), 0, st, p, label, sums, S, (int)rows, fl, gam);
-  else if (C == 2) hipLaunchKernelGGL(lx_sums_kernel<2>, grid, dim3(256), 0, st, p, label, sums, S, (int)rows, fl, gam);
-  else if (C == 3) hipLaunchKernelGGL(lx_sums_kernel<3>, grid, dim3(256), 0, st, p, label, sums, S, (int)rows, fl, gam);
-  else hipLaunchKernelGGL(lx_sums_kernel<4>, grid, dim3(256), 0, st, p, label, sums, S, (int)rows, fl, gam);
+  LTU_DISPATCH_C(C, {
+    if constexpr (CT >= 2 && CT <= LX_MAXC) {          // lx_check: no other class count gets here, none is instantiated
+      if (v4) hipLaunchKernelGGL((lx_sums_kernel<CT, true>), grid, dim3(256), 0, st, p, label, sums, S, (int)rows, fl, gam);
+      else hipLaunchKernelGGL((lx_sums_kernel<CT, false>), grid, dim3(256), 0, st, p, label, sums, S, (int)rows, fl, gam);
+    }
+  });
   hipLaunchKernelGGL(lx_finalize_kernel, dim3(1), dim3(LX_FIN), 0, st, sums, nblk, values, coef, B, S, C, c, scale_dev);
   return ltu_check_launch();
 }
@@ -541,21 +411,13 @@ extern "C" int ltu_loss_ext_bwd(const float* p, const uint8_t* label, const floa
   if (rc != LTU_OK) return rc;
   const float gam = cfg[LTU_LOSS_EXT_GAMMA];
   hipStream_t st = (hipStream_t)s;
-  const long long cap = 4096 / B > 1 ? 4096 / B : 1;
-  if (S % 4 == 0 && !ltu_knob("LTU_LOSS_SCALAR", 0)) {
-    long long bx = (S / 4 + 255) / 256;
-    if (bx > cap) bx = cap;
-    const dim3 grid((unsigned)bx, B);
-    if (C == 2) hipLaunchKernelGGL(lx_bwd_v4_kernel<2>, grid, dim3(256), 0, st, p, label, coef, gscale, dp, S, fl, gam);
-    else if (C == 3) hipLaunchKernelGGL(lx_bwd_v4_kernel<3>, grid, dim3(256), 0, st, p, label, coef, gscale, dp, S, fl, gam);
-    else hipLaunchKernelGGL(lx_bwd_v4_kernel<4>, grid, dim3(256), 0, st, p, label, coef, gscale, dp, S, fl, gam);
-    return ltu_check_launch();
-  }
-  long long bx = (S + 255) / 256;
-  if (bx > cap) bx = cap;
-  const dim3 grid((unsigned)bx, B);
-  if (C == 2) hipLaunchKernelGGL(lx_bwd_kernel<2>, grid, dim3(256), 0, st, p, label, coef, gscale, dp, S, fl, gam);
-  else if (C == 3) hipLaunchKernelGGL(lx_bwd_kernel<3>, grid, dim3(256), 0, st, p, label, coef, gscale, dp, S, fl, gam);
-  else hipLaunchKernelGGL(lx_bwd_kernel<4>, grid, dim3(256), 0, st, p, label, coef, gscale, dp, S, fl, gam);
+  const bool v4 = loss_v4(S, C);
+  const dim3 grid = loss_bwd_grid(B, S, v4);
+  LTU_DISPATCH_C(C, {
+    if constexpr (CT >= 2 && CT <= LX_MAXC) {
+      if (v4) hipLaunchKernelGGL((lx_bwd_kernel<CT, true>), grid, dim3(256), 0, st, p, label, coef, gscale, dp, S, fl, gam);
+      else hipLaunchKernelGGL((lx_bwd_kernel<CT, false>), grid, dim3(256), 0, st, p, label, coef, gscale, dp, S, fl, gam);
+    }
+  });
   return ltu_check_launch();
 }

@@ -206,9 +206,9 @@ def _loss_reference(p, lab, w, scale):
     return total.item(), [ce.item(), bal.item()] + [d.item() for d in dice] + [fg.item()], pr.grad
 
 
-def _check_level_loss(ops, C, S, wide):
+def _check_level_loss(ops, C, S, wide, B=2):
     """either layout of the level loss against float64, with and without the device-resident scale; two calls bit-identical"""
-    p, lab, w = _loss_inputs(C, S, 300 + C + S)
+    p, lab, w = _loss_inputs(C, S, 300 + C + S, B)
     for scale in (None, 0.37):
         total_ref, vals_ref, dp_ref = _loss_reference(p, lab, w, 1.0 if scale is None else scale)
         sc = None if scale is None else torch.tensor([scale], device=DEV)
