@@ -517,14 +517,6 @@ int ltu_window_blend(const float* seg, float* votes, float* wsum, const float* g
 int ltu_seg_metrics(const float* pred, const uint8_t* target, float* rows, float* values, int B, int C, int ci, int H, long long WD,
                     float threshold, ltu_stream_t s);
 
-/* post-processing of inference_multi_classes.py:104,148-151 = monai KeepLargestConnectedComponent(applied_labels = all foreground
- * channels, independent=False, connectivity=3): pred f32 [C][H][W][D] (rounded one-hot) is modified in place.  Scratch:
- * labels int32 [S], counts int32 [S+1] (zero), best u64 [1] (zero), changed int32 [1];  step 0 = initialise, step 1 = one label
- * propagation sweep (sets *changed), repeat until it stays 0, step 2 = keep the largest 26-connected component of the foreground
- * union, clear the rest, channel 0 = 1 - sum of the other channels. */
-int ltu_keep_largest_component(float* pred, int* labels, int* counts, unsigned long long* best, int* changed, int C, int H, int W,
-                               int D, int step, ltu_stream_t s);
-
 /* surface-distance metrics of the evaluation (no reference counterpart; csrc/surface.hip): per (sample b, class k) with
  * A = pred[b][k] >= threshold and B = target[b] == k, the boundary dX = voxels of X with a face neighbour outside X (beyond the
  * volume counts as outside), d(x, dY) = min over y in dY of sqrt(sum_i ((x_i - y_i) s_i)^2), DA = d(dA, dB), DB = d(dB, dA):
@@ -583,6 +575,14 @@ int ltu_class_metrics_finalize(const double* scratch, long long scratch_elems, f
  *   remove_small: pred f32 [B][C][H][W][D] (2 <= C <= 31, rounded values) in place: for each class k with bit k of `classes` set
  *            (bit 0 must be clear), every component of pred[b][k] > 0 with fewer than min_voxels voxels is cleared in channel k;
  *            then channel 0 = 1 - the sum of the others.  scratch: ltu_remove_small_ws_elems(B, H, W, D) int32.
+ *   keep_largest: the post-processing of inference_multi_classes.py:104,148-151 = monai KeepLargestConnectedComponent(
+ *            applied_labels = all foreground channels, independent=False, connectivity=3) for connectivity 3: pred f32
+ *            [B][C][H][W][D] (2 <= C <= 31, rounded values) in place: the foreground union (the fp32 sum of channels 1 .. C-1 in
+ *            channel order > 0) of every sample is labelled, channels 1 .. C-1 are cleared at the foreground voxels outside its
+ *            largest component (among equally large ones the raster-first, as bincount / argmax pick it; a sample without
+ *            foreground keeps its values), then channel 0 = 1 - the sum of the others.  One call for the batch, no host read.
+ *            scratch: ltu_keep_largest_ws_elems(B, H, W, D) int32, 8-byte aligned.
+ *            Both in-place calls: B outside 1 .. 65535 or C outside 2 .. 31 is LTU_E_SHAPE; a NULL or short scratch is LTU_E_ARG.
  *   lesion:  for sample b and class k, P = pred[b][k] >= threshold (pred f32 [B][C][H][W][D]) and G = target[b] == k (target u8
  *            [B][H][W][D]) are labelled into P_1 .. P_m and G_1 .. G_n; o_j = |G_j n P|, G_j is detected iff o_j >= 1, P_i is a
  *            false positive iff P_i n G is empty, U_j = the union of the P_i touching G_j, Dice_j = 2 o_j / (|G_j| + |U_j|).
@@ -598,6 +598,9 @@ int ltu_label_components(const uint8_t* mask, int* labels, int* counts, int* scr
 long long ltu_remove_small_ws_elems(int B, int H, int W, int D);
 int ltu_remove_small_components(float* pred, int* scratch, long long scratch_elems, int B, int C, int classes, int H, int W, int D,
                                 int min_voxels, int connectivity, ltu_stream_t s);
+long long ltu_keep_largest_ws_elems(int B, int H, int W, int D);
+int ltu_keep_largest_component(float* pred, int* scratch, long long scratch_elems, int B, int C, int H, int W, int D, int connectivity,
+                               ltu_stream_t s);
 long long ltu_lesion_ws_elems(int B, int H, int W, int D, long long pairs);
 int ltu_lesion_heads(const float* pred, const uint8_t* target, int* heads, int B, int C, int k, int H, int W, int D, float threshold,
                      int connectivity, ltu_stream_t s);

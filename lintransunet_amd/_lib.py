@@ -84,7 +84,6 @@ SIGNATURES = {
     'ltu_vote_finalize': [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     'ltu_window_gather_mirror': [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     'ltu_window_blend': [P, P, P, P, P, P, F, P, I, I, I, I, I, I, I, I, I, P],
-    'ltu_keep_largest_component': [P, P, P, P, P, I, I, I, I, I, P],
     'ltu_seg_metrics': [P, P, P, P, I, I, I, I, L, F, P],
     'ltu_surface_boundary': [P, P, P, P, I, I, I, I, I, I, F, P],
     'ltu_surface_ws_elems': [I, I, I],
@@ -98,6 +97,8 @@ SIGNATURES = {
     'ltu_label_components': [P, P, P, P, L, I, I, I, I, I, P],
     'ltu_remove_small_ws_elems': [I, I, I, I],
     'ltu_remove_small_components': [P, P, L, I, I, I, I, I, I, I, I, P],
+    'ltu_keep_largest_ws_elems': [I, I, I, I],
+    'ltu_keep_largest_component': [P, P, L, I, I, I, I, I, I, P],
     'ltu_lesion_ws_elems': [I, I, I, I, L],
     'ltu_lesion_heads': [P, P, P, I, I, I, I, I, I, F, I, P],
     'ltu_lesion_stats': [P, P, P, P, P, L, L, I, I, I, I, I, I, I, I, F, I, P],

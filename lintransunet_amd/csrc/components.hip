@@ -19,6 +19,11 @@
 // Small-component removal: labelling steps 1-3, then a root-indexed histogram (equal roots aggregated along the wave before the
 // atomic: runs along D are the common case) and a clearing pass; channel 0 = 1 - the rest at the end.
 //
+// Largest component (inference_multi_classes.py:104,148-151): the same labelling and histogram on the union of the foreground
+// channels, then per sample an atomicMax of (size << 32) | (0xFFFFFFFF - root) over the roots: integer atomics, so the order does
+// not matter, and among equally large components the smaller root = the raster-first one wins, as bincount / argmax decide it.
+// A clearing pass zeroes channels 1 .. C-1 of every other component; channel 0 = 1 - the rest at the end.
+//
 // Lesion statistics per (sample, class): P and G labelled (steps 1-3) into two parent arrays; one pass histograms |P_i|, |G_j|,
 // |P_i n G|, |G_j n P| by root; one pass inserts the distinct (root P, root G) pairs into a per-sample hash set of 64-bit keys
 // (atomicCAS, linear probing) from the "heads" of P n G only (voxels of P n G without a half-neighbour in P n G: every connected
@@ -34,13 +39,15 @@
 #define CC_RB 4096                                // voxels per block of the root count / rank / partial passes
 #define CC_EMPTY 0xffffffffffffffffull
 
-// a binary source plane: kind 0 u8 != 0, 1 f32 >= thr, 2 f32 > thr, 3 u8 == cls; sample b starts at p + b * stride elements
+// a binary source plane: kind 0 u8 != 0, 1 f32 >= thr, 2 f32 > thr, 3 u8 == cls, 4 the f32 sum of channels 1 .. cls - 1 (planes
+// `plane` elements apart, added in channel order) > 0; sample b starts at p + b * stride elements
 struct cc_src {
   const void* p;
   long long stride;
   int kind;
   int cls;
   float thr;
+  long long plane;
 };
 
 __device__ __forceinline__ bool cc_fg(const cc_src& s, int b, long long i) {
@@ -49,7 +56,12 @@ __device__ __forceinline__ bool cc_fg(const cc_src& s, int b, long long i) {
     case 0: return static_cast<const uint8_t*>(s.p)[o] != 0;
     case 1: return static_cast<const float*>(s.p)[o] >= s.thr;
     case 2: return static_cast<const float*>(s.p)[o] > s.thr;
-    default: return static_cast<const uint8_t*>(s.p)[o] == (uint8_t)s.cls;
+    case 3: return static_cast<const uint8_t*>(s.p)[o] == (uint8_t)s.cls;
+    default: {
+      float fg = 0.f;
+      for (int c = 1; c < s.cls; ++c) fg += static_cast<const float*>(s.p)[o + c * s.plane];
+      return fg > 0.f;
+    }
   }
 }
 
@@ -383,6 +395,56 @@ __global__ void __launch_bounds__(256) cc_channel0_kernel(float* __restrict__ pr
   }
 }
 
+// best[b] = the largest (size << 32) | (0xFFFFFFFF - root) over the non-empty roots of sample b (zero before).  grid = (nb, B)
+__global__ void __launch_bounds__(256) cc_pick_kernel(const int* __restrict__ size, unsigned long long* __restrict__ best, long long S) {
+  const int* sb = size + (long long)blockIdx.y * S;
+  const long long base = (long long)blockIdx.x * CC_RB;
+  for (int j = 0; j < CC_RB / 256; ++j) {
+    const long long v = base + j * 256 + threadIdx.x;
+    if (v >= S) break;
+    const int n = sb[v];
+    if (n > 0) atomicMax(&best[blockIdx.y], ((unsigned long long)(unsigned)n << 32) | (0xFFFFFFFFu - (unsigned)v));
+  }
+}
+
+// channels 1 .. C-1 of sample b cleared at the fg voxels whose root is not the one in best[b].  grid = (nb, B)
+__global__ void __launch_bounds__(256) cc_keep_kernel(float* __restrict__ pred, const int* __restrict__ par,
+                                                      const unsigned long long* __restrict__ best, long long S, int C) {
+  const int b = blockIdx.y;
+  const int* pb = par + (long long)b * S;
+  float* out = pred + (long long)b * C * S;
+  const int keep = (int)(0xFFFFFFFFu - (unsigned)(best[b] & 0xFFFFFFFFull));
+  const long long base = (long long)blockIdx.x * CC_RB;
+  for (int j = 0; j < CC_RB / 256; ++j) {
+    const long long v = base + j * 256 + threadIdx.x;
+    if (v >= S) break;
+    const int p = pb[v];
+    if (p < 0 || p == keep) continue;
+    for (int c = 1; c < C; ++c) out[c * S + v] = 0.f;
+  }
+}
+
+// what the in-place entry points refuse before any launch; need = their scratch query
+static int cc_inplace_check(const float* pred, const int* scratch, long long scratch_elems, long long need, int B, int C, int H, int W,
+                            int D, int connectivity) {
+  if (!cc_shape_ok(B, H, W, D) || C < 2 || C > 31) return LTU_E_SHAPE;
+  if (connectivity < 1 || connectivity > 3 || pred == nullptr || scratch == nullptr || scratch_elems < need) return LTU_E_ARG;
+  return LTU_OK;
+}
+
+// labelling steps 1-3 of src into par = scratch [B][S], then size = scratch + B S [B][S] = voxels per root; the `zeroed` elements
+// from size on are cleared first (size itself, and what the caller keeps behind it)
+static int cc_label_sizes(const cc_src& src, int* scratch, long long zeroed, int B, int H, int W, int D, int connectivity,
+                          hipStream_t st) {
+  const long long S = (long long)H * W * D;
+  int* size = scratch + (long long)B * S;
+  cc_label_roots(src, scratch, nullptr, B, H, W, D, connectivity, st);
+  const hipError_t e = hipMemsetAsync(size, 0, (size_t)zeroed * sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(cc_size_kernel, dim3((unsigned)cc_nblocks(H, W, D), B), dim3(256), 0, st, scratch, size, S);
+  return LTU_OK;
+}
+
 extern "C" long long ltu_remove_small_ws_elems(int B, int H, int W, int D) {
   if (!cc_shape_ok(B, H, W, D)) return 0;
   return (long long)B * 2 * ((long long)H * W * D);
@@ -390,10 +452,9 @@ extern "C" long long ltu_remove_small_ws_elems(int B, int H, int W, int D) {
 
 extern "C" int ltu_remove_small_components(float* pred, int* scratch, long long scratch_elems, int B, int C, int classes, int H, int W,
                                            int D, int min_voxels, int connectivity, ltu_stream_t s) {
-  if (!cc_shape_ok(B, H, W, D) || C < 2 || C > 31) return LTU_E_SHAPE;
-  if (connectivity < 1 || connectivity > 3) return LTU_E_ARG;
-  if (pred == nullptr || (classes & 1) || (classes >> C) != 0) return LTU_E_ARG;
-  if (scratch == nullptr || scratch_elems < ltu_remove_small_ws_elems(B, H, W, D)) return LTU_E_ARG;
+  const int refused = cc_inplace_check(pred, scratch, scratch_elems, ltu_remove_small_ws_elems(B, H, W, D), B, C, H, W, D, connectivity);
+  if (refused != LTU_OK) return refused;
+  if ((classes & 1) || (classes >> C) != 0) return LTU_E_ARG;
   hipStream_t st = (hipStream_t)s;
   const long long S = (long long)H * W * D;
   const int nb = (int)cc_nblocks(H, W, D);
@@ -402,13 +463,36 @@ extern "C" int ltu_remove_small_components(float* pred, int* scratch, long long 
   for (int k = 1; k < C; ++k) {
     if (!((classes >> k) & 1)) continue;
     const cc_src src{pred + (long long)k * S, (long long)C * S, 2, 0, 0.f};      // rounded values: fg = value > 0
-    cc_label_roots(src, par, nullptr, B, H, W, D, connectivity, st);
-    const hipError_t e = hipMemsetAsync(size, 0, (size_t)B * S * sizeof(int), st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cc_size_kernel, dim3(nb, B), dim3(256), 0, st, par, size, S);
+    const int e = cc_label_sizes(src, scratch, (long long)B * S, B, H, W, D, connectivity, st);
+    if (e != LTU_OK) return e;
     hipLaunchKernelGGL(cc_clear_kernel, dim3(nb, B), dim3(256), 0, st, pred, par, size, S, C, k, min_voxels);
   }
   hipLaunchKernelGGL(cc_channel0_kernel, dim3(nb, B), dim3(256), 0, st, pred, S, C);
+  return ltu_check_launch();
+}
+
+// ---- largest component ---------------------------------------------------------------------------------------------------
+// scratch in int32 elements: par [B][S], size [B][S], then the u64 keys best [B] (at 2 B S, an even offset)
+extern "C" long long ltu_keep_largest_ws_elems(int B, int H, int W, int D) {
+  if (!cc_shape_ok(B, H, W, D)) return 0;
+  return (long long)B * 2 * ((long long)H * W * D + 1);
+}
+
+extern "C" int ltu_keep_largest_component(float* pred, int* scratch, long long scratch_elems, int B, int C, int H, int W, int D,
+                                          int connectivity, ltu_stream_t s) {
+  const int refused = cc_inplace_check(pred, scratch, scratch_elems, ltu_keep_largest_ws_elems(B, H, W, D), B, C, H, W, D, connectivity);
+  if (refused != LTU_OK) return refused;
+  hipStream_t st = (hipStream_t)s;
+  const long long S = (long long)H * W * D;
+  const dim3 g((unsigned)cc_nblocks(H, W, D), B);
+  int* size = scratch + (long long)B * S;
+  unsigned long long* best = reinterpret_cast<unsigned long long*>(size + (long long)B * S);
+  const cc_src src{pred, (long long)C * S, 4, C, 0.f, S};                       // rounded values: fg = their sum over 1 .. C-1 > 0
+  const int e = cc_label_sizes(src, scratch, (long long)B * (S + 2), B, H, W, D, connectivity, st);
+  if (e != LTU_OK) return e;
+  hipLaunchKernelGGL(cc_pick_kernel, g, dim3(256), 0, st, size, best, S);
+  hipLaunchKernelGGL(cc_keep_kernel, g, dim3(256), 0, st, pred, scratch, best, S, C);
+  hipLaunchKernelGGL(cc_channel0_kernel, g, dim3(256), 0, st, pred, S, C);
   return ltu_check_launch();
 }
 

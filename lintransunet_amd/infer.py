@@ -227,30 +227,21 @@ def evaluate(predict, masks, threshold=0.5, class_index=1):
     return {name: values[i] for i, name in enumerate(METRIC_NAMES)}
 
 
-def keep_largest_component(predict, sweeps_per_check=8):
-    """inference_multi_classes.py:146-151 on predict [B, C, H, W, D] (the blended votes): round, keep the largest 26-connected
-    component of the foreground union (monai KeepLargestConnectedComponent(applied_labels=[1, 2], independent=False,
-    connectivity=3)), channel 0 = 1 - the rest.  Returns a new tensor."""
+def keep_largest_component(predict, connectivity=3):
+    """inference_multi_classes.py:146-151 on predict [B, C, H, W, D] (the blended votes): round, keep the largest component of
+    the foreground union (monai KeepLargestConnectedComponent(applied_labels=[1, 2], independent=False, connectivity=3); see
+    label_components for the connectivity; of equally large components the raster-first), channel 0 = 1 - the rest
+    (csrc/components.hip).  Returns a new tensor; one call for the batch, no host synchronisation."""
     if not predict.is_cuda:
         raise _lib.LtuError('keep_largest_component runs on the GPU only (no CPU fallback)')
-    B, C, H, W, D = predict.shape
-    S = H * W * D
+    conn = _connectivity(connectivity)
+    B, C, H, W, D = (int(v) for v in predict.shape)
     out = torch.round(predict.to(torch.float32)).contiguous()
-    dev = out.device
-    labels = torch.empty(S, device=dev, dtype=torch.int32)
-    for b in range(B):
-        counts = torch.zeros(S + 1, device=dev, dtype=torch.int32)
-        best = torch.zeros(1, device=dev, dtype=torch.int64)
-        changed = torch.zeros(1, device=dev, dtype=torch.int32)
-        args = (_p(out[b]), _p(labels), _p(counts), _p(best), _p(changed), C, H, W, D)
-        _lib.call('ltu_keep_largest_component', *args, 0, _s())
-        while True:
-            changed.zero_()
-            for _ in range(sweeps_per_check):
-                _lib.call('ltu_keep_largest_component', *args, 1, _s())
-            if changed.item() == 0:          # host check: an evaluation-time post-processing step, not on the training path
-                break
-        _lib.call('ltu_keep_largest_component', *args, 2, _s())
+    ws = _lib.load().ltu_keep_largest_ws_elems(B, H, W, D)
+    if ws <= 0:
+        raise _lib.LtuError(f'keep_largest_component: shape {tuple(predict.shape)} refused (H * W * D must be < 2^31)')
+    scratch = torch.empty(ws, device=out.device, dtype=torch.int32)
+    _lib.call('ltu_keep_largest_component', _p(out), _p(scratch), ws, B, C, H, W, D, conn, _s())
     return out
 
 
@@ -272,8 +263,8 @@ def surface_metrics(predict, masks, class_indices=(1,), spacing=(1.0, 1.0, 1.0),
     Both boundaries empty: HD = HD95 = ASSD = 0, NSD = 1; exactly one empty: HD = HD95 = ASSD = +inf, NSD = 0.
 
     Returns {name: f32 device tensor [B, len(class_indices)]} for SURFACE_METRIC_NAMES.  The exact Euclidean distance transform
-    runs over the bounding box of the two boundaries only; the boxes are read to the host once per call (launch geometry),
-    as keep_largest_component reads its convergence flag.  No CPU fallback."""
+    runs over the bounding box of the two boundaries only; the boxes are read to the host once per call (launch geometry).
+    No CPU fallback."""
     if not predict.is_cuda:
         raise _lib.LtuError('surface_metrics runs on the GPU only (no CPU fallback)')
     if predict.dim() != 5 or masks.dim() != 5 or masks.shape[1] != 1 or masks.shape[0] != predict.shape[0] \

@@ -1,7 +1,9 @@
 """Connected-component labelling, small-component removal and lesion-wise detection metrics of infer.label_components /
 infer.remove_small_components / infer.lesion_metrics (csrc/components.hip).  No reference counterpart: scipy.ndimage.label is the
 labelling oracle, and a numpy/scipy restatement of the definitions in the docstrings (checked on hand-built volumes whose answers
-are written here) is the oracle of the removal and of the lesion metrics."""
+are written here) is the oracle of the removal and of the lesion metrics.  infer.keep_largest_component runs on the same labeller:
+oracle.infer.keep_largest_component is its oracle, on volumes built around the labeller's 8 x 16 x 32 tile."""
+import functools
 import os
 import sys
 
@@ -13,11 +15,14 @@ from scipy import ndimage
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from lintransunet_amd.infer import LESION_METRIC_NAMES, label_components, lesion_metrics, remove_small_components  # noqa: E402
+from lintransunet_amd.infer import (LESION_METRIC_NAMES, keep_largest_component, label_components, lesion_metrics,  # noqa: E402
+                                    remove_small_components)
+from oracle import infer as O  # noqa: E402
 
 DEV = 'cuda'
 ENTRY_POINTS = ('ltu_label_ws_elems', 'ltu_label_components', 'ltu_remove_small_ws_elems', 'ltu_remove_small_components',
-                'ltu_lesion_ws_elems', 'ltu_lesion_heads', 'ltu_lesion_stats')
+                'ltu_keep_largest_ws_elems', 'ltu_keep_largest_component', 'ltu_lesion_ws_elems', 'ltu_lesion_heads',
+                'ltu_lesion_stats')
 INT_NAMES, RATE_NAMES = LESION_METRIC_NAMES[:5], LESION_METRIC_NAMES[5:]
 
 
@@ -108,6 +113,19 @@ def test_entry_points_declared_and_contract_errors():
     assert lib.ltu_remove_small_components(*rm[:10], 4, None) == -4
     assert lib.ltu_remove_small_components(*rm[:5], 0b111, *rm[6:]) == -4        # channel 0 is not a class to clean
     assert lib.ltu_remove_small_components(*rm[:3], 1, 3, 0b110, 2048, 1024, 1024, 5, 3, None) == -2
+    assert lib.ltu_keep_largest_ws_elems(1, 2048, 1024, 1024) == 0
+    need = lib.ltu_keep_largest_ws_elems(3, 5, 7, 9)                             # par + size + an aligned 64-bit key per sample
+    assert need >= 2 * 3 * 315 + 2 * 3
+    kl = (fake, fake, need, 3, 3, 5, 7, 9, 3, None)
+    assert lib.ltu_keep_largest_component(fake, fake, need - 1, *kl[3:]) == -4
+    assert lib.ltu_keep_largest_component(fake, None, *kl[2:]) == -4
+    assert lib.ltu_keep_largest_component(None, *kl[1:]) == -4
+    assert lib.ltu_keep_largest_component(*kl[:8], 0, None) == -4
+    assert lib.ltu_keep_largest_component(*kl[:8], 4, None) == -4
+    assert lib.ltu_keep_largest_component(*kl[:4], 1, *kl[5:]) == -2             # C = 1: no foreground channel
+    assert lib.ltu_keep_largest_component(*kl[:4], 32, *kl[5:]) == -2
+    assert lib.ltu_keep_largest_component(*kl[:3], 0, *kl[4:]) == -2
+    assert lib.ltu_keep_largest_component(*kl[:3], 1, 3, 2048, 1024, 1024, 3, None) == -2
     need = lib.ltu_lesion_ws_elems(2, 8, 8, 8, 10)
     st = [fake, fake, fake, fake, fake, need, 10, 2, 3, 1, 0, 2, 8, 8, 8, 0.5, 3, None]
     assert lib.ltu_lesion_stats(*st[:5], need - 1, *st[6:]) == -4
@@ -207,6 +225,146 @@ def test_restatement_remove_small():
     want[0, 0, 0, 0] = want[0, 2, 4, 4] = want[0, 3, 5, 5] = 0
     np.testing.assert_array_equal(out, _onehot(want))
     np.testing.assert_array_equal(restate_remove(pred * 0.8, 1), np.round(pred * 0.8))   # min_voxels <= 1: rounded input
+
+
+# ---------------------------------------------------------------------------------------------- largest component: the cases
+def restate_keep(pred, conn=3):
+    """oracle.infer.keep_largest_component with generate_binary_structure(3, conn) in place of the full 3x3x3 structure"""
+    out = np.round(np.asarray(pred, np.float32))
+    for b in range(out.shape[0]):
+        fg = out[b, 1:].sum(0) > 0
+        lab, n = ndimage.label(fg, _structure(conn))
+        if n > 0:
+            keep = np.argmax(np.bincount(lab.ravel())[1:]) + 1
+            out[b, 1:][:, fg & (lab != keep)] = 0
+        out[b, 0] = 1 - out[b, 1:].sum(0)
+    return out
+
+
+def _corner_labels():
+    """9 x 17 x 33, one voxel past the 8 x 16 x 32 tile on every axis: a class-1 and a class-2 voxel that meet only diagonally across
+    the tile corner, a class-1 pair at the origin, a lone class-1 voxel"""
+    lab = np.zeros((1, 9, 17, 33), np.int64)
+    lab[0, 7, 15, 31], lab[0, 8, 16, 32] = 1, 2
+    lab[0, 0, 0, 0:2] = 1
+    lab[0, 4, 8, 16] = 1
+    return lab
+
+
+def _face_labels(axis):
+    """12 x 20 x 36: a class-2 line of 6 inside the first tile against a class-1 bar of 8 that crosses the tile face of `axis`
+    (h = 7|8, w = 15|16 or d = 31|32) with 4 voxels on each side: no tile-local piece of the bar beats the line, the whole bar does"""
+    lab = np.zeros((1, 12, 20, 36), np.int64)
+    lab[0, 0, 0, 0:6] = 2
+    idx = [2, 10, 20]
+    idx[axis] = slice((8, 16, 32)[axis] - 4, (8, 16, 32)[axis] + 4)
+    lab[(0,) + tuple(idx)] = 1
+    return lab
+
+
+def _fold_labels(shape=(16, 16, 40), rows_w=(7, 9, 11, 13, 15), short=3):
+    """a class-1 boustrophedon path (rows along D on even h and the given w, joined at alternating ends, layers joined at the turn:
+    its raster order and its order along the path disagree everywhere) beside a compact class-2 block in w < rows_w[0] - 1 that
+    comes first in raster order and is `short` voxels smaller.  Returns (labels [1, H, W, D], path voxels)."""
+    H, W, D = shape
+    path = np.zeros(shape, bool)
+    rows = [(h, w) for i, h in enumerate(range(0, H, 2)) for w in (rows_w if i % 2 == 0 else rows_w[::-1])]
+    for i, (h, w) in enumerate(rows):
+        path[h, w, :] = True
+        if i + 1 < len(rows):
+            h2, w2 = rows[i + 1]
+            end = D - 1 if i % 2 == 0 else 0
+            if h2 == h:
+                path[h, min(w, w2) + 1, end] = True
+            else:
+                path[h + 1, w, end] = True
+    n = int(path.sum())
+    wb = rows_w[0] - 1
+    block = np.zeros(H * wb * D, bool)
+    block[:n - short] = True
+    lab = np.zeros((1,) + shape, np.int64)
+    lab[0][path] = 1
+    lab[0, :, :wb][block.reshape(H, wb, D)] = 2
+    return lab, n
+
+
+def _batch_labels():
+    """B = 3 over 10 x 18 x 34: sample 0 a block of 8 then a block of 27 (the later one wins), sample 1 without foreground,
+    sample 2 all foreground in stripes of both classes"""
+    lab = np.zeros((3, 10, 18, 34), np.int64)
+    lab[0, 0:2, 0:2, 0:2] = 1
+    lab[0, 6:9, 14:17, 30:33] = 2
+    lab[2] = 1 + (np.arange(34) // 3) % 2
+    return lab
+
+
+@functools.lru_cache(maxsize=None)
+def _keep_cases():
+    """{name: (predict tensor [B, C, H, W, D] on the CPU, connectivity, expected f32 tensor)}: expected from
+    oracle.infer.keep_largest_component (connectivity 3) or restate_keep; built once, never modified"""
+    rng = np.random.default_rng(31)
+    cases = {}
+
+    def add(name, pred, conn=3):
+        pred = pred if torch.is_tensor(pred) else torch.from_numpy(np.ascontiguousarray(pred, np.float32))
+        want = O.keep_largest_component(pred) if conn == 3 else torch.from_numpy(restate_keep(pred.float().numpy(), conn))
+        cases[name] = (pred, conn, want)
+
+    corner = _onehot(_corner_labels())
+    add('corner', corner)
+    add('corner_c1', corner, 1)
+    add('corner_c2', corner, 2)
+    for ax in range(3):
+        add(f'face_{ax}', _onehot(_face_labels(ax)))
+    add('fold', _onehot(_fold_labels()[0]))
+    add('batch', _onehot(_batch_labels()))
+    noise = rng.random((2, 20, 33, 35)) < P_C[3]                                  # many components, ties among the largest likely
+    add('noise_c2ch', _onehot(noise.astype(np.int64), 2))
+    add('noise_c1', _onehot(noise * rng.integers(1, 4, noise.shape), 4), 1)
+    line = np.zeros((1, 1, 1, 40), np.int64)
+    line[0, 0, 0, 3:9], line[0, 0, 0, 20:33] = 1, 1
+    add('axes_1x1xd', _onehot(line, 2))
+    add('axes_hx1x1', _onehot(np.array([1, 1, 0, 1, 1, 1, 0, 0, 1]).reshape(1, 9, 1, 1), 2))
+    votes = 0.9 * _onehot(noise * rng.integers(1, 3, noise.shape)) + 0.04
+    add('votes', votes)
+    add('votes_bf16', torch.from_numpy(votes).to(torch.bfloat16))
+    wide = torch.from_numpy(np.repeat(votes, 2, axis=4))
+    add('strided', wide[..., ::2])                                                # a non-contiguous view
+    return cases
+
+
+def _fg(t):
+    return t[:, 1:].sum(1) > 0
+
+
+def test_keep_largest_cases_make_the_oracle_do_what_they_claim():
+    """which component survives in each constructed input, by the oracle alone"""
+    cases = _keep_cases()
+    for name, (pred, conn, want) in cases.items():
+        assert want.dtype == torch.float32 and want.shape == pred.shape, name
+        if conn == 3:                                                            # the restatement is the oracle at connectivity 3
+            assert torch.equal(torch.from_numpy(restate_keep(pred.float().numpy(), 3)), want), name
+    origin = torch.zeros((1, 9, 17, 33), dtype=torch.bool)
+    origin[0, 0, 0, 0:2] = True
+    lab = _corner_labels()
+    for name in ('corner', 'corner_c1', 'corner_c2'):                           # a 2 : 2 tie (c = 3) or 2 : 1 : 1: the origin pair stays
+        assert torch.equal(_fg(cases[name][2]), origin), name
+    assert ndimage.label(lab[0] > 0, _structure(3))[1] == 3 and ndimage.label(lab[0] > 0, _structure(1))[1] == 4
+    for ax in range(3):                                                          # the bar of 8 beats the line of 6
+        assert torch.equal(_fg(cases[f'face_{ax}'][2]), torch.from_numpy(_face_labels(ax) == 1)), ax
+    lab, n = _fold_labels()
+    assert n >= 1000 and ndimage.label(lab[0] == 1, _structure(1))[1] == 1 and int((lab == 2).sum()) == n - 3
+    assert ndimage.label(lab[0] > 0, _structure(3))[1] == 2 and np.flatnonzero(lab)[0] == np.flatnonzero(lab == 2)[0]
+    assert torch.equal(_fg(cases['fold'][2]), torch.from_numpy(lab == 1))       # the path wins, though the block comes first
+    pred, _, want = cases['batch']
+    assert int(_fg(want)[0].sum()) == 27 and bool(_fg(want)[0, 7, 15, 31])
+    assert torch.equal(want[1], pred[1]) and bool((want[1, 0] == 1).all()) and torch.equal(want[2], pred[2])
+    assert torch.equal(cases['votes'][2], cases['strided'][2]) and not cases['strided'][0].is_contiguous()
+    assert cases['votes_bf16'][0].dtype == torch.bfloat16
+    for name in ('noise_c2ch', 'noise_c1', 'votes'):                            # something is cleared and something is kept
+        pred, _, want = cases[name]
+        kept, had = _fg(want).sum((1, 2, 3)), _fg(torch.round(pred.float())).sum((1, 2, 3))
+        assert bool((kept > 0).all()) and bool((kept < had).all()), name
 
 
 # ---------------------------------------------------------------------------------------------- GPU tests
@@ -426,3 +584,29 @@ def test_chain_sliding_window_remove_small_lesion_metrics():
     ref = restate_lesion(ref_post, masks.numpy(), (1, 2))
     assert ref['NumTrue'].sum() > 2 and ref['NumPred'].sum() > 2
     _check_lesion(got, ref)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', ('corner', 'corner_c1', 'corner_c2', 'face_0', 'face_1', 'face_2', 'fold', 'batch', 'noise_c2ch',
+                                  'noise_c1', 'axes_1x1xd', 'axes_hx1x1', 'votes', 'votes_bf16', 'strided'))
+def test_keep_largest_component_matches_oracle_around_the_tile(name):
+    pred, conn, want = _keep_cases()[name]
+    x = pred.to(DEV)
+    got = keep_largest_component(x, connectivity=conn)
+    assert got.dtype == torch.float32 and torch.equal(got.cpu(), want)
+    assert torch.equal(x.cpu(), pred)                                             # the input is not modified
+
+
+@pytest.mark.gpu
+def test_keep_largest_component_repeats_and_never_reads_the_host():
+    pred, _, want = _keep_cases()['batch']
+    x = pred.to(DEV)
+    first = keep_largest_component(x)
+    torch.cuda.synchronize()
+    mode = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode('error')
+    try:
+        again = keep_largest_component(x)                                         # a host read (.item(), .cpu()) would raise here
+    finally:
+        torch.cuda.set_sync_debug_mode(mode)
+    assert torch.equal(first, again) and torch.equal(again.cpu(), want) and torch.equal(x.cpu(), pred)

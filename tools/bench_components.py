@@ -1,8 +1,9 @@
-"""Time of infer.label_components (connectivity 3), infer.remove_small_components (2 classes) and infer.lesion_metrics (2 classes)
-on a synthetic 1x512x512xD CT-sized scan with a pancreas-sized organ (class 1), three tumour-sized lesions (class 2) and a few
-hundred noise specks; hip events around each call after warm-up, median of the repeats.  For context also times
-keep_largest_component on the same votes and scipy.ndimage.label on the host, and prints the ratio to the labelling floor (one
-read of the u8 mask plus one write of the int32 labels at 4.67 TB/s).  usage: bench_components.py [D] [repeats]"""
+"""Time of infer.label_components (connectivity 3), infer.remove_small_components (2 classes), infer.lesion_metrics (2 classes) and
+infer.keep_largest_component on a synthetic 1x512x512xD CT-sized scan with a pancreas-sized organ (class 1), three tumour-sized
+lesions (class 2) and a few hundred noise specks; hip events around each call after warm-up, median of the repeats.  For context
+also times scipy.ndimage.label on the host, and prints the ratio to the labelling floor (one read of the u8 mask plus one write of
+the int32 labels at 4.67 TB/s); with scipy the labels and the kept component are compared with the host's.
+usage: bench_components.py [D] [repeats]"""
 import os
 import statistics
 import sys
@@ -13,6 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lintransunet_amd import infer  # noqa: E402
+from oracle import infer as oracle_infer  # noqa: E402
 
 D = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -68,8 +70,9 @@ print(f'remove_small_components, 2 classes, min 10 voxels: {med:.3f} ms (min {lo
 med, lo, hi, vals = timed(lambda: infer.lesion_metrics(predict, masks, class_indices=(1, 2)))
 print(f'lesion_metrics, 2 classes: {med:.3f} ms (min {lo:.3f}, max {hi:.3f}); '
       + ', '.join(f'{k} {v[0].tolist()}' for k, v in vals.items()), flush=True)
-med, lo, hi, _ = timed(lambda: infer.keep_largest_component(predict))
-print(f'keep_largest_component (context): {med:.3f} ms (min {lo:.3f}, max {hi:.3f})', flush=True)
+med, lo, hi, kept = timed(lambda: infer.keep_largest_component(predict))
+print(f'keep_largest_component: {med:.3f} ms (min {lo:.3f}, max {hi:.3f}); '
+      f'kept {int(kept[0, 1:].sum())} of {int(predict[0, 1:].sum())} fg voxels', flush=True)
 try:
     from scipy import ndimage
     host = fg[0].cpu().numpy()
@@ -79,5 +82,7 @@ try:
     same = np.array_equal(ref, labels[0].cpu().numpy())
     print(f'scipy.ndimage.label on the host (context): {(t1 - t0) * 1e3:.1f} ms, {n} components, GPU labels identical: {same}',
           flush=True)
+    assert torch.equal(kept.cpu(), oracle_infer.keep_largest_component(predict.cpu())), 'keep_largest_component differs from the oracle'
+    print('keep_largest_component identical to oracle.infer.keep_largest_component', flush=True)
 except ImportError:
     print('scipy not installed: host timing skipped', flush=True)
