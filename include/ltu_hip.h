@@ -752,6 +752,36 @@ int ltu_crop_index_build(const uint8_t* lab, long long n_voxels, uint32_t* index
 int ltu_crop_index_select(const uint8_t* lab, long long n_voxels, const uint32_t* index, long long index_elems,
                           const uint32_t* queries, long long* out, int n, ltu_stream_t s);
 
+/* ---- intensity fingerprint: the value histogram of a stored scan (csrc/intensity.hip; nnU-Net's dataset fingerprint and
+ * CTNormalization statistics, which it takes with np.percentile on the host).  img: n_voxels contiguous voxels of dtype LTU_U8 /
+ * LTU_I16 / LTU_F32, lab: u8 of the same count or NULL, both 16-byte aligned.  A voxel is selected when lab is NULL or bit
+ * min(lab[i], 8) of mask_bits is set (the bin sets of crop_index_select).
+ *   hist:    every selected voxel gets a 16-bit key and adds 1 to hist[key], hist device uint32 [65536]; counts, device u64 [2], gets
+ *            {voxels binned, voxels rejected} ADDED; the caller zeroes both.  mode (must match dtype, else LTU_E_ARG):
+ *              LTU_HIST_U8       key = v
+ *              LTU_HIST_I16      key = v + 32768
+ *              LTU_HIST_F32_INT  an f32 holding an integer of -32768 .. 32767: key = (int)v + 32768; any other voxel is rejected
+ *              LTU_HIST_F32_HI   key = the top 16 bits of the float's ordered key: the bit pattern with all bits flipped when the
+ *                                sign is set and the sign bit set otherwise (-0.0 counts as +0.0), so keys order as the values do
+ *              LTU_HIST_F32_LO   key = the low 16 bits of the ordered key of the voxels whose top 16 bits equal `prefix`; the others
+ *                                are skipped (neither binned nor rejected)
+ *            In the three F32 modes a non-finite voxel is rejected.  Integer adds only: two calls give the same bytes; n_voxels <=
+ *            2^32 - 1, so no bin overflows.  One launch.
+ *   moments: out, device double [2] = {sum (v - centre), sum (v - centre)^2} over the selected finite voxels of an f32 scan, in fp64:
+ *            one pair per workgroup into parts (device double, parts_elems >= 2 * LTU_INTENSITY_MOMENT_PARTS), folded in index order by
+ *            a second launch.  The workgroup count depends on n_voxels alone and there are no floating-point atomics: two calls
+ *            give the same bits.
+ *   Voxels at or beyond n_voxels are neither loaded nor counted.  Nothing is allocated, set or synchronised: capturable.
+ *   Refused before any launch: n_voxels outside 1 .. 2^32 - 1 LTU_E_SHAPE; a NULL img / hist / counts / parts / out, a mode that
+ *   does not match dtype, mask_bits outside 0 .. 0x1ff, prefix outside 0 .. 0xffff, a short parts, a non-finite centre LTU_E_ARG;
+ *   img / lab not 16-byte, counts / parts / out not 8-byte, hist not 4-byte aligned LTU_E_ALIGN. */
+enum { LTU_HIST_U8 = 0, LTU_HIST_I16 = 1, LTU_HIST_F32_INT = 2, LTU_HIST_F32_HI = 3, LTU_HIST_F32_LO = 4 };
+#define LTU_INTENSITY_MOMENT_PARTS 512
+int ltu_intensity_hist(const void* img, int dtype, const uint8_t* lab, long long n_voxels, int mask_bits, int mode, int prefix,
+                       uint32_t* hist, unsigned long long* counts, ltu_stream_t s);
+int ltu_intensity_moments(const float* img, const uint8_t* lab, long long n_voxels, int mask_bits, double centre, double* parts,
+                          long long parts_elems, double* out, ltu_stream_t s);
+
 /* ---- augmentation of the NIfTI pipeline's patches (csrc/augment.hip; no reference counterpart: the monai driver crops, flips and
  * rot90s only).
  * sample_affine: patches [n][h][w][d] (f32 and / or u8, either pair NULL, not both) gathered from the scan [H][W][D] (the layout of

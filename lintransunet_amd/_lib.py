@@ -5,7 +5,7 @@ resolved, importing the ops raises immediately.
 """
 import ctypes
 import os
-from ctypes import c_float, c_int, c_longlong, c_uint64, c_void_p
+from ctypes import c_double, c_float, c_int, c_longlong, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LTU_LIB: another in-tree build of the same sources (e.g. `make EXPERIMENTS=1` output kept beside the product library for A/B runs)
@@ -33,6 +33,8 @@ SAMPLE_AFFINE_MAX = 32    # LTU_SAMPLE_AFFINE_MAX of include/ltu_hip.h
 ELASTIC_MAX_GRID, ELASTIC_MAX_DISP = 8, 64      # LTU_ELASTIC_MAX_GRID / LTU_ELASTIC_MAX_DISP of include/ltu_hip.h
 BLUR_MAX_N, BLUR_MAX_RADIUS = 16, 8      # LTU_BLUR_MAX_N / LTU_BLUR_MAX_RADIUS of include/ltu_hip.h
 U8, I16 = 2, 3            # LTU_U8 / LTU_I16 source dtypes of ltu_resample_grid (LTU_F32 = 0)
+HIST_U8, HIST_I16, HIST_F32_INT, HIST_F32_HI, HIST_F32_LO = range(5)      # LTU_HIST_* key modes of ltu_intensity_hist
+INTENSITY_MOMENT_PARTS = 512      # LTU_INTENSITY_MOMENT_PARTS of include/ltu_hip.h
 
 
 # name -> argument types (return type is always int).  Mirrors include/ltu_hip.h one to one.
@@ -110,6 +112,8 @@ SIGNATURES = {
     'ltu_crop_index_elems': [L],
     'ltu_crop_index_build': [P, L, P, L, P, P],
     'ltu_crop_index_select': [P, L, P, L, P, P, I, P],
+    'ltu_intensity_hist': [P, I, P, L, I, I, I, P, P, P],
+    'ltu_intensity_moments': [P, P, L, I, c_double, P, L, P, P],
     'ltu_sample_affine': [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
     'ltu_sample_elastic': [P, P, P, P, P, P, I, I, I, P, P, I, I, I, I, I, I, I, F, P],
     'ltu_gauss_blur3': [P, P, P, P, P, I, I, I, I, P],

@@ -456,12 +456,290 @@ def resample_argmax(probs, matrix, out_shape, src_strides=None, out_strides=None
     return ol, op
 
 
+# ---- intensity fingerprint (csrc/intensity.hip; nnU-Net's dataset fingerprint and CTNormalization, no reference counterpart: the
+# driver's window is four constants) -------------------------------------------------------------------------------------------------
+# A stored scan, optionally under its label, becomes an exact value histogram on the device; everything after that is integer
+# arithmetic on at most 65536 bins on the host.
+
+def _percentile_ranks(n, q):
+    """numpy's default ('linear') percentile on n sorted values: (lo, hi, g) with result lerp(x[lo], x[hi], g)"""
+    q = float(q)
+    if not 0.0 <= q <= 100.0:
+        raise ValueError(f'percentiles must be in 0 .. 100, got {q}')
+    h = np.float64(n - 1) * (np.float64(q) / 100.0)
+    lo = int(np.floor(h))
+    return lo, min(lo + 1, n - 1), h - np.float64(lo)
+
+
+def _lerp(a, b, g):
+    """numpy's _lerp on two float64 order statistics"""
+    a, b = np.float64(a), np.float64(b)
+    return float(b - (b - a) * (1.0 - g)) if g >= 0.5 else float(a + (b - a) * g)
+
+
+def _nan_stats(percentiles):
+    nan = float('nan')
+    return {'count': 0, 'min': nan, 'max': nan, 'mean': nan, 'std': nan, 'percentiles': [nan] * len(percentiles)}
+
+
+def _order_stats(n, stat, percentiles, slope, inter):
+    """min, max and percentiles of v * slope + inter from stat(r), the r-th smallest stored value as float64: the map is applied
+    to the order statistics in float64 (a negative slope reverses their order), the interpolation happens in scaled units"""
+    slope, inter = np.float64(slope), np.float64(inter)
+
+    def scaled(r):
+        return np.float64(stat(n - 1 - r if slope < 0 else r)) * slope + inter
+    pct = []
+    for q in percentiles:
+        lo, hi, g = _percentile_ranks(n, q)
+        pct.append(_lerp(scaled(lo), scaled(hi), g))
+    return float(scaled(0)), float(scaled(n - 1)), pct
+
+
+def histogram_stats(hist, percentiles=(0.5, 50.0, 99.5), offset=-32768, slope=1.0, inter=0.0):
+    """statistics of the values counted in an integer histogram whose bin b holds the value b + offset (pure host arithmetic):
+    {'count', 'min', 'max', 'mean', 'std' (population, ddof 0, as nnU-Net's np.std), 'percentiles'}.  The mean and the variance
+    numerator n sum c v^2 - (sum c v)^2 are exact integers, rounded once; a percentile is numpy's default ('linear') definition on
+    the exact order statistics, bit for bit np.percentile of the expanded values as float64.  slope / inter: the statistics of
+    v * slope + inter instead.  An empty histogram gives count 0 and NaN for the rest."""
+    h = np.asarray(hist).ravel()
+    bins = np.nonzero(h)[0]
+    cnts = [int(c) for c in h[bins]]
+    vals = [int(b) + int(offset) for b in bins]
+    n = sum(cnts)
+    if n == 0:
+        return _nan_stats(percentiles)
+    if min(cnts) < 0:
+        raise ValueError('a histogram holds no negative counts')
+    s1 = sum(c * v for c, v in zip(cnts, vals))
+    s2 = sum(c * v * v for c, v in zip(cnts, vals))
+    cum = np.cumsum(np.asarray(cnts, dtype=np.int64))
+    vmin, vmax, pct = _order_stats(n, lambda r: vals[int(np.searchsorted(cum, r, side='right'))], percentiles, slope, inter)
+    mean, std = s1 / n, float(np.sqrt((n * s2 - s1 * s1) / (n * n)))
+    return {'count': n, 'min': vmin, 'max': vmax, 'mean': float(np.float64(mean) * np.float64(slope) + np.float64(inter)),
+            'std': std * abs(float(slope)), 'percentiles': pct}
+
+
+def _hist_source(img, lab):
+    if not torch.is_tensor(img) or not img.is_cuda:
+        raise _lib.LtuError('the intensity histogram is taken on the GPU only (no CPU fallback)')
+    code = {torch.uint8: _lib.U8, torch.int16: _lib.I16, torch.float32: 0}.get(img.dtype)
+    if code is None or not img.is_contiguous() or img.numel() == 0:
+        raise ValueError(f'the intensity histogram takes a contiguous, non-empty uint8, int16 or float32 scan, got {img.dtype} {tuple(img.shape)}')
+    if lab is not None and (not torch.is_tensor(lab) or lab.dtype != torch.uint8 or lab.device != img.device
+                            or lab.numel() != img.numel() or not lab.is_contiguous()):
+        raise ValueError('the label is a contiguous uint8 tensor with the scan\'s voxel count, on its device')
+    return code
+
+
+def _hist_launch(img, lab, mask, code, mode, prefix=0):
+    """one ltu_intensity_hist launch into fresh buffers: (uint32 histogram as int32 words [65536], int64 {binned, rejected})"""
+    hist = torch.zeros(65536, device=img.device, dtype=torch.int32)
+    counts = torch.zeros(2, device=img.device, dtype=torch.int64)
+    _lib.call('ltu_intensity_hist', _p(img), code, _p(lab) if lab is not None else 0, img.numel(), int(mask) & 0x1ff, mode, int(prefix),
+              _p(hist), _p(counts), _s())
+    return hist, counts
+
+
+def intensity_histogram(img, lab=None, mask=FG_MASK):
+    """the exact value histogram of a device scan (uint8, int16, or float32 holding integers of the int16 range; any shape,
+    contiguous) over the voxels whose label value is in `mask` (the bin sets of CropIndex.select: FG_MASK, BG_MASK, 1 << c), all
+    voxels without a label.  Returns (int64 [65536] on the device, rejected): bin b counts the value b for a uint8 scan and b -
+    32768 otherwise; rejected = the selected float32 voxels that are not finite or no integer of the range (they are in no bin)."""
+    code = _hist_source(img, lab)
+    mode = {_lib.U8: _lib.HIST_U8, _lib.I16: _lib.HIST_I16, 0: _lib.HIST_F32_INT}[code]
+    hist, counts = _hist_launch(img, lab, mask, code, mode)
+    return hist.to(torch.int64) & 0xffffffff, int(counts[1].item())
+
+
+def _float_stats(img, lab, mask, percentiles, slope, inter):
+    """intensity_stats of a float32 scan: a histogram of the top 16 bits of the floats' ordered keys finds the bin of every wanted
+    rank, one histogram of the low 16 bits per distinct bin finds the value; the moments come from ltu_intensity_moments"""
+    hist, counts = _hist_launch(img, lab, mask, 0, _lib.HIST_F32_HI)
+    n, rejected = (int(v) for v in counts.cpu().tolist())
+    if rejected:
+        raise ValueError(f'{rejected} non-finite voxels in the scan')
+    if n == 0:
+        return _nan_stats(percentiles)
+    ranks = {0, n - 1}
+    for q in percentiles:                            # _order_stats asks for the mirrored ranks under a negative slope
+        ranks.update(n - 1 - r if slope < 0 else r for r in _percentile_ranks(n, q)[:2])
+    cum = np.cumsum(hist.cpu().numpy().view(np.uint32).astype(np.int64))
+    where = {r: int(np.searchsorted(cum, r, side='right')) for r in ranks}
+    value = {}
+    for prefix in sorted(set(where.values())):
+        low, _ = _hist_launch(img, lab, mask, 0, _lib.HIST_F32_LO, prefix)
+        cl = np.cumsum(low.cpu().numpy().view(np.uint32).astype(np.int64))
+        before = int(cum[prefix - 1]) if prefix else 0
+        for r, p in where.items():
+            if p == prefix:
+                key = (prefix << 16) | int(np.searchsorted(cl, r - before, side='right'))
+                bits = key ^ 0x80000000 if key & 0x80000000 else ~key & 0xffffffff
+                value[r] = np.float64(np.array([bits], dtype=np.uint32).view(np.float32)[0])
+    vmin, vmax, pct = _order_stats(n, value.__getitem__, percentiles, slope, inter)
+    parts = torch.empty(2 * _lib.INTENSITY_MOMENT_PARTS, device=img.device, dtype=torch.float64)
+    out = torch.empty(2, device=img.device, dtype=torch.float64)
+
+    def moments(centre):
+        _lib.call('ltu_intensity_moments', _p(img), _p(lab) if lab is not None else 0, img.numel(), int(mask) & 0x1ff, float(centre),
+                  _p(parts), parts.numel(), _p(out), _s())
+        return out.cpu().tolist()
+    mean = moments(0.0)[0] / n
+    d1, d2 = moments(mean)                           # about the mean: sum d^2 / n - (sum d / n)^2 cancels nothing
+    mean += d1 / n
+    std = float(np.sqrt(max(d2 / n - (d1 / n) ** 2, 0.0)))
+    return {'count': n, 'min': vmin, 'max': vmax, 'mean': mean * float(slope) + float(inter), 'std': std * abs(float(slope)),
+            'percentiles': pct}
+
+
+def intensity_stats(img, lab=None, mask=FG_MASK, percentiles=(0.5, 50.0, 99.5), slope=1.0, inter=0.0):
+    """histogram_stats' record for one device scan (selection as intensity_histogram), in units of v * slope + inter.  uint8 and
+    int16 go through the exact histogram.  float32 (any finite values) goes through the two-level histogram of the floats' ordered
+    bits, so min, max and the percentiles are exact too; its mean and std are fp64 sums in a fixed order.  A non-finite float32
+    voxel raises ValueError.  A load-time call: it reads 256 KiB histograms back between its passes."""
+    code = _hist_source(img, lab)
+    if code == 0:
+        return _float_stats(img, lab, mask, tuple(percentiles), slope, inter)
+    hist, _ = intensity_histogram(img, lab, mask)
+    return histogram_stats(hist.cpu().numpy(), percentiles, 0 if code == _lib.U8 else -32768, slope, inter)
+
+
+def _percentile_key(q):
+    """nnU-Net's name of a percentile in its fingerprint: 0.5 -> percentile_00_5, 99.5 -> percentile_99_5"""
+    whole, _, frac = repr(float(q)).partition('.')
+    return f'percentile_{int(whole):02d}_{frac}'
+
+
+class IntensityFingerprint:
+    """The intensity statistics of a training set's foreground, as nnU-Net's dataset fingerprint keeps them for CTNormalization:
+    an int64 histogram [65536] of the scaled values v * slope + inter (bin b counts the value b - 32768) that every scan is added
+    into by one kernel launch.  window() is the `intensity` of SpacedScan: (p_lo, p_hi, (p_lo - mean) / std, (p_hi - mean) / std)
+    for percentiles (lo, hi).  scans / empty_scans: the scans added / those among them whose selection was empty (a label without
+    foreground contributes nothing).  The histogram lives where the first scan lives; merge() adds another rank's part."""
+
+    def __init__(self, percentiles=(0.5, 99.5), device='cuda'):
+        self.percentiles = tuple(float(q) for q in percentiles)
+        if len(self.percentiles) != 2 or not 0.0 <= self.percentiles[0] <= self.percentiles[1] <= 100.0:
+            raise ValueError(f'a fingerprint keeps a (low, high) pair of percentiles, got {percentiles}')
+        self.device, self.hist, self.scans, self.empty_scans = device, None, 0, 0
+
+    def add_histogram(self, hist, offset=-32768, slope=1.0, inter=0.0, name='scan'):
+        """add a scan's histogram (integer tensor [65536] on any device, bin b = the stored value b + offset) under the scan's
+        slope / intercept: the bins are re-indexed onto the scaled values.  ValueError, naming the scan, unless slope is an
+        integer >= 1, inter an integer and every scaled value an int16."""
+        if float(slope) != int(slope) or int(slope) < 1 or float(inter) != int(inter):
+            raise ValueError(f'{name}: the fingerprint counts integer values, slope {slope} / intercept {inter} do not keep them integral '
+                             "(normalise such scans with intensity='zscore')")
+        h = torch.as_tensor(hist).to(torch.int64).reshape(-1)
+        if h.numel() != 65536:
+            raise ValueError(f'{name}: a histogram has 65536 bins, got {h.numel()}')
+        self.scans += 1
+        live = torch.nonzero(h).reshape(-1)
+        if live.numel() == 0:
+            self.empty_scans += 1
+            return
+        to = (live + int(offset)) * int(slope) + int(inter)
+        lo, hi = int(to[0].item()), int(to[-1].item())
+        if lo < -32768 or hi > 32767:
+            self.scans -= 1
+            raise ValueError(f'{name}: scaled values {lo} .. {hi} do not fit int16')
+        if self.hist is None:
+            self.hist = torch.zeros(65536, device=h.device, dtype=torch.int64)
+        self.hist.index_add_(0, (to + 32768).to(self.hist.device), h[live].to(self.hist.device))
+
+    def add_arrays(self, img, lab=None, slope=1.0, inter=0.0, mask=FG_MASK, name='scan'):
+        """add a device scan as stored (uint8, int16, or float32 holding integers) under its device label: one histogram launch"""
+        hist, rejected = intensity_histogram(img, lab, mask)
+        if rejected:
+            raise ValueError(f"{name}: {rejected} selected voxels are not integers of the int16 range; a fingerprint needs integral "
+                             "values (normalise such scans with intensity='zscore')")
+        self.add_histogram(hist, 0 if img.dtype == torch.uint8 else -32768, slope, inter, name)
+
+    def add(self, img_path, lab_path=None, mask=FG_MASK):
+        """add one NIfTI scan under its label file (all voxels without one): loaded, uploaded as stored, one histogram launch"""
+        ni = nifti.load(img_path)
+        rl = None
+        if lab_path is not None:
+            nl = nifti.load(lab_path)
+            geometry.check_pair(ni.shape, ni.affine, nl.shape, nl.affine)
+            lv = nl.data if (nl.slope, nl.inter) == (1.0, 0.0) else nl.scaled()
+            rl = torch.as_tensor(np.ascontiguousarray(label_u8(lv))).to(self.device)
+        raw, _ = _source_dtype(ni.data)
+        self.add_arrays(torch.as_tensor(np.ascontiguousarray(raw)).to(self.device), rl, ni.slope, ni.inter, mask, str(img_path))
+
+    def merge(self, other):
+        """add the scans another fingerprint saw (another rank's, or one restored by from_dict)"""
+        if other.hist is not None:
+            if self.hist is None:
+                self.hist = torch.zeros_like(other.hist)
+            self.hist += other.hist.to(self.hist.device)
+        self.scans += other.scans
+        self.empty_scans += other.empty_scans
+        return self
+
+    def _host_hist(self):
+        return np.zeros(65536, dtype=np.int64) if self.hist is None else self.hist.cpu().numpy()
+
+    def stats(self, percentiles=None):
+        """histogram_stats of everything added, at the fingerprint's percentiles (or the given ones)"""
+        return histogram_stats(self._host_hist(), self.percentiles if percentiles is None else percentiles)
+
+    def window(self):
+        """(p_lo, p_hi, (p_lo - mean) / std, (p_hi - mean) / std), std floored at 1e-8 as nnU-Net's CTNormalization does"""
+        st = self.stats()
+        if st['count'] == 0:
+            raise ValueError('window() of an empty fingerprint: no scan with a selected voxel was added')
+        (lo, hi), sd = st['percentiles'], max(st['std'], 1e-8)
+        return lo, hi, (lo - st['mean']) / sd, (hi - st['mean']) / sd
+
+    def to_dict(self):
+        """JSON-able: nnU-Net's foreground_intensity_properties keys (max, mean, median, min, percentile_00_5, percentile_99_5,
+        std; absent while empty), plus the non-empty bins [[value, count], ...] so that a saved fingerprint can still be merged"""
+        h = self._host_hist()
+        d = {'percentiles': list(self.percentiles), 'scans': self.scans, 'empty_scans': self.empty_scans,
+             'bins': [[int(b) - 32768, int(h[b])] for b in np.nonzero(h)[0]]}
+        st = self.stats(self.percentiles + (50.0,))
+        if st['count']:
+            d.update({'max': st['max'], 'mean': st['mean'], 'median': st['percentiles'][2], 'min': st['min'], 'std': st['std'],
+                      _percentile_key(self.percentiles[0]): st['percentiles'][0], _percentile_key(self.percentiles[1]): st['percentiles'][1]})
+        return d
+
+    @classmethod
+    def from_dict(cls, d, device='cpu'):
+        fp = cls(tuple(d['percentiles']), device)
+        fp.scans, fp.empty_scans = int(d['scans']), int(d['empty_scans'])
+        if d['bins']:
+            h = np.zeros(65536, dtype=np.int64)
+            for value, count in d['bins']:
+                h[int(value) + 32768] = int(count)
+            fp.hist = torch.from_numpy(h).to(device)
+        return fp
+
+
+def _resolve_intensity(intensity, raw, slope, inter):
+    """SpacedScan's `intensity` as a window 4-tuple or None: a fingerprint gives its window(); 'zscore' the statistics of all voxels
+    of this scan (no label, so training and inference agree) as the window (vmin, vmax, (vmin - mean) / std, (vmax - mean) / std),
+    the z-score with a clamp that never bites"""
+    if isinstance(intensity, IntensityFingerprint):
+        return intensity.window()
+    if isinstance(intensity, str):
+        if intensity != 'zscore':
+            raise ValueError(f"intensity is a window, None, an IntensityFingerprint or 'zscore', got {intensity!r}")
+        st = intensity_stats(raw, percentiles=(), slope=slope, inter=inter)
+        sd = max(st['std'], 1e-8)
+        return st['min'], st['max'], (st['min'] - st['mean']) / sd, (st['max'] - st['mean']) / sd
+    return intensity
+
+
 class SpacedScan:
     """The deterministic half of the driver's CacheDataset: one NIfTI image (and label) read, uploaded once as stored, and
     resampled on the device to `pixdim` in `axcodes` orientation.  img: f32 [H, W, D]; lab: u8 [H, W, D] (or None);
     crop_index: the label's CropIndex, built on first use (crop centres are drawn from it); label_host: the resampled label on the
     host, copied on first use (a scan that is only sampled through the index never copies it); affine: the output's 4x4 affine;
-    matrix: the 3x4 float64 pull matrix (RAS voxel -> file voxel); native_shape / native_affine / native: the file's grid and header."""
+    matrix: the 3x4 float64 pull matrix (RAS voxel -> file voxel); native_shape / native_affine / native: the file's grid and header.
+    intensity: a ScaleIntensityRange window (a_min, a_max, b_min, b_max) applied with its clip, None for the scaled voxels as they
+    are, an IntensityFingerprint for its window(), or 'zscore' for this scan's own mean and standard deviation over all voxels; the
+    attribute `intensity` keeps the resulting 4-tuple (or None)."""
 
     def __init__(self, img_path, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda'):
         ni = nifti.load(img_path)
@@ -476,6 +754,7 @@ class SpacedScan:
         if nl is not None:
             lv = nl.data if (nl.slope, nl.inter) == (1.0, 0.0) else nl.scaled()
             rl = torch.as_tensor(np.ascontiguousarray(label_u8(lv))).to(device)
+        intensity = _resolve_intensity(intensity, ri, ni.slope, ni.inter)
         self.img, self.lab = resample(ri, rl, self.matrix, self.shape, intensity_map(intensity, ni.slope, ni.inter), code)
         self.pixdim, self.intensity = tuple(float(p) for p in pixdim), intensity      # sample(augment=) rotates in mm, fills with the window's floor
         self._label_host = self._crop_index = None
