@@ -77,6 +77,12 @@ int ltu_selftest_last_arriver(const float* x, float* part, float* out, unsigned*
  * x f32 [B,1,H,W,D] (reference layout) -> y T [B,H/2,W/2,D,8]; channel kh*2+kw, channels 4..7 = 0
  * (padding so that the stem conv gathers whole vectors). */
 int ltu_window_embed(const float* x, void* y, int dtype, int B, int H, int W, int D, ltu_stream_t s);
+/* K input channels, 1 <= K <= LTU_MAX_INPUT_CHANNELS: x f32 [B,K,H,W,D] -> y T [B,H/2,W/2,D,CP], CP = 8 * ceil(4K / 8) (8 for K = 1, 2;
+ * 16 for K = 3, 4); channel 4c + 2kh + kw = x[b][c][2h+kh][2w+kw][d] (the inverse of the reference's windows_unembedding), channels
+ * 4K .. CP-1 = 0.  K = 1 writes the bits of ltu_window_embed.  NULL x / y, B < 0 LTU_E_ARG; K outside the range, odd H or W, an
+ * extent < 1 LTU_E_SHAPE; both before any launch. */
+#define LTU_MAX_INPUT_CHANNELS 4
+int ltu_window_embed_multi(const float* x, void* y, int dtype, int B, int K, int H, int W, int D, ltu_stream_t s);
 
 /* ---- weight repacking (weights are tiny; done per step) ----------------------------------------
  * GEMM weight operands are consumed in the activation dtype: these produce them from the fp32 masters.
@@ -815,6 +821,14 @@ int ltu_intensity_moments(const float* img, const uint8_t* lab, long long n_voxe
  *   mats, n as in sample_affine; no atomics, no workspace, no synchronisation: capturable.
  *   Refused before any launch: everything sample_affine refuses, with its codes; NULL phi LTU_E_ARG; a lattice extent outside
  *   4 .. LTU_ELASTIC_MAX_GRID LTU_E_SHAPE; phi not 4-byte aligned LTU_E_ALIGN.
+ * sample_channels: either gather for a scan of K channels on one grid, img f32 [K][H][W][D], 1 <= K <= LTU_MAX_INPUT_CHANNELS, with
+ *   the one label [H][W][D]: out_img [n][K][h][w][d], out_lab [n][h][w][d].  phi NULL runs sample_affine's kernels (gh, gw, gd are
+ *   then ignored), otherwise sample_elastic's.  fill: HOST float [K]; noise_sigma: HOST float [n][K] or NULL; seeds: HOST uint64
+ *   [n][K].  The coordinate, the spline displacement, the tap indices, weights and bounds tests and the label voxel are formed once
+ *   per output voxel; every channel then sums its own 8 taps.  Channel c of out_img has the bits of the single-channel entry point
+ *   called with img + c H W D, fill[c], noise_sigma[.][c] and seeds[.][c] and the same matrices (and lattice); out_lab has that
+ *   call's bits.  Refused as the single-channel calls refuse, and NULL fill or a non-finite fill[c] LTU_E_ARG, K outside its range
+ *   LTU_E_SHAPE.
  * gauss_blur3: out [n][H][W][D] f32 = mul_k * (3-D Gaussian blur of x [n][H][W][D]), out of place, one launch.  weights: HOST float
  *   [n][3][LTU_BLUR_MAX_RADIUS + 1], the half tables w[0 .. r] of the axes H, W, D (normalised so that w[0] + 2 sum w[t] = 1; entries
  *   beyond r are ignored); radii: HOST int [n][3], 0 = that axis untouched; mul: HOST float [n] or NULL (= 1), applied in the store.
@@ -834,6 +848,9 @@ int ltu_sample_affine(const float* img, const uint8_t* lab, float* out_img, uint
 int ltu_sample_elastic(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats, const float* phi,
                        int gh, int gw, int gd, const float* noise_sigma, const unsigned long long* seeds, int n, int H, int W, int D,
                        int h, int w, int d, float fill, ltu_stream_t s);
+int ltu_sample_channels(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats, const float* phi,
+                        int gh, int gw, int gd, const float* noise_sigma, const unsigned long long* seeds, const float* fill, int n,
+                        int K, int H, int W, int D, int h, int w, int d, ltu_stream_t s);
 int ltu_gauss_blur3(const float* x, float* out, const float* weights, const int* radii, const float* mul, int n, int H, int W, int D,
                     ltu_stream_t s);
 

@@ -34,7 +34,8 @@ ELASTIC_MAX_GRID, ELASTIC_MAX_DISP = 8, 64      # LTU_ELASTIC_MAX_GRID / LTU_ELA
 BLUR_MAX_N, BLUR_MAX_RADIUS = 16, 8      # LTU_BLUR_MAX_N / LTU_BLUR_MAX_RADIUS of include/ltu_hip.h
 U8, I16 = 2, 3            # LTU_U8 / LTU_I16 source dtypes of ltu_resample_grid (LTU_F32 = 0)
 HIST_U8, HIST_I16, HIST_F32_INT, HIST_F32_HI, HIST_F32_LO = range(5)      # LTU_HIST_* key modes of ltu_intensity_hist
-INTENSITY_MOMENT_PARTS = 512      # LTU_INTENSITY_MOMENT_PARTS of include/ltu_hip.h
+MAX_INPUT_CHANNELS = 4    # LTU_MAX_INPUT_CHANNELS of include/ltu_hip.h
+INTENSITY_MOMENT_PARTS = 512     # LTU_INTENSITY_MOMENT_PARTS of include/ltu_hip.h
 
 
 # name -> argument types (return type is always int).  Mirrors include/ltu_hip.h one to one.
@@ -44,6 +45,7 @@ SIGNATURES = {
     'ltu_config_set': [ctypes.c_char_p, I, I],
     'ltu_selftest_group_reduce': [P, P, P, I, I, P],
     'ltu_window_embed': [P, P, I, I, I, I, I, P],
+    'ltu_window_embed_multi': [P, P, I, I, I, I, I, I, P],
     'ltu_pack_conv_weight': [P, P, P, I, I, I, I, I, P],
     'ltu_unpack_conv_wgrad': [P, P, I, I, I, P],
     'ltu_transpose_f32': [P, P, I, I, I, I, I, P],
@@ -116,6 +118,7 @@ SIGNATURES = {
     'ltu_intensity_moments': [P, P, L, I, c_double, P, L, P, P],
     'ltu_sample_affine': [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
     'ltu_sample_elastic': [P, P, P, P, P, P, I, I, I, P, P, I, I, I, I, I, I, I, F, P],
+    'ltu_sample_channels': [P, P, P, P, P, P, I, I, I, P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_gauss_blur3': [P, P, P, P, P, I, I, I, I, P],
     'ltu_adamw': [P, P, P, P, L, F, F, F, F, F, L, F, P],
     'ltu_grad_sumsq_parts': [L],

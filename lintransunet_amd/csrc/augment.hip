@@ -1,7 +1,8 @@
 // Augmentation of the NIfTI pipeline's patches on the device (no reference counterpart: the monai driver crops, flips and rot90s
 // only).  Three kernels: ltu_sample_affine cuts rotated / zoomed / flipped patches straight from the scan in one gather (and adds
 // Gaussian noise in the store), ltu_sample_elastic is that gather with a B-spline free-form deformation folded in, ltu_gauss_blur3
-// blurs a batch of patches in one launch (three 1-D passes inside a workgroup).
+// blurs a batch of patches in one launch (three 1-D passes inside a workgroup).  ltu_sample_channels is either gather for a scan of
+// up to four channels on one grid: the same kernels, instantiated per channel count.
 //
 // ---- the noise generator (restated in numpy by lintransunet_amd/data.py::noise_reference) ------------------------------------
 // Stateless like the dropout masks: the normal deviate of voxel i (the linear index (x * w + y) * d + z inside its patch, < 2^32)
@@ -43,10 +44,18 @@ __device__ __forceinline__ void noise_pair(const NoiseKey& k, uint32_t j, float*
 // fp32 / int32, and a matrix with integer entries gives exact integers: the weights are then 1 and 0 and the sum of w * v returns
 // the source voxel's value (its bits, except that a source -0.0 comes out as +0.0: 0.f + -0.f, and adding the 0 * v terms).  The bracket is clamped to [-2 - base, S + 1 - base] before the conversion (base itself
 // is clamped to +-2^22, beyond every scan the entry point accepts), so the conversion is defined for every finite matrix.
-struct SampleAffineArgs {
-  double mat[LTU_SAMPLE_AFFINE_MAX][12];
-  unsigned long long seed[LTU_SAMPLE_AFFINE_MAX];
-  float sigma[LTU_SAMPLE_AFFINE_MAX];
+//
+// NCH > 1 (ltu_sample_channels): the scan holds NCH channels [NCH][H][W][D] on one grid.  Everything above is formed once per output
+// voxel; each channel then runs its own 8 taps (the same expressions in the same order as NCH == 1, so channel c has the bits of a
+// single-channel call on img[c]) with its own fill, sigma and seed.  A launch carries 32 patches of one channel or 8 of up to four
+// (the arguments stay below 4 KiB); the entry points split a call into such launches.
+template <int NCH>
+struct SampleArgs {
+  static constexpr int MAXN = NCH == 1 ? LTU_SAMPLE_AFFINE_MAX : 8;
+  double mat[MAXN][12];
+  unsigned long long seed[MAXN][NCH];
+  float sigma[MAXN][NCH];
+  float fill[NCH];
 };
 
 struct SaAxis { int base; float fr, lo, hi; };
@@ -69,12 +78,89 @@ __device__ __forceinline__ void sa_split(const SaAxis& a, float l, int* i0, floa
 // round half to even of base + l
 __device__ __forceinline__ int sa_round(int i0, float t) { return i0 + ((t > 0.5f || (t == 0.5f && (i0 & 1))) ? 1 : 0); }
 
+// An interpolated value must have the same bits in every instantiation (VEC, NCH, IDX): -ffp-contract=fast would fuse a product
+// into a following sum or not, depending on what else shares the operands (with several channels the compiler packs two channels'
+// products into one instruction and leaves them unfused).  So the tap sums are explicit fmaf chains, and a product that is to be
+// rounded before it is added goes through sa_rounded: an empty statement the compiler cannot look through, no instruction.
+__device__ __forceinline__ float sa_rounded(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+// the 8 trilinear taps of one voxel (lower corner i0, upper weights t): bounds test, weight and offset once, then every channel's
+// own sum in tap order into vi[ch][j].  fill is a copy in registers: read from the kernel's argument struct at the tap, "fill or
+// voxel" becomes one load through a pointer into either address space, a flat load (1.4x the time of the oblique gather).
+template <int NCH, typename IDX, int VEC>
+__device__ __forceinline__ void sa_taps(const float* __restrict__ img, long long HWD, const float (&fill)[NCH], const int (&i0)[3],
+                                        const float (&t)[3], int H, int W, int D, int j, float (&vi)[NCH][VEC]) {
+  float acc[NCH];
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) acc[ch] = 0.f;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int bx = r >> 2, by = (r >> 1) & 1, bz = r & 1;
+    const int xi = i0[0] + bx, yi = i0[1] + by, zi = i0[2] + bz;
+    const bool in = (unsigned)xi < (unsigned)H && (unsigned)yi < (unsigned)W && (unsigned)zi < (unsigned)D;
+    const float wt = (bx ? t[0] : 1.f - t[0]) * (by ? t[1] : 1.f - t[1]) * (bz ? t[2] : 1.f - t[2]);
+    float v[NCH];
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) v[ch] = fill[ch];
+    if (in) {                                      // one branch per tap, the channels' loads together behind it
+      const float* p = img + (((IDX)xi * W + yi) * D + zi);          // the offset exists only for a tap inside the scan
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch) v[ch] = p[ch * HWD];
+    }
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) acc[ch] = fmaf(wt, v[ch], acc[ch]);
+  }
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) vi[ch][j] = acc[ch];
+}
+
+// the store of a lane's VEC voxels at (x, y, z) of patch k: noise per channel, then whole vectors
+template <int VEC, int NCH>
+__device__ __forceinline__ void sa_store(float* __restrict__ oimg, uint8_t* __restrict__ olab, bool has_img, bool has_lab,
+                                         float (&vi)[NCH][VEC], const uint8_t (&vl)[VEC], const unsigned long long (&seed)[NCH],
+                                         const float (&sigma)[NCH], int k, int x, int y, int z, int h, int w, int d) {
+  const uint32_t vox = ((uint32_t)x * (uint32_t)w + (uint32_t)y) * (uint32_t)d + (uint32_t)z;       // < 2^32 (checked on the host)
+  const long long hwd = (long long)h * w * d;
+  if (has_img) {
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      const long long dst = ((long long)k * NCH + ch) * hwd + vox;
+      const float sg = sigma[ch];
+      if (sg > 0.f) {
+        const NoiseKey key = noise_key(seed[ch]);
+        if (VEC == 4) {                     // vox % 4 == 0: two whole pairs
+          float n[4];
+          noise_pair(key, vox >> 1, &n[0], &n[1]);
+          noise_pair(key, (vox >> 1) + 1, &n[2], &n[3]);
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) vi[ch][j] = fmaf(sg, n[j], vi[ch][j]);
+        } else {
+          float n0, n1;
+          noise_pair(key, vox >> 1, &n0, &n1);
+          vi[ch][0] = fmaf(sg, (vox & 1) ? n1 : n0, vi[ch][0]);
+        }
+      }
+      if (VEC == 4) *reinterpret_cast<float4*>(oimg + dst) = make_float4(vi[ch][0], vi[ch][1], vi[ch][2], vi[ch][3]);
+      else oimg[dst] = vi[ch][0];
+    }
+  }
+  if (has_lab) {
+    const long long dst = (long long)k * hwd + vox;
+    if (VEC == 4)
+      *reinterpret_cast<uint32_t*>(olab + dst) = (uint32_t)vl[0] | ((uint32_t)vl[1] << 8) | ((uint32_t)vl[2] << 16) | ((uint32_t)vl[3] << 24);
+    else olab[dst] = vl[0];
+  }
+}
+
 // ZDEC: every matrix of the launch has the form [[a, b, 0, .], [c, e, 0, .], [0, 0, g, .]] (rotation about D only): the in-plane
 // taps, weights and the label's in-plane voxel are computed once per lane, the VEC depth voxels are 1-D lerps on the four rows.
-template <bool ZDEC, int VEC, typename IDX>
+template <bool ZDEC, int VEC, int NCH, typename IDX>
 __global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lab,
-                                                            float* __restrict__ oimg, uint8_t* __restrict__ olab, SampleAffineArgs c,
-                                                            int H, int W, int D, int h, int w, int d, int zl_log2, int ty_log2, float fill) {
+                                                            float* __restrict__ oimg, uint8_t* __restrict__ olab, SampleArgs<NCH> c,
+                                                            int H, int W, int D, int h, int w, int d, int zl_log2, int ty_log2) {
   const int k = blockIdx.z;
   const int zl = 1 << zl_log2, ty = 1 << ty_log2;
   const int x = (int)(blockIdx.y << (8 - zl_log2 - ty_log2)) + (int)(threadIdx.x >> (zl_log2 + ty_log2));
@@ -94,7 +180,11 @@ __global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restr
     my[s] = (float)m[4 * s + 1];
     mz[s] = (float)m[4 * s + 2];
   }
-  float vi[VEC];
+  const long long HWD = (long long)H * W * D;          // channel ch of the scan begins at img + ch * HWD
+  float fill[NCH];
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) fill[ch] = c.fill[ch];
+  float vi[NCH][VEC];
   uint8_t vl[VEC];
   if (ZDEC) {
     int i0[2];
@@ -120,17 +210,21 @@ __global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restr
       float tz;
       sa_split(ax[2], fmaf(mz[2], (float)(zq + j), ax[2].fr), &iz, &tz);
       if (img != nullptr) {
-        float p[2];
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const int zi = iz + e;
-          const bool zin = (unsigned)zi < (unsigned)D;
-          float acc = 0.f;
+        for (int ch = 0; ch < NCH; ++ch) {
+          const float* ic = img + ch * HWD;
+          float p[2];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) acc += wxy[r] * ((in[r] && zin) ? img[row[r] + zi] : fill);
-          p[e] = acc;
+          for (int e = 0; e < 2; ++e) {
+            const int zi = iz + e;
+            const bool zin = (unsigned)zi < (unsigned)D;
+            float acc = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc = fmaf(wxy[r], (in[r] && zin) ? ic[row[r] + zi] : fill[ch], acc);
+            p[e] = acc;
+          }
+          vi[ch][j] = sa_rounded(sa_rounded(1.f - tz) * p[0]) + sa_rounded(tz * p[1]);
         }
-        vi[j] = (1.f - tz) * p[0] + tz * p[1];
       }
       if (lab != nullptr) {
         const int zr = sa_round(iz, tz);
@@ -144,20 +238,7 @@ __global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restr
       float t[3];
 #pragma unroll
       for (int s = 0; s < 3; ++s) sa_split(ax[s], fmaf(my[s], (float)yl, fmaf(mz[s], (float)(zq + j), ax[s].fr)), &i0[s], &t[s]);
-      if (img != nullptr) {
-        float acc = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          const int bx = r >> 2, by = (r >> 1) & 1, bz = r & 1;
-          const int xi = i0[0] + bx, yi = i0[1] + by, zi = i0[2] + bz;
-          const bool in = (unsigned)xi < (unsigned)H && (unsigned)yi < (unsigned)W && (unsigned)zi < (unsigned)D;
-          const float wt = (bx ? t[0] : 1.f - t[0]) * (by ? t[1] : 1.f - t[1]) * (bz ? t[2] : 1.f - t[2]);
-          float v = fill;
-          if (in) v = img[((IDX)xi * W + yi) * D + zi];          // the offset exists only for a tap inside the scan
-          acc += wt * v;
-        }
-        vi[j] = acc;
-      }
+      if (img != nullptr) sa_taps<NCH, IDX>(img, HWD, fill, i0, t, H, W, D, j, vi);
       if (lab != nullptr) {
         const int xr = sa_round(i0[0], t[0]), yr = sa_round(i0[1], t[1]), zr = sa_round(i0[2], t[2]);
         const bool in = (unsigned)xr < (unsigned)H && (unsigned)yr < (unsigned)W && (unsigned)zr < (unsigned)D;
@@ -167,37 +248,12 @@ __global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restr
       }
     }
   }
-  const uint32_t vox = ((uint32_t)x * (uint32_t)w + (uint32_t)y) * (uint32_t)d + (uint32_t)z;       // < 2^32 (checked on the host)
-  const long long dst = (long long)k * h * w * d + vox;
-  if (img != nullptr) {
-    const float sg = c.sigma[k];
-    if (sg > 0.f) {
-      const NoiseKey key = noise_key(c.seed[k]);
-      if (VEC == 4) {                     // vox % 4 == 0: two whole pairs
-        float n[4];
-        noise_pair(key, vox >> 1, &n[0], &n[1]);
-        noise_pair(key, (vox >> 1) + 1, &n[2], &n[3]);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) vi[j] = fmaf(sg, n[j], vi[j]);
-      } else {
-        float n0, n1;
-        noise_pair(key, vox >> 1, &n0, &n1);
-        vi[0] = fmaf(sg, (vox & 1) ? n1 : n0, vi[0]);
-      }
-    }
-    if (VEC == 4) *reinterpret_cast<float4*>(oimg + dst) = make_float4(vi[0], vi[1], vi[2], vi[3]);
-    else oimg[dst] = vi[0];
-  }
-  if (lab != nullptr) {
-    if (VEC == 4)
-      *reinterpret_cast<uint32_t*>(olab + dst) = (uint32_t)vl[0] | ((uint32_t)vl[1] << 8) | ((uint32_t)vl[2] << 16) | ((uint32_t)vl[3] << 24);
-    else olab[dst] = vl[0];
-  }
+  sa_store<VEC, NCH>(oimg, olab, img != nullptr, lab != nullptr, vi, vl, c.seed[k], c.sigma[k], k, x, y, z, h, w, d);
 }
 
-template <bool ZDEC, int VEC, typename IDX>
-static void sample_affine_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SampleAffineArgs& c, int n, int H,
-                                 int W, int D, int h, int w, int d, float fill, hipStream_t st) {
+template <bool ZDEC, int VEC, int NCH, typename IDX>
+static void sample_affine_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SampleArgs<NCH>& c, int n, int H,
+                                 int W, int D, int h, int w, int d, hipStream_t st) {
   const int per_lane = (d + VEC - 1) / VEC;
   int zl_log2 = 0;
   while ((1 << zl_log2) < per_lane && zl_log2 < (VEC == 4 ? 4 : 6)) ++zl_log2;
@@ -205,52 +261,8 @@ static void sample_affine_launch(const float* img, const uint8_t* lab, float* oi
   while ((1 << ty_log2) < w && zl_log2 + ty_log2 < 8) ++ty_log2;
   const int zl = 1 << zl_log2, ty = 1 << ty_log2, tx = 256 >> (zl_log2 + ty_log2);
   const unsigned tiles = cdiv(w, ty) * cdiv(d, zl * VEC);
-  hipLaunchKernelGGL((sample_affine_kernel<ZDEC, VEC, IDX>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c, H, W,
-                     D, h, w, d, zl_log2, ty_log2, fill);
-}
-
-extern "C" int ltu_sample_affine(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats,
-                                 const float* noise_sigma, const unsigned long long* seeds, int n, int H, int W, int D, int h, int w,
-                                 int d, float fill, ltu_stream_t s) {
-  if (mats == nullptr || (img == nullptr) != (out_img == nullptr) || (lab == nullptr) != (out_lab == nullptr) ||
-      (img == nullptr && lab == nullptr) || n < 0 || n > LTU_SAMPLE_AFFINE_MAX || (noise_sigma != nullptr && seeds == nullptr) ||
-      !(fill - fill == 0.f))
-    return LTU_E_ARG;
-  if (n == 0) return LTU_OK;
-  const int smax = 1 << 22;
-  if (H < 1 || W < 1 || D < 1 || H > smax || W > smax || D > smax || h < 1 || w < 1 || d < 1 || h > 65535 ||
-      (long long)h * w * d >= (1LL << 32) || (long long)cdiv(w, 4) * cdiv(d, 4) >= (1LL << 31))
-    return LTU_E_SHAPE;
-  SampleAffineArgs c;
-  bool zdec = true;
-  for (int k = 0; k < n; ++k) {
-    for (int j = 0; j < 12; ++j) {
-      const double v = mats[12 * k + j];
-      if (!(v - v == 0.0)) return LTU_E_ARG;             // NaN or infinite
-      c.mat[k][j] = v;
-    }
-    const double* m = mats + 12 * k;
-    zdec = zdec && m[2] == 0.0 && m[6] == 0.0 && m[8] == 0.0 && m[9] == 0.0;
-    const float sg = noise_sigma != nullptr ? noise_sigma[k] : 0.f;
-    if (!(sg >= 0.f) || !(sg - sg == 0.f)) return LTU_E_ARG;
-    c.sigma[k] = img != nullptr ? sg : 0.f;
-    c.seed[k] = seeds != nullptr ? seeds[k] : 0ull;
-  }
-  const int vec = (d % 4 == 0) ? 4 : 1;
-  if (vec == 4 && (((uintptr_t)out_img & 15) != 0 || ((uintptr_t)out_lab & 3) != 0)) return LTU_E_ALIGN;
-  const bool small = (long long)H * W * D < (1LL << 31);
-  const hipStream_t st = (hipStream_t)s;
-#define SA_GO(Z, V)                                                                                                       \
-  do {                                                                                                                    \
-    if (small) sample_affine_launch<Z, V, int>(img, lab, out_img, out_lab, c, n, H, W, D, h, w, d, fill, st);             \
-    else sample_affine_launch<Z, V, long long>(img, lab, out_img, out_lab, c, n, H, W, D, h, w, d, fill, st);             \
-  } while (0)
-  if (zdec && vec == 4) SA_GO(true, 4);
-  else if (zdec) SA_GO(true, 1);
-  else if (vec == 4) SA_GO(false, 4);
-  else SA_GO(false, 1);
-#undef SA_GO
-  return ltu_check_launch();
+  hipLaunchKernelGGL((sample_affine_kernel<ZDEC, VEC, NCH, IDX>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c, H,
+                     W, D, h, w, d, zl_log2, ty_log2);
 }
 
 // ---- ltu_sample_elastic --------------------------------------------------------------------------------------------------------
@@ -285,24 +297,31 @@ extern "C" int ltu_sample_affine(const float* img, const uint8_t* lab, float* ou
 #define SE_TX_MAX 8
 #define SE_PLANE (LTU_ELASTIC_MAX_GRID * LTU_ELASTIC_MAX_GRID)
 
-// s >= 0 -> (index of the first of the 4 control points, their weights)
-__device__ __forceinline__ void se_basis(float s, int g, int* i, float (&b)[4]) {
+// Every sum of the spline and of the displaced coordinate is an explicit fmaf chain (sa_rounded's comment: the patch must not
+// depend on the instantiation, and the channel kernels share all of this with the single-channel one).
+// patch coordinate t >= 0 at lattice scale -> (index of the first of the 4 control points, their weights)
+__device__ __forceinline__ void se_basis(float t, float scale, int g, int* i, float (&b)[4]) {
+  const float s = sa_rounded(t * scale);
   const int ii = min(max((int)floorf(s), 0), g - 4);
   const float f = s - (float)ii, f2 = f * f, f3 = f2 * f, om = 1.f - f;
   const float sixth = 1.f / 6.f;
   b[0] = om * om * om * sixth;
-  b[1] = (3.f * f3 - 6.f * f2 + 4.f) * sixth;
-  b[2] = (-3.f * f3 + 3.f * f2 + 3.f * f + 1.f) * sixth;
+  b[1] = fmaf(3.f, f3, fmaf(-6.f, f2, 4.f)) * sixth;
+  b[2] = fmaf(-3.f, f3, fmaf(3.f, f2, fmaf(3.f, f, 1.f))) * sixth;
   b[3] = f3 * sixth;
   *i = ii;
 }
+// w[0] p[0] + w[1] p[stride] + w[2] p[2 stride] + w[3] p[3 stride], summed in this order
+__device__ __forceinline__ float se_dot4(const float (&w)[4], const float* p, int stride) {
+  return fmaf(w[3], p[3 * stride], fmaf(w[2], p[2 * stride], fmaf(w[1], p[stride], w[0] * p[0])));
+}
 
-template <int VEC, int NC, typename IDX>
+template <int VEC, int NC, int NCH, typename IDX>
 __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lab,
-                                                             float* __restrict__ oimg, uint8_t* __restrict__ olab, SampleAffineArgs c,
+                                                             float* __restrict__ oimg, uint8_t* __restrict__ olab, SampleArgs<NCH> c,
                                                              const float* __restrict__ phi, int gh, int gw, int gd, float sx, float sy,
                                                              float sz, int H, int W, int D, int h, int w, int d, int zl_log2,
-                                                             int ty_log2, int tx_log2, float fill) {
+                                                             int ty_log2, int tx_log2) {
   static_assert(NC >= 4 && NC <= LTU_ELASTIC_MAX_GRID && (VEC == 4 || NC == 4), "NC columns cover a run of VEC voxels");
   __shared__ float A[SE_TX_MAX * 3 * SE_PLANE];
   const int k = blockIdx.z;
@@ -316,9 +335,9 @@ __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __rest
     if (x0 + xl < h) {
       int ix;
       float bx[4];
-      se_basis((float)(x0 + xl) * sx, gh, &ix, bx);
+      se_basis((float)(x0 + xl), sx, gh, &ix, bx);
       const float* p = pk + (cc * gh + ix) * plane + jq;             // rows ix .. ix + 3 <= gh - 1
-      v = bx[0] * p[0] + bx[1] * p[plane] + bx[2] * p[2 * plane] + bx[3] * p[3 * plane];
+      v = se_dot4(bx, p, plane);
     }
     A[e] = v;
   }
@@ -344,8 +363,8 @@ __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __rest
   }
   int iy, c0;
   float by[4], bz[4];
-  se_basis((float)y * sy, gw, &iy, by);
-  se_basis((float)z * sz, gd, &c0, bz);
+  se_basis((float)y, sy, gw, &iy, by);
+  se_basis((float)z, sz, gd, &c0, bz);
   float col[3][NC];
   {
     const float* a = A + xl * 3 * plane + iy * gd;                   // rows iy .. iy + 3 <= gw - 1
@@ -355,18 +374,22 @@ __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __rest
 #pragma unroll
       for (int cc = 0; cc < 3; ++cc) {
         const float* p = a + cc * plane + qi;
-        col[cc][q] = by[0] * p[0] + by[1] * p[gd] + by[2] * p[2 * gd] + by[3] * p[3 * gd];
+        col[cc][q] = se_dot4(by, p, gd);
       }
     }
   }
-  float vi[VEC];
+  const long long HWD = (long long)H * W * D;
+  float fill[NCH];
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) fill[ch] = c.fill[ch];
+  float vi[NCH][VEC];
   uint8_t vl[VEC];
 #pragma unroll
   for (int j = 0; j < VEC; ++j) {
     int off = 0;
     if (j > 0) {
       int iz;
-      se_basis((float)(z + j) * sz, gd, &iz, bz);
+      se_basis((float)(z + j), sz, gd, &iz, bz);
       off = min(max(iz - c0, 0), NC - 4);
     }
     float u[3];
@@ -378,7 +401,7 @@ __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __rest
         float v = col[cc][n];
 #pragma unroll
         for (int o = 1; o <= NC - 4; ++o) v = off == o ? col[cc][n + o] : v;
-        acc += bz[n] * v;
+        acc = fmaf(bz[n], v, acc);
       }
       u[cc] = fminf(fmaxf(acc, -(float)LTU_ELASTIC_MAX_DISP), (float)LTU_ELASTIC_MAX_DISP);
     }
@@ -386,22 +409,10 @@ __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __rest
     float t[3];
 #pragma unroll
     for (int s = 0; s < 3; ++s)
-      sa_split(ax[s], fmaf(my[s], (float)yl, fmaf(mz[s], (float)(zq + j), ax[s].fr)) + (mx[s] * u[0] + my[s] * u[1] + mz[s] * u[2]),
+      sa_split(ax[s], fmaf(my[s], (float)yl, fmaf(mz[s], (float)(zq + j), ax[s].fr)) +
+                          sa_rounded(fmaf(mz[s], u[2], fmaf(my[s], u[1], mx[s] * u[0]))),
                &i0[s], &t[s]);
-    if (img != nullptr) {
-      float acc = 0.f;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int bx = r >> 2, by2 = (r >> 1) & 1, bz2 = r & 1;
-        const int xi = i0[0] + bx, yi = i0[1] + by2, zi = i0[2] + bz2;
-        const bool in = (unsigned)xi < (unsigned)H && (unsigned)yi < (unsigned)W && (unsigned)zi < (unsigned)D;
-        const float wt = (bx ? t[0] : 1.f - t[0]) * (by2 ? t[1] : 1.f - t[1]) * (bz2 ? t[2] : 1.f - t[2]);
-        float v = fill;
-        if (in) v = img[((IDX)xi * W + yi) * D + zi];          // the offset exists only for a tap inside the scan
-        acc += wt * v;
-      }
-      vi[j] = acc;
-    }
+    if (img != nullptr) sa_taps<NCH, IDX>(img, HWD, fill, i0, t, H, W, D, j, vi);
     if (lab != nullptr) {
       const int xr = sa_round(i0[0], t[0]), yr = sa_round(i0[1], t[1]), zr = sa_round(i0[2], t[2]);
       const bool in = (unsigned)xr < (unsigned)H && (unsigned)yr < (unsigned)W && (unsigned)zr < (unsigned)D;
@@ -410,37 +421,12 @@ __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __rest
       vl[j] = lv;
     }
   }
-  const uint32_t vox = ((uint32_t)x * (uint32_t)w + (uint32_t)y) * (uint32_t)d + (uint32_t)z;       // < 2^32 (checked on the host)
-  const long long dst = (long long)k * h * w * d + vox;
-  if (img != nullptr) {
-    const float sg = c.sigma[k];
-    if (sg > 0.f) {
-      const NoiseKey key = noise_key(c.seed[k]);
-      if (VEC == 4) {                     // vox % 4 == 0: two whole pairs
-        float n[4];
-        noise_pair(key, vox >> 1, &n[0], &n[1]);
-        noise_pair(key, (vox >> 1) + 1, &n[2], &n[3]);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) vi[j] = fmaf(sg, n[j], vi[j]);
-      } else {
-        float n0, n1;
-        noise_pair(key, vox >> 1, &n0, &n1);
-        vi[0] = fmaf(sg, (vox & 1) ? n1 : n0, vi[0]);
-      }
-    }
-    if (VEC == 4) *reinterpret_cast<float4*>(oimg + dst) = make_float4(vi[0], vi[1], vi[2], vi[3]);
-    else oimg[dst] = vi[0];
-  }
-  if (lab != nullptr) {
-    if (VEC == 4)
-      *reinterpret_cast<uint32_t*>(olab + dst) = (uint32_t)vl[0] | ((uint32_t)vl[1] << 8) | ((uint32_t)vl[2] << 16) | ((uint32_t)vl[3] << 24);
-    else olab[dst] = vl[0];
-  }
+  sa_store<VEC, NCH>(oimg, olab, img != nullptr, lab != nullptr, vi, vl, c.seed[k], c.sigma[k], k, x, y, z, h, w, d);
 }
 
-template <int VEC, int NC, typename IDX>
-static void sample_elastic_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SampleAffineArgs& c,
-                                  const float* phi, int gh, int gw, int gd, int n, int H, int W, int D, int h, int w, int d, float fill,
+template <int VEC, int NC, int NCH, typename IDX>
+static void sample_elastic_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SampleArgs<NCH>& c,
+                                  const float* phi, int gh, int gw, int gd, int n, int H, int W, int D, int h, int w, int d,
                                   hipStream_t st) {
   const int per_lane = (d + VEC - 1) / VEC;
   int zl_log2 = 0;
@@ -455,51 +441,145 @@ static void sample_elastic_launch(const float* img, const uint8_t* lab, float* o
   const float sx = h > 1 ? (float)((double)(gh - 3) / (double)(h - 1)) : 0.f;
   const float sy = w > 1 ? (float)((double)(gw - 3) / (double)(w - 1)) : 0.f;
   const float sz = d > 1 ? (float)((double)(gd - 3) / (double)(d - 1)) : 0.f;
-  hipLaunchKernelGGL((sample_elastic_kernel<VEC, NC, IDX>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c, phi, gh,
-                     gw, gd, sx, sy, sz, H, W, D, h, w, d, zl_log2, ty_log2, tx_log2, fill);
+  hipLaunchKernelGGL((sample_elastic_kernel<VEC, NC, NCH, IDX>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c,
+                     phi, gh, gw, gd, sx, sy, sz, H, W, D, h, w, d, zl_log2, ty_log2, tx_log2);
+}
+
+// ---- the three entry points ------------------------------------------------------------------------------------------------------
+// One call of any of them: the scan's K channels, per-patch matrices, per-patch-and-channel sigmas and seeds, per-channel fills, and
+// the lattice when the call deforms.
+struct SampleCall {
+  const float* img;
+  const uint8_t* lab;
+  float* oi;
+  uint8_t* ol;
+  const double* mats;
+  const float* phi;                    // NULL: the affine kernels
+  int gh, gw, gd;
+  const float* sigma;                  // [n][K] or NULL
+  const unsigned long long* seeds;     // [n][K] or NULL
+  const float* fill;                   // [K]
+  int n, K, H, W, D, h, w, d;
+};
+
+// everything the entry points refuse, in sample_affine's order; LTU_OK with *run = false: nothing to do
+static int sample_check(const SampleCall& q, bool elastic, bool* run) {
+  *run = false;
+  if (q.mats == nullptr || (elastic && q.phi == nullptr) || (q.img == nullptr) != (q.oi == nullptr) ||
+      (q.lab == nullptr) != (q.ol == nullptr) || (q.img == nullptr && q.lab == nullptr) || q.n < 0 || q.n > LTU_SAMPLE_AFFINE_MAX ||
+      (q.sigma != nullptr && q.seeds == nullptr) || q.fill == nullptr)
+    return LTU_E_ARG;
+  if (q.K < 1 || q.K > LTU_MAX_INPUT_CHANNELS) return LTU_E_SHAPE;
+  for (int ch = 0; ch < q.K; ++ch)
+    if (!(q.fill[ch] - q.fill[ch] == 0.f)) return LTU_E_ARG;
+  if (elastic && (q.gh < 4 || q.gw < 4 || q.gd < 4 || q.gh > LTU_ELASTIC_MAX_GRID || q.gw > LTU_ELASTIC_MAX_GRID ||
+                  q.gd > LTU_ELASTIC_MAX_GRID))
+    return LTU_E_SHAPE;
+  if (q.n == 0) return LTU_OK;
+  const int smax = 1 << 22;
+  if (q.H < 1 || q.W < 1 || q.D < 1 || q.H > smax || q.W > smax || q.D > smax || q.h < 1 || q.w < 1 || q.d < 1 || q.h > 65535 ||
+      (long long)q.h * q.w * q.d >= (1LL << 32) || (long long)cdiv(q.w, 4) * cdiv(q.d, 4) >= (1LL << 31))
+    return LTU_E_SHAPE;
+  for (int k = 0; k < q.n; ++k) {
+    for (int j = 0; j < 12; ++j) {
+      const double v = q.mats[12 * k + j];
+      if (!(v - v == 0.0)) return LTU_E_ARG;             // NaN or infinite
+    }
+    for (int ch = 0; ch < q.K && q.sigma != nullptr; ++ch) {
+      const float sg = q.sigma[k * q.K + ch];
+      if (!(sg >= 0.f) || !(sg - sg == 0.f)) return LTU_E_ARG;
+    }
+  }
+  if ((elastic && ((uintptr_t)q.phi & 3) != 0) || (q.d % 4 == 0 && (((uintptr_t)q.oi & 15) != 0 || ((uintptr_t)q.ol & 3) != 0)))
+    return LTU_E_ALIGN;
+  *run = true;
+  return LTU_OK;
+}
+
+// a checked call as launches of at most SampleArgs<NCH>::MAXN patches; the kernel variant is chosen from the whole call, so that a
+// patch has the same bits wherever the call is split
+template <int NCH>
+static void sample_go(const SampleCall& q, hipStream_t st) {
+  bool zdec = true;
+  for (int k = 0; k < q.n; ++k) {
+    const double* m = q.mats + 12 * k;
+    zdec = zdec && m[2] == 0.0 && m[6] == 0.0 && m[8] == 0.0 && m[9] == 0.0;
+  }
+  const int vec = (q.d % 4 == 0) ? 4 : 1;
+  const bool small = (long long)q.H * q.W * q.D < (1LL << 31);
+  const bool two_cells = 3.0 * (q.gd - 3) <= 0.99 * (q.d - 1);       // a run of 4 voxels along z spans at most two lattice cells
+  const long long hwd = (long long)q.h * q.w * q.d;
+  SampleArgs<NCH> c;
+  for (int ch = 0; ch < NCH; ++ch) c.fill[ch] = q.fill[ch];
+  for (int k0 = 0; k0 < q.n; k0 += SampleArgs<NCH>::MAXN) {
+    const int n = q.n - k0 < SampleArgs<NCH>::MAXN ? q.n - k0 : SampleArgs<NCH>::MAXN;
+    for (int k = 0; k < n; ++k) {
+      for (int j = 0; j < 12; ++j) c.mat[k][j] = q.mats[12 * (k0 + k) + j];
+      for (int ch = 0; ch < NCH; ++ch) {
+        c.sigma[k][ch] = (q.img != nullptr && q.sigma != nullptr) ? q.sigma[(k0 + k) * NCH + ch] : 0.f;
+        c.seed[k][ch] = q.seeds != nullptr ? q.seeds[(k0 + k) * NCH + ch] : 0ull;
+      }
+    }
+    float* oi = q.oi != nullptr ? q.oi + k0 * NCH * hwd : nullptr;
+    uint8_t* ol = q.ol != nullptr ? q.ol + k0 * hwd : nullptr;
+#define SA_GO(Z, V)                                                                                                          \
+  do {                                                                                                                       \
+    if (small) sample_affine_launch<Z, V, NCH, int>(q.img, q.lab, oi, ol, c, n, q.H, q.W, q.D, q.h, q.w, q.d, st);            \
+    else sample_affine_launch<Z, V, NCH, long long>(q.img, q.lab, oi, ol, c, n, q.H, q.W, q.D, q.h, q.w, q.d, st);            \
+  } while (0)
+#define SE_GO(V, NCOL)                                                                                                                     \
+  do {                                                                                                                                     \
+    const float* pk = q.phi + (long long)k0 * 3 * q.gh * q.gw * q.gd;                                                                      \
+    if (small) sample_elastic_launch<V, NCOL, NCH, int>(q.img, q.lab, oi, ol, c, pk, q.gh, q.gw, q.gd, n, q.H, q.W, q.D, q.h, q.w, q.d, st); \
+    else sample_elastic_launch<V, NCOL, NCH, long long>(q.img, q.lab, oi, ol, c, pk, q.gh, q.gw, q.gd, n, q.H, q.W, q.D, q.h, q.w, q.d, st); \
+  } while (0)
+    if (q.phi != nullptr) {
+      if (vec == 1) SE_GO(1, 4);
+      else if (two_cells) SE_GO(4, 5);
+      else SE_GO(4, LTU_ELASTIC_MAX_GRID);
+    } else if (zdec && vec == 4) SA_GO(true, 4);
+    else if (zdec) SA_GO(true, 1);
+    else if (vec == 4) SA_GO(false, 4);
+    else SA_GO(false, 1);
+#undef SA_GO
+#undef SE_GO
+  }
+}
+
+static int sample_run(const SampleCall& q, bool elastic, ltu_stream_t s) {
+  bool run;
+  const int rc = sample_check(q, elastic, &run);
+  if (rc != LTU_OK || !run) return rc;
+  static_assert(LTU_MAX_INPUT_CHANNELS == 4, "one instantiation per channel count");
+  switch (q.K) {
+    case 1: sample_go<1>(q, (hipStream_t)s); break;
+    case 2: sample_go<2>(q, (hipStream_t)s); break;
+    case 3: sample_go<3>(q, (hipStream_t)s); break;
+    default: sample_go<4>(q, (hipStream_t)s); break;
+  }
+  return ltu_check_launch();
+}
+
+extern "C" int ltu_sample_affine(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats,
+                                 const float* noise_sigma, const unsigned long long* seeds, int n, int H, int W, int D, int h, int w,
+                                 int d, float fill, ltu_stream_t s) {
+  const SampleCall q = {img, lab, out_img, out_lab, mats, nullptr, 0, 0, 0, noise_sigma, seeds, &fill, n, 1, H, W, D, h, w, d};
+  return sample_run(q, false, s);
 }
 
 extern "C" int ltu_sample_elastic(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats,
                                   const float* phi, int gh, int gw, int gd, const float* noise_sigma, const unsigned long long* seeds,
                                   int n, int H, int W, int D, int h, int w, int d, float fill, ltu_stream_t s) {
-  if (mats == nullptr || phi == nullptr || (img == nullptr) != (out_img == nullptr) || (lab == nullptr) != (out_lab == nullptr) ||
-      (img == nullptr && lab == nullptr) || n < 0 || n > LTU_SAMPLE_AFFINE_MAX || (noise_sigma != nullptr && seeds == nullptr) ||
-      !(fill - fill == 0.f))
-    return LTU_E_ARG;
-  if (gh < 4 || gw < 4 || gd < 4 || gh > LTU_ELASTIC_MAX_GRID || gw > LTU_ELASTIC_MAX_GRID || gd > LTU_ELASTIC_MAX_GRID)
-    return LTU_E_SHAPE;
-  if (n == 0) return LTU_OK;
-  const int smax = 1 << 22;
-  if (H < 1 || W < 1 || D < 1 || H > smax || W > smax || D > smax || h < 1 || w < 1 || d < 1 || h > 65535 ||
-      (long long)h * w * d >= (1LL << 32) || (long long)cdiv(w, 4) * cdiv(d, 4) >= (1LL << 31))
-    return LTU_E_SHAPE;
-  SampleAffineArgs c;
-  for (int k = 0; k < n; ++k) {
-    for (int j = 0; j < 12; ++j) {
-      const double v = mats[12 * k + j];
-      if (!(v - v == 0.0)) return LTU_E_ARG;             // NaN or infinite
-      c.mat[k][j] = v;
-    }
-    const float sg = noise_sigma != nullptr ? noise_sigma[k] : 0.f;
-    if (!(sg >= 0.f) || !(sg - sg == 0.f)) return LTU_E_ARG;
-    c.sigma[k] = img != nullptr ? sg : 0.f;
-    c.seed[k] = seeds != nullptr ? seeds[k] : 0ull;
-  }
-  const int vec = (d % 4 == 0) ? 4 : 1;
-  if (((uintptr_t)phi & 3) != 0 || (vec == 4 && (((uintptr_t)out_img & 15) != 0 || ((uintptr_t)out_lab & 3) != 0))) return LTU_E_ALIGN;
-  const bool small = (long long)H * W * D < (1LL << 31);
-  const bool two_cells = 3.0 * (gd - 3) <= 0.99 * (d - 1);       // a run of 4 voxels along z spans at most two lattice cells
-  const hipStream_t st = (hipStream_t)s;
-#define SE_GO(V, NCOL)                                                                                                              \
-  do {                                                                                                                              \
-    if (small) sample_elastic_launch<V, NCOL, int>(img, lab, out_img, out_lab, c, phi, gh, gw, gd, n, H, W, D, h, w, d, fill, st);   \
-    else sample_elastic_launch<V, NCOL, long long>(img, lab, out_img, out_lab, c, phi, gh, gw, gd, n, H, W, D, h, w, d, fill, st);   \
-  } while (0)
-  if (vec == 1) SE_GO(1, 4);
-  else if (two_cells) SE_GO(4, 5);
-  else SE_GO(4, LTU_ELASTIC_MAX_GRID);
-#undef SE_GO
-  return ltu_check_launch();
+  const SampleCall q = {img, lab, out_img, out_lab, mats, phi, gh, gw, gd, noise_sigma, seeds, &fill, n, 1, H, W, D, h, w, d};
+  return sample_run(q, true, s);
+}
+
+extern "C" int ltu_sample_channels(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats,
+                                   const float* phi, int gh, int gw, int gd, const float* noise_sigma,
+                                   const unsigned long long* seeds, const float* fill, int n, int K, int H, int W, int D, int h, int w,
+                                   int d, ltu_stream_t s) {
+  const SampleCall q = {img, lab, out_img, out_lab, mats, phi, gh, gw, gd, noise_sigma, seeds, fill, n, K, H, W, D, h, w, d};
+  return sample_run(q, phi != nullptr, s);
 }
 
 // ---- ltu_gauss_blur3 -----------------------------------------------------------------------------------------------------------

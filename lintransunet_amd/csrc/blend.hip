@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(256) window_blend_kernel(const float* __restri
       const float wt = fmaxf(g0[v0] * g1[v1] * g2[v2], wmin);
       ws += wt;
 #pragma unroll
-      for (int c = 0; c < C; ++c) acc[c] += wt * sp[c];
+      for (int c = 0; c < C; ++c) acc[c] = fmaf(wt, sp[c], acc[c]);          // fused for every C: a channel's sum does not depend on C
     }
 #pragma unroll
     for (int c = 0; c < C; ++c) vp[c * vol] = acc[c];

@@ -39,6 +39,51 @@ extern "C" int ltu_window_embed(const float* x, void* y, int dtype, int B, int H
   return ltu_check_launch();
 }
 
+// x f32 [B,K,H,W,D] -> y T [B,H/2,W/2,D,CP], CP = 8 * ceil(4K / 8): channel 4c + 2kh + kw = x[b][c][2h+kh][2w+kw][d] (the inverse
+// of the reference's windows_unembedding, channel = c k^2 + kh k + kw), channels from 4K upward zero.  Lanes along d as above; a
+// lane writes its voxel's CP channels as CP / 4 four-channel vectors, input channel c filling vector c.
+template <typename T, int K>
+__global__ void window_embed_multi_kernel(const float* __restrict__ x, T* __restrict__ y, int B, int H, int W, int D) {
+  constexpr int CP = (4 * K + 7) / 8 * 8;
+  const int h2 = H / 2, w2 = W / 2;
+  const long long n = (long long)B * h2 * w2 * D, plane = (long long)W * D, vol = (long long)H * plane;
+  GRID_STRIDE(i, n) {
+    const int d = (int)(i % D);
+    long long t = i / D;
+    const int w = (int)(t % w2);
+    t /= w2;
+    const int h = (int)(t % h2);
+    const int b = (int)(t / h2);
+    const float* xb = x + (long long)b * K * vol + ((long long)2 * h * W + 2 * w) * D + d;
+#pragma unroll
+    for (int c = 0; c < CP / 4; ++c) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c < K) {
+        const float* xc = xb + c * vol;
+        v = make_float4(xc[0], xc[D], xc[plane], xc[plane + D]);   // (kh,kw) = 00,01,10,11
+      }
+      Vec4<T>::store(y + i * CP + 4 * c, v);
+    }
+  }
+}
+
+extern "C" int ltu_window_embed_multi(const float* x, void* y, int dtype, int B, int K, int H, int W, int D, ltu_stream_t s) {
+  if (x == nullptr || y == nullptr || B < 0) return LTU_E_ARG;
+  if (K < 1 || K > LTU_MAX_INPUT_CHANNELS || H < 2 || W < 2 || D < 1 || H % 2 || W % 2) return LTU_E_SHAPE;
+  const long long n = (long long)B * (H / 2) * (W / 2) * D;
+  if (n == 0) return LTU_OK;
+#define WE_GO(KK) \
+  LTU_DISPATCH_T(dtype, { hipLaunchKernelGGL((window_embed_multi_kernel<T, KK>), dim3(sgrid(n)), dim3(256), 0, (hipStream_t)s, x, (T*)y, B, H, W, D); })
+  switch (K) {
+    case 1: WE_GO(1); break;
+    case 2: WE_GO(2); break;
+    case 3: WE_GO(3); break;
+    default: WE_GO(4); break;
+  }
+#undef WE_GO
+  return ltu_check_launch();
+}
+
 // ------------------------------------------------------------------------------------------------ weight repacking
 // w [Co][Ci][27] -> wf [CoP][27][CiP], wd [CiP][27][CoP]  (zero padded), stored as TW (fp32 or bf16)
 template <typename TW>

@@ -309,15 +309,16 @@ def augment(img, lab, params):
     return img, lab8
 
 
-def synthetic_patches(batch, size, seed, device, n_classes=2, n_blobs=2):
+def synthetic_patches(batch, size, seed, device, n_classes=2, n_blobs=2, n_channels=1):
     """Synthetic CT-like training patches for benchmarks and soak runs: N(0,1) intensities clipped to
     the dataset's normalised HU range [(-91 - 86.9) / 39.4, (250 - 86.9) / 39.4] and a label volume that is a union of `n_blobs`
     random ellipsoids per patch (nested twice for 3 label values; for 4 .. 8 label values one further ellipsoid per class 2 .. k-1, every
     class 1 .. k-1 present in every patch).  Host generators (seeded), uploaded once: a benchmark keeps its
-    inputs resident in HBM.  Returns (x f32 [B,1,H,W,D], label u8 [B,1,H,W,D])."""
+    inputs resident in HBM.  Returns (x f32 [B,n_channels,H,W,D], label u8 [B,1,H,W,D]); n_channels > 1 draws that many intensity
+    volumes per patch ahead of the label's draws (1 draws what it always drew)."""
     g = torch.Generator().manual_seed(seed)
     H, W, D = size
-    x = torch.randn((batch, 1, H, W, D), generator=g).clamp_((LOW_CLIP - MEAN) / STD, (HIGH_CLIP - MEAN) / STD)
+    x = torch.randn((batch, int(n_channels), H, W, D), generator=g).clamp_((LOW_CLIP - MEAN) / STD, (HIGH_CLIP - MEAN) / STD)
     hh = torch.arange(H, dtype=torch.float32).view(H, 1, 1)
     ww = torch.arange(W, dtype=torch.float32).view(1, W, 1)
     dd = torch.arange(D, dtype=torch.float32).view(1, 1, D)
@@ -772,6 +773,62 @@ class SpacedScan:
         return self._crop_index
 
 
+def _is_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+class MultiScan(SpacedScan):
+    """SpacedScan for K = 1 .. 4 NIfTI images on ONE grid (T1 / T1c / T2 / FLAIR, T2 + ADC, PET + CT): img_paths is their sequence,
+    channel 0 first.  Every other image and the label must match channel 0 in shape and affine (geometry.check_pair: ValueError).
+    Each channel is resampled exactly as SpacedScan resamples it alone; img: one contiguous f32 [K, H, W, D]; lab, crop_index,
+    label_host, matrix, affine, shape, pixdim as on SpacedScan, native / native_shape / native_affine are channel 0's.
+    intensity: one spec for all channels (a window 4-tuple, None, an IntensityFingerprint or 'zscore') or a sequence of K specs;
+    the attribute `intensity` is the list of the K resulting tuples (or None).  channels == K."""
+
+    def __init__(self, img_paths, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda'):
+        paths = [img_paths] if isinstance(img_paths, (str, bytes)) or hasattr(img_paths, '__fspath__') else list(img_paths)
+        K = len(paths)
+        if not 1 <= K <= _lib.MAX_INPUT_CHANNELS:
+            raise ValueError(f'a MultiScan holds 1 .. {_lib.MAX_INPUT_CHANNELS} images, got {K}')
+        one = intensity is None or isinstance(intensity, (str, IntensityFingerprint)) or \
+            (len(intensity) == 4 and all(_is_number(v) for v in intensity))
+        specs = [intensity] * K if one else list(intensity)
+        if len(specs) != K:
+            raise ValueError(f'intensity is one spec or one per image: {len(specs)} specs for {K} images')
+        nis = [nifti.load(p) for p in paths]
+        nl = nifti.load(lab_path) if lab_path is not None else None
+        ni = nis[0]
+        for other in nis[1:] + ([nl] if nl is not None else []):
+            geometry.check_pair(ni.shape, ni.affine, other.shape, other.affine)
+        self.native, self.native_shape, self.native_affine = ni, ni.shape, ni.affine
+        self.matrix, self.shape, self.affine = geometry.spacing_plan(ni.shape, ni.affine, pixdim, axcodes)
+        rl = None
+        if nl is not None:
+            lv = nl.data if (nl.slope, nl.inter) == (1.0, 0.0) else nl.scaled()
+            rl = torch.as_tensor(np.ascontiguousarray(label_u8(lv))).to(device)
+        self.img = self.lab = None
+        self.intensity = []
+        for c, (nc, spec) in enumerate(zip(nis, specs)):
+            raw, code = _source_dtype(nc.data)
+            ri = torch.as_tensor(np.ascontiguousarray(raw)).to(device)
+            window = _resolve_intensity(spec, ri, nc.slope, nc.inter)
+            oi, ol = resample(ri, rl if c == 0 else None, self.matrix, self.shape, intensity_map(window, nc.slope, nc.inter), code)
+            if c == 0:
+                self.img, self.lab = torch.empty((K,) + tuple(oi.shape), device=oi.device, dtype=torch.float32), ol
+            self.img[c].copy_(oi)
+            self.intensity.append(window)
+        self.channels = K
+        self.pixdim = tuple(float(p) for p in pixdim)
+        self._label_host = self._crop_index = None
+
+
+def channel_seed(seed, c):
+    """the noise seed of channel c of a patch whose Augmentation.draw seed is `seed`: seed itself for c = 0, otherwise
+    seed ^ (c * 0x9E3779B97F4A7C15 mod 2^64); noise_reference(channel_seed(seed, c), count) replays channel c"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return seed if c == 0 else seed ^ ((int(c) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF)
+
+
 def orient_desc(flip, k):
     """(flip_h, flip_w, swap_hw) of "flip along axis 0 (if flip), then np.rot90(k, axes=(0, 1))" as the signed permutation
     out[x][y] = crop[a][b], (u, v) = swap ? (y, x) : (x, y), a = flip_h ? h-1-u : u, b = flip_w ? w-1-v : v"""
@@ -899,18 +956,26 @@ def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, 
     (round half even) with 0 outside.  noise_sigma [n] with seeds [n] (uint64) adds sigma_k * N(0, 1) to patch k in the store
     (noise_reference restates the generator).  elastic: [n, 3, gh, gw, gd] (ndarray or device tensor), one B-spline control lattice
     per patch in patch voxels; patch voxel p then reads the scan at M (p + u(p), 1), u = elastic_displacement (ltu_sample_elastic).
-    The lattice is checked on the host (extents 4 .. 8, finite, |phi| <= 64: ValueError) and uploaded once."""
+    The lattice is checked on the host (extents 4 .. 8, finite, |phi| <= 64: ValueError) and uploaded once.
+    A 4-D img [K,H,W,D] (K = 1 .. 4 channels on the label's grid, e.g. MultiScan.img) goes through ltu_sample_channels and returns
+    [n,K,h,w,d]: one gather whose coordinates, taps and label voxel are formed once for all channels.  fill is then a number or one
+    per channel, noise_sigma [n] or [n,K], seeds [n,K] (or [n]: channel c of patch k gets channel_seed(seeds[k], c)); channel c has
+    the bits of the 3-D call on img[c] with fill[c], noise_sigma[:, c] and seeds[:, c]."""
     if elastic is not None:
         elastic = _check_lattice(elastic)
     vol = img if img is not None else lab
     if vol is None or not vol.is_cuda:
         raise _lib.LtuError('data.sample_affine runs on the GPU only (no CPU fallback)')
-    if img is not None and lab is not None and img.shape != lab.shape:
+    multi = img is not None and img.dim() == 4
+    if img is not None and lab is not None and img.shape[-3:] != lab.shape:
         raise ValueError(f'image {tuple(img.shape)} and label {tuple(lab.shape)} differ in shape')
     if (img is not None and (img.dtype != torch.float32 or not img.is_contiguous())) or \
             (lab is not None and (lab.dtype != torch.uint8 or not lab.is_contiguous())):
         raise ValueError('sample_affine takes a contiguous float32 image and uint8 label')
-    H, W, D = vol.shape
+    K = int(img.shape[0]) if multi else 1
+    if not 1 <= K <= _lib.MAX_INPUT_CHANNELS:
+        raise ValueError(f'sample_affine takes 1 .. {_lib.MAX_INPUT_CHANNELS} channels, got {K}')
+    H, W, D = vol.shape[-3:]
     h, w, d = (int(s) for s in size)
     m = np.ascontiguousarray(np.asarray(mats, dtype=np.float64).reshape(-1, 12))
     n = m.shape[0]
@@ -918,25 +983,33 @@ def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, 
     if noise_sigma is not None:
         if seeds is None:
             raise ValueError('noise_sigma needs seeds')
-        sg = np.ascontiguousarray(np.asarray(noise_sigma, dtype=np.float32).reshape(n))
-        sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(n))
-    oi = torch.empty((n, 1, h, w, d), device=vol.device, dtype=torch.float32) if img is not None else None
+        sg = np.ascontiguousarray(np.broadcast_to(np.asarray(noise_sigma, dtype=np.float32).reshape(n, -1), (n, K)))
+        sd = np.asarray(seeds, dtype=np.uint64).reshape(n, -1)
+        if multi and sd.shape[1] == 1 and K > 1:
+            sd = np.array([[channel_seed(s, c) for c in range(K)] for s in sd[:, 0]], dtype=np.uint64)
+        sd = np.ascontiguousarray(sd.reshape(n, K))
+    oi = torch.empty((n, K, h, w, d), device=vol.device, dtype=torch.float32) if img is not None else None
     ol = torch.empty((n, 1, h, w, d), device=vol.device, dtype=torch.uint8) if lab is not None else None
+    g = (0, 0, 0)
     if elastic is not None:
         if elastic.shape[0] != n:
             raise ValueError(f'elastic holds {elastic.shape[0]} lattices for {n} matrices')
         lat = (elastic if torch.is_tensor(elastic) else torch.from_numpy(elastic)).to(vol.device)
         g = tuple(int(v) for v in lat.shape[2:])
+    if multi:
+        fl = np.ascontiguousarray(np.broadcast_to(np.asarray(fill, dtype=np.float32).reshape(-1), (K,)))
     for s in range(0, n, _lib.SAMPLE_AFFINE_MAX):
         e = min(n, s + _lib.SAMPLE_AFFINE_MAX)
-        if elastic is not None:
-            _lib.call('ltu_sample_elastic', _p(img), _p(lab), _p(oi[s:e]) if oi is not None else 0, _p(ol[s:e]) if ol is not None else 0,
-                      m[s:e].ctypes.data, _p(lat[s:e]), *g, sg[s:e].ctypes.data if sg is not None else 0,
-                      sd[s:e].ctypes.data if sd is not None else 0, e - s, H, W, D, h, w, d, float(fill), _s())
-            continue
-        _lib.call('ltu_sample_affine', _p(img), _p(lab), _p(oi[s:e]) if oi is not None else 0, _p(ol[s:e]) if ol is not None else 0,
-                  m[s:e].ctypes.data, sg[s:e].ctypes.data if sg is not None else 0, sd[s:e].ctypes.data if sd is not None else 0,
-                  e - s, H, W, D, h, w, d, float(fill), _s())
+        out = (_p(oi[s:e]) if oi is not None else 0, _p(ol[s:e]) if ol is not None else 0)
+        noise = (sg[s:e].ctypes.data if sg is not None else 0, sd[s:e].ctypes.data if sd is not None else 0)
+        if multi:
+            _lib.call('ltu_sample_channels', _p(img), _p(lab), *out, m[s:e].ctypes.data, _p(lat[s:e]) if elastic is not None else 0, *g,
+                      *noise, fl.ctypes.data, e - s, K, H, W, D, h, w, d, _s())
+        elif elastic is not None:
+            _lib.call('ltu_sample_elastic', _p(img), _p(lab), *out, m[s:e].ctypes.data, _p(lat[s:e]), *g, *noise, e - s, H, W, D, h, w, d,
+                      float(fill), _s())
+        else:
+            _lib.call('ltu_sample_affine', _p(img), _p(lab), *out, m[s:e].ctypes.data, *noise, e - s, H, W, D, h, w, d, float(fill), _s())
     return oi, ol
 
 
@@ -1074,14 +1147,37 @@ class Augmentation:
                                  f'= {cap:.3g} voxels (size {int(spatial_size[a])}, lattice {self.elastic_grid[a]})')
 
 
+def _multi(scan):
+    """the scan holds channels: img is [K, H, W, D] (a MultiScan)"""
+    img = getattr(scan, 'img', None)
+    return img is not None and img.dim() == 4
+
+
+def _scan_fill(scan, augment):
+    """the image value outside the scan: augment.fill, or (None) the floor of the scan's intensity window, 0.0 where it has none;
+    one per channel for a MultiScan"""
+    def floor(window):
+        lo = intensity_map(window)[2]
+        return float(lo) if np.isfinite(lo) else 0.0
+    multi = _multi(scan)
+    if augment is not None and augment.fill is not None:
+        return [float(augment.fill)] * scan.img.shape[0] if multi else augment.fill
+    if augment is None:
+        return [0.0] * scan.img.shape[0] if multi else 0.0
+    windows = getattr(scan, 'intensity', None)
+    return [floor(wd) for wd in windows] if multi else floor(windows)
+
+
 def _augmented(scan, draws, params, spatial_size, augment, spacing):
     """the patches of draws [(centre, flip, k)] under params (one Augmentation.draw per patch): one sample_affine, then one
-    gaussian_blur if a patch blurs or brightens, then adjust_contrast if a patch fires gamma"""
+    gaussian_blur if a patch blurs or brightens, then adjust_contrast if a patch fires gamma.  A MultiScan's K channels come out of
+    the one gather (noise per channel from channel_seed); blur, brightness and gamma see [n K, h, w, d] with each patch's
+    parameters repeated K times.  params None: the plain patches through patch_matrix's integer matrices (a MultiScan only)."""
     size = tuple(int(s) for s in spatial_size)
-    fill = augment.fill
-    if fill is None:
-        lo = intensity_map(getattr(scan, 'intensity', None))[2]
-        fill = float(lo) if np.isfinite(lo) else 0.0
+    fill = _scan_fill(scan, augment)
+    if params is None:
+        mats = [patch_matrix([max(c[a] - size[a] // 2, 0) for a in range(3)], size, f, k) for c, f, k in draws]
+        return sample_affine(scan.img, scan.lab, np.stack(mats), size, fill)
     mats = [patch_matrix([max(c[a] - size[a] // 2, 0) for a in range(3)], size, f, k,
                          p['angles'] if p['rotate'] else (0.0, 0.0, 0.0), p['zoom_factor'] if p['zoom'] else 1.0, spacing)
             for (c, f, k), p in zip(draws, params)]
@@ -1100,11 +1196,17 @@ def _augmented(scan, draws, params, spatial_size, augment, spacing):
     img, lab = sample_affine(scan.img, scan.lab, np.stack(mats), size, fill,
                              [p['noise_std'] if p['noise'] else 0.0 for p in params] if noisy else None,
                              [p['seed'] for p in params] if noisy else None, elastic=lattice)
+    shape, K = img.shape, img.shape[1]
+    img = img.view(-1, 1, *size)
+
+    def per_channel(values):
+        return [v for v in values for _ in range(K)]
     if any(p['blur'] or p['bright'] for p in params):
-        img = gaussian_blur(img, [p['sigma'] if p['blur'] else 0.0 for p in params], [p['mul'] if p['bright'] else 1.0 for p in params])
+        img = gaussian_blur(img, per_channel(p['sigma'] if p['blur'] else 0.0 for p in params),
+                            per_channel(p['mul'] if p['bright'] else 1.0 for p in params))
     if any(p['contrast'] for p in params):
-        img = adjust_contrast(img, [p['gamma'] if p['contrast'] else -1.0 for p in params])
-    return img, lab
+        img = adjust_contrast(img, per_channel(p['gamma'] if p['contrast'] else -1.0 for p in params))
+    return img.view(shape), lab
 
 
 def sample_draws(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_prob=0.5, host_centers=False, ratios=None,
@@ -1150,11 +1252,14 @@ def sample(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_p
     gamma; with elastic_prob > 0 also: deformation fire, its amplitude in millimetres, the control lattice).  The patches are then
     gathered through patch_matrix by one sample_affine (rotation in millimetres of scan.pixdim, the B-spline deformation of the
     patches that fire it folded into the same gather, noise in the store), blurred / brightened by one gaussian_blur and
-    gamma-adjusted by adjust_contrast.  None changes nothing: the same draws, patches and generator state."""
+    gamma-adjusted by adjust_contrast.  None changes nothing: the same draws, patches and generator state.
+    A MultiScan gives ([n,K,h,w,d] f32, [n,1,h,w,d] u8): the host draws do not depend on K, the K channels of a patch share its
+    geometry, blur, brightness and gamma and get independent noise (channel c from channel_seed(seed, c)); fill=None takes each
+    channel's own window floor.  Its plain path is the same gather through patch_matrix's integer matrices (the source voxels)."""
     if scan.lab is None:
         raise ValueError('sampling needs a label (RandCropByPosNegLabeld draws centres from it)')
     draws, params = sample_draws(scan, spatial_size, rand_state, num_samples, flip_prob, rot90_prob, host_centers, ratios, augment)
-    if augment is None:
+    if augment is None and not _multi(scan):
         return crop_orient(scan.img, scan.lab, draws, spatial_size)
     return _augmented(scan, draws, params, spatial_size, augment, getattr(scan, 'pixdim', (1.0, 1.0, 1.0)))
 

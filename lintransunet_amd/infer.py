@@ -117,9 +117,19 @@ def item_batches(items, sw_batch_size):
     return [items[g:g + sw_batch_size] for g in range(0, len(items), sw_batch_size)]
 
 
+def channel_items(items, channels):
+    """window descriptors of a [B, K, ...] volume viewed as B K single-channel volumes: every item (b, ...) becomes its K
+    descriptors (b K + c, ...), c = 0 .. K-1, adjacent and in channel order, so that a gather kernel, which writes its items
+    consecutively, fills windows [n, K, h, w, d].  channels == 1 returns the items as they are."""
+    K = int(channels)
+    if K == 1:
+        return list(items)
+    return [(it[0] * K + c, *it[1:]) for it in items for c in range(K)]
+
+
 def _blend_inference(vol, roi, pad_lo, img, starts, sw_batch_size, predictor, mode, sigma_scale, mirror_axes):
     """the weighted / mirrored path of sliding_window_inference (csrc/blend.hip)"""
-    B, img0, dev = vol.shape[0], tuple(int(v) for v in vol.shape[2:]), vol.device
+    B, K, img0, dev = vol.shape[0], vol.shape[1], tuple(int(v) for v in vol.shape[2:]), vol.device
     if int(sw_batch_size) < 1:
         raise ValueError(f'sw_batch_size must be >= 1, got {sw_batch_size}')
     g0, g1, g2, wmin = importance_tables(roi, mode, sigma_scale)
@@ -131,12 +141,14 @@ def _blend_inference(vol, roi, pad_lo, img, starts, sw_batch_size, predictor, mo
         n = len(chunk)
         parts = [(s, np.ascontiguousarray(chunk[s:s + _lib.BLEND_ITEMS_MAX], dtype=np.int32))
                  for s in range(0, n, _lib.BLEND_ITEMS_MAX)]
-        win = torch.empty((n, 1) + roi, device=dev, dtype=torch.float32)
-        for s, desc in parts:
-            _lib.call('ltu_window_gather_mirror', _p(vol), _p(win[s:]), desc.ctypes.data, len(desc), B, *img0, *img, *roi, _s())
+        win = torch.empty((n, K) + roi, device=dev, dtype=torch.float32)
+        flat, expanded = win.view((n * K,) + roi), channel_items(chunk, K)        # the gather's items: one per window and channel
+        for s in range(0, n * K, _lib.BLEND_ITEMS_MAX):
+            desc = np.ascontiguousarray(expanded[s:s + _lib.BLEND_ITEMS_MAX], dtype=np.int32)
+            _lib.call('ltu_window_gather_mirror', _p(vol), _p(flat[s:]), desc.ctypes.data, len(desc), B * K, *img0, *img, *roi, _s())
         seg = predictor(win)
         if seg.dim() != 5 or tuple(seg.shape[2:]) != roi or seg.shape[0] != n:
-            raise _lib.LtuError(f'predictor returned {tuple(seg.shape)} for windows {(n, 1) + roi}')
+            raise _lib.LtuError(f'predictor returned {tuple(seg.shape)} for windows {(n, K) + roi}')
         seg_cl = seg.permute(0, 2, 3, 4, 1)
         if seg_cl.dtype != torch.float32 or not seg_cl.is_contiguous():
             seg_cl = seg_cl.to(torch.float32).contiguous()
@@ -156,9 +168,10 @@ def _blend_inference(vol, roi, pad_lo, img, starts, sw_batch_size, predictor, mo
 
 def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.25, mode='constant', sigma_scale=0.125,
                              mirror_axes=()):
-    """inputs f32 [B, 1, H, W, D] on the GPU; predictor(windows [n, 1, h, w, d]) -> [n, C, h, w, d] (the eval-mode
-    MaskTransUnet: channels-last one-hot exposed in the reference's shape, or its softmax with probs=True).  Returns f32
-    [B, C, H, W, D], the per-voxel weighted average of the window outputs.
+    """inputs f32 [B, K, H, W, D] on the GPU, K = 1 .. 4 input channels; predictor(windows [n, K, h, w, d]) -> [n, C, h, w, d]
+    (the eval-mode MaskTransUnet: channels-last one-hot exposed in the reference's shape, or its softmax with probs=True).
+    Returns f32 [B, C, H, W, D], the per-voxel weighted average of the window outputs.  The K channels of a window are gathered as
+    K items of the single-channel gather kernels (channel_items); an output channel's sums do not depend on C.
 
     mode='constant' without mirror_axes is monai's mode="constant" (the reference's call): the plain average, on the vote
     kernels of csrc/infer.hip.  Otherwise (csrc/blend.hip): mode='gaussian' weights window voxel u by importance_tables(roi,
@@ -170,9 +183,9 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     mode, sig, axes = _blend_options(mode, sigma_scale, mirror_axes)
     if not inputs.is_cuda:
         raise _lib.LtuError('sliding_window_inference runs on the GPU only (no CPU fallback)')
-    if inputs.dim() != 5 or inputs.shape[1] != 1:
-        raise _lib.LtuError('inputs must be [B, 1, H, W, D]')
-    B = inputs.shape[0]
+    if inputs.dim() != 5 or not 1 <= inputs.shape[1] <= _lib.MAX_INPUT_CHANNELS:
+        raise _lib.LtuError(f'inputs must be [B, K, H, W, D] with K = 1 .. {_lib.MAX_INPUT_CHANNELS}')
+    B, K = inputs.shape[0], inputs.shape[1]
     img0 = tuple(int(v) for v in inputs.shape[2:])
     roi = tuple(int(r) if r and r > 0 else i for r, i in zip(roi_size, img0))
     pad_lo = tuple(max(r - i, 0) // 2 for r, i in zip(roi, img0))
@@ -187,14 +200,17 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     C = None
     for g in range(0, total, sw_batch_size):
         idxs = range(g, min(g + sw_batch_size, total))
-        desc = torch.tensor([[idx // nwin, *starts[idx % nwin]] for idx in idxs], dtype=torch.int32).to(dev)
+        items = [(idx // nwin, *starts[idx % nwin]) for idx in idxs]
+        desc = torch.tensor(items, dtype=torch.int32).reshape(-1, 4).to(dev)
+        # the volume as B K single-channel volumes, one gather item per window and channel; the votes keep the windows' descriptors
+        gdesc = desc if K == 1 else torch.tensor(channel_items(items, K), dtype=torch.int32).to(dev)
         n = len(idxs)
-        win = torch.empty((n, 1) + roi, device=dev, dtype=torch.float32)
-        _lib.call('ltu_window_gather', _p(vol), _p(win), _p(desc), n, img0[0], img0[1], img0[2], roi[0], roi[1], roi[2],
+        win = torch.empty((n, K) + roi, device=dev, dtype=torch.float32)
+        _lib.call('ltu_window_gather', _p(vol), _p(win), _p(gdesc), n * K, img0[0], img0[1], img0[2], roi[0], roi[1], roi[2],
                   pad_lo[0], pad_lo[1], pad_lo[2], _s())
         seg = predictor(win)
         if seg.dim() != 5 or tuple(seg.shape[2:]) != roi or seg.shape[0] != n:
-            raise _lib.LtuError(f'predictor returned {tuple(seg.shape)} for windows {(n, 1) + roi}')
+            raise _lib.LtuError(f'predictor returned {tuple(seg.shape)} for windows {(n, K) + roi}')
         seg_cl = seg.permute(0, 2, 3, 4, 1)
         if seg_cl.dtype != torch.float32 or not seg_cl.is_contiguous():
             seg_cl = seg_cl.to(torch.float32).contiguous()
@@ -524,7 +540,7 @@ class GraphedPredictor:
 
     def __init__(self, model, batch, roi, device, probs=False):
         self.model, self.n, self.probs = model, batch, bool(probs)
-        self.x = torch.zeros((batch, 1) + tuple(roi), device=device, dtype=torch.float32)
+        self.x = torch.zeros((batch, model.dim_input) + tuple(roi), device=device, dtype=torch.float32)
         self.ctx = ops.Context()          # own scratch arena: the graph bakes its addresses in, nobody else may move it
         fwd = (lambda x: model(x, probs=True)) if self.probs else model
         side = torch.cuda.Stream(device=device)
@@ -576,7 +592,8 @@ def infer_volume(model, images, depth_size=32, roi_xy=512, sw_batch_size=4, over
 
 
 def segment_scan(models, scan, classes=(), **infer_volume_kwargs):
-    """a data.SpacedScan to its prediction on the file's grid: infer_volume(model, scan.img[None, None], probs=True, ...) per
+    """a data.SpacedScan (or MultiScan) to its prediction on the file's grid: infer_volume(model, scan.img[None, None] (a
+    MultiScan: scan.img[None]), probs=True, ...) per
     member of `models` (one model or a sequence: the folds or checkpoints of an ensemble), the members' softmaxes summed in fp32 in
     member order, then one data.to_native_probs.  Defaults here: mode='gaussian', mirror_axes=(0, 1); every other default is
     infer_volume's.  The sum is not divided for the label (the arg-max does not change under a positive scale); with `classes` it is
@@ -588,8 +605,9 @@ def segment_scan(models, scan, classes=(), **infer_volume_kwargs):
     kw = dict(mode='gaussian', mirror_axes=(0, 1))
     kw.update(infer_volume_kwargs)
     total = None
+    images = scan.img[None] if scan.img.dim() == 4 else scan.img[None, None]
     for model in members:
-        p = infer_volume(model, scan.img[None, None], probs=True, **kw)
+        p = infer_volume(model, images, probs=True, **kw)
         total = p if total is None else total.add_(p)
     if classes and len(members) > 1:
         total.mul_(1.0 / len(members))

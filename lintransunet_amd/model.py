@@ -5,9 +5,12 @@ Drop-in contract:
     kernel_size=3, dropout=0.3)` builds a module whose `state_dict()` has exactly the reference's
     614 keys / shapes (checkpoints load with strict=True, including the 14 unused
     `decode.bridge_list.4.transformer.pos_encoders.{1..7}` tensors).
-  * `forward(x[B,1,H,W,D])` returns `(probs[B,C,H,W,D], [mask]*4)` in training mode and the one-hot
+  * `forward(x[B,dim_input,H,W,D])` returns `(probs[B,C,H,W,D], [mask]*4)` in training mode and the one-hot
     arg-max tensor in eval mode.  Returned tensors are channels-last in memory, exposed through a
     permuted view so indexing/shape follow the reference.
+  * `dim_input` = 1 .. 4 (the reference builds `Conv3d(dim_input * 4, ...)` but its window embedding reshapes one channel
+    only): input channel c fills the stem's channels 4c .. 4c + 3, so `encode.input_block.weight` is `[L0, 4 dim_input, 3, 3, 3]`
+    and every other key keeps its shape.
 
 The parameter containers are plain torch modules (they provide names, initialisation and the
 optimizer/DDP plumbing); their own forward() is never called - all arithmetic goes through
@@ -205,8 +208,9 @@ class MaskTransUnet(nn.Module):
         super().__init__()
         if kernel_size != 3:
             raise ValueError('only the reference default kernel_size=3 is supported')
-        if dim_input != 1:
-            raise ValueError('window embedding of the reference assumes dim_input=1 (Unet_3Dblock.py:131-132)')
+        # the reference's windows_embedding reshape assumes one channel (Unet_3Dblock.py:131-132); here channel c of the input fills
+        # the stem's channels 4c .. 4c + 3, the inverse of its windows_unembedding
+        ops.embed_channels(dim_input)        # ValueError outside 1 .. 4
         L = list(num_layers)
         nl = len(L)
         self.num_layers, self.roi_size_list, self.is_roi_list = L, list(roi_size_list), list(is_roi_list)
@@ -272,7 +276,7 @@ class MaskTransUnet(nn.Module):
             return st
         st = _WeightStore(device, self.act_dtype)
         enc, dec = self.encode, self.decode
-        st.add_conv(enc.input_block, cip=8)
+        st.add_conv(enc.input_block, cip=ops.embed_channels(self.dim_input))
         for blk in enc.block_list:
             st.add_conv(blk.conv1)
             st.add_conv(blk.conv2)
@@ -431,7 +435,9 @@ class MaskTransUnet(nn.Module):
         self._step += 1
         seeds = _SeedStream(torch.initial_seed() * 1000003 + self._step)
         self.last_boxes = []
-        B, _, H, W, D = x.shape
+        B, K, H, W, D = x.shape
+        if K != self.dim_input:
+            raise ValueError(f'the model was built for dim_input={self.dim_input}, got {K} input channels')
         if H % 2 or W % 2:
             raise ValueError('H and W must be even')
         enc, dec = self.encode, self.decode

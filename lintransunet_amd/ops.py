@@ -553,12 +553,23 @@ class LinPrep:
 # ---------------------------------------------------------------------------------------------- no-grad helpers
 
 def window_embed(x, dtype):
-    """[B,1,H,W,D] fp32 (reference layout) -> [B,H/2,W/2,D,8] channels-last, channels 4..7 zero."""
+    """[B,K,H,W,D] fp32 (reference layout), K = 1 .. 4 -> [B,H/2,W/2,D,CP] channels-last, CP = embed_channels(K): channel
+    4c + 2kh + kw = x[b, c, 2h+kh, 2w+kw, d], channels 4K .. CP-1 zero.  K = 1 goes through ltu_window_embed as before."""
     _chk(x, 'x')
-    B, _, H, W, D = x.shape
-    y = torch.empty((B, H // 2, W // 2, D, 8), device=x.device, dtype=dtype)
-    _lib.call('ltu_window_embed', _p(x), _p(y), _dt(y), B, H, W, D, _s())
+    B, K, H, W, D = x.shape
+    y = torch.empty((B, H // 2, W // 2, D, embed_channels(K)), device=x.device, dtype=dtype)
+    if K == 1:
+        _lib.call('ltu_window_embed', _p(x), _p(y), _dt(y), B, H, W, D, _s())
+    else:
+        _lib.call('ltu_window_embed_multi', _p(x), _p(y), _dt(y), B, K, H, W, D, _s())
     return y
+
+
+def embed_channels(dim_input):
+    """padded channel count of the window embedding of dim_input channels: 8 * ceil(4 dim_input / 8); ValueError outside 1 .. 4"""
+    if not isinstance(dim_input, int) or not 1 <= dim_input <= _lib.MAX_INPUT_CHANNELS:
+        raise ValueError(f'dim_input must be 1 .. {_lib.MAX_INPUT_CHANNELS}, got {dim_input!r}')
+    return (4 * dim_input + 7) // 8 * 8
 
 
 def label_maxpool(lab, kd):
