@@ -725,6 +725,35 @@ int ltu_resample_grid(const void* src_img, int src_dtype, const uint8_t* src_lab
 int ltu_resample_argmax(const float* probs, int C, long long cs, int S0, int S1, int S2, long long ss0, long long ss1, long long ss2,
                         uint8_t* out_lab, float* out_prob, int class_mask, long long ocs, int O0, int O1, int O2, long long os0,
                         long long os1, long long os2, const double* mat, int lane_axis, ltu_stream_t s);
+/* ---- cubic B-spline resampling (csrc/spline.hip; nnU-Net's image interpolation, no reference counterpart: the driver's Spacingd is
+ * trilinear).  Two calls: spline_prefilter turns a stored scan into B-spline coefficients, resample_spline gathers them through the
+ * pull matrix of resample_grid.  order0..2 (one per SOURCE axis, each 0, 1 or 3) mean the same in both calls.
+ * spline_prefilter: src as resample_grid's src_img (src_dtype LTU_U8 / LTU_I16 / LTU_F32, shape S0 x S1 x S2, element strides
+ *   ss0..2); every voxel is mapped as it is loaded, clamp(alpha * v + beta, lo, hi).  coef: dense f32, S0 S1 S2 elements, axis 0
+ *   fastest (strides 1, S0, S0 S1).  An axis of order 3 and length > 1 is filtered along itself as scipy.ndimage.spline_filter1d(
+ *   order 3, mode 'mirror'): pole z = sqrt(3) - 2, the samples times the gain 6, a causal recursion c+[i] = s[i] + z c+[i-1] from
+ *   c+[0] = sum_k z^k s[mirror(k)] (whole-sample mirror, period 2 n - 2: the exact periodic sum for n <= 24, cut after 24 terms
+ *   above that, |z|^24 = 1.9e-14), then c[n-1] = z / (z^2 - 1) (c+[n-1] + z c+[n-2]), c[i] = z (c[i+1] - c+[i]).  An axis of order
+ *   0 or 1, or of length 1, is left alone.  Axis 0 goes through 16 x 64 LDS tiles with the recursion state carried along the line,
+ *   axes 1 and 2 are walked in place with the lanes along axis 0.  fp32, explicit fused multiply-adds in a fixed order, no atomics,
+ *   no workspace: two calls give the same bytes.  LTU_E_ARG: NULL src or coef, an order outside {0, 1, 3}, a NaN in the map;
+ *   LTU_E_DTYPE: src_dtype; LTU_E_SHAPE: a size or stride < 1, a volume of 2^31 voxels or more. */
+int ltu_spline_prefilter(const void* src, int src_dtype, int S0, int S1, int S2, long long ss0, long long ss1, long long ss2,
+                         float* coef, int order0, int order1, int order2, float alpha, float beta, float lo, float hi,
+                         ltu_stream_t s);
+/* resample_spline: out[p] = clamp(sum_ijk w0[i] w1[j] w2[k] coef[tap0[i]][tap1[j]][tap2[k]], lo, hi) at c = M (p, 1), formed and
+ *   clamped to [0, size - 1] exactly as resample_grid does (mat, out shape O0 x O1 x O2, strides os0..2, lane_axis and the two tile
+ *   paths as there).  coef: what spline_prefilter wrote for the same orders (dense, axis 0 fastest).  Per source axis, f = floor(c),
+ *   t = c - f: order 3 taps f-1 .. f+2 with weights ((1-t)^3, 3t^3 - 6t^2 + 4, -3t^3 + 3t^2 + 3t + 1, t^3) / 6; order 1 taps f, f+1
+ *   with (1-t, t); order 0 the tap floor(c + 1/2).  A tap index outside [0, n-1] is mirrored (whole-sample, period 2 n - 2; 0 when
+ *   n = 1).  The sum runs in fp32 in a fixed order: axis 0 innermost as a fused multiply-add chain, then (w2 w1) row added by one
+ *   fused multiply-add, axis 1 inside axis 2.  lo / hi: the intensity map's clip (the spline rings past a clipped window); -inf /
+ *   +inf leave the sum as it is.  Orders built: (3, 3, 3), and 3 on two axes with 0 or 1 on the third; any other triple of
+ *   {0, 1, 3} is LTU_E_ARG, as are a NULL pointer, lane_axis outside 0..2 and a NaN bound.  LTU_E_SHAPE: a size or stride < 1, a
+ *   coefficient volume of 2^31 elements or more (tap offsets are 32-bit). */
+int ltu_resample_spline(const float* coef, int S0, int S1, int S2, int order0, int order1, int order2, float* out, int O0, int O1,
+                        int O2, long long os0, long long os1, long long os2, const double* mat, int lane_axis, float lo, float hi,
+                        ltu_stream_t s);
 /* crop_orient: patches [n][h][w][d] (f32 and / or u8, either pair NULL, not both) cut from vol [H][W][D] at desc, a HOST int32 array
  * [n][6] = (h0, w0, d0, flip_h, flip_w, swap_hw): out[k][x][y][z] = vol[h0 + a][w0 + b][d0 + z] with (u, v) = swap_hw ? (y, x) :
  * (x, y), a = flip_h ? h-1-u : u, b = flip_w ? w-1-v : v - a signed permutation of the (h, w) plane, which expresses "flip along

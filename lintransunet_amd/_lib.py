@@ -110,6 +110,8 @@ SIGNATURES = {
     'ltu_crop_flip': [P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_resample_grid': [P, I, P, I, I, I, L, L, L, P, P, I, I, I, L, L, L, P, I, F, F, F, F, P],
     'ltu_resample_argmax': [P, I, L, I, I, I, L, L, L, P, P, I, L, I, I, I, L, L, L, P, I, P],
+    'ltu_spline_prefilter': [P, I, I, I, I, L, L, L, P, I, I, I, F, F, F, F, P],
+    'ltu_resample_spline': [P, I, I, I, I, I, I, P, I, I, I, L, L, L, P, I, F, F, P],
     'ltu_crop_orient': [P, P, P, P, P, I, I, I, I, I, I, I, P],
     'ltu_crop_index_elems': [L],
     'ltu_crop_index_build': [P, L, P, L, P, P],

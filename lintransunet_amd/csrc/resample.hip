@@ -4,6 +4,7 @@
 // lintransunet_amd/geometry.py); a raw scan is uploaded once as stored (x fastest) and resampled straight into the RAS [H][W][D]
 // volume the rest of the project reads.
 #include "common.h"
+#include "resample_coords.h"
 
 // ---- resampling: out[p] = sample(src, M (p, 1)) ------------------------------------------------------------------------------
 // Tile = 64 outputs along the lane axis P (the output axis whose step moves the source address least: lanes of a wave then read
@@ -30,13 +31,7 @@ __device__ __forceinline__ float tap(const T* __restrict__ p) { return (float)*p
 // IDX: int when every source offset fits in 31 bits (the tap addressing is then 32-bit; the kernel is VALU-bound)
 // The tap code is shared by resample_grid_kernel and resample_argmax_kernel, so that a channel resampled by either has the same bits:
 // clamp_coords (border padding), tap_setup (per source axis the offsets of the two taps and the fp32 weight of the upper one) and
-// tap_sum (the 8 taps in the order k = 0 .. 7, each mapped first).
-__device__ __forceinline__ void clamp_coords(const int* S, double c0, double c1, double c2, double* c) {
-  c[0] = fmin(fmax(c0, 0.0), (double)(S[0] - 1));
-  c[1] = fmin(fmax(c1, 0.0), (double)(S[1] - 1));
-  c[2] = fmin(fmax(c2, 0.0), (double)(S[2] - 1));
-}
-
+// tap_sum (the 8 taps in the order k = 0 .. 7, each mapped first).  clamp_coords lives in resample_coords.h, shared with spline.hip.
 template <typename IDX>
 __device__ __forceinline__ void tap_setup(const int* S, const long long* ss, const double* c, IDX* o0, IDX* o1, float* t) {
 #pragma unroll

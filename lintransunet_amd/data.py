@@ -391,21 +391,71 @@ def label_u8(a):
     return a.astype(np.uint8)
 
 
+SPLINE_ORDERS = (0, 1, 3)             # per source axis: nearest, linear, cubic B-spline
+
+
+def resolve_order(order):
+    """an interpolation `order` (1, 3, or one of 0 / 1 / 3 per source axis) as the 3-tuple the kernels take.  Built: (1, 1, 1) (the
+    trilinear kernel), (3, 3, 3), and 3 on two axes with 0 or 1 on the third; anything else is a ValueError."""
+    if isinstance(order, (int, np.integer)) and not isinstance(order, bool):
+        if int(order) not in (1, 3):
+            raise ValueError(f'order is 1, 3 or a 3-tuple of {SPLINE_ORDERS}, got {order!r}')
+        return (int(order),) * 3
+    try:
+        orders = tuple(int(o) for o in order)
+        exact = all(o == v for o, v in zip(orders, order))
+    except (TypeError, ValueError):
+        orders, exact = (), False
+    if len(orders) != 3 or not exact or any(o not in SPLINE_ORDERS for o in orders):
+        raise ValueError(f'order is 1, 3 or a 3-tuple of {SPLINE_ORDERS}, got {order!r}')
+    if orders != (1, 1, 1) and sum(o == 3 for o in orders) < 2:
+        raise ValueError(f'orders {orders} are not built: (1, 1, 1), (3, 3, 3), or 3 on two axes with 0 or 1 on the third')
+    return orders
+
+
+def _source_layout(src, src_strides):
+    """(shape, element strides) per source axis of a device source: x fastest ([S2][S1][S0]) unless strides are given"""
+    if src_strides is None:
+        S = tuple(int(n) for n in src.shape[::-1])
+        return S, (1, S[0], S[0] * S[1])
+    return tuple(int(n) for n in src.shape), tuple(int(s) for s in src_strides)
+
+
+def spline_coefficients(src, orders, imap=(1.0, 0.0, -np.inf, np.inf), src_dtype=0, src_strides=None):
+    """ltu_spline_prefilter: the cubic B-spline coefficients of a device scan as stored (src_dtype, shape and `src_strides` as
+    data.resample), every voxel mapped first (clamp(alpha * v + beta, lo, hi)): an axis of order 3 is filtered as
+    scipy.ndimage.spline_filter1d(order=3, mode='mirror') filters it, an axis of order 0 or 1 (or of length 1) is left alone.
+    Returns a dense f32 tensor [S2][S1][S0] (the source's axes, x fastest)."""
+    if not torch.is_tensor(src) or not src.is_cuda:
+        raise _lib.LtuError('data.spline_coefficients runs on the GPU only (no CPU fallback)')
+    orders = tuple(int(o) for o in orders)
+    if len(orders) != 3 or any(o not in SPLINE_ORDERS for o in orders):
+        raise ValueError(f'orders is a 3-tuple of {SPLINE_ORDERS}, got {orders}')
+    if src.dim() != 3:
+        raise ValueError(f'spline_coefficients takes one volume, got {tuple(src.shape)}')
+    S, ss = _source_layout(src, src_strides)
+    coef = torch.empty(S[::-1], device=src.device, dtype=torch.float32)
+    _lib.call('ltu_spline_prefilter', _p(src), int(src_dtype), *S, *ss, _p(coef), *orders, *(float(v) for v in imap), _s())
+    return coef
+
+
 def resample(src_img, src_lab, matrix, out_shape, imap=(1.0, 0.0, -np.inf, np.inf), src_dtype=0, src_strides=None,
-             out_strides=None, lane_axis=None):
+             out_strides=None, lane_axis=None, order=1):
     """ltu_resample_grid: device sources (image of src_dtype / u8 label, either None) of shape (S0, S1, S2) read through
     `src_strides` (default: x fastest, i.e. a [S2][S1][S0] array), resampled through the 3x4 float64 pull matrix to outputs of
-    out_shape (default layout: [O0][O1][O2], the last axis fastest).  Returns (f32 image or None, u8 label or None)."""
+    out_shape (default layout: [O0][O1][O2], the last axis fastest).  Returns (f32 image or None, u8 label or None).
+    order: the image's interpolation, 1 (trilinear, the call as it always was), 3 (cubic B-spline) or one of 0 / 1 / 3 per source
+    axis (resolve_order).  Anything but 1 prefilters the mapped scan (spline_coefficients) and gathers the coefficients through the
+    same matrix (ltu_resample_spline), clamped to the map's [lo, hi]; the label still goes nearest through ltu_resample_grid."""
     src = src_img if src_img is not None else src_lab
     if src is None or not src.is_cuda:
         raise _lib.LtuError('data.resample runs on the GPU only (no CPU fallback)')
+    orders = resolve_order(order)
     if src_img is not None and src_lab is not None and (src_img.shape != src_lab.shape or src_img.stride() != src_lab.stride()):
         raise ValueError(f'image {tuple(src_img.shape)} and label {tuple(src_lab.shape)} are sampled through one matrix: same layout needed')
-    S = tuple(int(n) for n in src.shape[::-1]) if src_strides is None else None
-    if src_strides is None:
-        src_strides = (1, S[0], S[0] * S[1])
-    else:
-        S = tuple(int(n) for n in src.shape)
+    spline = src_img is not None and orders != (1, 1, 1)
+    coef = spline_coefficients(src_img, orders, imap, src_dtype, src_strides) if spline else None
+    S, src_strides = _source_layout(src, src_strides)
     O = tuple(int(n) for n in out_shape)
     if out_strides is None:
         out_strides, alloc = (O[1] * O[2], O[2], 1), O
@@ -413,10 +463,19 @@ def resample(src_img, src_lab, matrix, out_shape, imap=(1.0, 0.0, -np.inf, np.in
         alloc = tuple(O[a] for a in np.argsort(out_strides)[::-1])
     m = np.asarray(matrix, dtype=np.float64).reshape(3, 4)
     mat = torch.as_tensor(m.ravel().copy()).to(src.device)
-    lane = geometry.lane_axis(m, src_strides) if lane_axis is None else lane_axis
     oi = torch.empty(alloc, device=src.device, dtype=torch.float32) if src_img is not None else None
     ol = torch.empty(alloc, device=src.device, dtype=torch.uint8) if src_lab is not None else None
-    _lib.call('ltu_resample_grid', _p(src_img), int(src_dtype), _p(src_lab), *S, *(int(s) for s in src_strides), _p(oi), _p(ol),
+    if spline:
+        # the coefficients are dense with x fastest whatever the source's strides were: the lane axis follows THEIR layout
+        lane = geometry.lane_axis(m, (1, S[0], S[0] * S[1])) if lane_axis is None else lane_axis
+        _lib.call('ltu_resample_spline', _p(coef), *S, *orders, _p(oi), *O, *(int(s) for s in out_strides), _p(mat), lane,
+                  float(imap[2]), float(imap[3]), _s())
+        del coef
+        if src_lab is None:
+            return oi, ol
+    gi, go = (None, None) if spline else (src_img, oi)          # after the spline gather only the label is left, nearest
+    lane = geometry.lane_axis(m, src_strides) if lane_axis is None else lane_axis
+    _lib.call('ltu_resample_grid', _p(gi), int(src_dtype), _p(src_lab), *S, *src_strides, _p(go), _p(ol),
               *O, *(int(s) for s in out_strides), _p(mat), lane, *(float(v) for v in imap), _s())
     return oi, ol
 
@@ -740,13 +799,18 @@ class SpacedScan:
     matrix: the 3x4 float64 pull matrix (RAS voxel -> file voxel); native_shape / native_affine / native: the file's grid and header.
     intensity: a ScaleIntensityRange window (a_min, a_max, b_min, b_max) applied with its clip, None for the scaled voxels as they
     are, an IntensityFingerprint for its window(), or 'zscore' for this scan's own mean and standard deviation over all voxels; the
-    attribute `intensity` keeps the resulting 4-tuple (or None)."""
+    attribute `intensity` keeps the resulting 4-tuple (or None).
+    order: the image's interpolation as data.resample takes it (1: trilinear, the driver's; 3: cubic B-spline; a 3-tuple per FILE
+    axis), or 'auto' for geometry.resample_orders of the file's voxel sizes and pixdim (nnU-Net's rule: the coarse axis of an
+    anisotropic scan goes nearest); the attribute `order` keeps the resolved 3-tuple.  The label is nearest whatever the order."""
 
-    def __init__(self, img_path, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda'):
+    def __init__(self, img_path, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda',
+                 order=1):
         ni = nifti.load(img_path)
         nl = nifti.load(lab_path) if lab_path is not None else None
         if nl is not None:
             geometry.check_pair(ni.shape, ni.affine, nl.shape, nl.affine)
+        self.order = _scan_order(order, ni.affine, pixdim)
         self.native, self.native_shape, self.native_affine = ni, ni.shape, ni.affine
         self.matrix, self.shape, self.affine = geometry.spacing_plan(ni.shape, ni.affine, pixdim, axcodes)
         raw, code = _source_dtype(ni.data)
@@ -756,7 +820,8 @@ class SpacedScan:
             lv = nl.data if (nl.slope, nl.inter) == (1.0, 0.0) else nl.scaled()
             rl = torch.as_tensor(np.ascontiguousarray(label_u8(lv))).to(device)
         intensity = _resolve_intensity(intensity, ri, ni.slope, ni.inter)
-        self.img, self.lab = resample(ri, rl, self.matrix, self.shape, intensity_map(intensity, ni.slope, ni.inter), code)
+        self.img, self.lab = resample(ri, rl, self.matrix, self.shape, intensity_map(intensity, ni.slope, ni.inter), code,
+                                      order=self.order)
         self.pixdim, self.intensity = tuple(float(p) for p in pixdim), intensity      # sample(augment=) rotates in mm, fills with the window's floor
         self._label_host = self._crop_index = None
 
@@ -773,6 +838,15 @@ class SpacedScan:
         return self._crop_index
 
 
+def _scan_order(order, affine, pixdim):
+    """SpacedScan's `order` as the 3-tuple per file axis; 'auto' asks geometry.resample_orders"""
+    if isinstance(order, str):
+        if order != 'auto':
+            raise ValueError(f"order is 1, 3, a 3-tuple or 'auto', got {order!r}")
+        return resolve_order(geometry.resample_orders(geometry.voxel_spacing(affine), pixdim))
+    return resolve_order(order)
+
+
 def _is_number(v):
     return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
 
@@ -783,9 +857,11 @@ class MultiScan(SpacedScan):
     Each channel is resampled exactly as SpacedScan resamples it alone; img: one contiguous f32 [K, H, W, D]; lab, crop_index,
     label_host, matrix, affine, shape, pixdim as on SpacedScan, native / native_shape / native_affine are channel 0's.
     intensity: one spec for all channels (a window 4-tuple, None, an IntensityFingerprint or 'zscore') or a sequence of K specs;
-    the attribute `intensity` is the list of the K resulting tuples (or None).  channels == K."""
+    the attribute `intensity` is the list of the K resulting tuples (or None).  channels == K.  order: as SpacedScan's, one for all
+    channels."""
 
-    def __init__(self, img_paths, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda'):
+    def __init__(self, img_paths, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda',
+                 order=1):
         paths = [img_paths] if isinstance(img_paths, (str, bytes)) or hasattr(img_paths, '__fspath__') else list(img_paths)
         K = len(paths)
         if not 1 <= K <= _lib.MAX_INPUT_CHANNELS:
@@ -802,6 +878,7 @@ class MultiScan(SpacedScan):
             geometry.check_pair(ni.shape, ni.affine, other.shape, other.affine)
         self.native, self.native_shape, self.native_affine = ni, ni.shape, ni.affine
         self.matrix, self.shape, self.affine = geometry.spacing_plan(ni.shape, ni.affine, pixdim, axcodes)
+        self.order = _scan_order(order, ni.affine, pixdim)
         rl = None
         if nl is not None:
             lv = nl.data if (nl.slope, nl.inter) == (1.0, 0.0) else nl.scaled()
@@ -812,7 +889,8 @@ class MultiScan(SpacedScan):
             raw, code = _source_dtype(nc.data)
             ri = torch.as_tensor(np.ascontiguousarray(raw)).to(device)
             window = _resolve_intensity(spec, ri, nc.slope, nc.inter)
-            oi, ol = resample(ri, rl if c == 0 else None, self.matrix, self.shape, intensity_map(window, nc.slope, nc.inter), code)
+            oi, ol = resample(ri, rl if c == 0 else None, self.matrix, self.shape, intensity_map(window, nc.slope, nc.inter), code,
+                              order=self.order)
             if c == 0:
                 self.img, self.lab = torch.empty((K,) + tuple(oi.shape), device=oi.device, dtype=torch.float32), ol
             self.img[c].copy_(oi)

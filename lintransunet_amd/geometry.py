@@ -141,6 +141,25 @@ def spacing_plan(shape, affine, pixdim=(0.5, 0.5, 2.0), axcodes='RAS'):
     return (transform @ undo)[:3], tuple(final_shape), new_affine @ undo
 
 
+def voxel_spacing(affine):
+    """the voxel sizes of a 4x4 affine per file axis: its column norms"""
+    return tuple(float(v) for v in np.sqrt(np.sum(np.square(np.asarray(affine, dtype=np.float64)[:3, :3]), axis=0)))
+
+
+def resample_orders(spacing, new_spacing, threshold=3.0):
+    """nnU-Net's interpolation orders for an image, per file axis (restated from its resample_data_or_seg_to_shape /
+    get_do_separate_z / get_lowres_axis; nnU-Net is no dependency, so parity with it is unpinned): cubic (3) on every axis, unless
+    the scan is anisotropic - max / min of `spacing` (the file's voxel sizes) above `threshold` with exactly one axis holding the
+    maximum, which then gets 0 (nearest across slices); failing that, the same test on `new_spacing` (the target's)."""
+    for sp in (spacing, new_spacing):
+        sp = np.asarray(sp, dtype=np.float64).reshape(3)
+        if not np.all(np.isfinite(sp)) or np.any(sp <= 0):
+            raise ValueError(f'spacings are positive and finite, got {tuple(sp)}')
+        if sp.max() / sp.min() > threshold and np.count_nonzero(sp == sp.max()) == 1:
+            return tuple(0 if a == int(np.argmax(sp)) else 3 for a in range(3))
+    return (3, 3, 3)
+
+
 def check_pair(img_shape, img_affine, lab_shape, lab_affine, atol=1e-3):
     """an image / label pair is sampled through one matrix: shapes equal and affines within `atol`"""
     if tuple(img_shape) != tuple(lab_shape):
