@@ -613,6 +613,16 @@ int ltu_lesion_heads(const float* pred, const uint8_t* target, int* heads, int B
 int ltu_lesion_stats(const float* pred, const uint8_t* target, int* ints, float* rates, void* scratch, long long scratch_elems,
                      long long pairs, int B, int C, int k, int kk, int K, int H, int W, int D, float threshold, int connectivity,
                      ltu_stream_t s);
+/* fill_holes (scipy.ndimage.binary_fill_holes(mask[b], generate_binary_structure(3, connectivity)); monai FillHoles): mask u8
+ * [B][H][W][D] (nonzero = set) -> out u8 [B][H][W][D] = 1 on the mask and on every background voxel whose background component
+ * (adjacency of `connectivity`, as above) touches no face of the volume, 0 elsewhere.  The complement is labelled with the
+ * union-find above, one pass over the six faces marks the roots of the components that reach a face (plain stores of one value),
+ * one pass writes out: five launches, no host read, capturable; integer work only, two calls are bit-identical.  out == mask (in
+ * place) is allowed: the mask is read by the labelling only.  scratch: ltu_fill_holes_ws_elems(B, H, W, D) int32 (0 for a refused
+ * shape).  Shape rules and error codes as ltu_label_components; nothing is launched on a refusal. */
+long long ltu_fill_holes_ws_elems(int B, int H, int W, int D);
+int ltu_fill_holes(const uint8_t* mask, uint8_t* out, int* scratch, long long scratch_elems, int B, int H, int W, int D,
+                   int connectivity, ltu_stream_t s);
 
 /* ---- optimizer (train3D.py:193: torch.optim.AdamW(lr=1e-4)) -----------------------------------------------------
  * One AdamW step on flat, 16-byte aligned fp32 buffers (a gradient bucket and the parameters / moments laid out the same way):
@@ -816,6 +826,27 @@ int ltu_intensity_hist(const void* img, int dtype, const uint8_t* lab, long long
                        uint32_t* hist, unsigned long long* counts, ltu_stream_t s);
 int ltu_intensity_moments(const float* img, const uint8_t* lab, long long n_voxels, int mask_bits, double centre, double* parts,
                           long long parts_elems, double* out, ltu_stream_t s);
+
+/* ---- nonzero cropping and masked normalisation of a stored scan (csrc/nonzero.hip; nnU-Net's crop_to_nonzero and
+ * ZScoreNormalization under the nonzero mask, which it runs on host copies).  With ltu_fill_holes between the first two:
+ *   nonzero_mask:     mask[i] = (accumulate ? mask[i] : 0) | (fmaf(v, slope, inter) != 0) for the n_voxels voxels of img as stored
+ *                     (dtype LTU_U8 / LTU_I16 / LTU_F32, aligned to its element; mask u8, any alignment): one call per channel ORs
+ *                     the channels together.  A NaN counts as nonzero, -0.0 as zero.  16-byte loads and stores from the mask's
+ *                     first 16-byte boundary on where the image is aligned there too, element by element otherwise and at both ends.
+ *   mask_box:         mask u8 [B][H][W][D] (nonzero = set, any alignment) -> box int32 [B][6] = (h0, h1, w0, w1, d0, d1), the
+ *                     inclusive bounds of the set voxels, and count (device u64 [B]) their number; an empty mask gives h0 = H,
+ *                     h1 = -1, w0 = W, ... and count 0.  The call initialises both.  B <= 65535, H W D < 2^31.
+ *   normalize_masked: img (dtype as above) and mask u8 are volumes [S2][S1][S0] (x fastest); out f32 [n2][n1][n0], dense, =
+ *                     mask ? fmaf(v, alpha, beta) : 0 over the box that begins at (l0, l1, l2): the crop, the intensity map and
+ *                     the zeroing outside the mask in one launch.  The box must lie inside the volume (LTU_E_SHAPE).
+ *   Integer atomics only (min, max, add), no floating-point atomics: two calls give the same bytes.  Nothing is allocated or
+ *   synchronised: capturable.  n_voxels / S0 S1 S2 outside 1 .. 2^32 - 1 LTU_E_SHAPE, another dtype LTU_E_DTYPE, a NULL pointer
+ *   LTU_E_ARG, img not aligned to its element / box, out not 4-byte / count not 8-byte aligned LTU_E_ALIGN. */
+int ltu_nonzero_mask(const void* img, int dtype, long long n_voxels, float slope, float inter, uint8_t* mask, int accumulate,
+                     ltu_stream_t s);
+int ltu_mask_box(const uint8_t* mask, int B, int H, int W, int D, int* box, unsigned long long* count, ltu_stream_t s);
+int ltu_normalize_masked(const void* img, int dtype, const uint8_t* mask, int S0, int S1, int S2, int l0, int l1, int l2, int n0,
+                         int n1, int n2, float alpha, float beta, float* out, ltu_stream_t s);
 
 /* ---- augmentation of the NIfTI pipeline's patches (csrc/augment.hip; no reference counterpart: the monai driver crops, flips and
  * rot90s only).

@@ -106,6 +106,8 @@ SIGNATURES = {
     'ltu_lesion_ws_elems': [I, I, I, I, L],
     'ltu_lesion_heads': [P, P, P, I, I, I, I, I, I, F, I, P],
     'ltu_lesion_stats': [P, P, P, P, P, L, L, I, I, I, I, I, I, I, I, F, I, P],
+    'ltu_fill_holes_ws_elems': [I, I, I, I],
+    'ltu_fill_holes': [P, P, P, L, I, I, I, I, I, P],
     'ltu_ct_preprocess': [P, P, P, P, I, I, I, F, F, F, F, P],
     'ltu_crop_flip': [P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_resample_grid': [P, I, P, I, I, I, L, L, L, P, P, I, I, I, L, L, L, P, I, F, F, F, F, P],
@@ -118,6 +120,9 @@ SIGNATURES = {
     'ltu_crop_index_select': [P, L, P, L, P, P, I, P],
     'ltu_intensity_hist': [P, I, P, L, I, I, I, P, P, P],
     'ltu_intensity_moments': [P, P, L, I, c_double, P, L, P, P],
+    'ltu_nonzero_mask': [P, I, L, F, F, P, I, P],
+    'ltu_mask_box': [P, I, I, I, I, P, P, P],
+    'ltu_normalize_masked': [P, I, P, I, I, I, I, I, I, I, I, I, F, F, P, P],
     'ltu_sample_affine': [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
     'ltu_sample_elastic': [P, P, P, P, P, P, I, I, I, P, P, I, I, I, I, I, I, I, F, P],
     'ltu_sample_channels': [P, P, P, P, P, P, I, I, I, P, P, P, I, I, I, I, I, I, I, I, P],

@@ -24,6 +24,10 @@
 // not matter, and among equally large components the smaller root = the raster-first one wins, as bincount / argmax decide it.
 // A clearing pass zeroes channels 1 .. C-1 of every other component; channel 0 = 1 - the rest at the end.
 //
+// Hole filling (scipy.ndimage.binary_fill_holes; monai FillHoles): labelling steps 1-3 of the mask's COMPLEMENT, one pass over the
+// six faces of the volume stores a mark in the root slot of every background component that reaches a face (every writer stores
+// the same value: plain stores), one pass writes mask u {background whose root carries no mark}.  Five launches, no host read.
+//
 // Lesion statistics per (sample, class): P and G labelled (steps 1-3) into two parent arrays; one pass histograms |P_i|, |G_j|,
 // |P_i n G|, |G_j n P| by root; one pass inserts the distinct (root P, root G) pairs into a per-sample hash set of 64-bit keys
 // (atomicCAS, linear probing) from the "heads" of P n G only (voxels of P n G without a half-neighbour in P n G: every connected
@@ -40,7 +44,8 @@
 #define CC_EMPTY 0xffffffffffffffffull
 
 // a binary source plane: kind 0 u8 != 0, 1 f32 >= thr, 2 f32 > thr, 3 u8 == cls, 4 the f32 sum of channels 1 .. cls - 1 (planes
-// `plane` elements apart, added in channel order) > 0; sample b starts at p + b * stride elements
+// `plane` elements apart, added in channel order) > 0, 5 u8 == 0 (the complement of a mask); sample b starts at p + b * stride
+// elements
 struct cc_src {
   const void* p;
   long long stride;
@@ -57,6 +62,7 @@ __device__ __forceinline__ bool cc_fg(const cc_src& s, int b, long long i) {
     case 1: return static_cast<const float*>(s.p)[o] >= s.thr;
     case 2: return static_cast<const float*>(s.p)[o] > s.thr;
     case 3: return static_cast<const uint8_t*>(s.p)[o] == (uint8_t)s.cls;
+    case 5: return static_cast<const uint8_t*>(s.p)[o] == 0;
     default: {
       float fg = 0.f;
       for (int c = 1; c < s.cls; ++c) fg += static_cast<const float*>(s.p)[o + c * s.plane];
@@ -493,6 +499,73 @@ extern "C" int ltu_keep_largest_component(float* pred, int* scratch, long long s
   hipLaunchKernelGGL(cc_pick_kernel, g, dim3(256), 0, st, size, best, S);
   hipLaunchKernelGGL(cc_keep_kernel, g, dim3(256), 0, st, pred, scratch, best, S, C);
   hipLaunchKernelGGL(cc_channel0_kernel, g, dim3(256), 0, st, pred, S, C);
+  return ltu_check_launch();
+}
+
+// ---- hole filling ----------------------------------------------------------------------------------------------------------
+#define CC_OPEN (-2)                              // in a root's own par slot: its component reaches a face of the volume
+
+// every voxel of the six faces that is background of the mask marks the root of its component.  grid = (blocks, B) over
+// i < 2 (W D + H D + H W); edges and corners come twice.  Every writer of a slot stores the same value, and a slot that reads
+// CC_OPEN already is a marked root: no atomics.
+__global__ void __launch_bounds__(256) cc_faces_kernel(int* __restrict__ par, int H, int W, int D) {
+  int* pb = par + (long long)blockIdx.y * ((long long)H * W * D);
+  const long long nh = (long long)W * D, nw = (long long)H * D, nd = (long long)H * W;
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= 2 * (nh + nw + nd)) return;
+  int h, w, d;
+  if (i < 2 * nh) {
+    h = i < nh ? 0 : H - 1;
+    i = i < nh ? i : i - nh;
+    w = (int)(i / D);
+    d = (int)(i % D);
+  } else if (i < 2 * (nh + nw)) {
+    i -= 2 * nh;
+    w = i < nw ? 0 : W - 1;
+    i = i < nw ? i : i - nw;
+    h = (int)(i / D);
+    d = (int)(i % D);
+  } else {
+    i -= 2 * (nh + nw);
+    d = i < nd ? 0 : D - 1;
+    i = i < nd ? i : i - nd;
+    h = (int)(i / W);
+    w = (int)(i % W);
+  }
+  const int p = pb[((long long)h * W + w) * D + d];
+  if (p >= 0) pb[p] = CC_OPEN;                    // p < 0: a voxel of the mask (-1), or a root that is marked already
+}
+
+// out = 1 on the mask (par -1) and on the background components without a marked root, 0 elsewhere.  grid = (nb, B)
+__global__ void __launch_bounds__(256) cc_holes_kernel(const int* __restrict__ par, uint8_t* __restrict__ out, long long S) {
+  const int* pb = par + (long long)blockIdx.y * S;
+  uint8_t* ob = out + (long long)blockIdx.y * S;
+  const long long base = (long long)blockIdx.x * CC_RB;
+  for (int j = 0; j < CC_RB / 256; ++j) {
+    const long long v = base + j * 256 + threadIdx.x;
+    if (v >= S) break;
+    const int p = pb[v];
+    ob[v] = p == -1 ? 1 : p == CC_OPEN ? 0 : pb[p] != CC_OPEN;
+  }
+}
+
+extern "C" long long ltu_fill_holes_ws_elems(int B, int H, int W, int D) {
+  if (!cc_shape_ok(B, H, W, D)) return 0;
+  return (long long)B * ((long long)H * W * D);
+}
+
+extern "C" int ltu_fill_holes(const uint8_t* mask, uint8_t* out, int* scratch, long long scratch_elems, int B, int H, int W, int D,
+                              int connectivity, ltu_stream_t s) {
+  if (!cc_shape_ok(B, H, W, D)) return LTU_E_SHAPE;
+  if (connectivity < 1 || connectivity > 3 || mask == nullptr || out == nullptr) return LTU_E_ARG;
+  if (scratch == nullptr || scratch_elems < ltu_fill_holes_ws_elems(B, H, W, D)) return LTU_E_ARG;
+  hipStream_t st = (hipStream_t)s;
+  const long long S = (long long)H * W * D;
+  const long long faces = 2 * ((long long)W * D + (long long)H * D + (long long)H * W);
+  const cc_src src{mask, S, 5, 0, 0.f};           // the complement: the mask is read by the labelling only, so out may be mask
+  cc_label_roots(src, scratch, nullptr, B, H, W, D, connectivity, st);
+  hipLaunchKernelGGL(cc_faces_kernel, dim3(cdiv(faces, 256), B), dim3(256), 0, st, scratch, H, W, D);
+  hipLaunchKernelGGL(cc_holes_kernel, dim3((unsigned)cc_nblocks(H, W, D), B), dim3(256), 0, st, scratch, out, S);
   return ltu_check_launch();
 }
 

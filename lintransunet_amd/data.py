@@ -440,13 +440,15 @@ def spline_coefficients(src, orders, imap=(1.0, 0.0, -np.inf, np.inf), src_dtype
 
 
 def resample(src_img, src_lab, matrix, out_shape, imap=(1.0, 0.0, -np.inf, np.inf), src_dtype=0, src_strides=None,
-             out_strides=None, lane_axis=None, order=1):
+             out_strides=None, lane_axis=None, order=1, out=None):
     """ltu_resample_grid: device sources (image of src_dtype / u8 label, either None) of shape (S0, S1, S2) read through
     `src_strides` (default: x fastest, i.e. a [S2][S1][S0] array), resampled through the 3x4 float64 pull matrix to outputs of
     out_shape (default layout: [O0][O1][O2], the last axis fastest).  Returns (f32 image or None, u8 label or None).
     order: the image's interpolation, 1 (trilinear, the call as it always was), 3 (cubic B-spline) or one of 0 / 1 / 3 per source
     axis (resolve_order).  Anything but 1 prefilters the mapped scan (spline_coefficients) and gathers the coefficients through the
-    same matrix (ltu_resample_spline), clamped to the map's [lo, hi]; the label still goes nearest through ltu_resample_grid."""
+    same matrix (ltu_resample_spline), clamped to the map's [lo, hi]; the label still goes nearest through ltu_resample_grid.
+    out: (f32 image or None, u8 label or None) to write into instead of fresh tensors: device tensors (views allowed) whose
+    element [0, 0, 0] is output voxel (0, 0, 0) and whose memory `out_strides` describes, e.g. a box of a larger volume."""
     src = src_img if src_img is not None else src_lab
     if src is None or not src.is_cuda:
         raise _lib.LtuError('data.resample runs on the GPU only (no CPU fallback)')
@@ -463,8 +465,14 @@ def resample(src_img, src_lab, matrix, out_shape, imap=(1.0, 0.0, -np.inf, np.in
         alloc = tuple(O[a] for a in np.argsort(out_strides)[::-1])
     m = np.asarray(matrix, dtype=np.float64).reshape(3, 4)
     mat = torch.as_tensor(m.ravel().copy()).to(src.device)
-    oi = torch.empty(alloc, device=src.device, dtype=torch.float32) if src_img is not None else None
-    ol = torch.empty(alloc, device=src.device, dtype=torch.uint8) if src_lab is not None else None
+    if out is not None:
+        oi, ol = out
+        if (oi is None) != (src_img is None) or (ol is None) != (src_lab is None) or \
+                (oi is not None and oi.dtype != torch.float32) or (ol is not None and ol.dtype != torch.uint8):
+            raise ValueError('out holds a float32 tensor for the image and a uint8 tensor for the label, one per source given')
+    else:
+        oi = torch.empty(alloc, device=src.device, dtype=torch.float32) if src_img is not None else None
+        ol = torch.empty(alloc, device=src.device, dtype=torch.uint8) if src_lab is not None else None
     if spline:
         # the coefficients are dense with x fastest whatever the source's strides were: the lane axis follows THEIR layout
         lane = geometry.lane_axis(m, (1, S[0], S[0] * S[1])) if lane_axis is None else lane_axis
@@ -480,12 +488,13 @@ def resample(src_img, src_lab, matrix, out_shape, imap=(1.0, 0.0, -np.inf, np.in
     return oi, ol
 
 
-def resample_argmax(probs, matrix, out_shape, src_strides=None, out_strides=None, lane_axis=None, classes=()):
+def resample_argmax(probs, matrix, out_shape, src_strides=None, out_strides=None, lane_axis=None, classes=(), out=None):
     """ltu_resample_argmax: probs f32 [C, ...] on the device, C = 2 .. 8 channels of one volume of shape (S0, S1, S2) read through
     `src_strides` (default: x fastest, i.e. every channel a [S2][S1][S0] array), pulled through the 3x4 float64 matrix onto out_shape
     (layouts and the lane axis as data.resample) with the arg-max taken there: the first maximal class wins, as torch.argmax.
     Every channel is resampled bit for bit as data.resample resamples it alone; the coordinates and taps are formed once for all.
     classes: class ids whose resampled probabilities are returned too, in ascending order.
+    out: (u8 label, f32 probabilities [K, ...] or None) to write into instead of fresh tensors (views allowed, as data.resample's).
     Returns (label u8, probabilities f32 [K, ...] or None)."""
     if not torch.is_tensor(probs) or not probs.is_cuda:
         raise _lib.LtuError('data.resample_argmax runs on the GPU only (no CPU fallback)')
@@ -509,10 +518,16 @@ def resample_argmax(probs, matrix, out_shape, src_strides=None, out_strides=None
     m = np.asarray(matrix, dtype=np.float64).reshape(3, 4)
     mat = torch.as_tensor(m.ravel().copy()).to(probs.device)
     lane = geometry.lane_axis(m, src_strides) if lane_axis is None else lane_axis
-    ol = torch.empty(alloc, device=probs.device, dtype=torch.uint8)
-    op = torch.empty((len(ks),) + alloc, device=probs.device, dtype=torch.float32) if ks else None
+    if out is not None:
+        ol, op = out
+        if ol.dtype != torch.uint8 or (op is None) != (not ks) or (op is not None and (op.dtype != torch.float32 or op.shape[0] != len(ks))):
+            raise ValueError('out holds a uint8 label and float32 probabilities [K, ...], K = len(classes) (None for no class)')
+    else:
+        ol = torch.empty(alloc, device=probs.device, dtype=torch.uint8)
+        op = torch.empty((len(ks),) + alloc, device=probs.device, dtype=torch.float32) if ks else None
     _lib.call('ltu_resample_argmax', _p(probs), C, probs.stride(0), *S, *(int(s) for s in src_strides), _p(ol), _p(op),
-              sum(1 << k for k in ks), O[0] * O[1] * O[2], *O, *(int(s) for s in out_strides), _p(mat), lane, _s())
+              sum(1 << k for k in ks), int(op.stride(0)) if op is not None else O[0] * O[1] * O[2], *O,
+              *(int(s) for s in out_strides), _p(mat), lane, _s())
     return ol, op
 
 
@@ -776,6 +791,144 @@ class IntensityFingerprint:
         return fp
 
 
+# ---- nonzero cropping and masked normalisation (csrc/nonzero.hip, the hole filling of csrc/components.hip; nnU-Net's
+# crop_to_nonzero and ZScoreNormalization under the nonzero mask, no reference counterpart) -----------------------------------------
+# The nonzero mask of a scan is the union over its channels of value != 0 with holes filled; the scan is cropped to the mask's
+# bounding box and every channel z-scored with the statistics of its voxels inside the mask, 0 outside.
+
+def fill_holes_u8(mask, out, connectivity=1):
+    """ltu_fill_holes on a contiguous u8 device mask [B, H, W, D] into out (the same shape; `mask` itself for in place); returns
+    out.  infer.fill_holes is the public form."""
+    B, H, W, D = (int(v) for v in mask.shape)
+    ws = _lib.load().ltu_fill_holes_ws_elems(B, H, W, D)
+    if ws <= 0:
+        raise _lib.LtuError(f'fill_holes: shape {tuple(mask.shape)} refused (B <= 65535 and H * W * D < 2^31)')
+    scratch = torch.empty(ws, device=mask.device, dtype=torch.int32)
+    _lib.call('ltu_fill_holes', _p(mask), _p(out), _p(scratch), ws, B, H, W, D, int(connectivity), _s())
+    return out
+
+
+_STORED_CODES = {torch.uint8: _lib.U8, torch.int16: _lib.I16, torch.float32: 0}
+
+
+def _stored_volume(raw, what):
+    """the dtype code of a device volume as stored: contiguous [Z, Y, X] uint8, int16 or float32"""
+    if not torch.is_tensor(raw) or not raw.is_cuda:
+        raise _lib.LtuError(f'{what} runs on the GPU only (no CPU fallback)')
+    code = _STORED_CODES.get(raw.dtype)
+    if code is None or raw.dim() != 3 or not raw.is_contiguous() or raw.numel() == 0:
+        raise ValueError(f'{what} takes a contiguous, non-empty uint8, int16 or float32 volume [Z, Y, X], got {raw.dtype} {tuple(raw.shape)}')
+    return code
+
+
+def nonzero_mask(raws, scalings=None, fill_holes=True):
+    """the nonzero mask of a scan, nnU-Net's create_nonzero_mask: raws is one device volume as stored (uint8, int16 or float32
+    [Z, Y, X]) or a sequence of K of them on one grid, scalings one (slope, inter) per volume (default (1, 0)): the union over the
+    volumes of v * slope + inter != 0 (one fmaf in float32; a NaN counts as nonzero), then, with fill_holes, the background that no
+    6-connected path joins to a face of the volume (infer.fill_holes, scipy's binary_fill_holes).
+    Returns (mask u8 [Z, Y, X] on the device, box, count): box = one (lo, hi exclusive) pair per axis of the stored array, the
+    bounding box of the mask, count = its voxels.  One launch per volume, the hole filling, one box reduction and ONE host read (32
+    bytes).  An all-zero scan raises ValueError."""
+    vols = [raws] if torch.is_tensor(raws) else list(raws)
+    if not vols:
+        raise ValueError('nonzero_mask takes at least one volume')
+    scalings = [(1.0, 0.0)] * len(vols) if scalings is None else [(float(a), float(b)) for a, b in scalings]
+    if len(scalings) != len(vols):
+        raise ValueError(f'{len(scalings)} scalings for {len(vols)} volumes')
+    codes = [_stored_volume(v, 'data.nonzero_mask') for v in vols]
+    shape = tuple(int(n) for n in vols[0].shape)
+    if any(tuple(v.shape) != shape or v.device != vols[0].device for v in vols):
+        raise ValueError('the volumes of one scan share a grid and a device')
+    mask = torch.empty(shape, device=vols[0].device, dtype=torch.uint8)
+    for c, (v, code, (slope, inter)) in enumerate(zip(vols, codes, scalings)):
+        _lib.call('ltu_nonzero_mask', _p(v), code, v.numel(), slope, inter, _p(mask), int(c > 0), _s())
+    if fill_holes:
+        fill_holes_u8(mask.view(1, *shape), mask.view(1, *shape), 1)
+    res = torch.empty(4, device=mask.device, dtype=torch.int64)          # count, then the six int32 bounds
+    _lib.call('ltu_mask_box', _p(mask), 1, *shape, _p(res[1:]), _p(res), _s())
+    host = res.cpu().numpy()
+    count, bounds = int(host[0]), host[1:].view(np.int32)
+    if count == 0:
+        raise ValueError('the scan holds no nonzero voxel: there is nothing to crop to')
+    return mask, tuple((int(bounds[2 * a]), int(bounds[2 * a + 1]) + 1) for a in range(3)), count
+
+
+def _check_box(box, shape):
+    pairs = tuple(tuple(int(v) for v in p) for p in box)
+    if len(pairs) != 3 or any(len(p) != 2 or not 0 <= p[0] < p[1] <= n for p, n in zip(pairs, shape)):
+        raise ValueError(f'box {box!r} is not three (lo, hi) pairs inside a volume of shape {tuple(shape)}')
+    return pairs
+
+
+def normalize_masked(raw, mask, box, alpha, beta, src_dtype=None):
+    """ltu_normalize_masked: the box (one (lo, hi exclusive) pair per axis) of a device volume as stored (uint8, int16 or float32
+    [Z, Y, X]; src_dtype: its code, default from the tensor) under the u8 mask of the same shape, as a dense f32 volume of the box's
+    shape: mask ? fmaf(v, alpha, beta) : 0, alpha and beta rounded to float32 once.  One launch."""
+    code = _stored_volume(raw, 'data.normalize_masked')
+    if src_dtype is not None and int(src_dtype) != code:
+        raise ValueError(f'src_dtype {src_dtype} does not name the dtype of a {raw.dtype} volume')
+    if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.shape != raw.shape or mask.device != raw.device \
+            or not mask.is_contiguous():
+        raise ValueError('the mask is a contiguous uint8 tensor of the volume\'s shape, on its device')
+    Z, Y, X = (int(n) for n in raw.shape)
+    (z0, z1), (y0, y1), (x0, x1) = _check_box(box, (Z, Y, X))
+    out = torch.empty((z1 - z0, y1 - y0, x1 - x0), device=raw.device, dtype=torch.float32)
+    _lib.call('ltu_normalize_masked', _p(raw), code, _p(mask), X, Y, Z, x0, y0, z0, x1 - x0, y1 - y0, z1 - z0, float(alpha), float(beta),
+              _p(out), _s())
+    return out
+
+
+INTENSITY_NAMES = ('zscore', 'zscore_nonzero')
+CROP_NAMES = ('nonzero',)
+
+
+def _check_scan_options(crop, specs):
+    """the refusals SpacedScan / MultiScan make before a file is read or the GPU touched"""
+    if crop is not None and crop not in CROP_NAMES:
+        raise ValueError(f"crop is None or 'nonzero', got {crop!r}")
+    for spec in specs:
+        if isinstance(spec, str) and spec not in INTENSITY_NAMES:
+            raise ValueError(f"intensity is a window, None, an IntensityFingerprint, 'zscore' or 'zscore_nonzero', got {spec!r}")
+
+
+def _masked_spec(spec):
+    return isinstance(spec, str) and spec == 'zscore_nonzero'
+
+
+def _masked_zscore(raw, mask, slope, inter):
+    """'zscore_nonzero': (window 4-tuple, alpha, beta) from the statistics of the voxels of raw inside the mask, in units of
+    v * slope + inter: the z-score is fmaf(v, alpha, beta), alpha = slope / sd, beta = (inter - mean) / sd, sd = max(std, 1e-8),
+    formed in float64"""
+    st = intensity_stats(raw, lab=mask, mask=FG_MASK, percentiles=(), slope=slope, inter=inter)
+    sd = max(st['std'], 1e-8)
+    window = (st['min'], st['max'], (st['min'] - st['mean']) / sd, (st['max'] - st['mean']) / sd)
+    return window, float(slope) / sd, (float(inter) - st['mean']) / sd
+
+
+def _load_channel(ri, rl, code, spec, slope, inter, mask, box, plan, order):
+    """one channel of a scan that is cropped or normalised under its nonzero mask: (f32 image, u8 label or None, window).  ri / rl:
+    the device volumes as stored [Z, Y, X]; box: the crop in their axes; plan: (matrix, shape) of the box's resampling.
+    'zscore_nonzero' normalises the box first (normalize_masked) and resamples the f32 result with the identity map; every other
+    spec resamples the box of the stored volume through its strides, no copy.  The label is resampled from its box, nearest."""
+    matrix, shape = plan
+    Z, Y, X = (int(n) for n in ri.shape)
+    (z0, z1), (y0, y1), (x0, x1) = box
+    strides = (1, X, X * Y)
+
+    def boxed(t):                                     # the box as a view with x first, as `strides` describes it
+        return t[z0:z1, y0:y1, x0:x1].permute(2, 1, 0)
+    ol = None
+    if rl is not None:
+        _, ol = resample(None, boxed(rl), matrix, shape, src_strides=strides)
+    if _masked_spec(spec):
+        window, alpha, beta = _masked_zscore(ri, mask, slope, inter)
+        oi, _ = resample(normalize_masked(ri, mask, box, alpha, beta, code), None, matrix, shape, order=order)
+    else:
+        window = _resolve_intensity(spec, ri, slope, inter)
+        oi, _ = resample(boxed(ri), None, matrix, shape, intensity_map(window, slope, inter), code, src_strides=strides, order=order)
+    return oi, ol, window
+
+
 def _resolve_intensity(intensity, raw, slope, inter):
     """SpacedScan's `intensity` as a window 4-tuple or None: a fingerprint gives its window(); 'zscore' the statistics of all voxels
     of this scan (no label, so training and inference agree) as the window (vmin, vmax, (vmin - mean) / std, (vmax - mean) / std),
@@ -802,10 +955,22 @@ class SpacedScan:
     attribute `intensity` keeps the resulting 4-tuple (or None).
     order: the image's interpolation as data.resample takes it (1: trilinear, the driver's; 3: cubic B-spline; a 3-tuple per FILE
     axis), or 'auto' for geometry.resample_orders of the file's voxel sizes and pixdim (nnU-Net's rule: the coarse axis of an
-    anisotropic scan goes nearest); the attribute `order` keeps the resolved 3-tuple.  The label is nearest whatever the order."""
+    anisotropic scan goes nearest); the attribute `order` keeps the resolved 3-tuple.  The label is nearest whatever the order.
+    crop='nonzero' (nnU-Net's crop_to_nonzero; for skull-stripped MR, where most voxels are exact zeros): the scan's nonzero mask
+    (data.nonzero_mask: scaled value != 0, holes filled) is built on the device, and image and label are resampled from its
+    bounding box only: matrix, shape and affine are then those of the box (geometry.crop_plan, then spacing_plan), matrix: RAS voxel
+    -> BOX voxel; native, native_shape and native_affine stay the file's, and to_native / to_native_probs write into the box of a
+    file-sized volume.  intensity='zscore_nonzero' (with or without crop) z-scores with the mean and standard deviation of the
+    voxels inside that mask and puts 0 outside it, BEFORE resampling (nnU-Net's order): normalize_masked, then the f32 volume is
+    resampled at `order` with the identity map; `intensity` keeps (vmin, vmax, (vmin - mean) / std, (vmax - mean) / std) of the
+    masked statistics.  crop_box: the box per axis of the stored array [Z, Y, X] as (lo, hi exclusive) pairs, None without crop;
+    nonzero_count / nonzero_fraction: the mask's voxels / its bounding box's share of the file's voxels (nnU-Net uses the mask for
+    normalisation when the crop removes a quarter: fraction < 0.75), None when no mask was built; outside: the image value outside
+    the scan that data.sample(augment=) fills with, 0.0 under 'zscore_nonzero', else None (the window's floor)."""
 
     def __init__(self, img_path, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda',
-                 order=1):
+                 order=1, crop=None):
+        _check_scan_options(crop, [intensity])
         ni = nifti.load(img_path)
         nl = nifti.load(lab_path) if lab_path is not None else None
         if nl is not None:
@@ -819,11 +984,31 @@ class SpacedScan:
         if nl is not None:
             lv = nl.data if (nl.slope, nl.inter) == (1.0, 0.0) else nl.scaled()
             rl = torch.as_tensor(np.ascontiguousarray(label_u8(lv))).to(device)
-        intensity = _resolve_intensity(intensity, ri, ni.slope, ni.inter)
-        self.img, self.lab = resample(ri, rl, self.matrix, self.shape, intensity_map(intensity, ni.slope, ni.inter), code,
-                                      order=self.order)
+        self.crop_box = self.nonzero_count = self.nonzero_fraction = self.outside = None
+        if crop is None and not _masked_spec(intensity):
+            intensity = _resolve_intensity(intensity, ri, ni.slope, ni.inter)
+            self.img, self.lab = resample(ri, rl, self.matrix, self.shape, intensity_map(intensity, ni.slope, ni.inter), code,
+                                          order=self.order)
+        else:
+            if _masked_spec(intensity):
+                self.outside = 0.0
+            mask, box = self._nonzero_grid([ri], [(ni.slope, ni.inter)], crop, pixdim, axcodes)
+            self.img, self.lab, intensity = _load_channel(ri, rl, code, intensity, ni.slope, ni.inter, mask, box,
+                                                          (self.matrix, self.shape), self.order)
         self.pixdim, self.intensity = tuple(float(p) for p in pixdim), intensity      # sample(augment=) rotates in mm, fills with the window's floor
         self._label_host = self._crop_index = None
+
+    def _nonzero_grid(self, raws, scalings, crop, pixdim, axcodes):
+        """the nonzero mask of the stored volumes and the box to load: (mask, box).  Sets nonzero_count / nonzero_fraction and, under
+        crop, crop_box and the box's matrix, shape and affine"""
+        mask, bbox, self.nonzero_count = nonzero_mask(raws, scalings)
+        self.nonzero_fraction = float(np.prod([hi - lo for lo, hi in bbox], dtype=np.float64) / raws[0].numel())
+        if crop is None:
+            return mask, tuple((0, int(n)) for n in raws[0].shape)
+        self.crop_box = bbox
+        box_shape, affine = geometry.crop_plan(self.native_shape, self.native_affine, bbox[::-1])
+        self.matrix, self.shape, self.affine = geometry.spacing_plan(box_shape, affine, pixdim, axcodes)
+        return mask, bbox
 
     @property
     def label_host(self):
@@ -858,10 +1043,12 @@ class MultiScan(SpacedScan):
     label_host, matrix, affine, shape, pixdim as on SpacedScan, native / native_shape / native_affine are channel 0's.
     intensity: one spec for all channels (a window 4-tuple, None, an IntensityFingerprint or 'zscore') or a sequence of K specs;
     the attribute `intensity` is the list of the K resulting tuples (or None).  channels == K.  order: as SpacedScan's, one for all
-    channels."""
+    channels.  crop and 'zscore_nonzero' as SpacedScan's: ONE nonzero mask, the union over all K channels, crops the scan and selects
+    the voxels of every channel's statistics; crop_box, nonzero_count, nonzero_fraction as there, outside: a list of K (0.0 for a
+    'zscore_nonzero' channel, else None)."""
 
     def __init__(self, img_paths, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda',
-                 order=1):
+                 order=1, crop=None):
         paths = [img_paths] if isinstance(img_paths, (str, bytes)) or hasattr(img_paths, '__fspath__') else list(img_paths)
         K = len(paths)
         if not 1 <= K <= _lib.MAX_INPUT_CHANNELS:
@@ -871,7 +1058,8 @@ class MultiScan(SpacedScan):
         specs = [intensity] * K if one else list(intensity)
         if len(specs) != K:
             raise ValueError(f'intensity is one spec or one per image: {len(specs)} specs for {K} images')
-        nis = [nifti.load(p) for p in paths]
+        _check_scan_options(crop, specs)
+        nis =[nifti.load(p) for p in paths]
         nl = nifti.load(lab_path) if lab_path is not None else None
         ni = nis[0]
         for other in nis[1:] + ([nl] if nl is not None else []):
@@ -885,12 +1073,24 @@ class MultiScan(SpacedScan):
             rl = torch.as_tensor(np.ascontiguousarray(label_u8(lv))).to(device)
         self.img = self.lab = None
         self.intensity = []
+        self.crop_box = self.nonzero_count = self.nonzero_fraction = None
+        self.outside = [0.0 if _masked_spec(spec) else None for spec in specs]
+        masked = crop is not None or any(_masked_spec(spec) for spec in specs)
+        if masked:                                     # the mask is the union over ALL channels: they are uploaded together
+            stored = [_source_dtype(nc.data) for nc in nis]
+            raws = [torch.as_tensor(np.ascontiguousarray(raw)).to(device) for raw, _ in stored]
+            mask, box = self._nonzero_grid(raws, [(nc.slope, nc.inter) for nc in nis], crop, pixdim, axcodes)
         for c, (nc, spec) in enumerate(zip(nis, specs)):
-            raw, code = _source_dtype(nc.data)
-            ri = torch.as_tensor(np.ascontiguousarray(raw)).to(device)
-            window = _resolve_intensity(spec, ri, nc.slope, nc.inter)
-            oi, ol = resample(ri, rl if c == 0 else None, self.matrix, self.shape, intensity_map(window, nc.slope, nc.inter), code,
-                              order=self.order)
+            if masked:
+                oi, ol, window = _load_channel(raws[c], rl if c == 0 else None, stored[c][1], spec, nc.slope, nc.inter, mask, box,
+                                               (self.matrix, self.shape), self.order)
+                raws[c] = None
+            else:
+                raw, code = _source_dtype(nc.data)
+                ri = torch.as_tensor(np.ascontiguousarray(raw)).to(device)
+                window = _resolve_intensity(spec, ri, nc.slope, nc.inter)
+                oi, ol = resample(ri, rl if c == 0 else None, self.matrix, self.shape, intensity_map(window, nc.slope, nc.inter), code,
+                                  order=self.order)
             if c == 0:
                 self.img, self.lab = torch.empty((K,) + tuple(oi.shape), device=oi.device, dtype=torch.float32), ol
             self.img[c].copy_(oi)
@@ -1232,18 +1432,24 @@ def _multi(scan):
 
 
 def _scan_fill(scan, augment):
-    """the image value outside the scan: augment.fill, or (None) the floor of the scan's intensity window, 0.0 where it has none;
-    one per channel for a MultiScan"""
-    def floor(window):
+    """the image value outside the scan: augment.fill, or (None) scan.outside where the scan names one (0.0 under
+    'zscore_nonzero': the value of everything outside the mask), else the floor of the scan's intensity window, 0.0 where it has
+    none; one per channel for a MultiScan"""
+    multi = _multi(scan)
+    outside = getattr(scan, 'outside', None)
+
+    def floor(window, c=None):
+        named = outside if c is None or outside is None else outside[c]
+        if named is not None:
+            return float(named)
         lo = intensity_map(window)[2]
         return float(lo) if np.isfinite(lo) else 0.0
-    multi = _multi(scan)
     if augment is not None and augment.fill is not None:
         return [float(augment.fill)] * scan.img.shape[0] if multi else augment.fill
     if augment is None:
         return [0.0] * scan.img.shape[0] if multi else 0.0
     windows = getattr(scan, 'intensity', None)
-    return [floor(wd) for wd in windows] if multi else floor(windows)
+    return [floor(wd, c) for c, wd in enumerate(windows)] if multi else floor(windows)
 
 
 def _augmented(scan, draws, params, spatial_size, augment, spacing):
@@ -1352,7 +1558,15 @@ def to_native(label_map, scan):
     lm = lm.contiguous()
     H, W, D = scan.shape
     X, Y, Z = scan.native_shape
-    _, out = resample(None, lm, geometry.invert(scan.matrix), (X, Y, Z), src_strides=(W * D, D, 1), out_strides=(1, X, X * Y))
+    box = getattr(scan, 'crop_box', None)
+    if box is None:
+        _, out = resample(None, lm, geometry.invert(scan.matrix), (X, Y, Z), src_strides=(W * D, D, 1), out_strides=(1, X, X * Y))
+        return out
+    # a cropped scan: its matrix leads into the box, which is written in place inside a file-sized volume of zeros
+    (z0, z1), (y0, y1), (x0, x1) = box
+    out = torch.zeros((Z, Y, X), device=lm.device, dtype=torch.uint8)
+    resample(None, lm, geometry.invert(scan.matrix), (x1 - x0, y1 - y0, z1 - z0), src_strides=(W * D, D, 1),
+             out_strides=(1, X, X * Y), out=(None, out[z0:z1, y0:y1, x0:x1]))
     return out
 
 
@@ -1370,5 +1584,19 @@ def to_native_probs(probs, scan, classes=()):
         raise ValueError(f'to_native_probs takes float32 probabilities, got {probs.dtype}')
     H, W, D = scan.shape
     X, Y, Z = scan.native_shape
-    return resample_argmax(probs, geometry.invert(scan.matrix), (X, Y, Z), src_strides=(W * D, D, 1), out_strides=(1, X, X * Y),
-                           classes=classes)
+    box = getattr(scan, 'crop_box', None)
+    if box is None:
+        return resample_argmax(probs, geometry.invert(scan.matrix), (X, Y, Z), src_strides=(W * D, D, 1), out_strides=(1, X, X * Y),
+                               classes=classes)
+    # a cropped scan: outside the box the label is 0 and a requested map holds 1 for class 0, 0 for every other class
+    (z0, z1), (y0, y1), (x0, x1) = box
+    ks = sorted({int(k) for k in classes})
+    ol = torch.zeros((Z, Y, X), device=probs.device, dtype=torch.uint8)
+    op = None
+    if ks:
+        op = torch.zeros((len(ks), Z, Y, X), device=probs.device, dtype=torch.float32)
+        if ks[0] == 0:
+            op[0].fill_(1.0)
+    resample_argmax(probs, geometry.invert(scan.matrix), (x1 - x0, y1 - y0, z1 - z0), src_strides=(W * D, D, 1),
+                    out_strides=(1, X, X * Y), classes=classes, out=(ol[z0:z1, y0:y1, x0:x1], op[:, z0:z1, y0:y1, x0:x1] if ks else None))
+    return ol, op

@@ -141,6 +141,23 @@ def spacing_plan(shape, affine, pixdim=(0.5, 0.5, 2.0), axcodes='RAS'):
     return (transform @ undo)[:3], tuple(final_shape), new_affine @ undo
 
 
+def crop_plan(shape, affine, box):
+    """the grid of a crop of a volume of `shape` (x, y, z) with `affine`: box = one (lo, hi exclusive) pair per axis of `shape`.
+    Returns (box shape, affine') with affine' = affine . T(box lo) in float64: voxel i of the crop is voxel lo + i of the volume,
+    so both affines put it at the same place.  The full box returns the shape and the affine as they are.  ValueError for a box
+    that is empty or not inside the volume."""
+    affine = np.asarray(affine, dtype=np.float64)
+    shape = tuple(int(n) for n in shape)
+    pairs = [tuple(int(v) for v in p) for p in box]
+    if len(pairs) != len(shape) or any(len(p) != 2 for p in pairs):
+        raise ValueError(f'a box holds one (lo, hi) pair per axis of {shape}, got {box!r}')
+    if any(not 0 <= lo < hi <= n for (lo, hi), n in zip(pairs, shape)):
+        raise ValueError(f'box {pairs} is empty or not inside a volume of shape {shape}')
+    shift = np.eye(len(shape) + 1)
+    shift[:-1, -1] = [lo for lo, _ in pairs]
+    return tuple(hi - lo for lo, hi in pairs), affine @ shift
+
+
 def voxel_spacing(affine):
     """the voxel sizes of a 4x4 affine per file axis: its column norms"""
     return tuple(float(v) for v in np.sqrt(np.sum(np.square(np.asarray(affine, dtype=np.float64)[:3, :3]), axis=0)))
