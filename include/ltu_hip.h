@@ -889,6 +889,28 @@ int ltu_normalize_masked(const void* img, int dtype, const uint8_t* mask, int S0
  *   called with img + c H W D, fill[c], noise_sigma[.][c] and seeds[.][c] and the same matrices (and lattice); out_lab has that
  *   call's bits.  Refused as the single-channel calls refuse, and NULL fill or a non-finite fill[c] LTU_E_ARG, K outside its range
  *   LTU_E_SHAPE.
+ * sample_spline: sample_channels with a cubic B-spline image interpolation for the patches that ask for it (nnU-Net's spatial
+ *   transform: scipy.ndimage.map_coordinates(order=3, mode='constant', cval=fill)).  coef: f32 [K][H][W][D] like img, the B-spline
+ *   coefficients of each channel from ltu_spline_prefilter (mirror boundaries): the scan axes H and W filtered, D filtered for
+ *   order_d == 3 and left as it is for order_d == 1 (any other order_d LTU_E_ARG).  fill, lo, hi: HOST float [K]; cubic: HOST bytes
+ *   [n].  mats, phi, noise_sigma, seeds, the label and n per launch as in sample_channels; the coordinates are formed by the same
+ *   code (fp64 origin per tile, fp32 bracket within ~2e-5 voxel of fp64, the deformation's M[:, :3] u added inside the bracket).
+ *   cubic[k] == 0: patch k is gathered from img by the trilinear expressions; its image and label have the bits of sample_channels
+ *     on the same arguments (the kernel variant is chosen from the whole call in the same way), so a patch of integer coordinates
+ *     stays the source voxels.
+ *   cubic[k] != 0, per channel c: where every component of the coordinate lies in [0, S - 1] of its axis, ends included, the voxel is
+ *     clamp(sum of w * coef[c][taps], lo[c], hi[c]): per axis f = floor(coordinate), t = coordinate - f, an order-3 axis has the taps
+ *     f-1 .. f+2 with the weights of resample_spline, axis D at order_d == 1 the taps f, f+1 with (1-t, t); tap indices are
+ *     whole-sample mirrored (the zero-weight tap above the top edge is a valid address): 64 or 32 taps.  Everywhere else the voxel
+ *     is fill[c], unclamped: there is no blending across the edge (what mode='constant' does at order 3).  lo / hi: the intensity
+ *     window's clip (the spline rings past it), -inf / +inf for none.  The sum runs in fp32 in a fixed order: the taps along D as
+ *     the inner fused multiply-add chain, then (wx wy) row added by one fused multiply-add, W inside H.  Tap indices, weights and
+ *     the inside test are formed once per output voxel; channel c has the bits of a K == 1 call on img + c H W D, coef + c H W D
+ *     and that channel's fill, lo, hi, sigma and seed.  Noise is added in the store, after the clamp; the label is sample_affine's.
+ *   No atomics, no workspace, no synchronisation: capturable; two calls give the same bytes.
+ *   Refused before any launch: everything sample_channels refuses, with its codes; NULL coef, cubic, lo or hi, lo[c] > hi[c] or a
+ *   NaN bound LTU_E_ARG; a scan of 2^31 voxels or more per channel LTU_E_SHAPE (tap offsets are 32-bit, and spline_prefilter builds
+ *   no larger volume).
  * gauss_blur3: out [n][H][W][D] f32 = mul_k * (3-D Gaussian blur of x [n][H][W][D]), out of place, one launch.  weights: HOST float
  *   [n][3][LTU_BLUR_MAX_RADIUS + 1], the half tables w[0 .. r] of the axes H, W, D (normalised so that w[0] + 2 sum w[t] = 1; entries
  *   beyond r are ignored); radii: HOST int [n][3], 0 = that axis untouched; mul: HOST float [n] or NULL (= 1), applied in the store.
@@ -911,6 +933,10 @@ int ltu_sample_elastic(const float* img, const uint8_t* lab, float* out_img, uin
 int ltu_sample_channels(const float* img, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats, const float* phi,
                         int gh, int gw, int gd, const float* noise_sigma, const unsigned long long* seeds, const float* fill, int n,
                         int K, int H, int W, int D, int h, int w, int d, ltu_stream_t s);
+int ltu_sample_spline(const float* img, const float* coef, const uint8_t* lab, float* out_img, uint8_t* out_lab, const double* mats,
+                      const float* phi, int gh, int gw, int gd, const float* noise_sigma, const unsigned long long* seeds,
+                      const float* fill, const float* lo, const float* hi, const unsigned char* cubic, int n, int K, int H, int W,
+                      int D, int h, int w, int d, int order_d, ltu_stream_t s);
 int ltu_gauss_blur3(const float* x, float* out, const float* weights, const int* radii, const float* mul, int n, int H, int W, int D,
                     ltu_stream_t s);
 

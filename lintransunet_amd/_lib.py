@@ -126,6 +126,7 @@ SIGNATURES = {
     'ltu_sample_affine': [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
     'ltu_sample_elastic': [P, P, P, P, P, P, I, I, I, P, P, I, I, I, I, I, I, I, F, P],
     'ltu_sample_channels': [P, P, P, P, P, P, I, I, I, P, P, P, I, I, I, I, I, I, I, I, P],
+    'ltu_sample_spline': [P, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
     'ltu_gauss_blur3': [P, P, P, P, P, I, I, I, I, P],
     'ltu_adamw': [P, P, P, P, L, F, F, F, F, F, L, F, P],
     'ltu_grad_sumsq_parts': [L],

@@ -2,7 +2,9 @@
 // only).  Three kernels: ltu_sample_affine cuts rotated / zoomed / flipped patches straight from the scan in one gather (and adds
 // Gaussian noise in the store), ltu_sample_elastic is that gather with a B-spline free-form deformation folded in, ltu_gauss_blur3
 // blurs a batch of patches in one launch (three 1-D passes inside a workgroup).  ltu_sample_channels is either gather for a scan of
-// up to four channels on one grid: the same kernels, instantiated per channel count.
+// up to four channels on one grid: the same kernels, instantiated per channel count.  ltu_sample_spline is ltu_sample_channels with
+// a cubic B-spline image interpolation (64 or 32 taps on prefiltered coefficients) for the patches that ask for it: the same kernels
+// again, instantiated per tap count along D, with the cubic taps as a workgroup-uniform branch.
 //
 // ---- the noise generator (restated in numpy by lintransunet_amd/data.py::noise_reference) ------------------------------------
 // Stateless like the dropout masks: the normal deviate of voxel i (the linear index (x * w + y) * d + z inside its patch, < 2^32)
@@ -15,6 +17,7 @@
 //   r  = sqrt(-2 ln u1),  z[2j] = r cos(2 pi u2),  z[2j + 1] = r sin(2 pi u2)
 // in fp32 with logf / sqrtf / sincospif.  |z| <= sqrt(48 ln 2) = 5.77.
 #include "common.h"
+#include "resample_coords.h"
 
 struct NoiseKey { uint32_t ka, kb; };
 __device__ __forceinline__ NoiseKey noise_key(unsigned long long seed) {
@@ -57,6 +60,20 @@ struct SampleArgs {
   float sigma[MAXN][NCH];
   float fill[NCH];
 };
+// ltu_sample_spline (ND = taps along D: 4 at order 3, 2 at order 1) carries the coefficient volume, each channel's clamp and which
+// patches of the launch are cubic on top; the kernels of the three older entry points (ND == 0) keep SampleArgs as their argument
+template <int NCH>
+struct CubicArgs : SampleArgs<NCH> {
+  const float* coef;
+  float lo[NCH], hi[NCH];
+  unsigned char cubic[SampleArgs<NCH>::MAXN];
+};
+template <int NCH, int ND>
+using SaArgs = std::conditional_t<ND == 0, SampleArgs<NCH>, CubicArgs<NCH>>;
+template <int NCH>
+__device__ __forceinline__ bool sa_cubic(const SampleArgs<NCH>&, int) { return false; }
+template <int NCH>
+__device__ __forceinline__ bool sa_cubic(const CubicArgs<NCH>& c, int k) { return c.cubic[k] != 0; }
 
 struct SaAxis { int base; float fr, lo, hi; };
 __device__ __forceinline__ SaAxis sa_axis(double o, int S) {
@@ -77,6 +94,16 @@ __device__ __forceinline__ void sa_split(const SaAxis& a, float l, int* i0, floa
 }
 // round half to even of base + l
 __device__ __forceinline__ int sa_round(int i0, float t) { return i0 + ((t > 0.5f || (t == 0.5f && (i0 & 1))) ? 1 : 0); }
+// the label of one voxel: nearest, 0 outside the scan
+template <typename IDX>
+__device__ __forceinline__ uint8_t sa_label(const uint8_t* __restrict__ lab, const int (&i0)[3], const float (&t)[3], int H, int W,
+                                            int D) {
+  const int xr = sa_round(i0[0], t[0]), yr = sa_round(i0[1], t[1]), zr = sa_round(i0[2], t[2]);
+  const bool in = (unsigned)xr < (unsigned)H && (unsigned)yr < (unsigned)W && (unsigned)zr < (unsigned)D;
+  uint8_t lv = 0;
+  if (in) lv = lab[((IDX)xr * W + yr) * D + zr];
+  return lv;
+}
 
 // An interpolated value must have the same bits in every instantiation (VEC, NCH, IDX): -ffp-contract=fast would fuse a product
 // into a following sum or not, depending on what else shares the operands (with several channels the compiler packs two channels'
@@ -115,6 +142,91 @@ __device__ __forceinline__ void sa_taps(const float* __restrict__ img, long long
   }
 #pragma unroll
   for (int ch = 0; ch < NCH; ++ch) vi[ch][j] = acc[ch];
+}
+
+// ---- the cubic taps of ltu_sample_spline ----------------------------------------------------------------------------------------
+// One voxel of a cubic patch, from the same (i0, t) the trilinear taps take: scipy.ndimage.map_coordinates(order=3, mode='constant')
+// on mirror-prefiltered coefficients.  The voxel is inside when every coordinate component lies in [0, S - 1], ends included
+// (i0 >= 0 and i0 + t <= S - 1); it is then clamp(sum of w * coef[taps], lo, hi) with the taps f-1 .. f+2 per cubic axis (2 taps f, f+1
+// along D at ND == 2), whole-sample mirrored, and fill - unclamped - otherwise: there is no blending across the edge.  Inside test,
+// 4 + 4 + ND offsets and weights once per voxel; each channel then runs its own sum in the fixed order of sp_tap_sum (spline.hip):
+// the ND taps along D, adjacent floats away from the ends, as the inner fused multiply-add chain, then (wx wy) * row added by one
+// fused multiply-add, W inside H.  The 4 ND taps of one H index and channel are loaded before the first is used, so that they are
+// in flight together; the channels take their turn inside the H tap, so 4 ND loaded values and offsets are live at a time whatever
+// NCH is (128 registers at NCH = 1, 131 at NCH = 4, against 250 with the channel loop outermost).
+
+// the tap sum of one voxel per channel, in its fixed order; ADJ: the taps along D are oz[0] .. oz[0] + ND - 1
+template <int NCH, int ND, bool ADJ>
+__device__ __forceinline__ void sc_sum(const float* __restrict__ coef, long long HWD, const int (&ox)[4], const int (&oy)[4],
+                                       const int (&oz)[ND], const float (&wx)[4], const float (&wy)[4], const float (&wz)[ND],
+                                       float (&acc)[NCH]) {
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) acc[ch] = 0.f;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      const float* __restrict__ p = coef + ch * HWD;
+      float v[4][ND];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const float* __restrict__ q = p + (unsigned)(ox[a] + oy[b] + oz[0]);                // unsigned: a 32-bit offset on a uniform base
+#pragma unroll
+        for (int e = 0; e < ND; ++e) v[b][e] = ADJ ? q[e] : p[(unsigned)(ox[a] + oy[b] + oz[e])];
+      }
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        float row = wz[0] * v[b][0];
+#pragma unroll
+        for (int e = 1; e < ND; ++e) row = fmaf(wz[e], v[b][e], row);
+        acc[ch] = fmaf(wx[a] * wy[b], row, acc[ch]);
+      }
+      // without it the scheduler hoists every channel's loads of every H tap to the top: 250 registers at NCH >= 2
+      if (NCH > 1) __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+template <int NCH, int ND, int VEC>
+__device__ __forceinline__ void sc_taps(const float* __restrict__ coef, long long HWD, const float (&fill)[NCH], const float (&lo)[NCH],
+                                        const float (&hi)[NCH], const int (&i0)[3], const float (&t)[3], int H, int W, int D, int j,
+                                        float (&vi)[NCH][VEC]) {
+  const int S[3] = {H, W, D};
+  bool in = true;
+#pragma unroll
+  for (int s = 0; s < 3; ++s) in = in && i0[s] >= 0 && (i0[s] < S[s] - 1 || (i0[s] == S[s] - 1 && t[s] == 0.f));
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) vi[ch][j] = fill[ch];
+  if (!in) return;
+  int ox[4], oy[4], oz[ND];
+  float wx[4], wy[4], wz[ND];
+  sp_cubic_weights(t[0], wx);
+  sp_cubic_weights(t[1], wy);
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    ox[a] = sp_mirror(i0[0] - 1 + a, H) * (W * D);         // H W D < 2^31 (checked on the host)
+    oy[a] = sp_mirror(i0[1] - 1 + a, W) * D;
+  }
+  if (ND == 4) {
+    sp_cubic_weights(t[2], wz);
+#pragma unroll
+    for (int a = 0; a < ND; ++a) oz[a] = sp_mirror(i0[2] - 1 + a, D);
+  } else {
+    wz[0] = 1.f - t[2];
+    wz[1] = t[2];
+    oz[0] = i0[2];
+    oz[1] = sp_mirror(i0[2] + 1, D);                       // i0 + 1 == D only with t == 0: a valid address, weight 0
+  }
+  // away from the ends of D no tap along it is mirrored: the ND taps are adjacent floats, and the same sum with the offsets 0 ..
+  // ND - 1 as constants fetches a row with one load instead of ND (ltu_resample_spline's step from 1.76 to 0.89 ms)
+  bool adjacent = true;
+#pragma unroll
+  for (int e = 1; e < ND; ++e) adjacent = adjacent && oz[e] == oz[0] + e;
+  float acc[NCH];
+  if (adjacent) sc_sum<NCH, ND, true>(coef, HWD, ox, oy, oz, wx, wy, wz, acc);
+  else sc_sum<NCH, ND, false>(coef, HWD, ox, oy, oz, wx, wy, wz, acc);
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) vi[ch][j] = fminf(fmaxf(acc[ch], lo[ch]), hi[ch]);
 }
 
 // the store of a lane's VEC voxels at (x, y, z) of patch k: noise per channel, then whole vectors
@@ -157,9 +269,12 @@ __device__ __forceinline__ void sa_store(float* __restrict__ oimg, uint8_t* __re
 
 // ZDEC: every matrix of the launch has the form [[a, b, 0, .], [c, e, 0, .], [0, 0, g, .]] (rotation about D only): the in-plane
 // taps, weights and the label's in-plane voxel are computed once per lane, the VEC depth voxels are 1-D lerps on the four rows.
-template <bool ZDEC, int VEC, int NCH, typename IDX>
+// ND != 0 (ltu_sample_spline): a patch with c.cubic[k] takes the cubic taps at the general kernel's coordinates (with a z-decoupled
+// matrix they are the z-decoupled kernel's: fmaf(0, ., fr) == fr); every other patch runs the code below as it stands, so it has
+// the bits of the ND == 0 kernel the same call would have chosen.  A workgroup belongs to one patch: the branch is uniform.
+template <bool ZDEC, int VEC, int NCH, typename IDX, int ND = 0>
 __global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lab,
-                                                            float* __restrict__ oimg, uint8_t* __restrict__ olab, SampleArgs<NCH> c,
+                                                            float* __restrict__ oimg, uint8_t* __restrict__ olab, SaArgs<NCH, ND> c,
                                                             int H, int W, int D, int h, int w, int d, int zl_log2, int ty_log2) {
   const int k = blockIdx.z;
   const int zl = 1 << zl_log2, ty = 1 << ty_log2;
@@ -186,7 +301,25 @@ __global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restr
   for (int ch = 0; ch < NCH; ++ch) fill[ch] = c.fill[ch];
   float vi[NCH][VEC];
   uint8_t vl[VEC];
-  if (ZDEC) {
+  if (ND != 0 && sa_cubic(c, k)) {
+    if constexpr (ND != 0) {
+      float lo[NCH], hi[NCH];
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch) {
+        lo[ch] = c.lo[ch];
+        hi[ch] = c.hi[ch];
+      }
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        int i0[3];
+        float t[3];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) sa_split(ax[s], fmaf(my[s], (float)yl, fmaf(mz[s], (float)(zq + j), ax[s].fr)), &i0[s], &t[s]);
+        if (img != nullptr) sc_taps<NCH, ND>(c.coef, HWD, fill, lo, hi, i0, t, H, W, D, j, vi);
+        if (lab != nullptr) vl[j] = sa_label<IDX>(lab, i0, t, H, W, D);
+      }
+    }
+  } else if (ZDEC) {
     int i0[2];
     float t[2];
 #pragma unroll
@@ -239,20 +372,14 @@ __global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restr
 #pragma unroll
       for (int s = 0; s < 3; ++s) sa_split(ax[s], fmaf(my[s], (float)yl, fmaf(mz[s], (float)(zq + j), ax[s].fr)), &i0[s], &t[s]);
       if (img != nullptr) sa_taps<NCH, IDX>(img, HWD, fill, i0, t, H, W, D, j, vi);
-      if (lab != nullptr) {
-        const int xr = sa_round(i0[0], t[0]), yr = sa_round(i0[1], t[1]), zr = sa_round(i0[2], t[2]);
-        const bool in = (unsigned)xr < (unsigned)H && (unsigned)yr < (unsigned)W && (unsigned)zr < (unsigned)D;
-        uint8_t lv = 0;
-        if (in) lv = lab[((IDX)xr * W + yr) * D + zr];
-        vl[j] = lv;
-      }
+      if (lab != nullptr) vl[j] = sa_label<IDX>(lab, i0, t, H, W, D);
     }
   }
   sa_store<VEC, NCH>(oimg, olab, img != nullptr, lab != nullptr, vi, vl, c.seed[k], c.sigma[k], k, x, y, z, h, w, d);
 }
 
-template <bool ZDEC, int VEC, int NCH, typename IDX>
-static void sample_affine_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SampleArgs<NCH>& c, int n, int H,
+template <bool ZDEC, int VEC, int NCH, typename IDX, int ND>
+static void sample_affine_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SaArgs<NCH, ND>& c, int n, int H,
                                  int W, int D, int h, int w, int d, hipStream_t st) {
   const int per_lane = (d + VEC - 1) / VEC;
   int zl_log2 = 0;
@@ -261,7 +388,7 @@ static void sample_affine_launch(const float* img, const uint8_t* lab, float* oi
   while ((1 << ty_log2) < w && zl_log2 + ty_log2 < 8) ++ty_log2;
   const int zl = 1 << zl_log2, ty = 1 << ty_log2, tx = 256 >> (zl_log2 + ty_log2);
   const unsigned tiles = cdiv(w, ty) * cdiv(d, zl * VEC);
-  hipLaunchKernelGGL((sample_affine_kernel<ZDEC, VEC, NCH, IDX>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c, H,
+  hipLaunchKernelGGL((sample_affine_kernel<ZDEC, VEC, NCH, IDX, ND>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c, H,
                      W, D, h, w, d, zl_log2, ty_log2);
 }
 
@@ -316,9 +443,9 @@ __device__ __forceinline__ float se_dot4(const float (&w)[4], const float* p, in
   return fmaf(w[3], p[3 * stride], fmaf(w[2], p[2 * stride], fmaf(w[1], p[stride], w[0] * p[0])));
 }
 
-template <int VEC, int NC, int NCH, typename IDX>
+template <int VEC, int NC, int NCH, typename IDX, int ND = 0>
 __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lab,
-                                                             float* __restrict__ oimg, uint8_t* __restrict__ olab, SampleArgs<NCH> c,
+                                                             float* __restrict__ oimg, uint8_t* __restrict__ olab, SaArgs<NCH, ND> c,
                                                              const float* __restrict__ phi, int gh, int gw, int gd, float sx, float sy,
                                                              float sz, int H, int W, int D, int h, int w, int d, int zl_log2,
                                                              int ty_log2, int tx_log2) {
@@ -384,6 +511,15 @@ __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __rest
   for (int ch = 0; ch < NCH; ++ch) fill[ch] = c.fill[ch];
   float vi[NCH][VEC];
   uint8_t vl[VEC];
+  const bool cubic = ND != 0 && sa_cubic(c, k);        // uniform in the workgroup; the deformed coordinate is shared, the taps differ
+  [[maybe_unused]] float lo[NCH], hi[NCH];
+  if constexpr (ND != 0) {
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      lo[ch] = c.lo[ch];
+      hi[ch] = c.hi[ch];
+    }
+  }
 #pragma unroll
   for (int j = 0; j < VEC; ++j) {
     int off = 0;
@@ -412,20 +548,20 @@ __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __rest
       sa_split(ax[s], fmaf(my[s], (float)yl, fmaf(mz[s], (float)(zq + j), ax[s].fr)) +
                           sa_rounded(fmaf(mz[s], u[2], fmaf(my[s], u[1], mx[s] * u[0]))),
                &i0[s], &t[s]);
-    if (img != nullptr) sa_taps<NCH, IDX>(img, HWD, fill, i0, t, H, W, D, j, vi);
-    if (lab != nullptr) {
-      const int xr = sa_round(i0[0], t[0]), yr = sa_round(i0[1], t[1]), zr = sa_round(i0[2], t[2]);
-      const bool in = (unsigned)xr < (unsigned)H && (unsigned)yr < (unsigned)W && (unsigned)zr < (unsigned)D;
-      uint8_t lv = 0;
-      if (in) lv = lab[((IDX)xr * W + yr) * D + zr];
-      vl[j] = lv;
+    if (img != nullptr) {
+      if (cubic) {
+        if constexpr (ND != 0) sc_taps<NCH, ND>(c.coef, HWD, fill, lo, hi, i0, t, H, W, D, j, vi);
+      } else {
+        sa_taps<NCH, IDX>(img, HWD, fill, i0, t, H, W, D, j, vi);
+      }
     }
+    if (lab != nullptr) vl[j] = sa_label<IDX>(lab, i0, t, H, W, D);
   }
   sa_store<VEC, NCH>(oimg, olab, img != nullptr, lab != nullptr, vi, vl, c.seed[k], c.sigma[k], k, x, y, z, h, w, d);
 }
 
-template <int VEC, int NC, int NCH, typename IDX>
-static void sample_elastic_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SampleArgs<NCH>& c,
+template <int VEC, int NC, int NCH, typename IDX, int ND>
+static void sample_elastic_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SaArgs<NCH, ND>& c,
                                   const float* phi, int gh, int gw, int gd, int n, int H, int W, int D, int h, int w, int d,
                                   hipStream_t st) {
   const int per_lane = (d + VEC - 1) / VEC;
@@ -441,7 +577,7 @@ static void sample_elastic_launch(const float* img, const uint8_t* lab, float* o
   const float sx = h > 1 ? (float)((double)(gh - 3) / (double)(h - 1)) : 0.f;
   const float sy = w > 1 ? (float)((double)(gw - 3) / (double)(w - 1)) : 0.f;
   const float sz = d > 1 ? (float)((double)(gd - 3) / (double)(d - 1)) : 0.f;
-  hipLaunchKernelGGL((sample_elastic_kernel<VEC, NC, NCH, IDX>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c,
+  hipLaunchKernelGGL((sample_elastic_kernel<VEC, NC, NCH, IDX, ND>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c,
                      phi, gh, gw, gd, sx, sy, sz, H, W, D, h, w, d, zl_log2, ty_log2, tx_log2);
 }
 
@@ -460,6 +596,12 @@ struct SampleCall {
   const unsigned long long* seeds;     // [n][K] or NULL
   const float* fill;                   // [K]
   int n, K, H, W, D, h, w, d;
+  // ltu_sample_spline only (nd = the taps along D, 0 for the other entry points)
+  int nd;
+  const float* coef;
+  const float* lo;                     // [K]
+  const float* hi;                     // [K]
+  const unsigned char* cubic;          // [n]
 };
 
 // everything the entry points refuse, in sample_affine's order; LTU_OK with *run = false: nothing to do
@@ -490,6 +632,8 @@ static int sample_check(const SampleCall& q, bool elastic, bool* run) {
       if (!(sg >= 0.f) || !(sg - sg == 0.f)) return LTU_E_ARG;
     }
   }
+  // the cubic taps index the coefficients with 32 bits (ltu_spline_prefilter builds no larger volume either)
+  if (q.nd != 0 && (long long)q.H * q.W * q.D >= (1LL << 31)) return LTU_E_SHAPE;
   if ((elastic && ((uintptr_t)q.phi & 3) != 0) || (q.d % 4 == 0 && (((uintptr_t)q.oi & 15) != 0 || ((uintptr_t)q.ol & 3) != 0)))
     return LTU_E_ALIGN;
   *run = true;
@@ -497,8 +641,9 @@ static int sample_check(const SampleCall& q, bool elastic, bool* run) {
 }
 
 // a checked call as launches of at most SampleArgs<NCH>::MAXN patches; the kernel variant is chosen from the whole call, so that a
-// patch has the same bits wherever the call is split
-template <int NCH>
+// patch has the same bits wherever the call is split.  ND != 0 (ltu_sample_spline) chooses as ND == 0 does, so that its trilinear
+// patches run the expressions ltu_sample_channels would run on them; its scans are below 2^31 voxels: 32-bit indices only.
+template <int NCH, int ND>
 static void sample_go(const SampleCall& q, hipStream_t st) {
   bool zdec = true;
   for (int k = 0; k < q.n; ++k) {
@@ -509,8 +654,15 @@ static void sample_go(const SampleCall& q, hipStream_t st) {
   const bool small = (long long)q.H * q.W * q.D < (1LL << 31);
   const bool two_cells = 3.0 * (q.gd - 3) <= 0.99 * (q.d - 1);       // a run of 4 voxels along z spans at most two lattice cells
   const long long hwd = (long long)q.h * q.w * q.d;
-  SampleArgs<NCH> c;
+  SaArgs<NCH, ND> c;
   for (int ch = 0; ch < NCH; ++ch) c.fill[ch] = q.fill[ch];
+  if constexpr (ND != 0) {
+    c.coef = q.coef;
+    for (int ch = 0; ch < NCH; ++ch) {
+      c.lo[ch] = q.lo[ch];
+      c.hi[ch] = q.hi[ch];
+    }
+  }
   for (int k0 = 0; k0 < q.n; k0 += SampleArgs<NCH>::MAXN) {
     const int n = q.n - k0 < SampleArgs<NCH>::MAXN ? q.n - k0 : SampleArgs<NCH>::MAXN;
     for (int k = 0; k < n; ++k) {
@@ -519,19 +671,24 @@ static void sample_go(const SampleCall& q, hipStream_t st) {
         c.sigma[k][ch] = (q.img != nullptr && q.sigma != nullptr) ? q.sigma[(k0 + k) * NCH + ch] : 0.f;
         c.seed[k][ch] = q.seeds != nullptr ? q.seeds[(k0 + k) * NCH + ch] : 0ull;
       }
+      if constexpr (ND != 0) c.cubic[k] = q.cubic[k0 + k];
     }
     float* oi = q.oi != nullptr ? q.oi + k0 * NCH * hwd : nullptr;
     uint8_t* ol = q.ol != nullptr ? q.ol + k0 * hwd : nullptr;
 #define SA_GO(Z, V)                                                                                                          \
   do {                                                                                                                       \
-    if (small) sample_affine_launch<Z, V, NCH, int>(q.img, q.lab, oi, ol, c, n, q.H, q.W, q.D, q.h, q.w, q.d, st);            \
-    else sample_affine_launch<Z, V, NCH, long long>(q.img, q.lab, oi, ol, c, n, q.H, q.W, q.D, q.h, q.w, q.d, st);            \
+    if (small) sample_affine_launch<Z, V, NCH, int, ND>(q.img, q.lab, oi, ol, c, n, q.H, q.W, q.D, q.h, q.w, q.d, st);        \
+    else if constexpr (ND == 0)                                                                                              \
+      sample_affine_launch<Z, V, NCH, long long, ND>(q.img, q.lab, oi, ol, c, n, q.H, q.W, q.D, q.h, q.w, q.d, st);           \
   } while (0)
 #define SE_GO(V, NCOL)                                                                                                                     \
   do {                                                                                                                                     \
     const float* pk = q.phi + (long long)k0 * 3 * q.gh * q.gw * q.gd;                                                                      \
-    if (small) sample_elastic_launch<V, NCOL, NCH, int>(q.img, q.lab, oi, ol, c, pk, q.gh, q.gw, q.gd, n, q.H, q.W, q.D, q.h, q.w, q.d, st); \
-    else sample_elastic_launch<V, NCOL, NCH, long long>(q.img, q.lab, oi, ol, c, pk, q.gh, q.gw, q.gd, n, q.H, q.W, q.D, q.h, q.w, q.d, st); \
+    if (small)                                                                                                                             \
+      sample_elastic_launch<V, NCOL, NCH, int, ND>(q.img, q.lab, oi, ol, c, pk, q.gh, q.gw, q.gd, n, q.H, q.W, q.D, q.h, q.w, q.d, st);     \
+    else if constexpr (ND == 0)                                                                                                            \
+      sample_elastic_launch<V, NCOL, NCH, long long, ND>(q.img, q.lab, oi, ol, c, pk, q.gh, q.gw, q.gd, n, q.H, q.W, q.D, q.h, q.w, q.d,    \
+                                                         st);                                                                              \
   } while (0)
     if (q.phi != nullptr) {
       if (vec == 1) SE_GO(1, 4);
@@ -546,16 +703,25 @@ static void sample_go(const SampleCall& q, hipStream_t st) {
   }
 }
 
+template <int ND>
+static void sample_go_channels(const SampleCall& q, hipStream_t st) {
+  switch (q.K) {
+    case 1: sample_go<1, ND>(q, st); break;
+    case 2: sample_go<2, ND>(q, st); break;
+    case 3: sample_go<3, ND>(q, st); break;
+    default: sample_go<4, ND>(q, st); break;
+  }
+}
+
 static int sample_run(const SampleCall& q, bool elastic, ltu_stream_t s) {
   bool run;
   const int rc = sample_check(q, elastic, &run);
   if (rc != LTU_OK || !run) return rc;
   static_assert(LTU_MAX_INPUT_CHANNELS == 4, "one instantiation per channel count");
-  switch (q.K) {
-    case 1: sample_go<1>(q, (hipStream_t)s); break;
-    case 2: sample_go<2>(q, (hipStream_t)s); break;
-    case 3: sample_go<3>(q, (hipStream_t)s); break;
-    default: sample_go<4>(q, (hipStream_t)s); break;
+  switch (q.nd) {
+    case 0: sample_go_channels<0>(q, (hipStream_t)s); break;
+    case 2: sample_go_channels<2>(q, (hipStream_t)s); break;
+    default: sample_go_channels<4>(q, (hipStream_t)s); break;
   }
   return ltu_check_launch();
 }
@@ -579,6 +745,20 @@ extern "C" int ltu_sample_channels(const float* img, const uint8_t* lab, float* 
                                    const unsigned long long* seeds, const float* fill, int n, int K, int H, int W, int D, int h, int w,
                                    int d, ltu_stream_t s) {
   const SampleCall q = {img, lab, out_img, out_lab, mats, phi, gh, gw, gd, noise_sigma, seeds, fill, n, K, H, W, D, h, w, d};
+  return sample_run(q, phi != nullptr, s);
+}
+
+extern "C" int ltu_sample_spline(const float* img, const float* coef, const uint8_t* lab, float* out_img, uint8_t* out_lab,
+                                 const double* mats, const float* phi, int gh, int gw, int gd, const float* noise_sigma,
+                                 const unsigned long long* seeds, const float* fill, const float* lo, const float* hi,
+                                 const unsigned char* cubic, int n, int K, int H, int W, int D, int h, int w, int d, int order_d,
+                                 ltu_stream_t s) {
+  if (coef == nullptr || cubic == nullptr || lo == nullptr || hi == nullptr || (order_d != 1 && order_d != 3)) return LTU_E_ARG;
+  if (K < 1 || K > LTU_MAX_INPUT_CHANNELS) return LTU_E_SHAPE;
+  for (int ch = 0; ch < K; ++ch)
+    if (!(lo[ch] <= hi[ch])) return LTU_E_ARG;             // a NaN bound too
+  const SampleCall q = {img, lab, out_img, out_lab, mats, phi, gh, gw, gd, noise_sigma, seeds, fill, n, K, H, W, D, h, w, d,
+                        order_d == 3 ? 4 : 2, coef, lo, hi, cubic};
   return sample_run(q, phi != nullptr, s);
 }
 

@@ -243,15 +243,7 @@ struct SplineArgs {
   float lo, hi;
 };
 
-// whole-sample mirror of a tap index in -1 .. n + 1 (all that occurs after the clamp)
-__device__ __forceinline__ int sp_mirror(int i, int n) {
-  if (n == 1) return 0;
-  const int p = 2 * (n - 1);
-  i = i < 0 ? -i : i;
-  i = i >= p ? i - p : i;
-  return i > n - 1 ? p - i : i;
-}
-
+// sp_mirror and sp_cubic_weights: resample_coords.h
 template <int N>
 __device__ __forceinline__ void sp_axis_taps(int n, int stride, double c, int* off, float* w) {
   if (N == 1) {
@@ -269,11 +261,7 @@ __device__ __forceinline__ void sp_axis_taps(int n, int stride, double c, int* o
     w[1] = t;
     return;
   }
-  const float u = 1.f - t, t2 = t * t;
-  w[0] = u * u * u * (1.f / 6.f);
-  w[1] = fmaf(t2, fmaf(0.5f, t, -1.f), 2.f / 3.f);
-  w[2] = fmaf(t, fmaf(t, fmaf(-0.5f, t, 0.5f), 0.5f), 1.f / 6.f);
-  w[3] = t2 * t * (1.f / 6.f);
+  sp_cubic_weights(t, w);
 #pragma unroll
   for (int j = 0; j < 4; ++j) off[j] = sp_mirror(i - 1 + j, n) * stride;
 }

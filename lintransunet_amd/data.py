@@ -1022,6 +1022,25 @@ class SpacedScan:
             self._crop_index = CropIndex(self.lab)
         return self._crop_index
 
+    def spline_coefficients(self, order):
+        """the cubic B-spline coefficients of `img` (same shape, every channel of a MultiScan) for the gather's `order` (sample_order:
+        3, (3, 3, 3) or (3, 3, 1) per scan axis H, W, D), as sample_affine(order=, coef=) reads them: built on first use by
+        data.spline_coefficients and kept per order tuple.  While held they double the image's bytes on the device;
+        drop_coefficients() frees them."""
+        orders = sample_order(order)
+        if orders == (1, 1, 1):
+            raise ValueError('order 1 reads the image itself: there are no coefficients to build')
+        cache = self.__dict__.setdefault('_spline_coefficients', {})
+        if orders not in cache:
+            axes = (orders[2], orders[1], orders[0])         # data.spline_coefficients counts the axes from the fastest: D, W, H
+            vols = self.img if self.img.dim() == 4 else self.img[None]
+            cache[orders] = torch.stack([spline_coefficients(v, axes) for v in vols]).view(self.img.shape)
+        return cache[orders]
+
+    def drop_coefficients(self):
+        """free every coefficient volume spline_coefficients holds (the next call builds them again)"""
+        self.__dict__.pop('_spline_coefficients', None)
+
 
 def _scan_order(order, affine, pixdim):
     """SpacedScan's `order` as the 3-tuple per file axis; 'auto' asks geometry.resample_orders"""
@@ -1228,7 +1247,38 @@ def _check_lattice(elastic):
     return lat
 
 
-def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, elastic=None):
+SAMPLE_ORDERS = ((1, 1, 1), (3, 3, 3), (3, 3, 1))      # the gather's interpolation per scan axis H, W, D, as built
+
+
+def sample_order(order):
+    """the `order` of sample_affine / Augmentation / SpacedScan.spline_coefficients as a 3-tuple per scan axis H, W, D: 1 (trilinear),
+    3 (cubic B-spline on every axis) or one of SAMPLE_ORDERS; anything else is a ValueError"""
+    if isinstance(order, (int, np.integer)) and not isinstance(order, bool):
+        orders = (int(order),) * 3
+    else:
+        try:
+            orders = tuple(int(o) for o in order)
+            if len(orders) != 3 or any(o != v for o, v in zip(orders, order)):
+                orders = None
+        except (TypeError, ValueError):
+            orders = None
+    if orders not in SAMPLE_ORDERS:
+        raise ValueError(f'the patch gather is built for order 1, 3, (3, 3, 3) and (3, 3, 1) per scan axis H, W, D, got {order!r}')
+    return orders
+
+
+def _channel_bounds(clamp, K):
+    """sample_affine's clamp as float32 (lo [K], hi [K]): None, one (lo, hi) pair or one pair per channel"""
+    if clamp is None:
+        return np.full(K, -np.inf, dtype=np.float32), np.full(K, np.inf, dtype=np.float32)
+    c = np.asarray(clamp, dtype=np.float32)
+    if c.shape not in ((2,), (K, 2)) or not bool((np.broadcast_to(c, (K, 2))[:, 0] <= np.broadcast_to(c, (K, 2))[:, 1]).all()):
+        raise ValueError(f'clamp is (lo, hi) with lo <= hi, or one such pair per channel ({K}), got {clamp!r}')
+    c = np.broadcast_to(c, (K, 2))
+    return np.ascontiguousarray(c[:, 0]), np.ascontiguousarray(c[:, 1])
+
+
+def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, elastic=None, order=1, coef=None, clamp=None):
     """ltu_sample_affine: device patches ([n,1,h,w,d] f32 or None, [n,1,h,w,d] u8 or None) gathered from img / lab [H,W,D] through
     mats [n,3,4] (float64 pull matrices, patch voxel -> scan voxel): image trilinear with `fill` outside the scan, label nearest
     (round half even) with 0 outside.  noise_sigma [n] with seeds [n] (uint64) adds sigma_k * N(0, 1) to patch k in the store
@@ -1238,7 +1288,16 @@ def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, 
     A 4-D img [K,H,W,D] (K = 1 .. 4 channels on the label's grid, e.g. MultiScan.img) goes through ltu_sample_channels and returns
     [n,K,h,w,d]: one gather whose coordinates, taps and label voxel are formed once for all channels.  fill is then a number or one
     per channel, noise_sigma [n] or [n,K], seeds [n,K] (or [n]: channel c of patch k gets channel_seed(seeds[k], c)); channel c has
-    the bits of the 3-D call on img[c] with fill[c], noise_sigma[:, c] and seeds[:, c]."""
+    the bits of the 3-D call on img[c] with fill[c], noise_sigma[:, c] and seeds[:, c].
+    order (sample_order: 1, 3, (3, 3, 3) or (3, 3, 1) per scan axis H, W, D): 1, the default, is everything above.  Any other goes
+    through ltu_sample_spline and interpolates the image as scipy.ndimage.map_coordinates(order=3, mode='constant', cval=fill) does
+    (nnU-Net's spatial transform): the cubic tap sum where the coordinate lies inside [0, S - 1] on every axis, fill elsewhere, no
+    blending across the edge; (3, 3, 1) is linear along D, the coarse axis of an anisotropic scan.  coef: the B-spline coefficients
+    of img in its shape (SpacedScan.spline_coefficients(order) caches them); None builds them here with spline_coefficients, per
+    channel.  clamp: (lo, hi) or one pair per channel, applied to the tap sum, not to fill (the spline rings past a clipped
+    intensity window); None = no clamp.  A patch is cubic unless all 12 entries of its matrix are integers and it has no lattice or
+    an all-zero one: such a patch keeps the trilinear expressions, that is the source voxels.  The label is order 1's, byte for byte."""
+    orders = sample_order(order)
     if elastic is not None:
         elastic = _check_lattice(elastic)
     vol = img if img is not None else lab
@@ -1274,13 +1333,30 @@ def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, 
             raise ValueError(f'elastic holds {elastic.shape[0]} lattices for {n} matrices')
         lat = (elastic if torch.is_tensor(elastic) else torch.from_numpy(elastic)).to(vol.device)
         g = tuple(int(v) for v in lat.shape[2:])
-    if multi:
+    cubic = orders != (1, 1, 1) and img is not None        # a label alone has nothing to interpolate
+    if multi or cubic:
         fl = np.ascontiguousarray(np.broadcast_to(np.asarray(fill, dtype=np.float32).reshape(-1), (K,)))
+    if cubic:
+        if coef is None:
+            axes = (orders[2], orders[1], orders[0])         # spline_coefficients counts the axes from the fastest: D, W, H
+            coef = torch.stack([spline_coefficients(v, axes) for v in (img if multi else img[None])])
+        if not torch.is_tensor(coef) or coef.device != img.device or coef.dtype != torch.float32 or not coef.is_contiguous() or \
+                coef.numel() != img.numel() or coef.shape[-3:] != img.shape[-3:]:
+            raise ValueError(f'coef is a contiguous float32 tensor of the image\'s shape {tuple(img.shape)} on its device')
+        lo, hi = _channel_bounds(clamp, K)
+        which = (m != np.round(m)).any(1)
+        if elastic is not None:
+            which = which | (lat.reshape(n, -1) != 0).any(1).cpu().numpy()
+        which = np.ascontiguousarray(which.astype(np.uint8))
     for s in range(0, n, _lib.SAMPLE_AFFINE_MAX):
         e = min(n, s + _lib.SAMPLE_AFFINE_MAX)
         out = (_p(oi[s:e]) if oi is not None else 0, _p(ol[s:e]) if ol is not None else 0)
         noise = (sg[s:e].ctypes.data if sg is not None else 0, sd[s:e].ctypes.data if sd is not None else 0)
-        if multi:
+        if cubic:
+            _lib.call('ltu_sample_spline', _p(img), _p(coef), _p(lab), *out, m[s:e].ctypes.data,
+                      _p(lat[s:e]) if elastic is not None else 0, *g, *noise, fl.ctypes.data, lo.ctypes.data, hi.ctypes.data,
+                      which[s:e].ctypes.data, e - s, K, H, W, D, h, w, d, orders[2], _s())
+        elif multi:
             _lib.call('ltu_sample_channels', _p(img), _p(lab), *out, m[s:e].ctypes.data, _p(lat[s:e]) if elastic is not None else 0, *g,
                       *noise, fl.ctypes.data, e - s, K, H, W, D, h, w, d, _s())
         elif elastic is not None:
@@ -1365,11 +1441,15 @@ class Augmentation:
     magnifies; noise_std, blur_sigma (voxels), brightness and gamma are uniform ranges; fill: the image value outside the scan, None =
     the lower bound of the scan's intensity window (0.0 when it has none).  elastic_prob > 0 adds a B-spline free-form deformation
     (elastic_displacement): a control lattice of elastic_grid points per patch axis, uniform in +-elastic_mm millimetres of the scan
-    with elastic_mm drawn from its range; 0 (the default) makes no draw for it."""
+    with elastic_mm drawn from its range; 0 (the default) makes no draw for it.  order (sample_order: 1, 3, (3, 3, 3) or (3, 3, 1)
+    per scan axis H, W, D): the image interpolation of the patches that rotate, zoom or deform; 1, the default, is trilinear, any
+    other is sample_affine's cubic B-spline from scan.spline_coefficients(order) (nnU-Net interpolates at order 3), clamped to each
+    channel's intensity window.  It makes no draw: draw() returns the same values and leaves the generator in the same state."""
 
     def __init__(self, rot_prob=0.2, rot_range=(0.0, 0.0, np.pi), zoom_prob=0.2, zoom_range=(0.7, 1.4), noise_prob=0.1,
                  noise_std=(0.0, 0.1), blur_prob=0.2, blur_sigma=(0.5, 1.0), brightness_prob=0.15, brightness=(0.75, 1.25),
-                 gamma_prob=0.3, gamma=(0.7, 1.5), fill=None, elastic_prob=0.0, elastic_mm=(0.0, 4.0), elastic_grid=(6, 6, 4)):
+                 gamma_prob=0.3, gamma=(0.7, 1.5), fill=None, elastic_prob=0.0, elastic_mm=(0.0, 4.0), elastic_grid=(6, 6, 4), order=1):
+        self.order = sample_order(order)
         self.elastic_prob, self.elastic_mm = elastic_prob, tuple(float(v) for v in elastic_mm)
         self.elastic_grid = tuple(int(g) for g in elastic_grid)
         if len(self.elastic_grid) != 3 or not all(4 <= g <= _lib.ELASTIC_MAX_GRID for g in self.elastic_grid):
@@ -1477,9 +1557,16 @@ def _augmented(scan, draws, params, spatial_size, augment, spacing):
                 zf = p['zoom_factor'] if p['zoom'] else 1.0
                 for c, a in enumerate((1, 0, 2) if swap else (0, 1, 2)):
                     lattice[i, c] = p['phi'][c] * (p['elastic_mm'] * zf / float(spacing[a]))
+    cubic = {}
+    if augment.order != (1, 1, 1):
+        # the patches that rotate, zoom or deform are the ones without an integer matrix and a zero lattice: sample_affine's own
+        # rule picks them; the others stay the source voxels.  The clamp is each channel's window, +-inf where it has none
+        windows = scan.intensity if _multi(scan) else [getattr(scan, 'intensity', None)]
+        cubic = dict(order=augment.order, coef=scan.spline_coefficients(augment.order),
+                     clamp=[intensity_map(wd)[2:4] for wd in windows])
     img, lab = sample_affine(scan.img, scan.lab, np.stack(mats), size, fill,
                              [p['noise_std'] if p['noise'] else 0.0 for p in params] if noisy else None,
-                             [p['seed'] for p in params] if noisy else None, elastic=lattice)
+                             [p['seed'] for p in params] if noisy else None, elastic=lattice, **cubic)
     shape, K = img.shape, img.shape[1]
     img = img.view(-1, 1, *size)
 
