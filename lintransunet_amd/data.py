@@ -9,7 +9,9 @@ sample, from a `CropIndex` of the device label (csrc/crop_index.hip): the host k
 CT_pancreas_ids.py:121-134) to a batch of patches on the device; the random draws stay on the host.
 The third driver's data side (train3D_monai_version.py with dataset/CT_pancreas_monai.py: NIfTI scans of the Medical
 Segmentation Decathlon layout, ScaleIntensityRanged -> Spacingd -> Orientationd('RAS'), then crop + RandFlipd + RandRotate90d) is
-`SpacedScan` / `sample` / `to_native` / `to_native_probs` at the end of this file.
+`SpacedScan` / `sample` / `to_native` / `to_native_probs` at the end of this file.  Scans and patches have 1 to 4 channels and one
+path each: `SpacedScan` and `MultiScan` load through `SpacedScan._load` and `_load_channel`, and `sample_affine` gathers a 3-D image
+as the one-channel case of `ltu_sample_channels` (order 1) or `ltu_sample_spline` (cubic).
 """
 import warnings
 
@@ -394,19 +396,24 @@ def label_u8(a):
 SPLINE_ORDERS = (0, 1, 3)             # per source axis: nearest, linear, cubic B-spline
 
 
+def _order_tuple(order):
+    """an `order` argument as a 3-tuple of ints: the int 1 or 3 stands for all three axes, a sequence must be exactly three ints;
+    None for anything else.  resolve_order and sample_order each admit their own tuples and word their own refusal."""
+    if isinstance(order, (int, np.integer)) and not isinstance(order, bool):
+        return (int(order),) * 3 if int(order) in (1, 3) else None
+    try:
+        orders = tuple(int(o) for o in order)
+        exact = len(orders) == 3 and all(o == v for o, v in zip(orders, order))
+    except (TypeError, ValueError):
+        return None
+    return orders if exact else None
+
+
 def resolve_order(order):
     """an interpolation `order` (1, 3, or one of 0 / 1 / 3 per source axis) as the 3-tuple the kernels take.  Built: (1, 1, 1) (the
     trilinear kernel), (3, 3, 3), and 3 on two axes with 0 or 1 on the third; anything else is a ValueError."""
-    if isinstance(order, (int, np.integer)) and not isinstance(order, bool):
-        if int(order) not in (1, 3):
-            raise ValueError(f'order is 1, 3 or a 3-tuple of {SPLINE_ORDERS}, got {order!r}')
-        return (int(order),) * 3
-    try:
-        orders = tuple(int(o) for o in order)
-        exact = all(o == v for o, v in zip(orders, order))
-    except (TypeError, ValueError):
-        orders, exact = (), False
-    if len(orders) != 3 or not exact or any(o not in SPLINE_ORDERS for o in orders):
+    orders = _order_tuple(order)
+    if orders is None or any(o not in SPLINE_ORDERS for o in orders):
         raise ValueError(f'order is 1, 3 or a 3-tuple of {SPLINE_ORDERS}, got {order!r}')
     if orders != (1, 1, 1) and sum(o == 3 for o in orders) < 2:
         raise ValueError(f'orders {orders} are not built: (1, 1, 1), (3, 3, 3), or 3 on two axes with 0 or 1 on the third')
@@ -906,26 +913,28 @@ def _masked_zscore(raw, mask, slope, inter):
 
 
 def _load_channel(ri, rl, code, spec, slope, inter, mask, box, plan, order):
-    """one channel of a scan that is cropped or normalised under its nonzero mask: (f32 image, u8 label or None, window).  ri / rl:
-    the device volumes as stored [Z, Y, X]; box: the crop in their axes; plan: (matrix, shape) of the box's resampling.
-    'zscore_nonzero' normalises the box first (normalize_masked) and resamples the f32 result with the identity map; every other
-    spec resamples the box of the stored volume through its strides, no copy.  The label is resampled from its box, nearest."""
+    """one channel of a scan, for every crop and every spec: (f32 image, u8 label or None, window).  ri / rl: the device volumes as
+    stored [Z, Y, X] (rl None: no label, or not channel 0); box: the part to load in their axes, the whole volume without a crop;
+    mask: the scan's nonzero mask, None where it needs none; plan: (matrix, shape) of the box's resampling.
+    The box is read through the stored volume's strides, no copy; the whole volume's box is the layout data.resample assumes of a
+    source without strides.  'zscore_nonzero' normalises the box first (normalize_masked) and resamples the f32 result with the
+    identity map, the label from its box in a call of its own; every other spec resamples image and label in ONE call (at order 1
+    one launch).  The label is nearest."""
     matrix, shape = plan
     Z, Y, X = (int(n) for n in ri.shape)
     (z0, z1), (y0, y1), (x0, x1) = box
     strides = (1, X, X * Y)
 
     def boxed(t):                                     # the box as a view with x first, as `strides` describes it
-        return t[z0:z1, y0:y1, x0:x1].permute(2, 1, 0)
-    ol = None
-    if rl is not None:
-        _, ol = resample(None, boxed(rl), matrix, shape, src_strides=strides)
+        return None if t is None else t[z0:z1, y0:y1, x0:x1].permute(2, 1, 0)
     if _masked_spec(spec):
+        ol = resample(None, boxed(rl), matrix, shape, src_strides=strides)[1] if rl is not None else None
         window, alpha, beta = _masked_zscore(ri, mask, slope, inter)
         oi, _ = resample(normalize_masked(ri, mask, box, alpha, beta, code), None, matrix, shape, order=order)
     else:
         window = _resolve_intensity(spec, ri, slope, inter)
-        oi, _ = resample(boxed(ri), None, matrix, shape, intensity_map(window, slope, inter), code, src_strides=strides, order=order)
+        oi, ol = resample(boxed(ri), boxed(rl), matrix, shape, intensity_map(window, slope, inter), code, src_strides=strides,
+                          order=order)
     return oi, ol, window
 
 
@@ -946,7 +955,8 @@ def _resolve_intensity(intensity, raw, slope, inter):
 
 class SpacedScan:
     """The deterministic half of the driver's CacheDataset: one NIfTI image (and label) read, uploaded once as stored, and
-    resampled on the device to `pixdim` in `axcodes` orientation.  img: f32 [H, W, D]; lab: u8 [H, W, D] (or None);
+    resampled on the device to `pixdim` in `axcodes` orientation: the K = 1 case of the loader it shares with MultiScan (_load, every
+    channel through _load_channel), presented without the channel axis.  img: f32 [H, W, D]; lab: u8 [H, W, D] (or None);
     crop_index: the label's CropIndex, built on first use (crop centres are drawn from it); label_host: the resampled label on the
     host, copied on first use (a scan that is only sampled through the index never copies it); affine: the output's 4x4 affine;
     matrix: the 3x4 float64 pull matrix (RAS voxel -> file voxel); native_shape / native_affine / native: the file's grid and header.
@@ -970,45 +980,57 @@ class SpacedScan:
 
     def __init__(self, img_path, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda',
                  order=1, crop=None):
-        _check_scan_options(crop, [intensity])
-        ni = nifti.load(img_path)
+        img, (self.intensity,), (self.outside,) = self._load([img_path], lab_path, pixdim, axcodes, [intensity], device, order, crop)
+        self.img = img[0]
+
+    def _load(self, paths, lab_path, pixdim, axcodes, specs, device, order, crop):
+        """the loader of SpacedScan and MultiScan: K files with one intensity spec each -> (img f32 [K, H, W, D], the K windows, the
+        K `outside` values); every other attribute is set here.  A scan that needs no nonzero mask is uploaded, resampled and
+        released one channel at a time; a crop or a 'zscore_nonzero' channel uploads all K volumes first, because the mask is their
+        union.  The label is resampled with channel 0."""
+        _check_scan_options(crop, specs)
+        nis = [nifti.load(p) for p in paths]
         nl = nifti.load(lab_path) if lab_path is not None else None
-        if nl is not None:
-            geometry.check_pair(ni.shape, ni.affine, nl.shape, nl.affine)
-        self.order = _scan_order(order, ni.affine, pixdim)
+        ni, K = nis[0], len(nis)
+        for other in nis[1:] + ([nl] if nl is not None else []):
+            geometry.check_pair(ni.shape, ni.affine, other.shape, other.affine)
         self.native, self.native_shape, self.native_affine = ni, ni.shape, ni.affine
         self.matrix, self.shape, self.affine = geometry.spacing_plan(ni.shape, ni.affine, pixdim, axcodes)
-        raw, code = _source_dtype(ni.data)
-        ri = torch.as_tensor(np.ascontiguousarray(raw)).to(device)
+        self.order = _scan_order(order, ni.affine, pixdim)
+        self.pixdim = tuple(float(p) for p in pixdim)                # sample(augment=) rotates in millimetres
+        self._label_host = self._crop_index = None
         rl = None
         if nl is not None:
             lv = nl.data if (nl.slope, nl.inter) == (1.0, 0.0) else nl.scaled()
             rl = torch.as_tensor(np.ascontiguousarray(label_u8(lv))).to(device)
-        self.crop_box = self.nonzero_count = self.nonzero_fraction = self.outside = None
-        if crop is None and not _masked_spec(intensity):
-            intensity = _resolve_intensity(intensity, ri, ni.slope, ni.inter)
-            self.img, self.lab = resample(ri, rl, self.matrix, self.shape, intensity_map(intensity, ni.slope, ni.inter), code,
-                                          order=self.order)
-        else:
-            if _masked_spec(intensity):
-                self.outside = 0.0
-            mask, box = self._nonzero_grid([ri], [(ni.slope, ni.inter)], crop, pixdim, axcodes)
-            self.img, self.lab, intensity = _load_channel(ri, rl, code, intensity, ni.slope, ni.inter, mask, box,
-                                                          (self.matrix, self.shape), self.order)
-        self.pixdim, self.intensity = tuple(float(p) for p in pixdim), intensity      # sample(augment=) rotates in mm, fills with the window's floor
-        self._label_host = self._crop_index = None
 
-    def _nonzero_grid(self, raws, scalings, crop, pixdim, axcodes):
-        """the nonzero mask of the stored volumes and the box to load: (mask, box).  Sets nonzero_count / nonzero_fraction and, under
-        crop, crop_box and the box's matrix, shape and affine"""
-        mask, bbox, self.nonzero_count = nonzero_mask(raws, scalings)
-        self.nonzero_fraction = float(np.prod([hi - lo for lo, hi in bbox], dtype=np.float64) / raws[0].numel())
-        if crop is None:
-            return mask, tuple((0, int(n)) for n in raws[0].shape)
-        self.crop_box = bbox
-        box_shape, affine = geometry.crop_plan(self.native_shape, self.native_affine, bbox[::-1])
-        self.matrix, self.shape, self.affine = geometry.spacing_plan(box_shape, affine, pixdim, axcodes)
-        return mask, bbox
+        def upload(nc):
+            raw, code = _source_dtype(nc.data)
+            return torch.as_tensor(np.ascontiguousarray(raw)).to(device), code
+        self.crop_box = self.nonzero_count = self.nonzero_fraction = mask = None
+        box = tuple((0, n) for n in ni.shape[::-1])                   # the whole stored array [Z, Y, X]
+        raws = []
+        if crop is not None or any(_masked_spec(spec) for spec in specs):
+            raws = [upload(nc) for nc in nis]
+            mask, bbox, self.nonzero_count = nonzero_mask([raw for raw, _ in raws], [(nc.slope, nc.inter) for nc in nis])
+            self.nonzero_fraction = float(np.prod([hi - lo for lo, hi in bbox], dtype=np.float64) / raws[0][0].numel())
+            if crop is not None:                         # matrix, shape and affine become the box's
+                self.crop_box = box = bbox
+                box_shape, affine = geometry.crop_plan(self.native_shape, self.native_affine, bbox[::-1])
+                self.matrix, self.shape, self.affine = geometry.spacing_plan(box_shape, affine, pixdim, axcodes)
+        img, windows = None, []
+        for c, (nc, spec) in enumerate(zip(nis, specs)):
+            ri, code = raws.pop(0) if raws else upload(nc)
+            oi, ol, window = _load_channel(ri, rl if c == 0 else None, code, spec, nc.slope, nc.inter, mask, box,
+                                           (self.matrix, self.shape), self.order)
+            del ri                                       # every stored volume is dropped after its channel
+            if c == 0:
+                self.lab = ol
+                img = oi[None] if K == 1 else torch.empty((K,) + tuple(oi.shape), device=oi.device, dtype=torch.float32)
+            if K > 1:
+                img[c].copy_(oi)
+            windows.append(window)
+        return img, windows, [0.0 if _masked_spec(spec) else None for spec in specs]
 
     @property
     def label_host(self):
@@ -1032,9 +1054,7 @@ class SpacedScan:
             raise ValueError('order 1 reads the image itself: there are no coefficients to build')
         cache = self.__dict__.setdefault('_spline_coefficients', {})
         if orders not in cache:
-            axes = (orders[2], orders[1], orders[0])         # data.spline_coefficients counts the axes from the fastest: D, W, H
-            vols = self.img if self.img.dim() == 4 else self.img[None]
-            cache[orders] = torch.stack([spline_coefficients(v, axes) for v in vols]).view(self.img.shape)
+            cache[orders] = _gather_coefficients(self.img, orders)
         return cache[orders]
 
     def drop_coefficients(self):
@@ -1058,7 +1078,8 @@ def _is_number(v):
 class MultiScan(SpacedScan):
     """SpacedScan for K = 1 .. 4 NIfTI images on ONE grid (T1 / T1c / T2 / FLAIR, T2 + ADC, PET + CT): img_paths is their sequence,
     channel 0 first.  Every other image and the label must match channel 0 in shape and affine (geometry.check_pair: ValueError).
-    Each channel is resampled exactly as SpacedScan resamples it alone; img: one contiguous f32 [K, H, W, D]; lab, crop_index,
+    Each channel is resampled exactly as SpacedScan resamples it alone, by the same code (SpacedScan._load, which this class only
+    hands its K paths and K specs); img: one contiguous f32 [K, H, W, D]; lab, crop_index,
     label_host, matrix, affine, shape, pixdim as on SpacedScan, native / native_shape / native_affine are channel 0's.
     intensity: one spec for all channels (a window 4-tuple, None, an IntensityFingerprint or 'zscore') or a sequence of K specs;
     the attribute `intensity` is the list of the K resulting tuples (or None).  channels == K.  order: as SpacedScan's, one for all
@@ -1077,46 +1098,8 @@ class MultiScan(SpacedScan):
         specs = [intensity] * K if one else list(intensity)
         if len(specs) != K:
             raise ValueError(f'intensity is one spec or one per image: {len(specs)} specs for {K} images')
-        _check_scan_options(crop, specs)
-        nis =[nifti.load(p) for p in paths]
-        nl = nifti.load(lab_path) if lab_path is not None else None
-        ni = nis[0]
-        for other in nis[1:] + ([nl] if nl is not None else []):
-            geometry.check_pair(ni.shape, ni.affine, other.shape, other.affine)
-        self.native, self.native_shape, self.native_affine = ni, ni.shape, ni.affine
-        self.matrix, self.shape, self.affine = geometry.spacing_plan(ni.shape, ni.affine, pixdim, axcodes)
-        self.order = _scan_order(order, ni.affine, pixdim)
-        rl = None
-        if nl is not None:
-            lv = nl.data if (nl.slope, nl.inter) == (1.0, 0.0) else nl.scaled()
-            rl = torch.as_tensor(np.ascontiguousarray(label_u8(lv))).to(device)
-        self.img = self.lab = None
-        self.intensity = []
-        self.crop_box = self.nonzero_count = self.nonzero_fraction = None
-        self.outside = [0.0 if _masked_spec(spec) else None for spec in specs]
-        masked = crop is not None or any(_masked_spec(spec) for spec in specs)
-        if masked:                                     # the mask is the union over ALL channels: they are uploaded together
-            stored = [_source_dtype(nc.data) for nc in nis]
-            raws = [torch.as_tensor(np.ascontiguousarray(raw)).to(device) for raw, _ in stored]
-            mask, box = self._nonzero_grid(raws, [(nc.slope, nc.inter) for nc in nis], crop, pixdim, axcodes)
-        for c, (nc, spec) in enumerate(zip(nis, specs)):
-            if masked:
-                oi, ol, window = _load_channel(raws[c], rl if c == 0 else None, stored[c][1], spec, nc.slope, nc.inter, mask, box,
-                                               (self.matrix, self.shape), self.order)
-                raws[c] = None
-            else:
-                raw, code = _source_dtype(nc.data)
-                ri = torch.as_tensor(np.ascontiguousarray(raw)).to(device)
-                window = _resolve_intensity(spec, ri, nc.slope, nc.inter)
-                oi, ol = resample(ri, rl if c == 0 else None, self.matrix, self.shape, intensity_map(window, nc.slope, nc.inter), code,
-                                  order=self.order)
-            if c == 0:
-                self.img, self.lab = torch.empty((K,) + tuple(oi.shape), device=oi.device, dtype=torch.float32), ol
-            self.img[c].copy_(oi)
-            self.intensity.append(window)
+        self.img, self.intensity, self.outside = self._load(paths, lab_path, pixdim, axcodes, specs, device, order, crop)
         self.channels = K
-        self.pixdim = tuple(float(p) for p in pixdim)
-        self._label_host = self._crop_index = None
 
 
 def channel_seed(seed, c):
@@ -1253,18 +1236,18 @@ SAMPLE_ORDERS = ((1, 1, 1), (3, 3, 3), (3, 3, 1))      # the gather's interpolat
 def sample_order(order):
     """the `order` of sample_affine / Augmentation / SpacedScan.spline_coefficients as a 3-tuple per scan axis H, W, D: 1 (trilinear),
     3 (cubic B-spline on every axis) or one of SAMPLE_ORDERS; anything else is a ValueError"""
-    if isinstance(order, (int, np.integer)) and not isinstance(order, bool):
-        orders = (int(order),) * 3
-    else:
-        try:
-            orders = tuple(int(o) for o in order)
-            if len(orders) != 3 or any(o != v for o, v in zip(orders, order)):
-                orders = None
-        except (TypeError, ValueError):
-            orders = None
+    orders = _order_tuple(order)
     if orders not in SAMPLE_ORDERS:
         raise ValueError(f'the patch gather is built for order 1, 3, (3, 3, 3) and (3, 3, 1) per scan axis H, W, D, got {order!r}')
     return orders
+
+
+def _gather_coefficients(img, orders):
+    """the B-spline coefficients of img [H, W, D] or [K, H, W, D] in its shape for the gather's orders per scan axis H, W, D: one
+    spline_coefficients per channel (looked up in this module at call time)"""
+    axes = (orders[2], orders[1], orders[0])               # spline_coefficients counts the axes from the fastest: D, W, H
+    vols = img if img.dim() == 4 else img[None]
+    return torch.stack([spline_coefficients(v, axes) for v in vols]).view(img.shape)
 
 
 def _channel_bounds(clamp, K):
@@ -1279,18 +1262,20 @@ def _channel_bounds(clamp, K):
 
 
 def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, elastic=None, order=1, coef=None, clamp=None):
-    """ltu_sample_affine: device patches ([n,1,h,w,d] f32 or None, [n,1,h,w,d] u8 or None) gathered from img / lab [H,W,D] through
-    mats [n,3,4] (float64 pull matrices, patch voxel -> scan voxel): image trilinear with `fill` outside the scan, label nearest
-    (round half even) with 0 outside.  noise_sigma [n] with seeds [n] (uint64) adds sigma_k * N(0, 1) to patch k in the store
-    (noise_reference restates the generator).  elastic: [n, 3, gh, gw, gd] (ndarray or device tensor), one B-spline control lattice
-    per patch in patch voxels; patch voxel p then reads the scan at M (p + u(p), 1), u = elastic_displacement (ltu_sample_elastic).
+    """ltu_sample_channels (order 1) or ltu_sample_spline (any other order), for every image: device patches ([n,1,h,w,d] f32 or
+    None, [n,1,h,w,d] u8 or None) gathered from img / lab [H,W,D] through mats [n,3,4] (float64 pull matrices, patch voxel -> scan
+    voxel): image trilinear with `fill` outside the scan, label nearest (round half even) with 0 outside.  noise_sigma [n] with
+    seeds [n] (uint64) adds sigma_k * N(0, 1) to patch k in the store (noise_reference restates the generator).  elastic: [n, 3,
+    gh, gw, gd] (ndarray or device tensor), one B-spline control lattice per patch in patch voxels; patch voxel p then reads the
+    scan at M (p + u(p), 1), u = elastic_displacement; without it the call passes no lattice and runs the affine kernels.
     The lattice is checked on the host (extents 4 .. 8, finite, |phi| <= 64: ValueError) and uploaded once.
-    A 4-D img [K,H,W,D] (K = 1 .. 4 channels on the label's grid, e.g. MultiScan.img) goes through ltu_sample_channels and returns
+    A 3-D img is the K = 1 case (the kernels ltu_sample_affine / ltu_sample_elastic run, which no call here goes through).  A 4-D
+    img [K,H,W,D] (K = 1 .. 4 channels on the label's grid, e.g. MultiScan.img) returns
     [n,K,h,w,d]: one gather whose coordinates, taps and label voxel are formed once for all channels.  fill is then a number or one
     per channel, noise_sigma [n] or [n,K], seeds [n,K] (or [n]: channel c of patch k gets channel_seed(seeds[k], c)); channel c has
     the bits of the 3-D call on img[c] with fill[c], noise_sigma[:, c] and seeds[:, c].
-    order (sample_order: 1, 3, (3, 3, 3) or (3, 3, 1) per scan axis H, W, D): 1, the default, is everything above.  Any other goes
-    through ltu_sample_spline and interpolates the image as scipy.ndimage.map_coordinates(order=3, mode='constant', cval=fill) does
+    order (sample_order: 1, 3, (3, 3, 3) or (3, 3, 1) per scan axis H, W, D): 1, the default, is everything above.  Any other
+    interpolates the image as scipy.ndimage.map_coordinates(order=3, mode='constant', cval=fill) does
     (nnU-Net's spatial transform): the cubic tap sum where the coordinate lies inside [0, S - 1] on every axis, fill elsewhere, no
     blending across the edge; (3, 3, 1) is linear along D, the coarse axis of an anisotropic scan.  coef: the B-spline coefficients
     of img in its shape (SpacedScan.spline_coefficients(order) caches them); None builds them here with spline_coefficients, per
@@ -1303,13 +1288,12 @@ def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, 
     vol = img if img is not None else lab
     if vol is None or not vol.is_cuda:
         raise _lib.LtuError('data.sample_affine runs on the GPU only (no CPU fallback)')
-    multi = img is not None and img.dim() == 4
     if img is not None and lab is not None and img.shape[-3:] != lab.shape:
         raise ValueError(f'image {tuple(img.shape)} and label {tuple(lab.shape)} differ in shape')
     if (img is not None and (img.dtype != torch.float32 or not img.is_contiguous())) or \
             (lab is not None and (lab.dtype != torch.uint8 or not lab.is_contiguous())):
         raise ValueError('sample_affine takes a contiguous float32 image and uint8 label')
-    K = int(img.shape[0]) if multi else 1
+    K = int(img.shape[0]) if img is not None and img.dim() == 4 else 1          # a 3-D image is the one-channel case of the same call
     if not 1 <= K <= _lib.MAX_INPUT_CHANNELS:
         raise ValueError(f'sample_affine takes 1 .. {_lib.MAX_INPUT_CHANNELS} channels, got {K}')
     H, W, D = vol.shape[-3:]
@@ -1322,24 +1306,22 @@ def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, 
             raise ValueError('noise_sigma needs seeds')
         sg = np.ascontiguousarray(np.broadcast_to(np.asarray(noise_sigma, dtype=np.float32).reshape(n, -1), (n, K)))
         sd = np.asarray(seeds, dtype=np.uint64).reshape(n, -1)
-        if multi and sd.shape[1] == 1 and K > 1:
+        if sd.shape[1] == 1 and K > 1:
             sd = np.array([[channel_seed(s, c) for c in range(K)] for s in sd[:, 0]], dtype=np.uint64)
         sd = np.ascontiguousarray(sd.reshape(n, K))
     oi = torch.empty((n, K, h, w, d), device=vol.device, dtype=torch.float32) if img is not None else None
     ol = torch.empty((n, 1, h, w, d), device=vol.device, dtype=torch.uint8) if lab is not None else None
-    g = (0, 0, 0)
+    lat, g = None, (0, 0, 0)
     if elastic is not None:
         if elastic.shape[0] != n:
             raise ValueError(f'elastic holds {elastic.shape[0]} lattices for {n} matrices')
         lat = (elastic if torch.is_tensor(elastic) else torch.from_numpy(elastic)).to(vol.device)
         g = tuple(int(v) for v in lat.shape[2:])
     cubic = orders != (1, 1, 1) and img is not None        # a label alone has nothing to interpolate
-    if multi or cubic:
-        fl = np.ascontiguousarray(np.broadcast_to(np.asarray(fill, dtype=np.float32).reshape(-1), (K,)))
+    fl = np.full(K, fill, dtype=np.float32)                # a number for all channels, or one per channel
     if cubic:
         if coef is None:
-            axes = (orders[2], orders[1], orders[0])         # spline_coefficients counts the axes from the fastest: D, W, H
-            coef = torch.stack([spline_coefficients(v, axes) for v in (img if multi else img[None])])
+            coef = _gather_coefficients(img, orders)
         if not torch.is_tensor(coef) or coef.device != img.device or coef.dtype != torch.float32 or not coef.is_contiguous() or \
                 coef.numel() != img.numel() or coef.shape[-3:] != img.shape[-3:]:
             raise ValueError(f'coef is a contiguous float32 tensor of the image\'s shape {tuple(img.shape)} on its device')
@@ -1348,22 +1330,18 @@ def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, 
         if elastic is not None:
             which = which | (lat.reshape(n, -1) != 0).any(1).cpu().numpy()
         which = np.ascontiguousarray(which.astype(np.uint8))
+    def row(a, s):                          # the address of a[s], a contiguous tensor or ndarray (None: 0), without a view object
+        if a is None:
+            return 0
+        return a.data_ptr() + s * a.stride(0) * a.element_size() if torch.is_tensor(a) else a.ctypes.data + s * a.strides[0]
     for s in range(0, n, _lib.SAMPLE_AFFINE_MAX):
         e = min(n, s + _lib.SAMPLE_AFFINE_MAX)
-        out = (_p(oi[s:e]) if oi is not None else 0, _p(ol[s:e]) if ol is not None else 0)
-        noise = (sg[s:e].ctypes.data if sg is not None else 0, sd[s:e].ctypes.data if sd is not None else 0)
+        common = (row(oi, s), row(ol, s), row(m, s), row(lat, s), *g, row(sg, s), row(sd, s), fl.ctypes.data)
         if cubic:
-            _lib.call('ltu_sample_spline', _p(img), _p(coef), _p(lab), *out, m[s:e].ctypes.data,
-                      _p(lat[s:e]) if elastic is not None else 0, *g, *noise, fl.ctypes.data, lo.ctypes.data, hi.ctypes.data,
-                      which[s:e].ctypes.data, e - s, K, H, W, D, h, w, d, orders[2], _s())
-        elif multi:
-            _lib.call('ltu_sample_channels', _p(img), _p(lab), *out, m[s:e].ctypes.data, _p(lat[s:e]) if elastic is not None else 0, *g,
-                      *noise, fl.ctypes.data, e - s, K, H, W, D, h, w, d, _s())
-        elif elastic is not None:
-            _lib.call('ltu_sample_elastic', _p(img), _p(lab), *out, m[s:e].ctypes.data, _p(lat[s:e]), *g, *noise, e - s, H, W, D, h, w, d,
-                      float(fill), _s())
+            _lib.call('ltu_sample_spline', _p(img), _p(coef), _p(lab), *common, lo.ctypes.data, hi.ctypes.data, row(which, s),
+                      e - s, K, H, W, D, h, w, d, orders[2], _s())
         else:
-            _lib.call('ltu_sample_affine', _p(img), _p(lab), *out, m[s:e].ctypes.data, *noise, e - s, H, W, D, h, w, d, float(fill), _s())
+            _lib.call('ltu_sample_channels', _p(img), _p(lab), *common, e - s, K, H, W, D, h, w, d, _s())
     return oi, ol
 
 
@@ -1505,31 +1483,30 @@ class Augmentation:
                                  f'= {cap:.3g} voxels (size {int(spatial_size[a])}, lattice {self.elastic_grid[a]})')
 
 
-def _multi(scan):
-    """the scan holds channels: img is [K, H, W, D] (a MultiScan)"""
+def _channels(scan):
+    """any scan object as channels: (K, the K intensity windows, the K `outside` values).  A 3-D img (or none) is one channel whose
+    `intensity` and `outside` are single values; a 4-D img [K, H, W, D] carries lists of K (`outside` may be missing: K Nones)"""
     img = getattr(scan, 'img', None)
-    return img is not None and img.dim() == 4
+    windows, outside = getattr(scan, 'intensity', None), getattr(scan, 'outside', None)
+    if img is None or img.dim() != 4:
+        return 1, [windows], [outside]
+    K = int(img.shape[0])
+    return K, list(windows) if windows is not None else [None] * K, list(outside) if outside is not None else [None] * K
 
 
 def _scan_fill(scan, augment):
     """the image value outside the scan: augment.fill, or (None) scan.outside where the scan names one (0.0 under
     'zscore_nonzero': the value of everything outside the mask), else the floor of the scan's intensity window, 0.0 where it has
-    none; one per channel for a MultiScan"""
-    multi = _multi(scan)
-    outside = getattr(scan, 'outside', None)
-
-    def floor(window, c=None):
-        named = outside if c is None or outside is None else outside[c]
-        if named is not None:
-            return float(named)
-        lo = intensity_map(window)[2]
-        return float(lo) if np.isfinite(lo) else 0.0
-    if augment is not None and augment.fill is not None:
-        return [float(augment.fill)] * scan.img.shape[0] if multi else augment.fill
+    none.  One value per channel, in the scan's own presentation: a list of K for a 4-D img, the number itself for a 3-D one"""
+    K, windows, outside = _channels(scan)
     if augment is None:
-        return [0.0] * scan.img.shape[0] if multi else 0.0
-    windows = getattr(scan, 'intensity', None)
-    return [floor(wd, c) for c, wd in enumerate(windows)] if multi else floor(windows)
+        fills = [0.0] * K
+    elif augment.fill is not None:
+        fills = [float(augment.fill)] * K
+    else:
+        lows = [intensity_map(wd)[2] for wd in windows]
+        fills = [float(named) if named is not None else float(lo) if np.isfinite(lo) else 0.0 for named, lo in zip(outside, lows)]
+    return fills if scan.img is not None and scan.img.dim() == 4 else fills[0]
 
 
 def _augmented(scan, draws, params, spatial_size, augment, spacing):
@@ -1561,9 +1538,8 @@ def _augmented(scan, draws, params, spatial_size, augment, spacing):
     if augment.order != (1, 1, 1):
         # the patches that rotate, zoom or deform are the ones without an integer matrix and a zero lattice: sample_affine's own
         # rule picks them; the others stay the source voxels.  The clamp is each channel's window, +-inf where it has none
-        windows = scan.intensity if _multi(scan) else [getattr(scan, 'intensity', None)]
         cubic = dict(order=augment.order, coef=scan.spline_coefficients(augment.order),
-                     clamp=[intensity_map(wd)[2:4] for wd in windows])
+                     clamp=[intensity_map(wd)[2:4] for wd in _channels(scan)[1]])
     img, lab = sample_affine(scan.img, scan.lab, np.stack(mats), size, fill,
                              [p['noise_std'] if p['noise'] else 0.0 for p in params] if noisy else None,
                              [p['seed'] for p in params] if noisy else None, elastic=lattice, **cubic)
@@ -1630,7 +1606,7 @@ def sample(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_p
     if scan.lab is None:
         raise ValueError('sampling needs a label (RandCropByPosNegLabeld draws centres from it)')
     draws, params = sample_draws(scan, spatial_size, rand_state, num_samples, flip_prob, rot90_prob, host_centers, ratios, augment)
-    if augment is None and not _multi(scan):
+    if augment is None and (scan.img is None or scan.img.dim() == 3):          # the plain crop of one volume is its own kernel
         return crop_orient(scan.img, scan.lab, draws, spatial_size)
     return _augmented(scan, draws, params, spatial_size, augment, getattr(scan, 'pixdim', (1.0, 1.0, 1.0)))
 

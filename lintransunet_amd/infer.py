@@ -628,7 +628,7 @@ def segment_scan(models, scan, classes=(), **infer_volume_kwargs):
     kw = dict(mode='gaussian', mirror_axes=(0, 1))
     kw.update(infer_volume_kwargs)
     total = None
-    images = scan.img[None] if scan.img.dim() == 4 else scan.img[None, None]
+    images = scan.img.view(1, -1, *scan.img.shape[-3:])          # [1, K, H, W, D]; a SpacedScan is K = 1
     for model in members:
         p = infer_volume(model, images, probs=True, **kw)
         total = p if total is None else total.add_(p)
