@@ -6,7 +6,12 @@
 // The sampling grid is an outer product of a 1-D map along H and a 1-D map along W, so a "plan" holds,
 // per axis and sample, for every destination index its two source taps (gather form, used forward) and
 // for every source index the list of destinations that touch it (CSR form, used by the adjoint - no
-// atomics).  The index arithmetic repeats the reference's fp32 operation order without fma contraction.
+// atomics).  The index arithmetic repeats the reference's fp32 operation order without fma contraction.  Two expressions of the
+// warp-back map are not single divisions there: lines 69-70 write `roi_size / (x1 - x0)` and `(eval_roi_size - roi_size) /
+// (h - x1 + x0)` with a Python int on the left, and torch evaluates int / tensor as tensor.reciprocal() * int - two roundings.
+// map_back therefore forms the reciprocal and multiplies (one division there moves about one back-map coordinate in eight
+// off the reference's bits).  Every other quotient of the two maps has a tensor on the left and is one division.
+// tests/roi_common.py holds the same order as a scalar float32 replay, pinned to the reference's maps in tests/test_roi_sweep.py.
 #include "common.h"
 
 #define ROI_MAX_LEN 512
@@ -22,7 +27,15 @@ struct AxisPlan {
 
 __device__ __forceinline__ float fsub(float a, float b) { return __fsub_rn(a, b); }
 __device__ __forceinline__ float fadd(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float fmul(float a, float b) { return __fmul_rn(a, b); }
+// HIP's __fmul_rn / __fadd_rn are a plain product and sum, and the library is built with -ffp-contract=fast, under which the
+// backend fuses any product with the sum it feeds, whatever the source says (it did: idx * k2 + ... and (fl + 1) - ix were fmas,
+// a few ulps of a coordinate away from the reference in one coordinate of seven).  The empty asm makes the rounded product a
+// value of its own, so nothing is left to fuse.
+__device__ __forceinline__ float fmul(float a, float b) {
+  float p = __fmul_rn(a, b);
+  asm volatile("" : "+v"(p));
+  return p;
+}
 __device__ __forceinline__ float fdiv(float a, float b) { return __fdiv_rn(a, b); }
 
 // model/Unet_3Dblock.py:51-64
@@ -37,8 +50,8 @@ __device__ float map_fwd(float idx, float x0, float x1, int span, int roi, int e
 }
 // model/Unet_3Dblock.py:66-82
 __device__ float map_back(float idx, float x0, float x1, int span, int roi, int eval_roi) {
-  const float k2 = fdiv((float)roi, fsub(x1, x0));
-  const float k1 = fdiv((float)(eval_roi - roi), fadd(fsub((float)span, x1), x0));
+  const float k2 = fmul((float)roi, fdiv(1.f, fsub(x1, x0)));                                    // int / tensor: see the header
+  const float k1 = fmul((float)(eval_roi - roi), fdiv(1.f, fadd(fsub((float)span, x1), x0)));
   const float p0 = fmul(x0, k1);
   const float p1 = fsub((float)eval_roi, fmul(fsub((float)span, x1), k1));
   float pos = fadd(fmul(idx, k2), fmul(p0, fsub(1.f, fdiv(k2, k1))));
