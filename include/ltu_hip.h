@@ -487,24 +487,20 @@ int ltu_loss_topk_bwd(const float* p, const uint8_t* label, const void* scratch,
 /* label pyramid (utils/utils_3D_embed_full.py:64,73-76): u8 [B,H,W,D] -> max over (2,2,kd) windows */
 int ltu_label_maxpool(const uint8_t* x, uint8_t* y, int B, int H, int W, int D, int kd, ltu_stream_t s);
 
-/* ---- sliding-window whole-volume inference (inference_embed_attn.py:92-185; monai 0.7.0 sliding_window_inference,
- * constant blending) ------------------------------------------------------------------------------------------------
- * desc int32 [n][4] = (sample, h0, w0, d0) of each window in the PADDED image (a dimension smaller than the window is padded
- * symmetrically with zeros: pad_lo = (roi - dim) / 2).  vol f32 [B][H][W][D] (one channel); win f32 [n][h][w][d];
- * seg f32 [n][h][w][d][C] = the model's eval output (channels-last one-hot); votes f32 [B][C][Hp][Wp][Dp] and
- * count f32 [B][Hp][Wp][Dp] zero-filled accumulators; out f32 [B][C][H][W][D] = votes / count without the padding. */
-int ltu_window_gather(const float* vol, float* win, const int* desc, int n, int H, int W, int D, int h, int w, int d, int ph, int pw,
-                      int pd, ltu_stream_t s);
-int ltu_vote_accumulate(const float* seg, float* votes, float* count, const int* desc, int n, int Hp, int Wp, int Dp, int h, int w,
-                        int d, int C, ltu_stream_t s);
+/* ---- sliding-window whole-volume inference (inference_embed_attn.py:92-185; monai 0.7.0 sliding_window_inference) --------
+ * The windows live in the PADDED image Hp x Wp x Dp (a dimension smaller than the window is padded symmetrically with zeros:
+ * pad_lo = (roi - dim) / 2).  ltu_window_gather_mirror and ltu_window_blend (below) gather them and accumulate
+ * votes f32 [B][C][Hp][Wp][Dp] and count f32 [B][Hp][Wp][Dp] (the sum of the weights; zero-filled before the first blend) for
+ * every blending mode; finalize: out f32 [B][C][H][W][D] = votes / count without the padding, pad_lo = (ph, pw, pd). */
 int ltu_vote_finalize(const float* votes, const float* count, float* out, int B, int C, int H, int W, int D, int Hp, int Wp, int Dp,
                       int ph, int pw, int pd, ltu_stream_t s);
-/* ---- weighted and mirrored blending (monai 0.7.0 sliding_window_inference mode="gaussian", plus mirror test-time augmentation) --
+/* ---- window gather and blending (monai 0.7.0 sliding_window_inference mode="constant" / "gaussian", plus mirror test-time
+ * augmentation) ----------------------------------------------------------------------------------------------------------------
  * desc is a HOST int32 array [n][5] = (sample b, h0, w0, d0, mask) of n <= LTU_BLEND_ITEMS_MAX items (the descriptors travel as
  * kernel arguments); (h0, w0, d0) is the window start in the padded image Hp x Wp x Dp, which holds vol [B][H][W][D] at offset
  * pad_lo = (Hp - H) / 2 per axis (zeros elsewhere); bit a of mask flips axis a (0 = H, 1 = W, 2 = D) of the window.
  * gather_mirror: win [n][h][w][d] with win[k][u] = padded[b][start + u'], u'_a = r_a - 1 - u_a on a flipped axis, else u_a.
- * blend: seg f32 [n][h][w][d][C] channels-last (the model's softmax), 1 <= C <= 8; for every padded voxel p covered by item k,
+ * blend: seg f32 [n][h][w][d][C] channels-last (one-hot or softmax), 1 <= C <= 8; for every padded voxel p covered by item k,
  * v = p - start_k, u = v flipped as above: votes[b][c][p] += w(v) seg[k][u][c], wsum[b][p] += w(v), w(v) = max(g0[v0] g1[v1]
  * g2[v2], wmin) with device tables g0 [h], g1 [w], g2 [d] (tables of ones and wmin = 1: constant weights).  No atomics: each covered
  * voxel is read and written once per launch by one thread, which applies the covering items in item order, so the sums do not

@@ -83,8 +83,6 @@ SIGNATURES = {
     'ltu_linattn_fwd': [P, P, P, P, P, P, L, I, I, I, I, P],
     'ltu_linattn_ctx': [P, P, P, P, L, I, I, I, I, P],
     'ltu_linattn_bwd': [P, P, P, P, P, P, P, P, P, L, I, I, I, I, P],
-    'ltu_window_gather': [P, P, P, I, I, I, I, I, I, I, I, I, I, P],
-    'ltu_vote_accumulate': [P, P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_vote_finalize': [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     'ltu_window_gather_mirror': [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     'ltu_window_blend': [P, P, P, P, P, P, F, P, I, I, I, I, I, I, I, I, I, P],

@@ -1,8 +1,8 @@
-// Sliding-window whole-volume inference: restates inference_embed_attn.py:92-185 and the constant-weight
-// sliding_window_inference of monai 0.7.0 (monai/inferers/utils.py) on device.  Windows are gathered from the volume, the
-// model's eval forward yields one-hot arg-max windows (trans_3DUnet.py:199-202), votes and the hit count are accumulated in
-// HBM, the quotient is the blended prediction; the evaluation metrics of the driver (criterions.py DiceClassLoss 35-70,
-// Recall 280-311, Precision 348-379, LocalizationLoss 179-241) are computed from per-row sums of the thresholded prediction.
+// Sliding-window whole-volume inference, the two ends of inference_embed_attn.py:92-185 that are not the
+// window loop (csrc/blend.hip gathers the windows and accumulates votes [B][C][Hp][Wp][Dp] and their weight sum in HBM): the
+// quotient on the un-padded region is the blended prediction of monai 0.7.0's sliding_window_inference
+// (monai/inferers/utils.py); the evaluation metrics of the driver (criterions.py DiceClassLoss 35-70, Recall 280-311,
+// Precision 348-379, LocalizationLoss 179-241) are computed from per-row sums of the thresholded prediction.
 #include "common.h"
 
 static unsigned sgrid(long long n, int per_block = 256) {
@@ -13,47 +13,6 @@ static unsigned sgrid(long long n, int per_block = 256) {
 }
 #define GRID_STRIDE(i, n) \
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
-
-// win [n][h][w][d] (one channel) <- vol [B][H][W][D] at padded coordinates (start - pad); zero outside the volume.
-// desc [n][4] = (b, h0, w0, d0) in the padded image.
-__global__ void window_gather_kernel(const float* __restrict__ vol, float* __restrict__ win, const int* __restrict__ desc, int n,
-                                     int H, int W, int D, int h, int w, int d, int ph, int pw, int pd) {
-  const long long per = (long long)h * w * d, total = per * n;
-  GRID_STRIDE(i, total) {
-    const int k = (int)(i / per);
-    long long r = i - (long long)k * per;
-    const int z = (int)(r % d); r /= d;
-    const int y = (int)(r % w);
-    const int x = (int)(r / w);
-    const int b = desc[4 * k], sh = desc[4 * k + 1] + x - ph, sw = desc[4 * k + 2] + y - pw, sd = desc[4 * k + 3] + z - pd;
-    float v = 0.f;
-    if ((unsigned)sh < (unsigned)H && (unsigned)sw < (unsigned)W && (unsigned)sd < (unsigned)D)
-      v = vol[(((long long)b * H + sh) * W + sw) * D + sd];
-    win[i] = v;
-  }
-}
-
-// votes [B][C][Hp][Wp][Dp] += seg (channels-last [n][h][w][d][C]); count [B][Hp][Wp][Dp] += 1.  Windows of one batch may
-// overlap each other, hence atomics (at most a handful of writers per address).
-__global__ void vote_accumulate_kernel(const float* __restrict__ seg, float* __restrict__ votes, float* __restrict__ count,
-                                       const int* __restrict__ desc, int n, int Hp, int Wp, int Dp, int h, int w, int d, int C) {
-  const long long per = (long long)h * w * d, total = per * n;
-  const long long vol = (long long)Hp * Wp * Dp;
-  GRID_STRIDE(i, total) {
-    const int k = (int)(i / per);
-    long long r = i - (long long)k * per;
-    const int z = (int)(r % d); r /= d;
-    const int y = (int)(r % w);
-    const int x = (int)(r / w);
-    const int b = desc[4 * k];
-    const long long pos = ((long long)(desc[4 * k + 1] + x) * Wp + (desc[4 * k + 2] + y)) * Dp + (desc[4 * k + 3] + z);
-    for (int c = 0; c < C; ++c) {
-      const float v = seg[i * C + c];
-      if (v != 0.f) atomicAdd(votes + ((long long)b * C + c) * vol + pos, v);
-    }
-    atomicAdd(count + (long long)b * vol + pos, 1.f);
-  }
-}
 
 // out [B][C][H][W][D] = votes / count on the un-padded region
 __global__ void vote_finalize_kernel(const float* __restrict__ votes, const float* __restrict__ count, float* __restrict__ out,
@@ -139,21 +98,6 @@ __global__ void __launch_bounds__(256) seg_metrics_kernel(const float* __restric
   }
 }
 
-extern "C" int ltu_window_gather(const float* vol, float* win, const int* desc, int n, int H, int W, int D, int h, int w, int d,
-                                 int ph, int pw, int pd, ltu_stream_t s) {
-  if (n <= 0) return LTU_OK;
-  const long long total = (long long)n * h * w * d;
-  hipLaunchKernelGGL(window_gather_kernel, dim3(sgrid(total)), dim3(256), 0, (hipStream_t)s, vol, win, desc, n, H, W, D, h, w, d, ph, pw, pd);
-  return ltu_check_launch();
-}
-extern "C" int ltu_vote_accumulate(const float* seg, float* votes, float* count, const int* desc, int n, int Hp, int Wp, int Dp,
-                                   int h, int w, int d, int C, ltu_stream_t s) {
-  if (n <= 0) return LTU_OK;
-  if (h > Hp || w > Wp || d > Dp || C < 1) return LTU_E_SHAPE;
-  const long long total = (long long)n * h * w * d;
-  hipLaunchKernelGGL(vote_accumulate_kernel, dim3(sgrid(total)), dim3(256), 0, (hipStream_t)s, seg, votes, count, desc, n, Hp, Wp, Dp, h, w, d, C);
-  return ltu_check_launch();
-}
 extern "C" int ltu_vote_finalize(const float* votes, const float* count, float* out, int B, int C, int H, int W, int D, int Hp,
                                  int Wp, int Dp, int ph, int pw, int pd, ltu_stream_t s) {
   const long long total = (long long)B * C * H * W * D;

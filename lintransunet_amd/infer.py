@@ -4,9 +4,11 @@ Mirrors the reference driver inference_embed_attn.py:92-185:
     predict = sliding_window_inference(images, (512, 512, depth), 4, model, overlap=0.6, sigma_scale=0)   # monai 0.7.0
     predict2 = (predict >= 0.5).float()
     DiceClassLoss / Recall / Precision / LocalizationLoss (predict2, masks)
-with the same argument meaning.  Window scheduling is host integer logic; the windows, the votes of the model's eval
-(one-hot arg-max) output and the metrics stay in HBM and go through the C-ABI (csrc/infer.hip).  No CPU fallback.
-Gaussian-weighted and mirrored blending of the model's softmax (mode='gaussian', mirror_axes, probs) run on csrc/blend.hip.
+with the same argument meaning.  Window scheduling is host integer logic; the windows, the weighted votes of the model's eval
+output (its one-hot arg-max, or its softmax with probs) and the metrics stay in HBM and go through the C-ABI.  No CPU fallback.
+Every mode runs one window loop on the gather and blend kernels of csrc/blend.hip: the reference's call is the constant
+weight 1 without mirrors, mode='gaussian' and mirror_axes are the same loop with other tables and more items.  The division
+and the driver's metrics are csrc/infer.hip.
 """
 import math
 
@@ -127,17 +129,43 @@ def channel_items(items, channels):
     return [(it[0] * K + c, *it[1:]) for it in items for c in range(K)]
 
 
-def _blend_inference(vol, roi, pad_lo, img, starts, sw_batch_size, predictor, mode, sigma_scale, mirror_axes):
-    """the weighted / mirrored path of sliding_window_inference (csrc/blend.hip)"""
-    B, K, img0, dev = vol.shape[0], vol.shape[1], tuple(int(v) for v in vol.shape[2:]), vol.device
+def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.25, mode='constant', sigma_scale=0.125,
+                             mirror_axes=()):
+    """inputs f32 [B, K, H, W, D] on the GPU, K = 1 .. 4 input channels; predictor(windows [n, K, h, w, d]) -> [n, C, h, w, d],
+    C = 1 .. 8 (the eval-mode MaskTransUnet: channels-last one-hot exposed in the reference's shape, or its softmax with
+    probs=True).  Returns f32 [B, C, H, W, D], the per-voxel weighted average of the window outputs.  The K channels of a window
+    are gathered as K items of the single-channel gather kernel (channel_items); an output channel's sums do not depend on C.
+
+    One loop for every mode (csrc/blend.hip): window voxel u is weighted by importance_tables(roi, mode, sigma_scale), which is 1
+    for mode='constant' (monai's mode="constant", the reference's call: the plain average) and monai's mode="gaussian" map for
+    mode='gaussian'; mirror_axes = A (distinct axes of (0, 1, 2) = H, W, D) predicts every window 2^|A| times, variant m flipped
+    along the axes of mirror_masks(A)[m], and blends each prediction flipped back, with the weight of its un-flipped position.
+    The predictor sees consecutive chunks of sw_batch_size items of window_items (sample-major, the variants of a window
+    adjacent).  Each voxel's sums are formed in fp32 in item order: the result is bit-identical between calls and for every
+    sw_batch_size; with weight 1 and a one-hot predictor they are small integers, exact in any order.  Bad mode, sigma_scale or
+    mirror_axes raise ValueError before anything runs; more than 8 output channels raise LtuError once the predictor has
+    returned its first batch, before anything is blended (the blend kernel, like the heads, the losses and class_metrics, stops
+    at 8 classes)."""
+    mode, sig, axes = _blend_options(mode, sigma_scale, mirror_axes)
+    if not inputs.is_cuda:
+        raise _lib.LtuError('sliding_window_inference runs on the GPU only (no CPU fallback)')
+    if inputs.dim() != 5 or not 1 <= inputs.shape[1] <= _lib.MAX_INPUT_CHANNELS:
+        raise _lib.LtuError(f'inputs must be [B, K, H, W, D] with K = 1 .. {_lib.MAX_INPUT_CHANNELS}')
     if int(sw_batch_size) < 1:
         raise ValueError(f'sw_batch_size must be >= 1, got {sw_batch_size}')
-    g0, g1, g2, wmin = importance_tables(roi, mode, sigma_scale)
+    B, K, dev = inputs.shape[0], inputs.shape[1], inputs.device
+    img0 = tuple(int(v) for v in inputs.shape[2:])
+    roi = tuple(int(r) if r and r > 0 else i for r, i in zip(roi_size, img0))
+    pad_lo = tuple(max(r - i, 0) // 2 for r, i in zip(roi, img0))
+    img = tuple(max(i, r) for i, r in zip(img0, roi))
+    starts = patch_starts(img, roi, scan_interval(img, roi, overlap))
+    vol = inputs.to(torch.float32).contiguous()
+    g0, g1, g2, wmin = importance_tables(roi, mode, sig)
     tab = torch.tensor(np.concatenate((g0, g1, g2)), dtype=torch.float32).to(dev)
     t0, t1, t2 = tab[:roi[0]], tab[roi[0]:roi[0] + roi[1]], tab[roi[0] + roi[1]:]
     votes = wsum = None
     C = None
-    for chunk in item_batches(window_items(B, starts, mirror_axes), sw_batch_size):
+    for chunk in item_batches(window_items(B, starts, axes), int(sw_batch_size)):
         n = len(chunk)
         parts = [(s, np.ascontiguousarray(chunk[s:s + _lib.BLEND_ITEMS_MAX], dtype=np.int32))
                  for s in range(0, n, _lib.BLEND_ITEMS_MAX)]
@@ -154,6 +182,8 @@ def _blend_inference(vol, roi, pad_lo, img, starts, sw_batch_size, predictor, mo
             seg_cl = seg_cl.to(torch.float32).contiguous()
         if votes is None:
             C = seg.shape[1]
+            if not 1 <= C <= 8:
+                raise _lib.LtuError(f'sliding_window_inference blends 1 .. 8 output channels, the predictor returned {C}')
             votes = torch.zeros((B, C) + img, device=dev, dtype=torch.float32)
             wsum = torch.zeros((B,) + img, device=dev, dtype=torch.float32)
         elif seg.shape[1] != C:
@@ -163,66 +193,6 @@ def _blend_inference(vol, roi, pad_lo, img, starts, sw_batch_size, predictor, mo
                       len(desc), B, C, *img, *roi, _s())
     out = torch.empty((B, C) + img0, device=dev, dtype=torch.float32)
     _lib.call('ltu_vote_finalize', _p(votes), _p(wsum), _p(out), B, C, *img0, *img, *pad_lo, _s())
-    return out
-
-
-def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.25, mode='constant', sigma_scale=0.125,
-                             mirror_axes=()):
-    """inputs f32 [B, K, H, W, D] on the GPU, K = 1 .. 4 input channels; predictor(windows [n, K, h, w, d]) -> [n, C, h, w, d]
-    (the eval-mode MaskTransUnet: channels-last one-hot exposed in the reference's shape, or its softmax with probs=True).
-    Returns f32 [B, C, H, W, D], the per-voxel weighted average of the window outputs.  The K channels of a window are gathered as
-    K items of the single-channel gather kernels (channel_items); an output channel's sums do not depend on C.
-
-    mode='constant' without mirror_axes is monai's mode="constant" (the reference's call): the plain average, on the vote
-    kernels of csrc/infer.hip.  Otherwise (csrc/blend.hip): mode='gaussian' weights window voxel u by importance_tables(roi,
-    'gaussian', sigma_scale) (monai's mode="gaussian"), and mirror_axes = A (distinct axes of (0, 1, 2) = H, W, D) predicts every
-    window 2^|A| times, variant m flipped along the axes of mirror_masks(A)[m], and blends each prediction flipped back, with the
-    weight of its un-flipped position.  The predictor sees consecutive chunks of sw_batch_size items of window_items (the variants
-    of a window adjacent).  Each voxel's sums are formed in fp32 in item order: the result is bit-identical between calls and for
-    every sw_batch_size.  Bad mode, sigma_scale or mirror_axes raise ValueError before anything runs."""
-    mode, sig, axes = _blend_options(mode, sigma_scale, mirror_axes)
-    if not inputs.is_cuda:
-        raise _lib.LtuError('sliding_window_inference runs on the GPU only (no CPU fallback)')
-    if inputs.dim() != 5 or not 1 <= inputs.shape[1] <= _lib.MAX_INPUT_CHANNELS:
-        raise _lib.LtuError(f'inputs must be [B, K, H, W, D] with K = 1 .. {_lib.MAX_INPUT_CHANNELS}')
-    B, K = inputs.shape[0], inputs.shape[1]
-    img0 = tuple(int(v) for v in inputs.shape[2:])
-    roi = tuple(int(r) if r and r > 0 else i for r, i in zip(roi_size, img0))
-    pad_lo = tuple(max(r - i, 0) // 2 for r, i in zip(roi, img0))
-    img = tuple(max(i, r) for i, r in zip(img0, roi))
-    starts = patch_starts(img, roi, scan_interval(img, roi, overlap))
-    nwin, total = len(starts), len(starts) * B
-    dev = inputs.device
-    vol = inputs.to(torch.float32).contiguous()
-    if mode != 'constant' or axes:
-        return _blend_inference(vol, roi, pad_lo, img, starts, int(sw_batch_size), predictor, mode, sig, axes)
-    votes = count = None
-    C = None
-    for g in range(0, total, sw_batch_size):
-        idxs = range(g, min(g + sw_batch_size, total))
-        items = [(idx // nwin, *starts[idx % nwin]) for idx in idxs]
-        desc = torch.tensor(items, dtype=torch.int32).reshape(-1, 4).to(dev)
-        # the volume as B K single-channel volumes, one gather item per window and channel; the votes keep the windows' descriptors
-        gdesc = desc if K == 1 else torch.tensor(channel_items(items, K), dtype=torch.int32).to(dev)
-        n = len(idxs)
-        win = torch.empty((n, K) + roi, device=dev, dtype=torch.float32)
-        _lib.call('ltu_window_gather', _p(vol), _p(win), _p(gdesc), n * K, img0[0], img0[1], img0[2], roi[0], roi[1], roi[2],
-                  pad_lo[0], pad_lo[1], pad_lo[2], _s())
-        seg = predictor(win)
-        if seg.dim() != 5 or tuple(seg.shape[2:]) != roi or seg.shape[0] != n:
-            raise _lib.LtuError(f'predictor returned {tuple(seg.shape)} for windows {(n, K) + roi}')
-        seg_cl = seg.permute(0, 2, 3, 4, 1)
-        if seg_cl.dtype != torch.float32 or not seg_cl.is_contiguous():
-            seg_cl = seg_cl.to(torch.float32).contiguous()
-        if votes is None:
-            C = seg.shape[1]
-            votes = torch.zeros((B, C) + img, device=dev, dtype=torch.float32)
-            count = torch.zeros((B,) + img, device=dev, dtype=torch.float32)
-        _lib.call('ltu_vote_accumulate', _p(seg_cl), _p(votes), _p(count), _p(desc), n, img[0], img[1], img[2], roi[0], roi[1],
-                  roi[2], C, _s())
-    out = torch.empty((B, C) + img0, device=dev, dtype=torch.float32)
-    _lib.call('ltu_vote_finalize', _p(votes), _p(count), _p(out), B, C, img0[0], img0[1], img0[2], img[0], img[1], img[2],
-              pad_lo[0], pad_lo[1], pad_lo[2], _s())
     return out
 
 

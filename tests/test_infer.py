@@ -110,7 +110,7 @@ def test_infer_volume_with_model():
 @pytest.mark.gpu
 def test_config5_window_batch_vs_oracle():
     """BASELINE config 5 at its real window size: a 512x512x40 scan = two 512x512x32 windows (overlap 0.6, sw batch 4) through
-    the window gather / vote accumulate / finalize kernels, against oracle/infer.py with the same stand-in predictor: exact"""
+    the window gather / blend / finalize kernels, against oracle/infer.py with the same stand-in predictor: exact"""
     from lintransunet_amd import infer as P
     g = torch.Generator().manual_seed(6)
     x = torch.randn((1, 1, 512, 512, 40), generator=g)

@@ -1,7 +1,7 @@
 """Gaussian-weighted and mirrored sliding-window inference (csrc/blend.hip, infer.sliding_window_inference(mode=, sigma_scale=,
 mirror_axes=)): the importance tables against a float64 restatement of monai 0.7.0's compute_importance_map, the item order,
 the refusals, and on the GPU the blend against a float64 numpy restatement of the contract, flip equivariance, determinism across
-calls and window batch sizes, equality with the vote kernel on one-hot windows, and the real model's softmax output."""
+calls and window batch sizes, exact integer sums of unit tables on one-hot windows, and the real model's softmax output."""
 import ctypes
 import math
 import os
@@ -304,13 +304,14 @@ def test_flip_equivariant_predictor(mode, shape, overlap, tol):
 
 
 @pytest.mark.gpu
-def test_deterministic_across_calls_and_batch_sizes():
+@pytest.mark.parametrize('mode,axes', [('gaussian', (0, 2)), ('constant', ())], ids=['gaussian_mirror', 'constant'])
+def test_deterministic_across_calls_and_batch_sizes(mode, axes):
     """fixed per-voxel item order: bit-identical between calls and for every sw_batch_size (40 > 32 items splits a predictor
-    batch into two launches)"""
+    batch into two launches), for the plain average of a soft predictor as for the Gaussian / mirrored blend"""
     from lintransunet_amd import infer as P
     g = torch.Generator().manual_seed(14)
     x = torch.randn((2, 1, 37, 21, 12), generator=g).to(DEV)
-    kw = dict(overlap=0.6, mode='gaussian', mirror_axes=(0, 2))
+    kw = dict(overlap=0.6, mode=mode, mirror_axes=axes)
     first = P.sliding_window_inference(x, (16, 16, 8), 4, _soft_predictor, **kw)
     assert torch.equal(P.sliding_window_inference(x, (16, 16, 8), 4, _soft_predictor, **kw), first)
     for sw in (1, 3, 8, 40):
@@ -318,8 +319,9 @@ def test_deterministic_across_calls_and_batch_sizes():
 
 
 @pytest.mark.gpu
-def test_unit_tables_equal_vote_accumulate_on_one_hot():
-    """ltu_window_blend with tables of ones on one-hot windows = ltu_vote_accumulate exactly (integer sums)"""
+def test_unit_tables_are_integer_sums_on_one_hot():
+    """ltu_window_blend with tables of ones and wmin = 1 on one-hot windows (a repeated window, partial overlaps, both samples of
+    B = 2) = the integer accumulation of the same items on the host, exactly"""
     from lintransunet_amd import _lib
     from lintransunet_amd.ops import _p, _s
     g = torch.Generator().manual_seed(15)
@@ -327,17 +329,44 @@ def test_unit_tables_equal_vote_accumulate_on_one_hot():
     items = [(0, 0, 0, 0), (0, 8, 4, 4), (1, 2, 2, 2), (0, 0, 0, 0), (0, 4, 4, 0), (1, 8, 4, 4)]
     n = len(items)
     cls = torch.randint(0, C, (n,) + roi, generator=g)
-    seg = torch.nn.functional.one_hot(cls, C).to(torch.float32).to(DEV).contiguous()     # [n, h, w, d, C]
-    v1 = torch.zeros((B, C) + img, device=DEV)
-    c1 = torch.zeros((B,) + img, device=DEV)
-    v2, c2 = v1.clone(), c1.clone()
-    ddev = torch.tensor(items, dtype=torch.int32).to(DEV)
-    _lib.call('ltu_vote_accumulate', _p(seg), _p(v1), _p(c1), _p(ddev), n, *img, *roi, C, _s())
+    onehot = torch.nn.functional.one_hot(cls, C)                                         # [n, h, w, d, C]
+    seg = onehot.to(torch.float32).to(DEV).contiguous()
+    ref_v = np.zeros((B, C) + img, dtype=np.int64)
+    ref_c = np.zeros((B,) + img, dtype=np.int64)
+    for (b, h0, w0, d0), oh in zip(items, onehot.numpy()):
+        sl = (slice(h0, h0 + roi[0]), slice(w0, w0 + roi[1]), slice(d0, d0 + roi[2]))
+        ref_v[b][(slice(None),) + sl] += np.moveaxis(oh, -1, 0)
+        ref_c[b][sl] += 1
+    votes = torch.zeros((B, C) + img, device=DEV)
+    wsum = torch.zeros((B,) + img, device=DEV)
     ones = torch.ones(sum(roi), device=DEV)
     desc = np.array([it + (0,) for it in items], dtype=np.int32)
-    _lib.call('ltu_window_blend', _p(seg), _p(v2), _p(c2), _p(ones), _p(ones[roi[0]:]), _p(ones[roi[0] + roi[1]:]), 1.0,
+    _lib.call('ltu_window_blend', _p(seg), _p(votes), _p(wsum), _p(ones), _p(ones[roi[0]:]), _p(ones[roi[0] + roi[1]:]), 1.0,
               desc.ctypes.data, n, B, C, *img, *roi, _s())
-    assert torch.equal(v2, v1) and torch.equal(c2, c1)
+    assert torch.equal(votes.cpu(), torch.from_numpy(ref_v).to(torch.float32))
+    assert torch.equal(wsum.cpu(), torch.from_numpy(ref_c).to(torch.float32))
+
+
+def _onehot8_predictor(w):
+    """8 classes from thresholds of the window intensities, one-hot, channels-last memory"""
+    cls = sum((w[:, 0] > t).long() for t in (-1.2, -0.7, -0.3, 0.0, 0.3, 0.7, 1.2))
+    return torch.nn.functional.one_hot(cls, 8).to(torch.float32).permute(0, 4, 1, 2, 3)
+
+
+@pytest.mark.gpu
+def test_constant_mode_channel_limit():
+    """the blend kernels stop at 8 output channels: 8 one-hot channels equal the oracle exactly, a 9th is refused as an LtuError
+    that names the limit, not as the library's LTU_E_SHAPE"""
+    from lintransunet_amd import _lib, infer as P
+    g = torch.Generator().manual_seed(18)
+    x = torch.randn((1, 1, 10, 9, 7), generator=g)
+    roi = (6, 6, 4)
+    ref = O.sliding_window_inference(x, roi, 3, _onehot8_predictor, overlap=0.5)
+    got = P.sliding_window_inference(x.to(DEV), roi, 3, _onehot8_predictor, overlap=0.5)
+    assert got.shape == ref.shape == (1, 8, 10, 9, 7) and torch.equal(got.cpu(), ref)
+    with pytest.raises(_lib.LtuError, match='1 .. 8') as err:
+        P.sliding_window_inference(x.to(DEV), roi, 3, lambda w: torch.cat((_onehot8_predictor(w), w), 1), overlap=0.5)
+    assert 'LTU_E_SHAPE' not in str(err.value)
 
 
 def _model():

@@ -1,8 +1,8 @@
-"""Weighted / mirrored blending (csrc/blend.hip) on one MI355X.  usage: bench_infer_blend.py [kernels|scan|all] [reps]
+"""Window blending (csrc/blend.hip) on one MI355X.  usage: bench_infer_blend.py [kernels|scan|all] [reps]
 
 kernels: ltu_window_blend on 4 items of 512x512x32, C = 2, Gaussian tables - once the four (0, 1) mirror variants of one window,
-         once four distinct windows of a 512x512x96 scan (D starts 0, 12, 24, 36 at overlap 0.6) - and, on the same windows with
-         one-hot predictions and tables of ones, ltu_window_blend against ltu_vote_accumulate.  Algorithmic bytes = the seg reads
+         once four distinct windows of a 512x512x96 scan (D starts 0, 12, 24, 36 at overlap 0.6) - and on the same windows with
+         one-hot predictions and tables of ones (the constant mode).  Algorithmic bytes = the seg reads
          (n h w d C 4) + one read and one write of votes and wsum per covered voxel ((C + 1) 4 2 per voxel of the union).
 scan:    whole 512x512x96 scans through infer_volume with the reference model in bf16, graph replay, sw_batch_size 4, overlap 0.6:
          constant / one-hot (the reference's call), Gaussian / probs, Gaussian / probs + mirror (0, 1) and (0, 1, 2), alternated.
@@ -70,21 +70,14 @@ def kernels():
             _lib.call('ltu_window_blend', _p(seg), _p(votes), _p(wsum), _p(tab), _p(tab[roi[0]:]), _p(tab[roi[0] + roi[1]:]), w,
                       desc.ctypes.data, len(items), B, C, *img, *roi, _s())
 
-        ddev = torch.tensor([it[:4] for it in items], dtype=torch.int32, device=DEV)
-
-        def vote():
-            _lib.call('ltu_vote_accumulate', _p(onehot), _p(votes), _p(wsum), _p(ddev), len(items), *img, *roi, C, _s())
-
         t_g = _time(lambda: blend(soft, gauss, wmin), REPS)
         t_b1 = _time(lambda: blend(onehot, ones, 1.0), REPS)
-        t_v = _time(vote, REPS)
         res[name] = {'gaussian_ms': statistics.median(t_g), 'gaussian_TBps': nbytes / statistics.median(t_g) / 1e9,
                      'bytes': nbytes, 'covered_voxels': vox,
-                     'onehot_blend_ms': statistics.median(t_b1), 'onehot_vote_accumulate_ms': statistics.median(t_v),
-                     'spread_gaussian_ms': [min(t_g), max(t_g)]}
+                     'onehot_blend_ms': statistics.median(t_b1), 'spread_gaussian_ms': [min(t_g), max(t_g)]}
         print(f'{name}: ltu_window_blend gaussian {statistics.median(t_g) * 1e3:.1f} us ({nbytes / 1e6:.0f} MB algorithmic, '
-              f'{nbytes / statistics.median(t_g) / 1e9:.2f} TB/s event-timed); one-hot, unit tables: blend '
-              f'{statistics.median(t_b1) * 1e3:.1f} us vs vote_accumulate {statistics.median(t_v) * 1e3:.1f} us', flush=True)
+              f'{nbytes / statistics.median(t_g) / 1e9:.2f} TB/s event-timed); one-hot, unit tables: '
+              f'{statistics.median(t_b1) * 1e3:.1f} us', flush=True)
     return res
 
 
