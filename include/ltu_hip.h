@@ -936,6 +936,55 @@ int ltu_sample_spline(const float* img, const float* coef, const uint8_t* lab, f
 int ltu_gauss_blur3(const float* x, float* out, const float* weights, const int* radii, const float* mul, int n, int H, int W, int D,
                     ltu_stream_t s);
 
+/* ---- intensity augmentation of a batch of patches (csrc/intensity_aug.hip; nnU-Net's ContrastAugmentation, GammaTransform with
+ * invert_image / retain_stats and SimulateLowResolution; no reference counterpart).  x: n volumes of `per` contiguous f32, one per
+ * (patch, channel), 16-byte aligned at its base; a volume that does not begin on a 16-byte boundary is read and written with a scalar
+ * head and tail around whole 16-byte quads.  1 <= per < 2^31.
+ *   patch_stats:       stats, device double [n][4] = {min, max, sum x, sum x^2} of every volume, the sums in fp64.  One record of 4
+ *                      doubles per workgroup into parts (device double, parts_elems >= ltu_patch_stats_parts_elems(n, per) = 4 n
+ *                      blocks(per), blocks <= LTU_PATCH_STATS_MAX_PARTS), folded per volume in index order by a second launch.  The
+ *                      workgroup count depends on per alone and there are no floating-point atomics: two calls give the same bytes.
+ *                      n <= 65535.
+ *   intensity_apply:   out[k] = op_k(x[k]) with ops, params HOST arrays [n] (n <= LTU_INTENSITY_AUG_MAX_N: they travel as kernel
+ *                      arguments) and stats the patch_stats of x on the device:
+ *                        LTU_IAUG_NONE       out = x, bit for bit (also any op with a parameter <= 0)
+ *                        LTU_IAUG_CONTRAST   out = clip((x - m) f + m, min, max), m = (float)(sum / per), f = params[k]
+ *                        LTU_IAUG_GAMMA      out = ((x - min) / max(r, 1e-7))^g r + min, r = max - min, g = params[k]
+ *                        LTU_IAUG_GAMMA_INV  the same on u = -x, negated back: out = -(((u - min u) / max(r, 1e-7))^g r + min u)
+ *                      t^g is exp2(g log2 t) on the hardware transcendentals, t = 0 gives 0; a gamma volume with max == min is copied.
+ *                      out_stats non-NULL: the same pass writes the records of what it stored into parts (capacity as above) and a
+ *                      second launch folds them into out_stats, device double [n][4]: the patch_stats of out without reading it
+ *                      again.  out_stats NULL: one launch, parts is not touched and may be NULL.  out may be x.
+ *   intensity_rescale: nnU-Net's retain_stats, in place: y[k] = (y[k] - mean y) * std x / max(std y, 1e-7) + mean x for the volumes
+ *                      with on[k] != 0 (HOST bytes [n], n <= LTU_INTENSITY_AUG_MAX_N), means and population standard deviations
+ *                      from stats_x and stats_y (device, patch_stats records) in fp64, the voxel in fp32 as one fused multiply-add.
+ *                      The formula commutes with the inversion, so it serves both gammas.  A volume with on[k] == 0, or whose
+ *                      stats_x has max == min, is not touched; no volume asking launches nothing.
+ *   lowres_gather:     out [n][H][W][D] = trilinear_up(nearest_exact_down(x [n][H][W][D])), out of place, as one 8-tap gather; no
+ *                      low-resolution volume exists.  tables: device int32 [n][3][H + W + D], per volume three planes over the
+ *                      output indices of axis H, then W, then D: the source index of the lower tap, of the upper tap, and the bits
+ *                      of the f32 weight l of the upper tap (built on the host in float64, lintransunet_amd/data.py::
+ *                      lowres_tables).  A workgroup stages its tables in LDS, the indices clamped into their axis (any content gives
+ *                      addresses inside the volume); a wave stores 64 consecutive floats.  out = sum of w v over the taps, w = (wx wy) wz with (1 - l | l) per axis, in the
+ *                      fixed order x, y, z: the first product, then one fused multiply-add per tap, a tap of weight 0 left out, so
+ *                      l = 0 on every axis returns the input's bits.  Extents <= LTU_LOWRES_MAX_EXTENT, n <= 65535.
+ *   Nothing is allocated or synchronised and nothing is read back: capturable.
+ *   Refused before any launch: a NULL pointer (parts only with out_stats), x == out in lowres_gather, n < 0 or above its limit in
+ *   apply / rescale, an op outside the enum, a non-finite parameter, a parts_elems below what the launch writes LTU_E_ARG; per or an
+ *   extent outside its range, n > 65535 LTU_E_SHAPE; x / out / y not 16-byte (lowres_gather: 4-byte),
+ *   parts / stats not 8-byte, tables not 4-byte aligned LTU_E_ALIGN. */
+enum { LTU_IAUG_NONE = 0, LTU_IAUG_CONTRAST = 1, LTU_IAUG_GAMMA = 2, LTU_IAUG_GAMMA_INV = 3 };
+#define LTU_INTENSITY_AUG_MAX_N 64
+#define LTU_PATCH_STATS_MAX_PARTS 256
+#define LTU_LOWRES_MAX_EXTENT 1024
+long long ltu_patch_stats_parts_elems(int n, long long per);
+int ltu_patch_stats(const float* x, int n, long long per, double* parts, long long parts_elems, double* stats, ltu_stream_t s);
+int ltu_intensity_apply(const float* x, float* out, const int* ops, const float* params, const double* stats, int n, long long per,
+                        double* parts, long long parts_elems, double* out_stats, ltu_stream_t s);
+int ltu_intensity_rescale(float* y, const unsigned char* on, const double* stats_x, const double* stats_y, int n, long long per,
+                          ltu_stream_t s);
+int ltu_lowres_gather(const float* x, float* out, const int* tables, int n, int H, int W, int D, ltu_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,8 @@ U8, I16 = 2, 3            # LTU_U8 / LTU_I16 source dtypes of ltu_resample_grid 
 HIST_U8, HIST_I16, HIST_F32_INT, HIST_F32_HI, HIST_F32_LO = range(5)      # LTU_HIST_* key modes of ltu_intensity_hist
 MAX_INPUT_CHANNELS = 4    # LTU_MAX_INPUT_CHANNELS of include/ltu_hip.h
 INTENSITY_MOMENT_PARTS = 512     # LTU_INTENSITY_MOMENT_PARTS of include/ltu_hip.h
+IAUG_NONE, IAUG_CONTRAST, IAUG_GAMMA, IAUG_GAMMA_INV = range(4)      # LTU_IAUG_* ops of ltu_intensity_apply
+INTENSITY_AUG_MAX_N, LOWRES_MAX_EXTENT = 64, 1024      # LTU_INTENSITY_AUG_MAX_N / LTU_LOWRES_MAX_EXTENT of include/ltu_hip.h
 
 
 # name -> argument types (return type is always int).  Mirrors include/ltu_hip.h one to one.
@@ -126,6 +128,11 @@ SIGNATURES = {
     'ltu_sample_channels': [P, P, P, P, P, P, I, I, I, P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_sample_spline': [P, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
     'ltu_gauss_blur3': [P, P, P, P, P, I, I, I, I, P],
+    'ltu_patch_stats_parts_elems': [I, L],
+    'ltu_patch_stats': [P, I, L, P, L, P, P],
+    'ltu_intensity_apply': [P, P, P, P, P, I, L, P, L, P, P],
+    'ltu_intensity_rescale': [P, P, P, P, I, L, P],
+    'ltu_lowres_gather': [P, P, P, I, I, I, I, P],
     'ltu_adamw': [P, P, P, P, L, F, F, F, F, F, L, F, P],
     'ltu_grad_sumsq_parts': [L],
     'ltu_grad_sumsq': [P, L, F, P, L, P],
@@ -210,7 +217,8 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = args
         fn.restype = c_longlong if (name.endswith(('_ws_floats', '_ws_elems')) or name in ('ltu_layer_tail_blocks', 'ltu_grad_sumsq_parts', 'ltu_crop_index_elems', 'ltu_distmap_scratch_elems',
-                                                                                           'ltu_loss_boundary_sums_floats', 'ltu_loss_topk_scratch_elems')) else c_int
+                                                                                           'ltu_loss_boundary_sums_floats', 'ltu_loss_topk_scratch_elems',
+                                                                                           'ltu_patch_stats_parts_elems')) else c_int
     for name, args in EXPERIMENT_SIGNATURES.items():
         fn = getattr(lib, name, None)
         if fn is not None:

@@ -13,6 +13,7 @@ Segmentation Decathlon layout, ScaleIntensityRanged -> Spacingd -> Orientationd(
 path each: `SpacedScan` and `MultiScan` load through `SpacedScan._load` and `_load_channel`, and `sample_affine` gathers a 3-D image
 as the one-channel case of `ltu_sample_channels` (order 1) or `ltu_sample_spline` (cubic).
 """
+import functools
 import warnings
 
 import numpy as np
@@ -1386,6 +1387,147 @@ def gaussian_blur(x, sigmas, mul=None):
     return out.view(x.shape)
 
 
+def _f32_volumes(x, what):
+    v = _vol4(x)
+    if v.dtype != torch.float32:
+        raise ValueError(f'{what} takes float32 patches, got {v.dtype}')
+    return v, v.shape[0], v.numel() // max(v.shape[0], 1)
+
+
+def _stats_parts(n, per, device):
+    """the scratch of one statistics launch over n volumes of per floats (4 doubles per workgroup)"""
+    return torch.empty(max(int(_lib.load().ltu_patch_stats_parts_elems(n, per)), 4), dtype=torch.float64, device=device)
+
+
+def patch_stats(x):
+    """ltu_patch_stats: x [n,(1,)H,W,D] f32 -> [n, 4] float64 on the device, {min, max, sum, sum of squares} of every volume (the sums
+    in fp64, bit-reproducible).  Nothing is read back."""
+    v, n, per = _f32_volumes(x, 'patch_stats')
+    out = torch.empty((n, 4), dtype=torch.float64, device=v.device)
+    if n:
+        parts = _stats_parts(n, per, v.device)
+        _lib.call('ltu_patch_stats', _p(v), n, per, _p(parts), parts.numel(), _p(out), _s())
+    return out
+
+
+def _intensity_apply(v, ops, params, retain):
+    """ltu_intensity_apply (+ ltu_intensity_rescale on the volumes of `retain`) over v [n,H,W,D], LTU_INTENSITY_AUG_MAX_N volumes per
+    launch; ops, params, retain: host lists of n"""
+    n, per = v.shape[0], v.numel() // max(v.shape[0], 1)
+    ops = np.ascontiguousarray(ops, dtype=np.int32)
+    par = np.ascontiguousarray(params, dtype=np.float32)
+    if not np.isfinite(par).all():
+        raise ValueError(f'an intensity parameter is a finite number, got {list(params)}')
+    par = np.where(par > 0, par, np.float32(0.0)).astype(np.float32)          # non-positive: the volume is left untouched
+    on = np.ascontiguousarray(np.asarray(retain, dtype=bool) & (par > 0) & (ops >= _lib.IAUG_GAMMA), dtype=np.uint8)
+    out = torch.empty_like(v)
+    step = _lib.INTENSITY_AUG_MAX_N
+    for s in range(0, n, step):
+        e = min(n, s + step)
+        m = e - s
+        parts = _stats_parts(m, per, v.device)
+        sx = torch.empty((m, 4), dtype=torch.float64, device=v.device)
+        _lib.call('ltu_patch_stats', _p(v[s:e]), m, per, _p(parts), parts.numel(), _p(sx), _s())
+        if on[s:e].any():
+            sy = torch.empty((m, 4), dtype=torch.float64, device=v.device)
+            _lib.call('ltu_intensity_apply', _p(v[s:e]), _p(out[s:e]), ops[s:e].ctypes.data, par[s:e].ctypes.data, _p(sx), m, per,
+                      _p(parts), parts.numel(), _p(sy), _s())
+            _lib.call('ltu_intensity_rescale', _p(out[s:e]), on[s:e].ctypes.data, _p(sx), _p(sy), m, per, _s())
+        else:
+            _lib.call('ltu_intensity_apply', _p(v[s:e]), _p(out[s:e]), ops[s:e].ctypes.data, par[s:e].ctypes.data, _p(sx), m, per,
+                      0, 0, 0, _s())
+    return out
+
+
+def contrast(x, factors):
+    """nnU-Net's contrast augmentation per volume of x [n,(1,)H,W,D] f32: clip((x - mean) * f + mean, min, max) with the volume's own
+    mean, min and max (taken on the device, never read back).  A factor <= 0 leaves that volume untouched, bit for bit."""
+    v, n, _ = _f32_volumes(x, 'contrast')
+    f = np.asarray(factors, dtype=np.float64).reshape(n)
+    return _intensity_apply(v, np.full(n, _lib.IAUG_CONTRAST), f, np.zeros(n, bool)).view(x.shape)
+
+
+def gamma_transform(x, gammas, invert=False, retain_stats=True):
+    """nnU-Net's gamma transform per volume of x [n,(1,)H,W,D] f32, on u = -x when invert (one flag or one per volume):
+    v = ((u - min u) / max(r, 1e-7))^g * r + min u with r = max u - min u; retain_stats then rescales v to the mean and standard
+    deviation of u; the result is -v when invert.  g <= 0 leaves that volume untouched, a constant volume comes back unchanged.
+    Statistics stay on the device: the call can be captured."""
+    v, n, _ = _f32_volumes(x, 'gamma_transform')
+    g = np.asarray(gammas, dtype=np.float64).reshape(n)
+    inv = np.broadcast_to(np.asarray(invert, dtype=bool), (n,))
+    ops = np.where(inv, _lib.IAUG_GAMMA_INV, _lib.IAUG_GAMMA)
+    return _intensity_apply(v, ops, g, np.broadcast_to(np.asarray(retain_stats, dtype=bool), (n,))).view(x.shape)
+
+
+def lowres_tables(size, scale, axes=(0, 1, 2)):
+    """the gather tables of nnU-Net's low-resolution simulation for one volume of extents size = (H, W, D): nearest-exact down to
+    S' = max(int(round(S * scale)), 1) on the axes in `axes` (S' = S on the others), then trilinear up, composed per output index o:
+      src = max((o + 0.5) * S' / S - 0.5, 0),  j0 = min(floor(src), S' - 1),  j1 = min(j0 + 1, S' - 1),  l = src - j0 (0 where j0 == j1)
+    in float64, and the low index j reads the high index min(((2 j + 1) S) // (2 S'), S - 1).  Returns (idx int32 [2][H + W + D], lam
+    float32 [H + W + D]): the high-resolution indices of the lower and the upper tap and the upper tap's weight, axis H first.  An
+    axis with S' == S gives idx[0] == o and l == 0: the identity.  scale outside (0, 1] raises ValueError."""
+    t = _lowres_packed(size, [scale], axes)[0]
+    return t[:2].copy(), t[2].view(np.float32).copy()
+
+
+@functools.lru_cache(maxsize=4096)
+def _lowres_axis(S, Sl):
+    """one axis of extent S through a low extent Sl, int32 [3][S]: lower tap, upper tap, the float32 weight's bits.  Kept per (S, Sl):
+    a training run draws scales without end but meets at most S low extents per axis"""
+    src = np.maximum((np.arange(S, dtype=np.float64) + 0.5) * Sl / S - 0.5, 0.0)
+    j0 = np.minimum(np.floor(src).astype(np.int64), Sl - 1)
+    j1 = np.minimum(j0 + 1, Sl - 1)
+    out = np.empty((3, S), dtype=np.int32)
+    out[0] = np.minimum(((2 * j0 + 1) * S) // (2 * Sl), S - 1)
+    out[1] = np.minimum(((2 * j1 + 1) * S) // (2 * Sl), S - 1)
+    out[2].view(np.float32)[...] = np.where(j0 == j1, 0.0, src - j0)
+    out.setflags(write=False)
+    return out
+
+
+def _lowres_packed(size, scales, axes):
+    """lowres_tables of n scales as ltu_lowres_gather takes them, int32 [n][3][H + W + D] (plane 2: the float32 weights' bits)"""
+    size = tuple(int(v) for v in size)
+    sc = [float(s) for s in scales]
+    for s in sc:
+        if not 0.0 < s <= 1.0:
+            raise ValueError(f'a low-resolution scale lies in (0, 1], got {s}')
+    axes = tuple(int(a) for a in axes)
+    if any(a not in (0, 1, 2) for a in axes):
+        raise ValueError(f'lowres axes are patch axes 0, 1, 2, got {axes}')
+    out = np.empty((len(sc), 3, sum(size)), dtype=np.int32)
+    off = 0
+    for a, S in enumerate(size):
+        for k, s in enumerate(sc):
+            out[k, :, off:off + S] = _lowres_axis(S, max(int(round(S * s)), 1) if a in axes else S)
+        off += S
+    return out
+
+
+def lowres_device_tables(size, scales, axes=(0, 1, 2), device='cuda'):
+    """lowres_tables of every scale as ltu_lowres_gather takes them: int32 [n][3][H + W + D] on the device (the third plane holds the
+    float32 weights' bits).  A scale <= 0 gives the identity table (that volume stays untouched)."""
+    sc = np.asarray(scales, dtype=np.float64).reshape(-1)
+    return torch.from_numpy(_lowres_packed(size, np.where(sc > 0, sc, 1.0), axes)).to(device)
+
+
+def simulate_lowres(x, scales, axes=(0, 1, 2), tables=None):
+    """nnU-Net's SimulateLowResolution per volume of x [n,(1,)H,W,D] f32: F.interpolate(F.interpolate(x, size=S', mode='nearest-exact'),
+    size=S, mode='trilinear') as one 8-tap gather (ltu_lowres_gather), no low-resolution volume in between.  scales: one per volume
+    in (0, 1]; above 1 raises ValueError, <= 0 leaves that volume untouched; an axis outside `axes`, or scale 1, returns the input's
+    bits.  tables: lowres_device_tables(...) made beforehand (their upload is the one step of this call that cannot be captured);
+    scales and axes are then not looked at."""
+    v, n, _ = _f32_volumes(x, 'simulate_lowres')
+    _, H, W, D = v.shape
+    if tables is None:
+        tables = lowres_device_tables((H, W, D), np.asarray(scales, dtype=np.float64).reshape(n), axes, v.device)
+    if tables.dtype != torch.int32 or tuple(tables.shape) != (n, 3, H + W + D) or tables.device != v.device or not tables.is_contiguous():
+        raise ValueError(f'tables are a contiguous int32 [{n}][3][{H + W + D}] on {v.device}')
+    out = torch.empty_like(v)
+    _lib.call('ltu_lowres_gather', _p(v), _p(out), _p(tables), n, H, W, D, _s())
+    return out.view(x.shape)
+
+
 def _fmix32(h):
     h = h ^ (h >> np.uint32(16))
     h = h * np.uint32(0x85EBCA6B)
@@ -1422,11 +1564,28 @@ class Augmentation:
     with elastic_mm drawn from its range; 0 (the default) makes no draw for it.  order (sample_order: 1, 3, (3, 3, 3) or (3, 3, 1)
     per scan axis H, W, D): the image interpolation of the patches that rotate, zoom or deform; 1, the default, is trilinear, any
     other is sample_affine's cubic B-spline from scan.spline_coefficients(order) (nnU-Net interpolates at order 3), clamped to each
-    channel's intensity window.  It makes no draw: draw() returns the same values and leaves the generator in the same state."""
+    channel's intensity window.  It makes no draw: draw() returns the same values and leaves the generator in the same state.
+    contrast_prob, lowres_prob, invgamma_prob > 0 add nnU-Net's contrast (data.contrast, factor from `contrast`), low-resolution
+    simulation (data.simulate_lowres, scale from lowres_scale on the patch axes lowres_axes) and gamma on the inverted image
+    (data.gamma_transform(invert=True), exponent from invgamma); each draws (fire, value) behind the elastic draws, in this order,
+    and 0 (the default) makes no draw for it.  retain_stats=True runs both gammas through data.gamma_transform with the patch's mean
+    and standard deviation restored (nnU-Net's GammaTransform); False keeps the gamma draw on monai's adjust_contrast.  It makes no
+    draw either.  Augmentation.nnunet() is the record with nnU-Net's default probabilities and ranges."""
 
     def __init__(self, rot_prob=0.2, rot_range=(0.0, 0.0, np.pi), zoom_prob=0.2, zoom_range=(0.7, 1.4), noise_prob=0.1,
                  noise_std=(0.0, 0.1), blur_prob=0.2, blur_sigma=(0.5, 1.0), brightness_prob=0.15, brightness=(0.75, 1.25),
-                 gamma_prob=0.3, gamma=(0.7, 1.5), fill=None, elastic_prob=0.0, elastic_mm=(0.0, 4.0), elastic_grid=(6, 6, 4), order=1):
+                 gamma_prob=0.3, gamma=(0.7, 1.5), fill=None, elastic_prob=0.0, elastic_mm=(0.0, 4.0), elastic_grid=(6, 6, 4), order=1,
+                 contrast_prob=0.0, contrast=(0.75, 1.25), lowres_prob=0.0, lowres_scale=(0.5, 1.0), lowres_axes=(0, 1, 2),
+                 invgamma_prob=0.0, invgamma=(0.7, 1.5), retain_stats=False):
+        self.contrast_prob, self.contrast = contrast_prob, tuple(float(v) for v in contrast)
+        self.lowres_prob, self.lowres_scale = lowres_prob, tuple(float(v) for v in lowres_scale)
+        self.lowres_axes = tuple(int(a) for a in lowres_axes)
+        if not all(a in (0, 1, 2) for a in self.lowres_axes):
+            raise ValueError(f'lowres_axes are patch axes 0, 1, 2, got {lowres_axes}')
+        if not 0.0 < min(self.lowres_scale) <= max(self.lowres_scale) <= 1.0:
+            raise ValueError(f'lowres_scale is a range inside (0, 1], got {lowres_scale}')
+        self.invgamma_prob, self.invgamma = invgamma_prob, tuple(float(v) for v in invgamma)
+        self.retain_stats = bool(retain_stats)
         self.order = sample_order(order)
         self.elastic_prob, self.elastic_mm = elastic_prob, tuple(float(v) for v in elastic_mm)
         self.elastic_grid = tuple(int(g) for g in elastic_grid)
@@ -1461,7 +1620,27 @@ class Augmentation:
             p['elastic'] = rs.rand() < self.elastic_prob
             p['elastic_mm'] = rs.uniform(*self.elastic_mm)
             p['phi'] = rs.uniform(-1, 1, (3, *self.elastic_grid))
+        if self.contrast_prob > 0:
+            p['scale_contrast'] = rs.rand() < self.contrast_prob
+            p['contrast_factor'] = rs.uniform(*self.contrast)
+        if self.lowres_prob > 0:
+            p['lowres'] = rs.rand() < self.lowres_prob
+            p['lowres_scale'] = rs.uniform(*self.lowres_scale)
+        if self.invgamma_prob > 0:
+            p['invgamma'] = rs.rand() < self.invgamma_prob
+            p['invgamma_g'] = rs.uniform(*self.invgamma)
         return p
+
+    @classmethod
+    def nnunet(cls, **overrides):
+        """nnU-Net's default training augmentation: rotation 0.2, zoom 0.2 over (0.7, 1.4), noise 0.1, blur 0.2, brightness 0.15,
+        contrast 0.15, low resolution 0.25 over (0.5, 1), inverted gamma 0.1 and gamma 0.3 over (0.7, 1.5) with retain_stats, order-3
+        interpolation.  overrides replace any of them."""
+        kw = dict(rot_prob=0.2, zoom_prob=0.2, zoom_range=(0.7, 1.4), noise_prob=0.1, blur_prob=0.2, brightness_prob=0.15,
+                  contrast_prob=0.15, contrast=(0.75, 1.25), lowres_prob=0.25, lowres_scale=(0.5, 1.0), invgamma_prob=0.1,
+                  invgamma=(0.7, 1.5), gamma_prob=0.3, gamma=(0.7, 1.5), retain_stats=True, order=3)
+        kw.update(overrides)
+        return cls(**kw)
 
     def check_fold(self, spatial_size, pixdim, swap=True):
         """ValueError unless the largest control displacement this record can draw stays within 0.4 lattice cells on every patch
@@ -1511,9 +1690,10 @@ def _scan_fill(scan, augment):
 
 def _augmented(scan, draws, params, spatial_size, augment, spacing):
     """the patches of draws [(centre, flip, k)] under params (one Augmentation.draw per patch): one sample_affine, then one
-    gaussian_blur if a patch blurs or brightens, then adjust_contrast if a patch fires gamma.  A MultiScan's K channels come out of
-    the one gather (noise per channel from channel_seed); blur, brightness and gamma see [n K, h, w, d] with each patch's
-    parameters repeated K times.  params None: the plain patches through patch_matrix's integer matrices (a MultiScan only)."""
+    gaussian_blur if a patch blurs or brightens, then contrast, simulate_lowres and gamma_transform(invert=True) where a patch fires
+    them, then the gamma draw: adjust_contrast, or gamma_transform under augment.retain_stats.  A MultiScan's K channels come out of
+    the one gather (noise per channel from channel_seed); every later stage sees [n K, h, w, d] with each patch's parameters repeated
+    K times (statistics are per channel).  params None: the plain patches through patch_matrix's integer matrices (a MultiScan only)."""
     size = tuple(int(s) for s in spatial_size)
     fill = _scan_fill(scan, augment)
     if params is None:
@@ -1551,8 +1731,16 @@ def _augmented(scan, draws, params, spatial_size, augment, spacing):
     if any(p['blur'] or p['bright'] for p in params):
         img = gaussian_blur(img, per_channel(p['sigma'] if p['blur'] else 0.0 for p in params),
                             per_channel(p['mul'] if p['bright'] else 1.0 for p in params))
+    if any(p.get('scale_contrast') for p in params):
+        img = contrast(img, per_channel(p['contrast_factor'] if p.get('scale_contrast') else -1.0 for p in params))
+    if any(p.get('lowres') for p in params):
+        img = simulate_lowres(img, per_channel(p['lowres_scale'] if p.get('lowres') else -1.0 for p in params), augment.lowres_axes)
+    if any(p.get('invgamma') for p in params):
+        img = gamma_transform(img, per_channel(p['invgamma_g'] if p.get('invgamma') else -1.0 for p in params), invert=True,
+                              retain_stats=augment.retain_stats)
     if any(p['contrast'] for p in params):
-        img = adjust_contrast(img, per_channel(p['gamma'] if p['contrast'] else -1.0 for p in params))
+        gammas = per_channel(p['gamma'] if p['contrast'] else -1.0 for p in params)
+        img = gamma_transform(img, gammas, invert=False, retain_stats=True) if augment.retain_stats else adjust_contrast(img, gammas)
     return img.view(shape), lab
 
 
@@ -1596,10 +1784,13 @@ def sample(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_p
     RandCropByPosNegLabeld to RandCropByLabelClassesd (class_centers / class_crop_centers, num_samples 1 per sample).
     augment: an Augmentation.  The draws above keep their place; behind them come, per sample, Augmentation.draw's (rotation fire,
     three angles; zoom fire, factor; noise fire, std, two seed words; blur fire, sigma; brightness fire, multiplier; gamma fire,
-    gamma; with elastic_prob > 0 also: deformation fire, its amplitude in millimetres, the control lattice).  The patches are then
+    gamma; with elastic_prob > 0 also: deformation fire, its amplitude in millimetres, the control lattice; with contrast_prob,
+    lowres_prob, invgamma_prob > 0 also, in this order and each only for its own probability: fire and factor, fire and scale, fire
+    and exponent).  The patches are then
     gathered through patch_matrix by one sample_affine (rotation in millimetres of scan.pixdim, the B-spline deformation of the
-    patches that fire it folded into the same gather, noise in the store), blurred / brightened by one gaussian_blur and
-    gamma-adjusted by adjust_contrast.  None changes nothing: the same draws, patches and generator state.
+    patches that fire it folded into the same gather, noise in the store), blurred / brightened by one gaussian_blur, then
+    contrast, simulate_lowres and the inverted gamma_transform where fired, and gamma-adjusted by adjust_contrast (gamma_transform
+    with augment.retain_stats).  None changes nothing: the same draws, patches and generator state.
     A MultiScan gives ([n,K,h,w,d] f32, [n,1,h,w,d] u8): the host draws do not depend on K, the K channels of a patch share its
     geometry, blur, brightness and gamma and get independent noise (channel c from channel_seed(seed, c)); fill=None takes each
     channel's own window floor.  Its plain path is the same gather through patch_matrix's integer matrices (the source voxels)."""
