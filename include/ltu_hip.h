@@ -661,6 +661,28 @@ int ltu_adamw_guard(const float* scratch, long long parts, void* state, float gr
                     int skip_nonfinite, float beta1, float beta2, ltu_stream_t s);
 int ltu_adamw_guarded(float* p, const float* g, float* m, float* v, float* ema /* nullable */, long long n, float lr, float beta1,
                       float beta2, float eps, float weight_decay, float ema_decay, const void* state, ltu_stream_t s);
+/* SGD with momentum / Nesterov (train3D.py:194: torch.optim.SGD(lr=1e-4, momentum=0.9); nnU-Net: momentum 0.99, Nesterov, weight
+ * decay 3e-5) on the same flat, 16-byte aligned fp32 buffers, torch.optim.SGD's arithmetic per element:
+ *   g' = g * coef;  weight_decay != 0: g' += weight_decay * p
+ *   momentum != 0: buf = g' on the first applied step, buf = momentum * buf + (1 - dampening) * g' afterwards;
+ *                  g' = g' + momentum * buf (nesterov) or g' = buf
+ *   p -= lr * g';  ema = ema_decay * ema + (1 - ema_decay) * p (guarded form, ema != NULL)
+ * Every multiply-add is an explicit fmaf (csrc/optim.hip states the expression), so the plain and the guarded form, with or
+ * without an EMA, give the same parameter and buffer bits for the same inputs.  buf is NULL iff momentum == 0 (no buffer is read
+ * or written then).
+ *   ltu_sgd          coef = grad_scale, lr and first_step (!= 0: the first step) from the host, as ltu_adamw takes lr and step.
+ *   ltu_sgd_guarded  after ltu_grad_sumsq per bucket and ONE ltu_adamw_guard (betas 0; bc1 / bc2 are not read) it takes coef, skip
+ *                    and first = (applied == 1) from the guard state: a skipped first step leaves the first case to the next applied
+ *                    one.  skip = 1: returns without writing anything.  The learning rate is read from DEVICE memory (lr_dev, one
+ *                    fp32, 4-byte aligned, a uniform load), so a captured launch stays valid while a schedule moves the value.
+ * LTU_E_ARG (nothing launched, nothing written): a NULL or misaligned pointer (16 bytes for buffers and state, 4 for lr_dev), buf
+ * present without momentum or absent with it, a negative or NaN lr / momentum / weight_decay, a NaN dampening or grad_scale, nesterov
+ * with momentum <= 0 or dampening != 0, ema_decay outside [0, 1) with an EMA buffer.  n <= 0 with valid scalars: LTU_OK. */
+int ltu_sgd(float* p, const float* g, float* buf /* NULL iff momentum == 0 */, long long n, float lr, float momentum, float dampening,
+            float weight_decay, int nesterov, int first_step, float grad_scale, ltu_stream_t s);
+int ltu_sgd_guarded(float* p, const float* g, float* buf /* NULL iff momentum == 0 */, float* ema /* nullable */, long long n,
+                    const float* lr_dev, float momentum, float dampening, float weight_decay, int nesterov, float ema_decay,
+                    const void* state, ltu_stream_t s);
 
 /* ---- data-parallel gradient exchange (replaces the reduce half of nn.DataParallel, train3D.py:119) -------------------------------
  * Direct RCCL calls: one communicator per process (= per GPU), created from a 128-byte unique id that rank 0 generates and the

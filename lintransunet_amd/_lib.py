@@ -138,6 +138,8 @@ SIGNATURES = {
     'ltu_grad_sumsq': [P, L, F, P, L, P],
     'ltu_adamw_guard': [P, L, P, F, F, I, F, F, P],
     'ltu_adamw_guarded': [P, P, P, P, P, L, F, F, F, F, F, F, P, P],
+    'ltu_sgd': [P, P, P, L, F, F, F, F, I, I, F, P],
+    'ltu_sgd_guarded': [P, P, P, P, L, P, F, F, F, I, F, P, P],
     'ltu_norm_ws_floats': [],
     'ltu_instnorm_stats': [P, P, P, L, I, L, I, I, P],
     'ltu_instnorm_apply': [P, P, P, P, I, L, I, I, F, F, U, P, I, P],

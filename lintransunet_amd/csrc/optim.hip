@@ -2,6 +2,7 @@
 //   per bucket   ltu_grad_sumsq     sum of (g * grad_scale)^2, one fp32 partial per workgroup into the caller's scratch row
 //   once         ltu_adamw_guard    folds the partials of ALL buckets in fp64 -> guard state (norm, coef, skip, counters, bias corrections)
 //   per bucket   ltu_adamw_guarded  adamw_kernel's arithmetic (misc.hip) with coef / bc1 / bc2 / skip read from the guard state, + EMA
+//   per bucket   ltu_sgd_guarded    the SGD family behind the same two guard launches (below, with its plain form ltu_sgd)
 // Nothing is read back and nothing is atomic: the partial count is a function of n alone and every fold runs in a fixed order, so
 // two calls on the same buckets give the same bits, and every rank of a data-parallel run takes the same decision from its own
 // copy of the reduced buckets.
@@ -159,5 +160,119 @@ extern "C" int ltu_adamw_guarded(float* p, const float* g, float* m, float* v, f
   else
     hipLaunchKernelGGL(adamw_guarded_kernel<false>, grid, block, 0, (hipStream_t)s, p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay,
                        0.f, (const GuardState*)state);
+  return ltu_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------ SGD (momentum, Nesterov)
+// torch.optim.SGD's arithmetic per element on the same flat buckets, with the same guard (ltu_grad_sumsq + ltu_adamw_guard with
+// betas of 0: the norm, the decision and the counters are the optimizer-independent part of the state):
+//   g' = g * coef;  wd != 0: g' += wd * p;  momentum: buf = g' on the first applied step, else momentum * buf + (1 - dampening) * g';
+//   g' = g' + momentum * buf (Nesterov) or buf;  p -= lr * g';  ema = d * ema + (1 - d) * p
+// ROUNDING: every multiply-add below is an explicit fmaf and every other product is rounded on its own (a product that is an
+// operand of fmaf cannot be contracted any further), so -ffp-contract=fast has nothing left to decide and all instantiations
+// (plain / guarded, EMA or not, vector body / tail) give the same parameter and buffer bits:
+//   g' = g * coef;  g' = fmaf(wd, p, g');  buf = fmaf(momentum, buf, (1 - dampening) * g');  g' = fmaf(momentum, buf, g');
+//   p = fmaf(-lr, g', p);  ema = fmaf(d, ema, (1 - d) * p)
+// GUARDED reads coef / skip / applied from the guard state and the learning rate from device memory (one uniform load per
+// thread), so a captured launch follows a schedule without being captured again; the plain form takes them from the host.
+// MOM = false passes no buffer and makes no load or store of one.
+template <bool MOM, bool NEST>
+__device__ __forceinline__ float sgd_elem(float p, float g, float& b, float coef, float wd, float mom, float omd, float lr, bool first) {
+  float gg = g * coef;
+  if (wd != 0.f) gg = fmaf(wd, p, gg);
+  if (MOM) {
+    b = first ? gg : fmaf(mom, b, omd * gg);
+    gg = NEST ? fmaf(mom, b, gg) : b;
+  }
+  return fmaf(-lr, gg, p);
+}
+
+template <bool GUARDED, bool MOM, bool NEST, bool EMA>
+__global__ void __launch_bounds__(256) sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                  float* __restrict__ ema, long long n, float lr_host, const float* __restrict__ lr_dev,
+                                                  float mom, float omd, float wd, float d, float coef_host, int first_host,
+                                                  const GuardState* __restrict__ state) {
+  if (GUARDED && state->skip) return;                    // uniform: the whole launch leaves every buffer untouched
+  const float coef = GUARDED ? state->coef : coef_host, lr = GUARDED ? *lr_dev : lr_host;
+  const bool first = GUARDED ? state->applied == 1 : first_host != 0;
+  const float omd_e = 1.f - d;
+  const long long nv = n >> 2;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) {
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 bv, ev;
+    if (MOM) bv = reinterpret_cast<float4*>(buf)[i];
+    if (EMA) ev = reinterpret_cast<float4*>(ema)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float b = MOM ? f4at(bv, k) : 0.f;
+      const float pn = sgd_elem<MOM, NEST>(f4at(pv, k), f4at(gv, k), b, coef, wd, mom, omd, lr, first);
+      f4at(pv, k) = pn;
+      if (MOM) f4at(bv, k) = b;
+      if (EMA) f4at(ev, k) = fmaf(d, f4at(ev, k), omd_e * pn);
+    }
+    reinterpret_cast<float4*>(p)[i] = pv;
+    if (MOM) reinterpret_cast<float4*>(buf)[i] = bv;
+    if (EMA) reinterpret_cast<float4*>(ema)[i] = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {        // tail
+    const long long i = (nv << 2) + threadIdx.x;
+    float b = MOM ? buf[i] : 0.f;
+    const float pn = sgd_elem<MOM, NEST>(p[i], g[i], b, coef, wd, mom, omd, lr, first);
+    p[i] = pn;
+    if (MOM) buf[i] = b;
+    if (EMA) ema[i] = fmaf(d, ema[i], omd_e * pn);
+  }
+}
+
+// the checks both entry points share; LTU_OK with *launch = false for n <= 0
+static int sgd_check(const float* p, const float* g, const float* buf, const float* ema, long long n, float momentum, float dampening,
+                     float weight_decay, int nesterov, bool* launch) {
+  *launch = false;
+  if (!(momentum >= 0.f) || dampening != dampening || !(weight_decay >= 0.f)) return LTU_E_ARG;      // NaN included
+  if (nesterov && (momentum <= 0.f || dampening != 0.f)) return LTU_E_ARG;                           // torch's rule
+  if (n <= 0) return LTU_OK;
+  if (p == nullptr || g == nullptr || (buf == nullptr) != (momentum == 0.f)) return LTU_E_ARG;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf | (uintptr_t)ema) & 15) return LTU_E_ARG;
+  *launch = true;
+  return LTU_OK;
+}
+
+template <bool GUARDED, bool EMA, typename... Args>
+static void sgd_launch(bool mom, bool nest, long long n, hipStream_t s, Args... args) {
+  const dim3 grid((unsigned)optim_blocks(n)), block(256);
+  if (!mom)
+    hipLaunchKernelGGL((sgd_kernel<GUARDED, false, false, EMA>), grid, block, 0, s, args...);
+  else if (!nest)
+    hipLaunchKernelGGL((sgd_kernel<GUARDED, true, false, EMA>), grid, block, 0, s, args...);
+  else
+    hipLaunchKernelGGL((sgd_kernel<GUARDED, true, true, EMA>), grid, block, 0, s, args...);
+}
+
+extern "C" int ltu_sgd(float* p, const float* g, float* buf, long long n, float lr, float momentum, float dampening, float weight_decay,
+                       int nesterov, int first_step, float grad_scale, ltu_stream_t s) {
+  if (!(lr >= 0.f) || grad_scale != grad_scale) return LTU_E_ARG;
+  bool launch;
+  const int rc = sgd_check(p, g, buf, nullptr, n, momentum, dampening, weight_decay, nesterov, &launch);
+  if (!launch) return rc;
+  sgd_launch<false, false>(momentum != 0.f, nesterov != 0, n, (hipStream_t)s, p, g, buf, (float*)nullptr, n, lr, (const float*)nullptr, momentum,
+                           1.f - dampening, weight_decay, 0.f, grad_scale, first_step, (const GuardState*)nullptr);
+  return ltu_check_launch();
+}
+
+extern "C" int ltu_sgd_guarded(float* p, const float* g, float* buf, float* ema, long long n, const float* lr_dev, float momentum,
+                               float dampening, float weight_decay, int nesterov, float ema_decay, const void* state, ltu_stream_t s) {
+  if (state == nullptr || ((uintptr_t)state & 15) || lr_dev == nullptr || ((uintptr_t)lr_dev & 3)) return LTU_E_ARG;
+  if (ema != nullptr && !(ema_decay >= 0.f && ema_decay < 1.f)) return LTU_E_ARG;
+  bool launch;
+  const int rc = sgd_check(p, g, buf, ema, n, momentum, dampening, weight_decay, nesterov, &launch);
+  if (!launch) return rc;
+  const bool mom = momentum != 0.f, nest = nesterov != 0;
+  if (ema != nullptr)
+    sgd_launch<true, true>(mom, nest, n, (hipStream_t)s, p, g, buf, ema, n, 0.f, lr_dev, momentum, 1.f - dampening, weight_decay, ema_decay,
+                           0.f, 0, (const GuardState*)state);
+  else
+    sgd_launch<true, false>(mom, nest, n, (hipStream_t)s, p, g, buf, ema, n, 0.f, lr_dev, momentum, 1.f - dampening, weight_decay, 0.f, 0.f,
+                            0, (const GuardState*)state);
   return ltu_check_launch();
 }
