@@ -484,6 +484,41 @@ int ltu_loss_topk_fwd(const float* p, const uint8_t* label, void* scratch, long 
 int ltu_loss_topk_bwd(const float* p, const uint8_t* label, const void* scratch, long long scratch_elems, float w,
                       const float* scale_dev, const float* gscale, float* dp, int accumulate, int B, long long S, int C,
                       ltu_stream_t s);
+/* ---- losses for class-imbalanced tasks: Tversky, focal Tversky, focal cross-entropy (csrc/loss_imbalance.hip) -------------------
+ * The fourth stage of a level's loss chain.  p f32 [B][S][C] probabilities (2 <= C <= 8), label u8 [B][S].  With t_c = [label == c]
+ * (t = 0 in every class where label >= C, as in the base losses) the sums pass accumulates per (b, c), each sum directly and none
+ * as a difference of two others (no cancellation when p[label] == 1.0 on most voxels; all four are >= 0):
+ *     I = sum p t    FP = sum p (1 - t)    FN = sum t (1 - p)    F = sum t (1 - p)^gf (-log max(p, 1e-6))
+ * Tversky term k (K <= 8 terms, class classes[k], weight w[k]; Salehi et al., focal form of Abraham & Khan) with the shared
+ * params = {alpha, beta, gamma, eps, batch}, alpha, beta >= 0, alpha + beta > 0, 1 <= gamma <= 3 (1: plain Tversky), eps > 0, batch 0 / 1:
+ *     1 - TI = (alpha FP + beta FN) / (I + alpha FP + beta FN + eps)          (TI = (I + eps) / (the same denominator))
+ *     batch == 0:  value_k = (1 / B) sum_b (1 - TI[b, c])^(1 / gamma)
+ *     batch == 1:  I, FP, FN summed over b first (in the order of b), value_k = (1 - TI[c])^(1 / gamma)       (nnU-Net's batch_dice;
+ *                  alpha = beta = 0.5, eps = 0.5e-5 is its soft Dice (2 I + 1e-5) / (P + T + 1e-5); the batch is this call's)
+ *   Where 1 - TI is exactly 0 and gamma > 1 the power's derivative is infinite: the gradient of that term is 0 there (the chosen
+ *   subgradient).
+ * Focal cross-entropy (weight w_focal; gf = focal_gamma is 0 or in [1, 5] - in (0, 1) the derivative at p = 1 is unbounded;
+ * focal_alpha: C class weights a_c, finite and >= 0, NULL = all 1):
+ *     value = (1 / (B S)) sum_{b, c} a_c F[b, c]          (gf = 0, a = 1: the plain mean of -log max(p[label], 1e-6))
+ *   With w_focal == 0 the term is not evaluated (no log per voxel) and its value reads 0.
+ *   Voxels with label >= C add 0 and count in B S.  The gradient is that of the clamped expression: below p = 1e-6 the
+ *   -(1 - p)^gf / p part is absent.
+ * values [K + 3] = {total, value_0 .. value_{K-1}, focal value, total again}, total = (base_total ? base_total[0] : 0) + scale
+ * (sum_k w[k] value_k + w_focal value), scale = scale_dev ? scale_dev[0] : 1 read on the device.  coef [B][C][3], already weighted
+ * and scaled, serves the backward: dp[b][s][c] = gscale[0] (A + t_c (Bc + G f'(p))), f = (1 - p)^gf log max(p, 1e-6), written
+ * (accumulate == 0) or added into what dp holds (accumulate != 0); pass the forward's focal_gamma.
+ * Per-workgroup partials folded in a fixed order, no floating-point atomics: two calls agree bit for bit; no host read, capturable.
+ * sums: ltu_loss_imb_ws_floats(B, S, C) floats, no initialisation (0: a shape the calls refuse).
+ * LTU_E_SHAPE: C outside 2 .. 8, B < 1, S < 1, B C 4 > 256 (the finalize kernel's rows, as ltu_loss_wide_fwd); LTU_E_ARG: a NULL
+ * pointer (base_total, focal_alpha and scale_dev may be NULL; classes and w when K == 0), K outside 0 .. 8, short sums or coef, a
+ * term of a class >= C, a non-finite weight or parameter, a parameter outside the ranges above; all before anything is launched. */
+long long ltu_loss_imb_ws_floats(int B, long long S, int C);
+int ltu_loss_imb_fwd(const float* p, const uint8_t* label, float* sums, long long sums_floats, float* values /* K + 3 */,
+                     float* coef /* [B][C][3] */, const float* base_total, const int* classes, const float* w, int K,
+                     const float* params /* 5 */, float w_focal, float focal_gamma, const float* focal_alpha, const float* scale_dev,
+                     int B, long long S, int C, ltu_stream_t s);
+int ltu_loss_imb_bwd(const float* p, const uint8_t* label, const float* coef, long long coef_floats, float focal_gamma,
+                     const float* gscale, float* dp, int accumulate, int B, long long S, int C, ltu_stream_t s);
 /* label pyramid (utils/utils_3D_embed_full.py:64,73-76): u8 [B,H,W,D] -> max over (2,2,kd) windows */
 int ltu_label_maxpool(const uint8_t* x, uint8_t* y, int B, int H, int W, int D, int kd, ltu_stream_t s);
 

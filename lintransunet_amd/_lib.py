@@ -182,6 +182,9 @@ SIGNATURES = {
     'ltu_loss_topk_scratch_elems': [I, L],
     'ltu_loss_topk_fwd': [P, P, P, L, P, P, F, F, P, P, I, L, I, P],
     'ltu_loss_topk_bwd': [P, P, P, L, F, P, P, P, I, I, L, I, P],
+    'ltu_loss_imb_ws_floats': [I, L, I],
+    'ltu_loss_imb_fwd': [P, P, P, L, P, P, P, P, P, I, P, F, F, P, P, I, L, I, P],
+    'ltu_loss_imb_bwd': [P, P, P, L, F, P, P, I, I, L, I, P],
     'ltu_label_maxpool': [P, P, I, I, I, I, I, P],
     'ltu_comm_load': [ctypes.c_char_p],
     'ltu_comm_unique_id': [P],

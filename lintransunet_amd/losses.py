@@ -7,10 +7,42 @@ every module is `forward(predict[N,C,...], target) -> 0-dim tensor`.  `target` i
 volume [N,1,...] (or a one-hot [N,C,...] tensor, as the multi-class scripts pass).  All losses of one
 decoder level share one streaming reduction (`LevelCriterion`).
 """
+import dataclasses
+import math
+from typing import Optional, Tuple
+
 import torch
 import torch.nn as nn
 
 from . import ops
+
+
+@dataclasses.dataclass(frozen=True)
+class Imbalance:
+    """Parameters of the imbalance names of a LevelCriterion spec ('TverskyLoss..', 'FocalCELoss'; csrc/loss_imbalance.hip), checked
+    on the host (ValueError).  alpha, beta: weights of the false positives and false negatives in every Tversky term of the spec,
+    both >= 0 and not both 0 (0.5, 0.5: Dice; beta > alpha favours recall); tversky_gamma in [1, 3]: the term is (1 - TI)^(1 /
+    gamma), 1 the plain Tversky loss, 4/3 the focal Tversky loss of Abraham & Khan; batch: sum I, FP and FN over the batch before
+    the ratio (nnU-Net's batch_dice; the batch is this rank's); eps > 0.  focal_gamma: 0 (plain cross-entropy) or in [1, 5];
+    focal_alpha: None or one weight >= 0 per class.  The record is fixed when a step is captured: there is no run-time setter."""
+    alpha: float = 0.3
+    beta: float = 0.7
+    tversky_gamma: float = 1.0
+    batch: bool = False
+    eps: float = 1e-5
+    focal_gamma: float = 2.0
+    focal_alpha: Optional[Tuple[float, ...]] = None
+
+    def __post_init__(self):
+        if self.focal_alpha is not None:
+            object.__setattr__(self, 'focal_alpha', tuple(float(a) for a in self.focal_alpha))
+        ops.imbalance_stage(((0,), (1.0,), self.tversky_params), (1.0, self.focal_gamma, self.focal_alpha))      # raises ValueError
+        if self.focal_alpha is not None and not 2 <= len(self.focal_alpha) <= ops.LOSS_WIDE_MAXC:
+            raise ValueError(f'focal_alpha: one weight per class, 2 .. {ops.LOSS_WIDE_MAXC} classes')
+
+    @property
+    def tversky_params(self):
+        return {'alpha': self.alpha, 'beta': self.beta, 'gamma': self.tversky_gamma, 'eps': self.eps, 'batch': bool(self.batch)}
 
 
 def _channels_last(predict):
@@ -32,12 +64,12 @@ def _labels(target, n_class):
 class LevelCriterion(nn.Module):
     """Weighted sum of the training losses of one decoder level on one prediction, one kernel pass.
 
-    spec: {name: weight}.  Every spec runs through ops.level_loss_chain, one autograd node of up to three stages.  The base stage
+    spec: {name: weight}.  Every spec runs through ops.level_loss_chain, one autograd node of up to four stages.  The base stage
     carries the names of the original family, {'CrossEntroLoss', 'BalanceDiceLoss', 'DiceClassLoss' (class 1), 'DiceClassLoss2' ..
     'DiceClassLoss7' (classes 2 .. 7, the reference's multi_criterions.DiceClassLoss(class_index)), 'DiceClassLoss0c' (class 0),
     'DiceClassLoss0' (foreground union 1 - class 0, multi_criterions.py:30-56)}: ltu_loss on predictions of up to 4 classes and
     ltu_loss_wide on 5 .. 8 (both csrc/loss.hip), or, with any name of `EXT`, ltu_loss_ext (csrc/loss_ext.hip), which also carries the
-    original terms but stops at 4 classes.  It is absent only from a spec made of boundary and top-k names alone.
+    original terms but stops at 4 classes.  It is absent only from a spec made of boundary, top-k and imbalance names alone.
     The boundary names 'BoundaryLoss' (class 1), 'BoundaryLoss2' .. 'BoundaryLoss7' and 'BoundaryLoss0c' (class 0) add Kervadec's
     boundary term w * mean(p_c * phi_c) on the signed distance maps of the label (ops.signed_distance_maps with `spacing`, or the
     `phi` given to forward: [B,K,...] in the order of `boundary_classes`) as the second stage (csrc/loss_boundary.hip; up to 8
@@ -46,6 +78,11 @@ class LevelCriterion(nn.Module):
     -log(max(p[label], 1e-6)) over the hardest `topk_fraction` of the voxels of the whole batch (up to 8 classes, or 4 beside a name
     of `EXT`); `topk_fraction_dev` (1-element fp32 device tensor) replaces the fraction at run time.  Voxels tied at the threshold
     share the remaining weight (see ops.level_loss_topk).  A spec without boundary and top-k names launches what it always launched.
+    The imbalance names add the fourth stage (csrc/loss_imbalance.hip; up to 8 classes, or 4 beside a name of `EXT`) with the
+    parameters of `imbalance` (an `Imbalance` record, None = its defaults): 'TverskyLoss' (class 1), 'TverskyLoss2' ..
+    'TverskyLoss7' and 'TverskyLoss0c' (class 0) are (1 - TI_c)^(1 / gamma) with TI the Tversky index of the class, per sample or
+    over the batch; 'FocalCELoss' is the mean of alpha[label] (1 - p[label])^gamma (-log max(p[label], 1e-6)) over all voxels
+    (see ops.level_loss_imbalance).  A spec without these names launches what it launched before, whatever `imbalance` holds.
     params: the parameters
     of the wider family (ops.LOSS_EXT_PARAMS: gamma, sigma, alpha, alpha2, eps; defaults ops.LOSS_EXT_DEFAULTS).  Returns
     (total, {name: w * value}) with values detached: what the reference scripts log (`criterions_w * l(...)`,
@@ -63,13 +100,17 @@ class LevelCriterion(nn.Module):
     BOUNDARY = {'BoundaryLoss': 1, 'BoundaryLoss2': 2, 'BoundaryLoss0c': 0, 'BoundaryLoss3': 3, 'BoundaryLoss4': 4, 'BoundaryLoss5': 5,
                 'BoundaryLoss6': 6, 'BoundaryLoss7': 7}      # boundary term (csrc/loss_boundary.hip) of class ...
     TOPK = 'TopKCELoss'     # top-k cross-entropy (csrc/loss_topk.hip)
+    TVERSKY = {'TverskyLoss': 1, 'TverskyLoss2': 2, 'TverskyLoss0c': 0, 'TverskyLoss3': 3, 'TverskyLoss4': 4, 'TverskyLoss5': 5,
+               'TverskyLoss6': 6, 'TverskyLoss7': 7}         # Tversky term (csrc/loss_imbalance.hip) of class ...
+    FOCALCE = 'FocalCELoss'     # focal cross-entropy (csrc/loss_imbalance.hip)
 
     def __init__(self, spec: dict, scale: float = 1.0, scale_dev=None, params=None, spacing=(1.0, 1.0, 1.0), term_scale_dev=None,
-                 topk_fraction: float = 0.1, topk_fraction_dev=None):
+                 topk_fraction: float = 0.1, topk_fraction_dev=None, imbalance=None):
         super().__init__()
         if 'DistributionLoss' in spec:
             raise KeyError(_DISTRIBUTION_REFUSED)
-        unknown = set(spec) - set(self._TERM) - set(self._DICE) - set(self.EXT) - set(self.BOUNDARY) - {self.TOPK}
+        unknown = (set(spec) - set(self._TERM) - set(self._DICE) - set(self.EXT) - set(self.BOUNDARY) - {self.TOPK} - set(self.TVERSKY)
+                   - {self.FOCALCE})
         if unknown:
             raise KeyError(f'no HIP kernel for losses {sorted(unknown)}')
         self.spec = dict(spec)
@@ -78,7 +119,13 @@ class LevelCriterion(nn.Module):
         self.params = dict(params or {})
         self.extended = any(name in self.EXT for name in self.spec)
         self.boundary = [name for name in self.spec if name in self.BOUNDARY]
-        self.base_names = [name for name in self.spec if name not in self.BOUNDARY and name != self.TOPK]      # what the base entry runs
+        self.tversky = [name for name in self.spec if name in self.TVERSKY]
+        self.focalce = self.FOCALCE in self.spec
+        if imbalance is not None and not isinstance(imbalance, Imbalance):
+            raise ValueError('imbalance: a losses.Imbalance record')
+        self.imbalance = imbalance      # parameters of the Tversky and focal cross-entropy names (None: the record's defaults)
+        self.base_names = [name for name in self.spec if name not in self.BOUNDARY and name != self.TOPK
+                           and name not in self.TVERSKY and name != self.FOCALCE]      # what the base entry runs
         self.spacing = tuple(float(v) for v in spacing)      # of the label's voxels (H, W, D): the maps' unit of length
         self.term_scale_dev = term_scale_dev      # 1-element fp32 device tensor: run-time factor of the boundary terms alone
         self.topk = self.TOPK in self.spec
@@ -104,6 +151,12 @@ class LevelCriterion(nn.Module):
             raise ValueError(f'{absent or self.boundary}: the boundary term of a class the prediction does not have ({C} classes)')
         if self.topk and C < 2:
             raise ValueError(f'{self.TOPK}: needs a prediction of at least 2 classes')
+        absent = [name for name in self.tversky if self.TVERSKY[name] >= C]
+        if absent or ((self.tversky or self.focalce) and C < 2):
+            raise ValueError(f'{absent or self.tversky or self.FOCALCE}: a term of a class the prediction does not have ({C} classes)')
+        fa = self.imbalance.focal_alpha if self.imbalance is not None else None
+        if self.focalce and fa is not None and len(fa) != C:
+            raise ValueError(f'{self.FOCALCE}: focal_alpha has {len(fa)} weights, the prediction has {C} classes')
 
     def dice_weights(self, C):
         """the Dice weights of the spec as the kernels take them: per class, then the foreground union - 5 entries for C <= 4
@@ -125,8 +178,8 @@ class LevelCriterion(nn.Module):
             raise ValueError(f'the level losses have kernels for C <= {ops.LOSS_WIDE_MAXC} classes, the prediction has {C}')
         p = _channels_last(predict)
         lab = _labels(target, C)
-        base = boundary = topk = None
-        if self.base_names or not (self.boundary or self.topk):
+        base = boundary = topk = imbalance = None
+        if self.base_names or not (self.boundary or self.topk or self.tversky or self.focalce):
             base = self._base_entry(C, dict(self.params, **(params or {})))
         if self.boundary:
             if phi is None:
@@ -136,11 +189,24 @@ class LevelCriterion(nn.Module):
             boundary = (phi, self.boundary_classes, [self.spec[name] * self.scale for name in self.boundary], self.term_scale_dev)
         if self.topk:
             topk = (self.spec[self.TOPK] * self.scale, self.topk_fraction, self.topk_fraction_dev)
-        total, base_values, boundary_values, topk_values = ops.level_loss_chain(p, lab, base, boundary, topk, self.scale_dev)
+        if self.tversky or self.focalce:
+            im = self.imbalance or Imbalance()
+            tversky = focal = None
+            if self.tversky:
+                tversky = ([self.TVERSKY[name] for name in self.tversky], [self.spec[name] * self.scale for name in self.tversky],
+                           im.tversky_params)
+            if self.focalce:
+                focal = (self.spec[self.FOCALCE] * self.scale, im.focal_gamma, im.focal_alpha)
+            imbalance = (tversky, focal)
+        total, base_values, boundary_values, topk_values, imbalance_values = ops.level_loss_chain(p, lab, base, boundary, topk,
+                                                                                                  self.scale_dev, imbalance)
         value = {name: base_values[self._value_index(name, C)] for name in self.base_names}
         value.update((name, boundary_values[k]) for k, name in enumerate(self.boundary))
         if self.topk:
             value[self.TOPK] = topk_values[0]
+        value.update((name, imbalance_values[k]) for k, name in enumerate(self.tversky))
+        if self.focalce:
+            value[self.FOCALCE] = imbalance_values[len(self.tversky)]
         return total, {name: value[name] if w == 1.0 else value[name] * w for name, w in self.spec.items()}
 
     def _term(self, name):
@@ -353,6 +419,40 @@ class TopKCELoss(nn.Module):
         return self.impl(predict, target)[0]
 
 
+def tversky_name(class_index: int) -> str:
+    """the spec name of the Tversky term of class `class_index`: 'TverskyLoss0c', 'TverskyLoss', 'TverskyLoss2' .. 'TverskyLoss7'"""
+    return _class_name('TverskyLoss', class_index)
+
+
+class TverskyLoss(nn.Module):
+    """Salehi et al., "Tversky loss function for image segmentation using 3D fully convolutional deep networks", and with gamma > 1
+    the focal Tversky loss of Abraham & Khan (no reference counterpart): (1 - TI)^(1 / gamma) of class `class_index`, TI = (I + eps)
+    / (I + alpha FP + beta FN + eps), per sample and averaged, or with `batch` on sums over the whole batch
+    (ops.level_loss_imbalance)"""
+
+    def __init__(self, class_index: int = 1, alpha: float = 0.3, beta: float = 0.7, gamma: float = 1.0, batch: bool = False):
+        super().__init__()
+        self.impl = LevelCriterion({tversky_name(class_index): 1.0},
+                                   imbalance=Imbalance(alpha=alpha, beta=beta, tversky_gamma=gamma, batch=batch))
+
+    def forward(self, predict, target):
+        return self.impl(predict, target)[0]
+
+
+class FocalCELoss(nn.Module):
+    """Focal cross-entropy on the label's channel at up to 8 classes (Lin et al.; no reference counterpart - the reference's
+    FocalLoss is the term of the wider family, which stops at 4 classes): the mean over all voxels of alpha[label] (1 - p[label])^gamma
+    (-log max(p[label], 1e-6)); gamma 0 or in [1, 5], 0 without alpha being the plain mean cross-entropy of nnU-Net and monai's
+    DiceCELoss (ops.level_loss_imbalance)"""
+
+    def __init__(self, gamma: float = 2.0, alpha=None):
+        super().__init__()
+        self.impl = LevelCriterion({'FocalCELoss': 1.0}, imbalance=Imbalance(focal_gamma=gamma, focal_alpha=alpha))
+
+    def forward(self, predict, target):
+        return self.impl(predict, target)[0]
+
+
 class _EvalMetric(nn.Module):
     """the evaluation losses train3D.py:143 requests besides the Dice losses (`eval_list`): computed on the un-thresholded class
     probabilities by the metric kernels of the inference driver (csrc/infer.hip); evaluation only, no gradient"""
@@ -411,6 +511,8 @@ Loss_Dict = {
     'ClassifyLoss': ClassifyLoss,
     'BoundaryLoss': BoundaryLoss,
     'TopKCELoss': TopKCELoss,
+    'TverskyLoss': TverskyLoss,
+    'FocalCELoss': FocalCELoss,
     'Recall': Recall,
     'Precision': Precision,
 }
@@ -419,7 +521,8 @@ Loss_Dict = {
 def get_criterions(name_list):
     """loss/criterions.py:773-782, and the training losses of loss/multi_criterions.py that a `--criterion_list` can name
     (BalanceDiceLoss2, CrossEntroLoss0, ClassifyLoss, DiceClassLoss0, DiceClassLoss2), and BoundaryLoss (class 1, unit spacing) and
-    TopKCELoss (k = 10 percent).  DistributionLoss is refused."""
+    TopKCELoss (k = 10 percent), and TverskyLoss (class 1, alpha 0.3, beta 0.7) and FocalCELoss (gamma 2).  DistributionLoss is
+    refused."""
     if 'DistributionLoss' in name_list:
         raise KeyError(_DISTRIBUTION_REFUSED)
     return {name: Loss_Dict[name]() for name in name_list}

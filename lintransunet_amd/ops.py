@@ -1741,18 +1741,81 @@ def _topk_bwd(topk, scratch, p, label, g, dp, written, scale_dev, B, S, C):
               B, S, C, _s())
 
 
+IMBALANCE_MAX_TERMS = 8     # most Tversky terms of one ltu_loss_imb_* call
+IMBALANCE_DEFAULTS = {'alpha': 0.3, 'beta': 0.7, 'gamma': 1.0, 'eps': 1e-5, 'batch': False}      # of the Tversky terms
+
+
+def imbalance_stage(tversky=None, focal=None, C=None):
+    """The arguments of the imbalance stage, checked on the host (ValueError) -> the `imbalance` of level_loss_chain.
+    tversky = (classes, weights, params): up to IMBALANCE_MAX_TERMS class ids with one weight each and {alpha, beta, gamma, eps,
+    batch} (missing keys: IMBALANCE_DEFAULTS) with alpha, beta >= 0, alpha + beta > 0, 1 <= gamma <= 3, eps > 0; focal = (weight,
+    gamma, alpha): gamma 0 or in [1, 5], alpha None or one finite weight >= 0 per class.  C: the class count, where known."""
+    if tversky is None and focal is None:
+        raise ValueError('imbalance stage: at least one of tversky and focal')
+    classes, weights, params = tversky if tversky is not None else ((), (), None)
+    unknown = set(params or {}) - set(IMBALANCE_DEFAULTS)
+    if unknown:
+        raise ValueError(f'imbalance stage: unknown Tversky parameters {sorted(unknown)}')
+    pr = dict(IMBALANCE_DEFAULTS, **(params or {}))
+    K = len(classes)
+    if len(weights) != K or K > IMBALANCE_MAX_TERMS or (tversky is not None and K < 1):
+        raise ValueError(f'imbalance stage: 1 .. {IMBALANCE_MAX_TERMS} Tversky classes, one weight each')
+    if any(int(c) < 0 or (C is not None and int(c) >= C) for c in classes):
+        raise ValueError(f'imbalance stage: Tversky classes {tuple(classes)} outside the {C} classes of the prediction')
+    alpha, beta, gamma, eps = (float(pr[k]) for k in ('alpha', 'beta', 'gamma', 'eps'))
+    if not all(math.isfinite(v) for v in (alpha, beta, gamma, eps, *[float(w) for w in weights])):
+        raise ValueError('imbalance stage: non-finite Tversky weight or parameter')
+    if alpha < 0.0 or beta < 0.0 or alpha + beta <= 0.0:
+        raise ValueError(f'imbalance stage: alpha {alpha}, beta {beta}: both >= 0 and not both 0')
+    if not 1.0 <= gamma <= 3.0:
+        raise ValueError(f'imbalance stage: Tversky gamma {gamma} outside [1, 3]')
+    if not eps > 0.0:
+        raise ValueError(f'imbalance stage: eps {eps} must be positive')
+    w_focal, gf, fa = focal if focal is not None else (0.0, 0.0, None)
+    w_focal, gf = float(w_focal), float(gf)
+    if not math.isfinite(w_focal) or not (gf == 0.0 or 1.0 <= gf <= 5.0):
+        raise ValueError(f'imbalance stage: focal gamma {gf} must be 0 or in [1, 5] (in (0, 1) the derivative at p = 1 is unbounded)')
+    if fa is not None:
+        fa = [float(a) for a in fa]
+        if (C is not None and len(fa) != C) or not all(math.isfinite(a) and a >= 0.0 for a in fa):
+            raise ValueError(f'imbalance stage: focal alpha needs one finite weight >= 0 for each of the {C} classes')
+        fa = (ctypes.c_float * len(fa))(*fa)
+    return (_int_array(classes), (ctypes.c_float * K)(*[float(w) for w in weights]), K,
+            (ctypes.c_float * 5)(alpha, beta, gamma, eps, 1.0 if pr['batch'] else 0.0), w_focal, gf, fa)
+
+
+def _imbalance_fwd(imb, p, label, before, scale_dev, B, S, C):
+    """imb = imbalance_stage(..) (csrc/loss_imbalance.hip).  Returns (buf = [total, Tversky values [K], focal value, total], coef):
+    buf[-1] repeats the total as the differentiable output, as in _base_fwd"""
+    cls, wv, K, params, w_focal, gf, fa = imb
+    need = _lib.load().ltu_loss_imb_ws_floats(B, S, C)
+    if need <= 0:
+        raise _lib.LtuError('ltu_loss_imb_ws_floats: 2 <= C <= 8 classes and B * C * 4 <= 256')
+    sums = torch.empty(need, device=p.device, dtype=torch.float32)      # partials + sums: no zero fill
+    buf = torch.empty(K + 3, device=p.device, dtype=torch.float32)
+    coef = torch.empty((B, C, 3), device=p.device, dtype=torch.float32)
+    _lib.call('ltu_loss_imb_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(buf), _p(coef), _p(before), cls, wv, K, params, w_focal, gf,
+              fa, _p(scale_dev), B, S, C, _s())
+    return buf, coef
+
+
+def _imbalance_bwd(imb, coef, p, label, g, dp, written, B, S, C):
+    _lib.call('ltu_loss_imb_bwd', _p(p), _p(label), _p(coef), _n(coef), imb[5], _p(g), _p(dp), written, B, S, C, _s())
+
+
 class _LevelLossChain(torch.autograd.Function):
     """The loss of one decoder level as a chain of optional stages (None = absent): `base`, then `boundary` on the maps `phi`, then
-    `topk`, each as its _*_fwd above takes it.  Each forward adds the total before it and each backward adds into the dp the one
-    before it wrote: no torch arithmetic and no copy joins them.  Returns (total, base report, boundary values [K], top-k values
-    [2] = (value, tau)), None for an absent stage: views of the stages' buffers, the reports detached."""
+    `topk`, then `imbalance`, each as its _*_fwd above takes it.  Each forward adds the total before it and each backward adds into
+    the dp the one before it wrote: no torch arithmetic and no copy joins them.  Returns (total, base report, boundary values [K],
+    top-k values [2] = (value, tau), imbalance values [K + 1] = (Tversky values .., focal value)), None for an absent stage: views
+    of the stages' buffers, the reports detached."""
 
     @staticmethod
-    def forward(ctx, p, label, phi, base, boundary, topk, scale_dev):
+    def forward(ctx, p, label, phi, base, boundary, topk, scale_dev, imbalance):
         B, C = p.shape[0], p.shape[-1]
         S = p.numel() // (B * C)
-        before = coef = scratch = None
-        reports = [None, None, None]
+        before = coef = scratch = icoef = None
+        reports = [None, None, None, None]
         if base is not None:
             before, coef = _base_fwd(base, p, label, scale_dev, B, S, C)
             reports[0] = before[:-1]
@@ -1762,9 +1825,12 @@ class _LevelLossChain(torch.autograd.Function):
         if topk is not None:
             before, scratch = _topk_fwd(topk, p, label, before, scale_dev, B, S, C)
             reports[2] = before[1:]
-        total = before[-1] if boundary is None and topk is None else before[0]      # of the last stage's buffer
-        ctx.stages, ctx.scale_dev = (base, boundary, topk), scale_dev
-        ctx.save_for_backward(p, label, phi, coef, scratch)
+        if imbalance is not None:
+            before, icoef = _imbalance_fwd(imbalance, p, label, before, scale_dev, B, S, C)
+            reports[3] = before[1:-1]
+        total = before[-1] if imbalance is not None or (boundary is None and topk is None) else before[0]      # of the last stage's buffer
+        ctx.stages, ctx.scale_dev = (base, boundary, topk, imbalance), scale_dev
+        ctx.save_for_backward(p, label, phi, coef, scratch, icoef)
         ctx.mark_non_differentiable(*(r for r in reports if r is not None))
         ctx.set_materialize_grads(False)         # no zero-filled gradient tensor for the report outputs
         return (total, *reports)
@@ -1772,9 +1838,9 @@ class _LevelLossChain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, *_reports):
         if g is None:
-            return (None,) * 7
-        p, label, phi, coef, scratch = ctx.saved_tensors
-        base, boundary, topk = ctx.stages
+            return (None,) * 8
+        p, label, phi, coef, scratch, icoef = ctx.saved_tensors
+        base, boundary, topk, imbalance = ctx.stages
         B, C = p.shape[0], p.shape[-1]
         S = p.numel() // (B * C)
         g = g.contiguous().to(torch.float32)
@@ -1788,19 +1854,30 @@ class _LevelLossChain(torch.autograd.Function):
             written = 1
         if topk is not None:
             _topk_bwd(topk, scratch, p, label, g, dp, written, ctx.scale_dev, B, S, C)
-        return (dp,) + (None,) * 6
+            written = 1
+        if imbalance is not None:
+            _imbalance_bwd(imbalance, icoef, p, label, g, dp, written, B, S, C)
+        return (dp,) + (None,) * 7
 
 
-def level_loss_chain(p, label, base=None, boundary=None, topk=None, scale_dev=None):
+def level_loss_chain(p, label, base=None, boundary=None, topk=None, scale_dev=None, imbalance=None):
     """p fp32 [B,...,C] channels-last probabilities, label uint8 [B,...]: the sum of the given stages, at least one, in one autograd
     node.  base = ('ltu_loss' | 'ltu_loss_wide', (w_ce, w_bal, w_dice)) or ('ltu_loss_ext', loss_ext_cfg(..)), as level_loss /
     level_loss_wide / level_loss_ext launch it; boundary = (phi, classes, weights, term_scale_dev), see level_loss_boundary; topk =
-    (weight, frac, frac_dev), see level_loss_topk.  scale_dev: optional 1-element fp32 device tensor multiplying all weights at run
-    time.  Returns (total, base values, boundary values, top-k values), None for a stage not given, values detached; every check
-    is made before the first launch and there is no host synchronisation."""
-    if base is None and boundary is None and topk is None:
-        raise ValueError('level_loss_chain: at least one of base, boundary and topk')
+    (weight, frac, frac_dev), see level_loss_topk; imbalance = (tversky, focal), see level_loss_imbalance, runs last.  scale_dev:
+    optional 1-element fp32 device tensor multiplying all weights at run time.  Returns (total, base values, boundary values, top-k
+    values, imbalance values), None for a stage not given, values detached; every check is made before the first launch and there
+    is no host synchronisation."""
+    if base is None and boundary is None and topk is None and imbalance is None:
+        raise ValueError('level_loss_chain: at least one of base, boundary, topk and imbalance')
     _chk(p, 'p'); _chk(label, 'label')
+    if imbalance is not None:
+        B, C = p.shape[0], p.shape[-1]
+        if not 2 <= C <= LOSS_WIDE_MAXC or B * C * 4 > 256:
+            raise ValueError(f'imbalance stage: 2 .. {LOSS_WIDE_MAXC} classes and batch * classes <= 64, got {B} x {C}')
+        if p.dtype != torch.float32 or label.dtype != torch.uint8:
+            raise ValueError('imbalance stage: p must be fp32 and label uint8')
+        imbalance = imbalance_stage(*imbalance, C=C)
     phi = None
     if boundary is not None:
         phi, classes, weights, term_scale_dev = boundary
@@ -1817,7 +1894,7 @@ def level_loss_chain(p, label, base=None, boundary=None, topk=None, scale_dev=No
             raise ValueError(f'level_loss_chain: frac {frac} outside (0, 1]')
         if frac_dev is not None and (frac_dev.dtype != torch.float32 or frac_dev.numel() != 1 or not frac_dev.is_cuda):
             raise ValueError('top-k loss: frac_dev must be a 1-element fp32 device tensor')
-    return _LevelLossChain.apply(p, label, phi, base, boundary, topk, scale_dev)
+    return _LevelLossChain.apply(p, label, phi, base, boundary, topk, scale_dev, imbalance)
 
 
 def level_loss(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
@@ -1900,5 +1977,21 @@ def level_loss_topk(p, label, weight, frac=0.1, frac_dev=None, base=None, scale_
         raise ValueError(f'level_loss_topk: frac {frac} outside (0, 1]')
     if boundary is not None and (len(boundary[1]) != len(boundary[2]) or not 1 <= len(boundary[1]) <= BOUNDARY_MAX_TERMS):
         raise ValueError(f'level_loss_topk: 1 .. {BOUNDARY_MAX_TERMS} boundary classes, one weight each')
-    total, base_values, bnd_values, values = level_loss_chain(p, label, base, boundary, (weight, frac, frac_dev), scale_dev)
+    total, base_values, bnd_values, values, _ = level_loss_chain(p, label, base, boundary, (weight, frac, frac_dev), scale_dev)
     return (total, base_values, values) if boundary is None else (total, base_values, values, bnd_values)
+
+
+def level_loss_imbalance(p, label, tversky=None, focal=None, base=None, scale_dev=None):
+    """p fp32 [B,...,C] channels-last probabilities (2 <= C <= 8, B * C <= 64), label uint8 [B,...]: the level's existing loss
+    `base` (as level_loss_boundary takes it, or None) plus scale_dev[0] * (sum_k weights[k] * value_k + weight * value_focal)
+    (csrc/loss_imbalance.hip).  tversky = (classes, weights, params): value_k = (1 - TI)^(1 / gamma) of class classes[k] with 1 - TI =
+    (alpha FP + beta FN) / (I + alpha FP + beta FN + eps) on I = sum p t, FP = sum p (1 - t), FN = sum t (1 - p), per sample and
+    averaged over the batch, or with params['batch'] on sums over the whole batch (nnU-Net's batch_dice); params: {alpha, beta,
+    gamma, eps, batch}, defaults IMBALANCE_DEFAULTS; where 1 - TI is exactly 0 and gamma > 1 that term's gradient is 0.  focal =
+    (weight, gamma, alpha): the mean over all B S voxels of alpha[label] (1 - p[label])^gamma (-log max(p[label], 1e-6)); gamma 0
+    or in [1, 5], alpha None (all 1) or one weight per class; gamma 0 without alpha is the plain mean cross-entropy (not evaluated, value 0, without `focal` or at weight 0).  Voxels with
+    label >= C belong to no class: they add to FP only, add 0 to the focal term and count in B S.  Two calls agree bit for bit.
+    Returns (total, base values or None, (Tversky values .., focal value)), values detached; every check is made before the first
+    launch and there is no host synchronisation."""
+    total, base_values, _, _, values = level_loss_chain(p, label, base, scale_dev=scale_dev, imbalance=(tversky, focal))
+    return total, base_values, values

@@ -88,7 +88,7 @@ def has_topk(specs):
 
 
 def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0, level_scale=None, pyr=None, spacing=(1.0, 1.0, 1.0),
-                          boundary_scale=None, phis=None, topk_fraction=0.1):
+                          boundary_scale=None, phis=None, topk_fraction=0.1, imbalance=None):
     """Per-level fused losses (utils/utils_3D_embed_full.py:66-82).  Returns (list of weighted level totals,
     list of {name: value}); `sum(totals)` is the reference's total_loss * scale.
     level_scale: optional fp32 device tensor [n_levels] that REPLACES `weights[lvl] * scale` at run time (a captured graph
@@ -97,21 +97,24 @@ def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0,
     tensor multiplying the boundary terms alone at run time (Kervadec's alpha schedule); phis: the levels' distance maps, already
     built (boundary_maps).  A spec list without boundary names uses none of the three.
     topk_fraction: the fraction of the hardest voxels that 'TopKCELoss' averages over, the same at every level: a number, or a
-    1-element fp32 device tensor read at run time."""
+    1-element fp32 device tensor read at run time.
+    imbalance: a losses.Imbalance record, the parameters of the 'TverskyLoss..' and 'FocalCELoss' names at every level (None: its
+    defaults)."""
     n = len(weights)
     specs = specs or level_specs(n)
     pyr = pyr or label_pyramid(label, n)      # pyr: the pyramid, already built (train_step builds it beside the encoder)
     if phis is None and has_boundary(specs):
         phis = boundary_maps(pyr, specs, spacing)
-    topk = {'topk_fraction_dev': topk_fraction} if torch.is_tensor(topk_fraction) else {'topk_fraction': topk_fraction}
+    kw = {'topk_fraction_dev': topk_fraction} if torch.is_tensor(topk_fraction) else {'topk_fraction': topk_fraction}
+    kw['imbalance'] = imbalance
     totals, named = [], []
     for lvl in range(n):
         pred = predict if lvl == 0 else masks[-lvl]
         if level_scale is not None:
             crit = LevelCriterion(specs[-lvl - 1], scale=1.0, scale_dev=level_scale[lvl:lvl + 1], term_scale_dev=boundary_scale,
-                                  **topk)
+                                  **kw)
         else:
-            crit = LevelCriterion(specs[-lvl - 1], scale=weights[lvl] * scale, term_scale_dev=boundary_scale, **topk)
+            crit = LevelCriterion(specs[-lvl - 1], scale=weights[lvl] * scale, term_scale_dev=boundary_scale, **kw)
         if crit.boundary:
             tot, vals = crit(pred, pyr[lvl].unsqueeze(1), phi=phis[lvl])
         else:
@@ -122,13 +125,13 @@ def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0,
 
 
 def train_step(model, images, labels, weights, step_times=1, specs=None, reducer=None, ctx=None, level_scale=None, reduce=True,
-               spacing=(1.0, 1.0, 1.0), boundary_scale=None, topk_fraction=0.1):
+               spacing=(1.0, 1.0, 1.0), boundary_scale=None, topk_fraction=0.1, imbalance=None):
     """forward + 5-level loss + backward for one batch of patches (one `j` of utils_3D_embed_full.py:55-86).
     Returns the list of weighted level losses (device scalars, no host sync).
     Gradient accumulation (utils_3D_embed_full.py:85-91): call `step_times` times with reduce=False except on the last
     micro-step; the caller zeroes the gradients before the first one.
     spacing, boundary_scale: see deep_supervision_loss; the distance maps of the levels with a boundary name are built behind the
-    label pyramid on the side stream.  topk_fraction: see deep_supervision_loss."""
+    label pyramid on the side stream.  topk_fraction, imbalance: see deep_supervision_loss."""
     lc = ctx or ops.current()
     with ops.use(lc):
         lc.begin_step(images.device)
@@ -144,7 +147,7 @@ def train_step(model, images, labels, weights, step_times=1, specs=None, reducer
         lc.side_join()
         totals, named = deep_supervision_loss(predict, masks, labels, weights, specs, scale=1.0 / step_times, level_scale=level_scale,
                                               pyr=pyr, spacing=spacing, boundary_scale=boundary_scale, phis=phis if boundary else None,
-                                              topk_fraction=topk_fraction)
+                                              topk_fraction=topk_fraction, imbalance=imbalance)
         if reducer is not None:
             reducer.prepare(lc, reduce=reduce)
         one = lc.one(images.device)
@@ -351,15 +354,18 @@ class GraphedStep:
     * per-epoch level weights (train3D.py:122-137) live in a device tensor read by the loss kernels: `set_weights(w)` updates
       it in place, no re-capture.  The factor of the boundary terms (specs with a 'BoundaryLoss..' name; `spacing` = millimetres of
       the patch's voxels) lives in another: `set_boundary_scale(a)`.  The fraction of 'TopKCELoss' (the same at all levels) lives in
-      a third: `set_topk_fraction(f)`, e.g. annealed from 1.0 (plain cross-entropy) down to 0.1.
+      a third: `set_topk_fraction(f)`, e.g. annealed from 1.0 (plain cross-entropy) down to 0.1.  The parameters of the
+      'TverskyLoss..' and 'FocalCELoss' names (`imbalance`, a losses.Imbalance record) are host arguments of their kernels and are
+      baked into the capture: there is no run-time setter for them; build a new step to change them.
     * every replay first checks that parameter and gradient storage is where it was at capture time (e.g. an optimizer built
       afterwards that re-homes `p.data`); if not, the step is captured again.
     * the step owns its `ops.Context` (scratch arena frozen after capture), so other graphs / eager steps cannot move it.
     """
 
     def __init__(self, model, images, labels, weights, reducer, step_times=1, specs=None, warmup=2, overlap=None,
-                 spacing=(1.0, 1.0, 1.0), boundary_scale=1.0, topk_fraction=0.1):
+                 spacing=(1.0, 1.0, 1.0), boundary_scale=1.0, topk_fraction=0.1, imbalance=None):
         self.model, self.reducer = model, reducer
+        self.imbalance = imbalance
         self.spacing = tuple(float(v) for v in spacing)
         self.step_times, self.specs, self.warmup = int(step_times), specs, warmup
         self.n_levels = len(weights)
@@ -435,7 +441,7 @@ class GraphedStep:
                               reducer=self.reducer, ctx=self.ctx, level_scale=self.level_scale,
                               reduce=reduce and self.overlap in ('graph', 'segments'), spacing=self.spacing,
                               boundary_scale=self.boundary_scale,
-                              topk_fraction=0.1 if self.topk_fraction is None else self.topk_fraction)
+                              topk_fraction=0.1 if self.topk_fraction is None else self.topk_fraction, imbalance=self.imbalance)
         finally:
             self.ctx.wq_install(None)
 
