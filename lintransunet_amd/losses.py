@@ -61,56 +61,66 @@ def _labels(target, n_class):
     return target.reshape(target.shape[0], *target.shape[2:]).to(torch.uint8).contiguous()
 
 
+def _class_name(stem, class_index):
+    if not 0 <= int(class_index) < ops.LOSS_WIDE_MAXC:
+        raise ValueError(f'{stem}: class_index {class_index} outside 0 .. {ops.LOSS_WIDE_MAXC - 1}')
+    return {0: stem + '0c', 1: stem}.get(int(class_index), f'{stem}{int(class_index)}')
+
+
+def _class_names(stem):
+    """{the spec name of `stem` for class c: c}, every class the kernels take"""
+    return {_class_name(stem, c): c for c in range(ops.LOSS_WIDE_MAXC)}
+
+
 class LevelCriterion(nn.Module):
     """Weighted sum of the training losses of one decoder level on one prediction, one kernel pass.
 
-    spec: {name: weight}.  Every spec runs through ops.level_loss_chain, one autograd node of up to four stages.  The base stage
-    carries the names of the original family, {'CrossEntroLoss', 'BalanceDiceLoss', 'DiceClassLoss' (class 1), 'DiceClassLoss2' ..
-    'DiceClassLoss7' (classes 2 .. 7, the reference's multi_criterions.DiceClassLoss(class_index)), 'DiceClassLoss0c' (class 0),
-    'DiceClassLoss0' (foreground union 1 - class 0, multi_criterions.py:30-56)}: ltu_loss on predictions of up to 4 classes and
-    ltu_loss_wide on 5 .. 8 (both csrc/loss.hip), or, with any name of `EXT`, ltu_loss_ext (csrc/loss_ext.hip), which also carries the
-    original terms but stops at 4 classes.  It is absent only from a spec made of boundary, top-k and imbalance names alone.
-    The boundary names 'BoundaryLoss' (class 1), 'BoundaryLoss2' .. 'BoundaryLoss7' and 'BoundaryLoss0c' (class 0) add Kervadec's
-    boundary term w * mean(p_c * phi_c) on the signed distance maps of the label (ops.signed_distance_maps with `spacing`, or the
-    `phi` given to forward: [B,K,...] in the order of `boundary_classes`) as the second stage (csrc/loss_boundary.hip; up to 8
-    classes, or 4 beside a name of `EXT`); `term_scale_dev` (1-element fp32 device tensor) scales the boundary terms alone at run
-    time.  'TopKCELoss' adds nnU-Net's top-k cross-entropy as the third stage (csrc/loss_topk.hip): the mean of
-    -log(max(p[label], 1e-6)) over the hardest `topk_fraction` of the voxels of the whole batch (up to 8 classes, or 4 beside a name
-    of `EXT`); `topk_fraction_dev` (1-element fp32 device tensor) replaces the fraction at run time.  Voxels tied at the threshold
-    share the remaining weight (see ops.level_loss_topk).  A spec without boundary and top-k names launches what it always launched.
-    The imbalance names add the fourth stage (csrc/loss_imbalance.hip; up to 8 classes, or 4 beside a name of `EXT`) with the
-    parameters of `imbalance` (an `Imbalance` record, None = its defaults): 'TverskyLoss' (class 1), 'TverskyLoss2' ..
-    'TverskyLoss7' and 'TverskyLoss0c' (class 0) are (1 - TI_c)^(1 / gamma) with TI the Tversky index of the class, per sample or
-    over the batch; 'FocalCELoss' is the mean of alpha[label] (1 - p[label])^gamma (-log max(p[label], 1e-6)) over all voxels
-    (see ops.level_loss_imbalance).  A spec without these names launches what it launched before, whatever `imbalance` holds.
-    params: the parameters
-    of the wider family (ops.LOSS_EXT_PARAMS: gamma, sigma, alpha, alpha2, eps; defaults ops.LOSS_EXT_DEFAULTS).  Returns
-    (total, {name: w * value}) with values detached: what the reference scripts log (`criterions_w * l(...)`,
+    spec: {name: weight}.  Every spec runs through ops.level_loss_chain, one autograd node with one stage for each row of `_STAGES`
+    that owns a name of the spec (`OWNED`); a stage without a name is not launched, whatever its parameters hold.  The stages take
+    up to 8 classes, or 4 beside a name of `EXT`:
+    base - the names of the original family, {'CrossEntroLoss', 'BalanceDiceLoss', 'DiceClassLoss' (class 1), 'DiceClassLoss2' ..
+      'DiceClassLoss7' (classes 2 .. 7, the reference's multi_criterions.DiceClassLoss(class_index)), 'DiceClassLoss0c' (class 0),
+      'DiceClassLoss0' (foreground union 1 - class 0, multi_criterions.py:30-56)}: ltu_loss on predictions of up to 4 classes and
+      ltu_loss_wide on 5 .. 8 (both csrc/loss.hip), or, with any name of `EXT`, ltu_loss_ext (csrc/loss_ext.hip), which also carries
+      the original terms; `params`: the parameters of the wider family (ops.LOSS_EXT_PARAMS: gamma, sigma, alpha, alpha2, eps;
+      defaults ops.LOSS_EXT_DEFAULTS).  A spec without any name runs it too, at weight 0.
+    boundary - 'BoundaryLoss' (class 1), 'BoundaryLoss2' .. 'BoundaryLoss7' and 'BoundaryLoss0c' (class 0): Kervadec's boundary term
+      w * mean(p_c * phi_c) on the signed distance maps of the label (ops.signed_distance_maps with `spacing`, or the `phi` given to
+      forward: [B,K,...] in the order of `boundary_classes`; csrc/loss_boundary.hip); `term_scale_dev` (1-element fp32 device
+      tensor) scales the boundary terms alone at run time.
+    topk - 'TopKCELoss': nnU-Net's top-k cross-entropy (csrc/loss_topk.hip), the mean of -log(max(p[label], 1e-6)) over the hardest
+      `topk_fraction` of the voxels of the whole batch; `topk_fraction_dev` (1-element fp32 device tensor) replaces the fraction at
+      run time.  Voxels tied at the threshold share the remaining weight (see ops.level_loss_topk).
+    imbalance - with the parameters of `imbalance` (an `Imbalance` record, None = its defaults; csrc/loss_imbalance.hip): 'TverskyLoss'
+      (class 1), 'TverskyLoss2' .. 'TverskyLoss7' and 'TverskyLoss0c' (class 0) are (1 - TI_c)^(1 / gamma) with TI the Tversky index
+      of the class, per sample or over the batch; 'FocalCELoss' is the mean of alpha[label] (1 - p[label])^gamma (-log max(p[label],
+      1e-6)) over all voxels (see ops.level_loss_imbalance).
+    Returns (total, {name: w * value}) with values detached: what the reference scripts log (`criterions_w * l(...)`,
     utils_3D_multi_class.py:85; all weights are 1 in the single-class script).
     """
     FG = 'fg'           # key of the foreground union in _DICE (every other value is a class index)
-    _DICE = {'DiceClassLoss': 1, 'DiceClassLoss2': 2, 'DiceClassLoss0c': 0, 'DiceClassLoss0': FG,
-             'DiceClassLoss3': 3, 'DiceClassLoss4': 4, 'DiceClassLoss5': 5, 'DiceClassLoss6': 6, 'DiceClassLoss7': 7}
+    _DICE = dict(_class_names('DiceClassLoss'), DiceClassLoss0=FG)
     # every name -> its term of the wider family (ops.LOSS_EXT_TERMS)
     _TERM = {'CrossEntroLoss': 'CE', 'BalanceDiceLoss': 'BAL', 'DiceClassLoss0c': 'DICE0', 'DiceClassLoss': 'DICE1',
              'DiceClassLoss2': 'DICE2', 'DiceClassLoss3': 'DICE3', 'DiceClassLoss0': 'FG'}
     EXT = {'DiceLoss': 'DICE', 'IOULoss': 'IOU', 'SSLoss': 'SS', 'FocalLoss': 'FOCAL', 'MSELoss': 'MSE', 'ContainLoss': 'CONTAIN',
            'ContainLoss2': 'CONTAIN2', 'BalanceDiceLoss2': 'BAL2', 'CrossEntroLoss0': 'CE0', 'ClassifyLoss': 'CLASSIFY'}
     EXT_MAXC = 4        # class limit of the wider family (csrc/loss_ext.hip)
-    BOUNDARY = {'BoundaryLoss': 1, 'BoundaryLoss2': 2, 'BoundaryLoss0c': 0, 'BoundaryLoss3': 3, 'BoundaryLoss4': 4, 'BoundaryLoss5': 5,
-                'BoundaryLoss6': 6, 'BoundaryLoss7': 7}      # boundary term (csrc/loss_boundary.hip) of class ...
+    BOUNDARY = _class_names('BoundaryLoss')     # boundary term (csrc/loss_boundary.hip) of class ...
     TOPK = 'TopKCELoss'     # top-k cross-entropy (csrc/loss_topk.hip)
-    TVERSKY = {'TverskyLoss': 1, 'TverskyLoss2': 2, 'TverskyLoss0c': 0, 'TverskyLoss3': 3, 'TverskyLoss4': 4, 'TverskyLoss5': 5,
-               'TverskyLoss6': 6, 'TverskyLoss7': 7}         # Tversky term (csrc/loss_imbalance.hip) of class ...
+    TVERSKY = _class_names('TverskyLoss')       # Tversky term (csrc/loss_imbalance.hip) of class ...
     FOCALCE = 'FocalCELoss'     # focal cross-entropy (csrc/loss_imbalance.hip)
+    # the names each stage of ops.level_loss_chain owns, in chain order, and the class a name stands for (None: no single class)
+    OWNED = {'base': dict(dict.fromkeys([*_TERM, *EXT]), **_class_names('DiceClassLoss')), 'boundary': BOUNDARY,
+             'topk': {TOPK: None}, 'imbalance': dict(TVERSKY, **{FOCALCE: None})}
 
     def __init__(self, spec: dict, scale: float = 1.0, scale_dev=None, params=None, spacing=(1.0, 1.0, 1.0), term_scale_dev=None,
                  topk_fraction: float = 0.1, topk_fraction_dev=None, imbalance=None):
         super().__init__()
         if 'DistributionLoss' in spec:
             raise KeyError(_DISTRIBUTION_REFUSED)
-        unknown = (set(spec) - set(self._TERM) - set(self._DICE) - set(self.EXT) - set(self.BOUNDARY) - {self.TOPK} - set(self.TVERSKY)
-                   - {self.FOCALCE})
+        self.names = stage_names(spec)
+        unknown = set(spec) - set().union(*self.names.values())
         if unknown:
             raise KeyError(f'no HIP kernel for losses {sorted(unknown)}')
         self.spec = dict(spec)
@@ -118,17 +128,14 @@ class LevelCriterion(nn.Module):
         self.scale_dev = scale_dev          # 1-element fp32 device tensor: run-time factor on top of `scale` (captured graphs)
         self.params = dict(params or {})
         self.extended = any(name in self.EXT for name in self.spec)
-        self.boundary = [name for name in self.spec if name in self.BOUNDARY]
-        self.tversky = [name for name in self.spec if name in self.TVERSKY]
-        self.focalce = self.FOCALCE in self.spec
+        self.base_names, self.boundary = self.names['base'], self.names['boundary']      # what the base entry runs; the boundary names
+        self.tversky = [name for name in self.names['imbalance'] if name != self.FOCALCE]
+        self.focalce, self.topk = self.FOCALCE in self.spec, self.TOPK in self.spec
         if imbalance is not None and not isinstance(imbalance, Imbalance):
             raise ValueError('imbalance: a losses.Imbalance record')
         self.imbalance = imbalance      # parameters of the Tversky and focal cross-entropy names (None: the record's defaults)
-        self.base_names = [name for name in self.spec if name not in self.BOUNDARY and name != self.TOPK
-                           and name not in self.TVERSKY and name != self.FOCALCE]      # what the base entry runs
         self.spacing = tuple(float(v) for v in spacing)      # of the label's voxels (H, W, D): the maps' unit of length
         self.term_scale_dev = term_scale_dev      # 1-element fp32 device tensor: run-time factor of the boundary terms alone
-        self.topk = self.TOPK in self.spec
         self.topk_fraction = float(topk_fraction)
         if self.topk and topk_fraction_dev is None and not 0.0 < self.topk_fraction <= 1.0:
             raise ValueError(f'topk_fraction {topk_fraction} outside (0, 1]')
@@ -140,20 +147,13 @@ class LevelCriterion(nn.Module):
         return tuple(self.BOUNDARY[name] for name in self.boundary)
 
     def _check_classes(self, C):
-        """the Dice names of the spec against the C classes of a prediction; raises before anything is launched.  (Up to 4 classes
+        """the names of the spec against the C classes of a prediction; raises before anything is launched.  (Up to 4 classes
         ltu_loss_fwd takes a weight for each of its 4 class slots and ignores those of absent classes, as it always did.)"""
-        first = C if self.extended or C > 4 else 4
-        absent = [name for name in self.spec if name in self._DICE and self._DICE[name] != self.FG and self._DICE[name] >= first]
-        if absent:
-            raise ValueError(f'{absent}: the Dice of a class the prediction does not have ({C} classes)')
-        absent = [name for name in self.boundary if self.BOUNDARY[name] >= C]
-        if absent or (self.boundary and C < 2):
-            raise ValueError(f'{absent or self.boundary}: the boundary term of a class the prediction does not have ({C} classes)')
-        if self.topk and C < 2:
-            raise ValueError(f'{self.TOPK}: needs a prediction of at least 2 classes')
-        absent = [name for name in self.tversky if self.TVERSKY[name] >= C]
-        if absent or ((self.tversky or self.focalce) and C < 2):
-            raise ValueError(f'{absent or self.tversky or self.FOCALCE}: a term of a class the prediction does not have ({C} classes)')
+        for key, what, _, _ in self._STAGES:
+            names, limit = self.names[key], C if key != 'base' or self.extended or C > 4 else 4
+            absent = [name for name in names if (self.OWNED[key][name] or 0) >= limit]
+            if absent or (names and key != 'base' and C < 2):
+                raise ValueError(f'{absent or names}: {what} ({C} classes)')
         fa = self.imbalance.focal_alpha if self.imbalance is not None else None
         if self.focalce and fa is not None and len(fa) != C:
             raise ValueError(f'{self.FOCALCE}: focal_alpha has {len(fa)} weights, the prediction has {C} classes')
@@ -178,35 +178,12 @@ class LevelCriterion(nn.Module):
             raise ValueError(f'the level losses have kernels for C <= {ops.LOSS_WIDE_MAXC} classes, the prediction has {C}')
         p = _channels_last(predict)
         lab = _labels(target, C)
-        base = boundary = topk = imbalance = None
-        if self.base_names or not (self.boundary or self.topk or self.tversky or self.focalce):
-            base = self._base_entry(C, dict(self.params, **(params or {})))
-        if self.boundary:
-            if phi is None:
-                if lab.dim() != 4:
-                    raise ValueError('the boundary term builds its distance maps from 3-D label patches [B,1,H,W,D]; pass `phi` otherwise')
-                phi = ops.signed_distance_maps(lab, self.boundary_classes, self.spacing)
-            boundary = (phi, self.boundary_classes, [self.spec[name] * self.scale for name in self.boundary], self.term_scale_dev)
-        if self.topk:
-            topk = (self.spec[self.TOPK] * self.scale, self.topk_fraction, self.topk_fraction_dev)
-        if self.tversky or self.focalce:
-            im = self.imbalance or Imbalance()
-            tversky = focal = None
-            if self.tversky:
-                tversky = ([self.TVERSKY[name] for name in self.tversky], [self.spec[name] * self.scale for name in self.tversky],
-                           im.tversky_params)
-            if self.focalce:
-                focal = (self.spec[self.FOCALCE] * self.scale, im.focal_gamma, im.focal_alpha)
-            imbalance = (tversky, focal)
-        total, base_values, boundary_values, topk_values, imbalance_values = ops.level_loss_chain(p, lab, base, boundary, topk,
-                                                                                                  self.scale_dev, imbalance)
-        value = {name: base_values[self._value_index(name, C)] for name in self.base_names}
-        value.update((name, boundary_values[k]) for k, name in enumerate(self.boundary))
-        if self.topk:
-            value[self.TOPK] = topk_values[0]
-        value.update((name, imbalance_values[k]) for k, name in enumerate(self.tversky))
-        if self.focalce:
-            value[self.FOCALCE] = imbalance_values[len(self.tversky)]
+        present = [key for key, names in self.names.items() if names] or ['base']      # no name at all: the base, at weight 0
+        args = {key: arg(self, C, lab, params, phi) for key, _, arg, _ in self._STAGES if key in present}
+        total, *reports = ops.level_loss_chain(p, lab, scale_dev=self.scale_dev, **args)
+        value = {}
+        for (key, _, _, entries), report in zip(self._STAGES, reports):
+            value.update(zip(self.names[key], (report[k] for k in entries(self, C))))
         return total, {name: value[name] if w == 1.0 else value[name] * w for name, w in self.spec.items()}
 
     def _term(self, name):
@@ -234,6 +211,42 @@ class LevelCriterion(nn.Module):
         cls = self._DICE[name]
         return 3 + ((4 if C <= 4 else C) if cls == self.FG else cls)
 
+    def _boundary_arg(self, C, lab, params, phi):
+        if phi is None:
+            if lab.dim() != 4:
+                raise ValueError('the boundary term builds its distance maps from 3-D label patches [B,1,H,W,D]; pass `phi` otherwise')
+            phi = ops.signed_distance_maps(lab, self.boundary_classes, self.spacing)
+        return phi, self.boundary_classes, [self.spec[name] * self.scale for name in self.boundary], self.term_scale_dev
+
+    def _imbalance_arg(self, C, lab, params, phi):
+        im = self.imbalance or Imbalance()
+        tversky = [self.TVERSKY[name] for name in self.tversky], [self.spec[name] * self.scale for name in self.tversky], im.tversky_params
+        focal = self.spec.get(self.FOCALCE, 0.0) * self.scale, im.focal_gamma, im.focal_alpha
+        return tversky if self.tversky else None, focal if self.focalce else None
+
+    # one row per stage of ops.level_loss_chain, in chain order: its keyword there, what the check of its names' classes says,
+    # (self, C, lab, params, phi) -> its argument, (self, C) -> where its report holds the value of each of its names
+    _STAGES = (('base', 'the Dice of a class the prediction does not have',
+                lambda self, C, lab, params, phi: self._base_entry(C, dict(self.params, **(params or {}))),
+                lambda self, C: [self._value_index(name, C) for name in self.base_names]),
+               ('boundary', 'the boundary term of a class the prediction does not have', _boundary_arg,
+                lambda self, C: range(len(self.boundary))),
+               ('topk', 'needs a prediction of at least 2 classes',
+                lambda self, C, lab, params, phi: (self.spec[self.TOPK] * self.scale, self.topk_fraction, self.topk_fraction_dev),
+                lambda self, C: [0]),
+               ('imbalance', 'a term of a class the prediction does not have', _imbalance_arg,
+                lambda self, C: [self.tversky.index(name) if name != self.FOCALCE else len(self.tversky) for name in self.names['imbalance']]))
+
+
+def stage_names(spec):
+    """{stage of ops.level_loss_chain: the names of `spec` that it owns, in spec order}, the stages in chain order"""
+    return {key: [name for name in spec if name in owned] for key, owned in LevelCriterion.OWNED.items()}
+
+
+def boundary_classes(spec):
+    """the classes of the boundary names of `spec`, in the order of the distance maps a LevelCriterion of it builds or takes"""
+    return tuple(LevelCriterion.BOUNDARY[name] for name in stage_names(spec)['boundary'])
+
 
 _DISTRIBUTION_REFUSED = ('no HIP kernel for DistributionLoss: the reference module (loss/criterions.py:119-176) raises a shape '
                          'error on ordinary inputs such as 2x2x8x6x4, so there is no behaviour to port')
@@ -253,12 +266,6 @@ class _Single(nn.Module):
 class CrossEntroLoss(_Single):
     """loss/criterions.py:696-735"""
     NAME = 'CrossEntroLoss'
-
-
-def _class_name(stem, class_index):
-    if not 0 <= int(class_index) < ops.LOSS_WIDE_MAXC:
-        raise ValueError(f'{stem}: class_index {class_index} outside 0 .. {ops.LOSS_WIDE_MAXC - 1}')
-    return {0: stem + '0c', 1: stem}.get(int(class_index), f'{stem}{int(class_index)}')
 
 
 def dice_class_name(class_index: int) -> str:

@@ -1677,187 +1677,217 @@ def _int_array(values):
     return (ctypes.c_int * len(values))(*[int(v) for v in values])
 
 
-# The stages of a level's loss, in the order they chain.  Every forward takes `before`, the buffer whose slot 0 holds the total of the
-# stages before it (None for the first), and returns its own buffer with the new total in slot 0; every backward but the base's
-# takes `written`: 0 writes dp, 1 adds into it.
+def _float_array(values):
+    return (ctypes.c_float * len(values))(*[float(v) for v in values])
 
-def _base_fwd(base, p, label, scale_dev, B, S, C):
+
+class _Stage:
+    """One stage of a level's loss.  The constructor takes the stage's argument as level_loss_chain documents it and the class
+    count C of the prediction, checks them and keeps the argument as the C-ABI takes it; check(p, label, phi) makes the checks that
+    need the tensors.  forward(p, label, phi, before, scale_dev, B, S, C) takes `before`, the buffer whose slot 0 holds the total
+    of the stages before it (None for the first), and returns (buf, the tensor its backward reads) with the new total in slot 0 of
+    buf.  backward(saved, p, label, g, dp, written, scale_dev, B, S, C) takes that tensor; written 0 writes dp, 1 adds into it.
+    `phi`, the distance maps of the chain, is read by the boundary stage alone."""
+    REPORT, TOTAL = slice(1, None), 0      # of buf: the view that is the detached report; the element the chain can return as the total
+
+    def check(self, p, label, phi):
+        pass
+
+    def report(self, buf):
+        return buf[self.REPORT]
+
+    def total(self, buf):
+        return buf[self.TOTAL]
+
+
+class _BaseStage(_Stage):
     """base = (entry, args): 'ltu_loss' (C <= 4) / 'ltu_loss_wide' (C <= 8) of csrc/loss.hip with args = (w_ce, w_bal, w_dice: 5 /
-    C + 1 weights), or 'ltu_loss_ext' of csrc/loss_ext.hip with args = loss_ext_cfg(..).  Always the first stage.  Returns (buf,
-    coef): buf[:-1] is the report [total, terms ..] and buf[-1] repeats the total as the differentiable output, so no copy kernel
-    is needed to separate the two"""
-    entry, args = base
-    ext = entry == 'ltu_loss_ext'
-    if ext:
-        nv, weights = len(LOSS_EXT_TERMS) + 2, (args,)
-    else:
-        w_ce, w_bal, w_dice = args
-        nv, weights = len(w_dice) + 4, (float(w_ce), float(w_bal), (ctypes.c_float * len(w_dice))(*w_dice))
-    sums = torch.empty(getattr(_lib.load(), entry + '_ws_floats')(B, S, C), device=p.device, dtype=torch.float32)      # partials + sums: no zero fill
-    buf = torch.empty(nv, device=p.device, dtype=torch.float32)
-    coef = torch.empty((B, C, 8 if ext else 3), device=p.device, dtype=torch.float32)
-    _lib.call(entry + '_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(buf), _p(coef), B, S, C, *weights, _p(scale_dev), _s())
-    return buf, coef
+    C + 1 weights), or 'ltu_loss_ext' of csrc/loss_ext.hip with args = loss_ext_cfg(..).  Always the first stage: it takes no
+    `before` and writes dp.  buf[:-1] is the report [total, terms ..] and buf[-1] repeats the total as the differentiable output,
+    so no copy kernel is needed to separate the two"""
+    REPORT, TOTAL = slice(None, -1), -1
+
+    def __init__(self, base, C):
+        self.entry, args = base
+        self.ext = self.entry == 'ltu_loss_ext'
+        if self.ext:
+            self.nv, self.weights, self.cfg = len(LOSS_EXT_TERMS) + 2, (args,), (args,)
+        else:
+            w_ce, w_bal, w_dice = args
+            if self.entry == 'ltu_loss_wide' and len(w_dice) != C + 1:
+                raise ValueError(f'level_loss_wide: w_dice has {len(w_dice)} entries, {C} classes need {C + 1} (per class, then the foreground union)')
+            self.nv, self.weights, self.cfg = len(w_dice) + 4, (float(w_ce), float(w_bal), _float_array(w_dice)), ()
+
+    def forward(self, p, label, phi, before, scale_dev, B, S, C):
+        sums = torch.empty(getattr(_lib.load(), self.entry + '_ws_floats')(B, S, C), device=p.device, dtype=torch.float32)      # partials + sums: no zero fill
+        buf = torch.empty(self.nv, device=p.device, dtype=torch.float32)
+        coef = torch.empty((B, C, 8 if self.ext else 3), device=p.device, dtype=torch.float32)
+        _lib.call(self.entry + '_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(buf), _p(coef), B, S, C, *self.weights, _p(scale_dev), _s())
+        return buf, coef
+
+    def backward(self, coef, p, label, g, dp, written, scale_dev, B, S, C):
+        _lib.call(self.entry + '_bwd', _p(p), _p(label), _p(coef), *self.cfg, _p(g), _p(dp), B, S, C, _s())
 
 
-def _base_bwd(base, coef, p, label, g, dp, B, S, C):
-    entry, args = base
-    cfg = (args,) if entry == 'ltu_loss_ext' else ()
-    _lib.call(entry + '_bwd', _p(p), _p(label), _p(coef), *cfg, _p(g), _p(dp), B, S, C, _s())
+class _BoundaryStage(_Stage):
+    """boundary = (phi, classes, weights, term_scale_dev), see level_loss_boundary; the maps phi [B,K,...] come from the chain
+    (csrc/loss_boundary.hip).  buf = [total, value_0 .. value_{K-1}]"""
+
+    def __init__(self, boundary, C):
+        _, classes, weights, self.term_scale_dev = boundary
+        self.K = len(classes)
+        if len(weights) != self.K or not 1 <= self.K <= BOUNDARY_MAX_TERMS:
+            raise ValueError(f'level_loss_chain: 1 .. {BOUNDARY_MAX_TERMS} boundary classes, one weight each')
+        self.cls, self.wv = _int_array(classes), _float_array(weights)
+
+    def check(self, p, label, phi):
+        _chk(phi, 'phi')
+        if phi.dtype != torch.float32 or phi.numel() * p.shape[-1] != self.K * p.numel():
+            raise ValueError(f'boundary loss: phi must be fp32 [B, {self.K}, ...] over the voxels of p')
+
+    def forward(self, p, label, phi, before, scale_dev, B, S, C):
+        need = _lib.load().ltu_loss_boundary_sums_floats(B, S, self.K)
+        sums = torch.empty((need + 1) // 2, device=p.device, dtype=torch.float64).view(torch.float32)      # doubles: 8-byte aligned, no zero fill
+        buf = torch.empty(self.K + 1, device=p.device, dtype=torch.float32)
+        _lib.call('ltu_loss_boundary_fwd', _p(p), _p(phi), self.cls, self.wv, self.K, _p(sums), _n(sums), _p(buf), _p(before),
+                  _p(scale_dev), _p(self.term_scale_dev), B, S, C, _s())
+        return buf, phi
+
+    def backward(self, phi, p, label, g, dp, written, scale_dev, B, S, C):
+        _lib.call('ltu_loss_boundary_bwd', _p(phi), self.cls, self.wv, self.K, _p(scale_dev), _p(self.term_scale_dev), _p(g), _p(dp),
+                  written, B, S, C, _s())
 
 
-def _boundary_fwd(boundary, p, phi, before, scale_dev, B, S, C):
-    """boundary = (classes int array, weights float array, K, term_scale_dev) on the maps phi [B,K,...] (csrc/loss_boundary.hip).
-    Returns buf = [total, value_0 .. value_{K-1}]"""
-    cls, wv, K, term_scale_dev = boundary
-    need = _lib.load().ltu_loss_boundary_sums_floats(B, S, K)
-    sums = torch.empty((need + 1) // 2, device=p.device, dtype=torch.float64).view(torch.float32)      # doubles: 8-byte aligned, no zero fill
-    buf = torch.empty(K + 1, device=p.device, dtype=torch.float32)
-    _lib.call('ltu_loss_boundary_fwd', _p(p), _p(phi), cls, wv, K, _p(sums), _n(sums), _p(buf), _p(before), _p(scale_dev),
-              _p(term_scale_dev), B, S, C, _s())
-    return buf
+class _TopkStage(_Stage):
+    """topk = (weight, frac, frac_dev), see level_loss_topk (csrc/loss_topk.hip).  buf = [total, value, tau]"""
 
+    def __init__(self, topk, C):
+        weight, frac, self.frac_dev = topk
+        self.weight, self.frac = float(weight), float(frac)
+        if self.frac_dev is None and not 0.0 < self.frac <= 1.0:
+            raise ValueError(f'level_loss_chain: frac {frac} outside (0, 1]')
+        if self.frac_dev is not None and (self.frac_dev.dtype != torch.float32 or self.frac_dev.numel() != 1 or not self.frac_dev.is_cuda):
+            raise ValueError('top-k loss: frac_dev must be a 1-element fp32 device tensor')
 
-def _boundary_bwd(boundary, phi, g, dp, written, scale_dev, B, S, C):
-    cls, wv, K, term_scale_dev = boundary
-    _lib.call('ltu_loss_boundary_bwd', _p(phi), cls, wv, K, _p(scale_dev), _p(term_scale_dev), _p(g), _p(dp), written, B, S, C, _s())
+    def forward(self, p, label, phi, before, scale_dev, B, S, C):
+        need = _lib.load().ltu_loss_topk_scratch_elems(B, S)
+        if need <= 0:
+            raise _lib.LtuError('ltu_loss_topk_scratch_elems: 2 <= C <= 8 classes and 1 .. 2^31 - 1 voxels in the batch')
+        scratch = torch.empty(need, device=p.device, dtype=torch.int32)      # histograms, record and the per-voxel losses: no fill
+        buf = torch.empty(3, device=p.device, dtype=torch.float32)
+        _lib.call('ltu_loss_topk_fwd', _p(p), _p(label), _p(scratch), _n(scratch), _p(buf), _p(before), self.weight, self.frac,
+                  _p(self.frac_dev), _p(scale_dev), B, S, C, _s())
+        return buf, scratch
 
-
-def _topk_fwd(topk, p, label, before, scale_dev, B, S, C):
-    """topk = (weight, frac, frac_dev) (csrc/loss_topk.hip).  Returns (buf = [total, value, tau], scratch)"""
-    weight, frac, frac_dev = topk
-    need = _lib.load().ltu_loss_topk_scratch_elems(B, S)
-    if need <= 0:
-        raise _lib.LtuError('ltu_loss_topk_scratch_elems: 2 <= C <= 8 classes and 1 .. 2^31 - 1 voxels in the batch')
-    scratch = torch.empty(need, device=p.device, dtype=torch.int32)      # histograms, record and the per-voxel losses: no fill
-    buf = torch.empty(3, device=p.device, dtype=torch.float32)
-    _lib.call('ltu_loss_topk_fwd', _p(p), _p(label), _p(scratch), _n(scratch), _p(buf), _p(before), float(weight), float(frac),
-              _p(frac_dev), _p(scale_dev), B, S, C, _s())
-    return buf, scratch
-
-
-def _topk_bwd(topk, scratch, p, label, g, dp, written, scale_dev, B, S, C):
-    _lib.call('ltu_loss_topk_bwd', _p(p), _p(label), _p(scratch), _n(scratch), float(topk[0]), _p(scale_dev), _p(g), _p(dp), written,
-              B, S, C, _s())
+    def backward(self, scratch, p, label, g, dp, written, scale_dev, B, S, C):
+        _lib.call('ltu_loss_topk_bwd', _p(p), _p(label), _p(scratch), _n(scratch), self.weight, _p(scale_dev), _p(g), _p(dp), written,
+                  B, S, C, _s())
 
 
 IMBALANCE_MAX_TERMS = 8     # most Tversky terms of one ltu_loss_imb_* call
 IMBALANCE_DEFAULTS = {'alpha': 0.3, 'beta': 0.7, 'gamma': 1.0, 'eps': 1e-5, 'batch': False}      # of the Tversky terms
 
 
+class _ImbalanceStage(_Stage):
+    """imbalance = (tversky, focal), see level_loss_imbalance and imbalance_stage (csrc/loss_imbalance.hip); every check raises
+    ValueError.  buf = [total, Tversky values [K], focal value, total]: buf[-1] repeats the total as the differentiable output, as
+    the base's does"""
+    REPORT, TOTAL = slice(1, -1), -1
+
+    def __init__(self, imbalance, C=None):
+        tversky, focal = imbalance
+        if tversky is None and focal is None:
+            raise ValueError('imbalance stage: at least one of tversky and focal')
+        classes, weights, params = tversky if tversky is not None else ((), (), None)
+        unknown = set(params or {}) - set(IMBALANCE_DEFAULTS)
+        if unknown:
+            raise ValueError(f'imbalance stage: unknown Tversky parameters {sorted(unknown)}')
+        pr = dict(IMBALANCE_DEFAULTS, **(params or {}))
+        self.K = len(classes)
+        if len(weights) != self.K or self.K > IMBALANCE_MAX_TERMS or (tversky is not None and self.K < 1):
+            raise ValueError(f'imbalance stage: 1 .. {IMBALANCE_MAX_TERMS} Tversky classes, one weight each')
+        if any(int(c) < 0 or (C is not None and int(c) >= C) for c in classes):
+            raise ValueError(f'imbalance stage: Tversky classes {tuple(classes)} outside the {C} classes of the prediction')
+        alpha, beta, gamma, eps = (float(pr[k]) for k in ('alpha', 'beta', 'gamma', 'eps'))
+        if not all(math.isfinite(v) for v in (alpha, beta, gamma, eps, *[float(w) for w in weights])):
+            raise ValueError('imbalance stage: non-finite Tversky weight or parameter')
+        if alpha < 0.0 or beta < 0.0 or alpha + beta <= 0.0:
+            raise ValueError(f'imbalance stage: alpha {alpha}, beta {beta}: both >= 0 and not both 0')
+        if not 1.0 <= gamma <= 3.0:
+            raise ValueError(f'imbalance stage: Tversky gamma {gamma} outside [1, 3]')
+        if not eps > 0.0:
+            raise ValueError(f'imbalance stage: eps {eps} must be positive')
+        w_focal, gf, fa = focal if focal is not None else (0.0, 0.0, None)
+        self.w_focal, self.gf = float(w_focal), float(gf)
+        if not math.isfinite(self.w_focal) or not (self.gf == 0.0 or 1.0 <= self.gf <= 5.0):
+            raise ValueError(f'imbalance stage: focal gamma {self.gf} must be 0 or in [1, 5] (in (0, 1) the derivative at p = 1 is unbounded)')
+        self.fa = None if fa is None else _float_array(fa)
+        if fa is not None and ((C is not None and len(fa) != C) or not all(math.isfinite(a) and a >= 0.0 for a in self.fa)):
+            raise ValueError(f'imbalance stage: focal alpha needs one finite weight >= 0 for each of the {C} classes')
+        self.cls, self.wv = _int_array(classes), _float_array(weights)
+        self.params = _float_array((alpha, beta, gamma, eps, 1.0 if pr['batch'] else 0.0))
+
+    def check(self, p, label, phi):
+        B, C = p.shape[0], p.shape[-1]
+        if not 2 <= C <= LOSS_WIDE_MAXC or B * C * 4 > 256:
+            raise ValueError(f'imbalance stage: 2 .. {LOSS_WIDE_MAXC} classes and batch * classes <= 64, got {B} x {C}')
+        if p.dtype != torch.float32 or label.dtype != torch.uint8:
+            raise ValueError('imbalance stage: p must be fp32 and label uint8')
+
+    def forward(self, p, label, phi, before, scale_dev, B, S, C):
+        need = _lib.load().ltu_loss_imb_ws_floats(B, S, C)
+        if need <= 0:
+            raise _lib.LtuError('ltu_loss_imb_ws_floats: 2 <= C <= 8 classes and B * C * 4 <= 256')
+        sums = torch.empty(need, device=p.device, dtype=torch.float32)      # partials + sums: no zero fill
+        buf = torch.empty(self.K + 3, device=p.device, dtype=torch.float32)
+        coef = torch.empty((B, C, 3), device=p.device, dtype=torch.float32)
+        _lib.call('ltu_loss_imb_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(buf), _p(coef), _p(before), self.cls, self.wv, self.K,
+                  self.params, self.w_focal, self.gf, self.fa, _p(scale_dev), B, S, C, _s())
+        return buf, coef
+
+    def backward(self, coef, p, label, g, dp, written, scale_dev, B, S, C):
+        _lib.call('ltu_loss_imb_bwd', _p(p), _p(label), _p(coef), _n(coef), self.gf, _p(g), _p(dp), written, B, S, C, _s())
+
+
 def imbalance_stage(tversky=None, focal=None, C=None):
-    """The arguments of the imbalance stage, checked on the host (ValueError) -> the `imbalance` of level_loss_chain.
+    """The arguments of the imbalance stage, checked on the host (ValueError) -> the stage as level_loss_chain runs it.
     tversky = (classes, weights, params): up to IMBALANCE_MAX_TERMS class ids with one weight each and {alpha, beta, gamma, eps,
     batch} (missing keys: IMBALANCE_DEFAULTS) with alpha, beta >= 0, alpha + beta > 0, 1 <= gamma <= 3, eps > 0; focal = (weight,
     gamma, alpha): gamma 0 or in [1, 5], alpha None or one finite weight >= 0 per class.  C: the class count, where known."""
-    if tversky is None and focal is None:
-        raise ValueError('imbalance stage: at least one of tversky and focal')
-    classes, weights, params = tversky if tversky is not None else ((), (), None)
-    unknown = set(params or {}) - set(IMBALANCE_DEFAULTS)
-    if unknown:
-        raise ValueError(f'imbalance stage: unknown Tversky parameters {sorted(unknown)}')
-    pr = dict(IMBALANCE_DEFAULTS, **(params or {}))
-    K = len(classes)
-    if len(weights) != K or K > IMBALANCE_MAX_TERMS or (tversky is not None and K < 1):
-        raise ValueError(f'imbalance stage: 1 .. {IMBALANCE_MAX_TERMS} Tversky classes, one weight each')
-    if any(int(c) < 0 or (C is not None and int(c) >= C) for c in classes):
-        raise ValueError(f'imbalance stage: Tversky classes {tuple(classes)} outside the {C} classes of the prediction')
-    alpha, beta, gamma, eps = (float(pr[k]) for k in ('alpha', 'beta', 'gamma', 'eps'))
-    if not all(math.isfinite(v) for v in (alpha, beta, gamma, eps, *[float(w) for w in weights])):
-        raise ValueError('imbalance stage: non-finite Tversky weight or parameter')
-    if alpha < 0.0 or beta < 0.0 or alpha + beta <= 0.0:
-        raise ValueError(f'imbalance stage: alpha {alpha}, beta {beta}: both >= 0 and not both 0')
-    if not 1.0 <= gamma <= 3.0:
-        raise ValueError(f'imbalance stage: Tversky gamma {gamma} outside [1, 3]')
-    if not eps > 0.0:
-        raise ValueError(f'imbalance stage: eps {eps} must be positive')
-    w_focal, gf, fa = focal if focal is not None else (0.0, 0.0, None)
-    w_focal, gf = float(w_focal), float(gf)
-    if not math.isfinite(w_focal) or not (gf == 0.0 or 1.0 <= gf <= 5.0):
-        raise ValueError(f'imbalance stage: focal gamma {gf} must be 0 or in [1, 5] (in (0, 1) the derivative at p = 1 is unbounded)')
-    if fa is not None:
-        fa = [float(a) for a in fa]
-        if (C is not None and len(fa) != C) or not all(math.isfinite(a) and a >= 0.0 for a in fa):
-            raise ValueError(f'imbalance stage: focal alpha needs one finite weight >= 0 for each of the {C} classes')
-        fa = (ctypes.c_float * len(fa))(*fa)
-    return (_int_array(classes), (ctypes.c_float * K)(*[float(w) for w in weights]), K,
-            (ctypes.c_float * 5)(alpha, beta, gamma, eps, 1.0 if pr['batch'] else 0.0), w_focal, gf, fa)
-
-
-def _imbalance_fwd(imb, p, label, before, scale_dev, B, S, C):
-    """imb = imbalance_stage(..) (csrc/loss_imbalance.hip).  Returns (buf = [total, Tversky values [K], focal value, total], coef):
-    buf[-1] repeats the total as the differentiable output, as in _base_fwd"""
-    cls, wv, K, params, w_focal, gf, fa = imb
-    need = _lib.load().ltu_loss_imb_ws_floats(B, S, C)
-    if need <= 0:
-        raise _lib.LtuError('ltu_loss_imb_ws_floats: 2 <= C <= 8 classes and B * C * 4 <= 256')
-    sums = torch.empty(need, device=p.device, dtype=torch.float32)      # partials + sums: no zero fill
-    buf = torch.empty(K + 3, device=p.device, dtype=torch.float32)
-    coef = torch.empty((B, C, 3), device=p.device, dtype=torch.float32)
-    _lib.call('ltu_loss_imb_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(buf), _p(coef), _p(before), cls, wv, K, params, w_focal, gf,
-              fa, _p(scale_dev), B, S, C, _s())
-    return buf, coef
-
-
-def _imbalance_bwd(imb, coef, p, label, g, dp, written, B, S, C):
-    _lib.call('ltu_loss_imb_bwd', _p(p), _p(label), _p(coef), _n(coef), imb[5], _p(g), _p(dp), written, B, S, C, _s())
+    return _ImbalanceStage((tversky, focal), C)
 
 
 class _LevelLossChain(torch.autograd.Function):
-    """The loss of one decoder level as a chain of optional stages (None = absent): `base`, then `boundary` on the maps `phi`, then
-    `topk`, then `imbalance`, each as its _*_fwd above takes it.  Each forward adds the total before it and each backward adds into
-    the dp the one before it wrote: no torch arithmetic and no copy joins them.  Returns (total, base report, boundary values [K],
-    top-k values [2] = (value, tau), imbalance values [K + 1] = (Tversky values .., focal value)), None for an absent stage: views
-    of the stages' buffers, the reports detached."""
+    """The loss of one decoder level as a chain of stages (objects of the classes above, in the order level_loss_chain gives them)
+    on the maps `phi` (None without a boundary stage).  Each forward adds the total before it and each backward adds into the dp
+    the one before it wrote: no torch arithmetic and no copy joins them.  Returns (total, the report of every stage ..): views of
+    the stages' buffers, the total that of the last stage, the reports detached."""
 
     @staticmethod
-    def forward(ctx, p, label, phi, base, boundary, topk, scale_dev, imbalance):
+    def forward(ctx, p, label, phi, scale_dev, stages):
         B, C = p.shape[0], p.shape[-1]
         S = p.numel() // (B * C)
-        before = coef = scratch = icoef = None
-        reports = [None, None, None, None]
-        if base is not None:
-            before, coef = _base_fwd(base, p, label, scale_dev, B, S, C)
-            reports[0] = before[:-1]
-        if boundary is not None:
-            before = _boundary_fwd(boundary, p, phi, before, scale_dev, B, S, C)
-            reports[1] = before[1:]
-        if topk is not None:
-            before, scratch = _topk_fwd(topk, p, label, before, scale_dev, B, S, C)
-            reports[2] = before[1:]
-        if imbalance is not None:
-            before, icoef = _imbalance_fwd(imbalance, p, label, before, scale_dev, B, S, C)
-            reports[3] = before[1:-1]
-        total = before[-1] if imbalance is not None or (boundary is None and topk is None) else before[0]      # of the last stage's buffer
-        ctx.stages, ctx.scale_dev = (base, boundary, topk, imbalance), scale_dev
-        ctx.save_for_backward(p, label, phi, coef, scratch, icoef)
-        ctx.mark_non_differentiable(*(r for r in reports if r is not None))
+        buf, reports, saved = None, [], []
+        for stage in stages:
+            buf, tensor = stage.forward(p, label, phi, buf, scale_dev, B, S, C)
+            reports.append(stage.report(buf))
+            saved.append(tensor)
+        ctx.stages, ctx.scale_dev, ctx.dims = stages, scale_dev, (B, S, C)
+        ctx.save_for_backward(p, label, *saved)
+        ctx.mark_non_differentiable(*reports)
         ctx.set_materialize_grads(False)         # no zero-filled gradient tensor for the report outputs
-        return (total, *reports)
+        return (stages[-1].total(buf), *reports)
 
     @staticmethod
     def backward(ctx, g, *_reports):
         if g is None:
-            return (None,) * 8
-        p, label, phi, coef, scratch, icoef = ctx.saved_tensors
-        base, boundary, topk, imbalance = ctx.stages
-        B, C = p.shape[0], p.shape[-1]
-        S = p.numel() // (B * C)
+            return (None,) * len(ctx.needs_input_grad)
+        p, label, *saved = ctx.saved_tensors
         g = g.contiguous().to(torch.float32)
         dp = torch.empty_like(p)
-        written = 0
-        if base is not None:
-            _base_bwd(base, coef, p, label, g, dp, B, S, C)
-            written = 1
-        if boundary is not None:
-            _boundary_bwd(boundary, phi, g, dp, written, ctx.scale_dev, B, S, C)
-            written = 1
-        if topk is not None:
-            _topk_bwd(topk, scratch, p, label, g, dp, written, ctx.scale_dev, B, S, C)
-            written = 1
-        if imbalance is not None:
-            _imbalance_bwd(imbalance, icoef, p, label, g, dp, written, B, S, C)
-        return (dp,) + (None,) * 7
+        for k, (stage, tensor) in enumerate(zip(ctx.stages, saved)):
+            stage.backward(tensor, p, label, g, dp, int(k > 0), ctx.scale_dev, *ctx.dims)
+        return (dp,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
 def level_loss_chain(p, label, base=None, boundary=None, topk=None, scale_dev=None, imbalance=None):
@@ -1868,33 +1898,16 @@ def level_loss_chain(p, label, base=None, boundary=None, topk=None, scale_dev=No
     optional 1-element fp32 device tensor multiplying all weights at run time.  Returns (total, base values, boundary values, top-k
     values, imbalance values), None for a stage not given, values detached; every check is made before the first launch and there
     is no host synchronisation."""
-    if base is None and boundary is None and topk is None and imbalance is None:
+    phi, *_ = boundary or [None]      # the maps travel beside the stages: the chain saves them for the backward
+    args = {_BaseStage: base, _BoundaryStage: boundary, _TopkStage: topk, _ImbalanceStage: imbalance}      # in chain order
+    if all(arg is None for arg in args.values()):
         raise ValueError('level_loss_chain: at least one of base, boundary, topk and imbalance')
     _chk(p, 'p'); _chk(label, 'label')
-    if imbalance is not None:
-        B, C = p.shape[0], p.shape[-1]
-        if not 2 <= C <= LOSS_WIDE_MAXC or B * C * 4 > 256:
-            raise ValueError(f'imbalance stage: 2 .. {LOSS_WIDE_MAXC} classes and batch * classes <= 64, got {B} x {C}')
-        if p.dtype != torch.float32 or label.dtype != torch.uint8:
-            raise ValueError('imbalance stage: p must be fp32 and label uint8')
-        imbalance = imbalance_stage(*imbalance, C=C)
-    phi = None
-    if boundary is not None:
-        phi, classes, weights, term_scale_dev = boundary
-        K = len(classes)
-        if len(weights) != K or not 1 <= K <= BOUNDARY_MAX_TERMS:
-            raise ValueError(f'level_loss_chain: 1 .. {BOUNDARY_MAX_TERMS} boundary classes, one weight each')
-        _chk(phi, 'phi')
-        if phi.dtype != torch.float32 or phi.numel() * p.shape[-1] != K * p.numel():
-            raise ValueError(f'boundary loss: phi must be fp32 [B, {K}, ...] over the voxels of p')
-        boundary = (_int_array(classes), (ctypes.c_float * K)(*[float(w) for w in weights]), K, term_scale_dev)
-    if topk is not None:
-        _, frac, frac_dev = topk
-        if frac_dev is None and not 0.0 < float(frac) <= 1.0:
-            raise ValueError(f'level_loss_chain: frac {frac} outside (0, 1]')
-        if frac_dev is not None and (frac_dev.dtype != torch.float32 or frac_dev.numel() != 1 or not frac_dev.is_cuda):
-            raise ValueError('top-k loss: frac_dev must be a 1-element fp32 device tensor')
-    return _LevelLossChain.apply(p, label, phi, base, boundary, topk, scale_dev, imbalance)
+    stages = [stage(arg, p.shape[-1]) for stage, arg in args.items() if arg is not None]
+    for stage in stages:
+        stage.check(p, label, phi)
+    out = iter(_LevelLossChain.apply(p, label, phi, scale_dev, stages))
+    return (next(out), *(None if arg is None else next(out) for arg in args.values()))
 
 
 def level_loss(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
@@ -1908,9 +1921,6 @@ def level_loss(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
 def level_loss_wide(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
     """level_loss for 2 <= C <= 8 classes: w_dice has C + 1 entries (the Dice weight of every class, then that of the foreground
     union); values = [total, CE, balanced Dice, Dice_0 .. Dice_{C-1}, union Dice] (detached)."""
-    C = p.shape[-1]
-    if len(w_dice) != C + 1:
-        raise ValueError(f'level_loss_wide: w_dice has {len(w_dice)} entries, {C} classes need {C + 1} (per class, then the foreground union)')
     return level_loss_chain(p, label, ('ltu_loss_wide', (w_ce, w_bal, tuple(float(w) for w in w_dice))), scale_dev=scale_dev)[:2]
 
 
@@ -1948,8 +1958,6 @@ def level_loss_boundary(p, label, phi, classes, weights, base=None, scale_dev=No
     mean over (b, s) of p[b, s, classes[k]] * phi[b, k, s] and scale = scale_dev[0] * term_scale_dev[0] (1-element fp32 device
     tensors read at run time, None = 1).  Returns (total, base values or None, boundary values [K]), values detached; no host
     synchronisation."""
-    if len(classes) != len(weights) or not 1 <= len(classes) <= BOUNDARY_MAX_TERMS:
-        raise ValueError(f'level_loss_boundary: 1 .. {BOUNDARY_MAX_TERMS} classes, one weight each')
     return level_loss_chain(p, label, base, (phi, classes, weights, term_scale_dev), scale_dev=scale_dev)[:3]
 
 
@@ -1973,10 +1981,6 @@ def level_loss_topk(p, label, weight, frac=0.1, frac_dev=None, base=None, scale_
     Returns (total, base values or None, (value, tau)), values detached; no host synchronisation.
     boundary = (phi, classes, weights, term_scale_dev) puts the boundary terms of level_loss_boundary between the two; their values
     are then returned as a fourth entry."""
-    if frac_dev is None and not 0.0 < float(frac) <= 1.0:
-        raise ValueError(f'level_loss_topk: frac {frac} outside (0, 1]')
-    if boundary is not None and (len(boundary[1]) != len(boundary[2]) or not 1 <= len(boundary[1]) <= BOUNDARY_MAX_TERMS):
-        raise ValueError(f'level_loss_topk: 1 .. {BOUNDARY_MAX_TERMS} boundary classes, one weight each')
     total, base_values, bnd_values, values, _ = level_loss_chain(p, label, base, boundary, (weight, frac, frac_dev), scale_dev)
     return (total, base_values, values) if boundary is None else (total, base_values, values, bnd_values)
 

@@ -15,7 +15,7 @@ import torch.distributed as dist
 
 from . import comm as _comm
 from . import ops
-from .losses import LevelCriterion
+from .losses import LevelCriterion, boundary_classes, stage_names
 
 
 def get_weight(t, T, default_weight=0.2, initial_weight=1.0, final_weight=1.0):
@@ -63,28 +63,24 @@ def label_pyramid(label, n_levels=5):
 
 
 def boundary_maps(pyr, specs, spacing=(1.0, 1.0, 1.0)):
-    """signed distance maps for the levels whose spec has a boundary name (losses.LevelCriterion.BOUNDARY), from the pyramid's
+    """signed distance maps for the levels whose spec has a boundary name (losses.boundary_classes), from the pyramid's
     labels: a list over levels of fp32 [B,K,h,w,d] or None.  The voxels of level l are `spacing` * (H_0 / H_l, W_0 / W_l,
     D_0 / D_l) apart."""
-    n = len(pyr)
     full = pyr[0].shape[1:]
     phis = []
-    for lvl in range(n):
-        classes = LevelCriterion(specs[-lvl - 1]).boundary_classes
-        if not classes:
-            phis.append(None)
-            continue
+    for lvl in range(len(pyr)):
+        classes = boundary_classes(specs[-lvl - 1])
         sp = tuple(float(s) * f / c for s, f, c in zip(spacing, full, pyr[lvl].shape[1:]))
-        phis.append(ops.signed_distance_maps(pyr[lvl], classes, sp))
+        phis.append(ops.signed_distance_maps(pyr[lvl], classes, sp) if classes else None)
     return phis
 
 
 def has_boundary(specs):
-    return any(name in LevelCriterion.BOUNDARY for spec in specs for name in spec)
+    return any(stage_names(spec)['boundary'] for spec in specs)
 
 
 def has_topk(specs):
-    return any(LevelCriterion.TOPK in spec for spec in specs)
+    return any(stage_names(spec)['topk'] for spec in specs)
 
 
 def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0, level_scale=None, pyr=None, spacing=(1.0, 1.0, 1.0),
@@ -103,22 +99,16 @@ def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0,
     n = len(weights)
     specs = specs or level_specs(n)
     pyr = pyr or label_pyramid(label, n)      # pyr: the pyramid, already built (train_step builds it beside the encoder)
-    if phis is None and has_boundary(specs):
-        phis = boundary_maps(pyr, specs, spacing)
+    if phis is None:
+        phis = boundary_maps(pyr, specs, spacing)      # None at the levels without a boundary name: nothing is launched for them
     kw = {'topk_fraction_dev': topk_fraction} if torch.is_tensor(topk_fraction) else {'topk_fraction': topk_fraction}
-    kw['imbalance'] = imbalance
     totals, named = [], []
     for lvl in range(n):
         pred = predict if lvl == 0 else masks[-lvl]
-        if level_scale is not None:
-            crit = LevelCriterion(specs[-lvl - 1], scale=1.0, scale_dev=level_scale[lvl:lvl + 1], term_scale_dev=boundary_scale,
-                                  **kw)
-        else:
-            crit = LevelCriterion(specs[-lvl - 1], scale=weights[lvl] * scale, term_scale_dev=boundary_scale, **kw)
-        if crit.boundary:
-            tot, vals = crit(pred, pyr[lvl].unsqueeze(1), phi=phis[lvl])
-        else:
-            tot, vals = crit(pred, pyr[lvl].unsqueeze(1))
+        crit = LevelCriterion(specs[-lvl - 1], scale=weights[lvl] * scale if level_scale is None else 1.0,
+                              scale_dev=None if level_scale is None else level_scale[lvl:lvl + 1], term_scale_dev=boundary_scale,
+                              imbalance=imbalance, **kw)
+        tot, vals = crit(pred, pyr[lvl].unsqueeze(1), phi=phis[lvl])
         totals.append(tot)
         named.append(vals)
     return totals, named
@@ -136,17 +126,15 @@ def train_step(model, images, labels, weights, step_times=1, specs=None, reducer
     with ops.use(lc):
         lc.begin_step(images.device)
         pyr, phis = [], []
-        boundary = specs is not None and has_boundary(specs)
 
         def side():
             pyr.extend(label_pyramid(labels, len(weights)))
-            if boundary:
-                phis.extend(boundary_maps(pyr, specs, spacing))
+            phis.extend(boundary_maps(pyr, specs or level_specs(len(weights)), spacing))
         lc.side_run(side)                    # beside the encoder (joined inside the model's forward)
         predict, masks = model(images)
         lc.side_join()
         totals, named = deep_supervision_loss(predict, masks, labels, weights, specs, scale=1.0 / step_times, level_scale=level_scale,
-                                              pyr=pyr, spacing=spacing, boundary_scale=boundary_scale, phis=phis if boundary else None,
+                                              pyr=pyr, spacing=spacing, boundary_scale=boundary_scale, phis=phis,
                                               topk_fraction=topk_fraction, imbalance=imbalance)
         if reducer is not None:
             reducer.prepare(lc, reduce=reduce)

@@ -1,6 +1,7 @@
-"""ops.level_loss_chain on the GPU: every combination of two or three stages (base of each loss family, boundary, top-k) against
-the same stages run alone - total and gradient to one joined fp32 add, every report bit for bit - on a shape the four-voxel
-kernels take and one the scalar kernels take (S % 4 != 0).  Inputs are those of tests/topk_common.py."""
+"""ops.level_loss_chain on the GPU: combinations of two to four stages (base of each loss family, boundary, top-k, imbalance), and
+the imbalance stage alone, against the same stages run alone - total and gradient to one joined fp32 add, every report bit for
+bit - on a shape the four-voxel kernels take and one the scalar kernels take (S % 4 != 0).  Inputs are those of
+tests/topk_common.py."""
 import functools
 
 import pytest
@@ -15,8 +16,11 @@ SHAPES = [(2, (12, 10, 8)), (1, (9, 7, 5))]
 # classes of the prediction.  4 for ltu_loss: it writes the Dice slot of every class the prediction has and leaves the slots of absent
 # classes of its 4-class report unwritten, so only there is the whole report defined
 FAMILIES = {'orig': 4, 'wide': 5, 'ext': 3}
-STAGES = ('base', 'boundary', 'topk')
-COMBOS = [(f, s) for f in FAMILIES for s in (('base', 'boundary'), ('base', 'topk'), STAGES)] + [('orig', ('boundary', 'topk'))]
+STAGES = ('base', 'boundary', 'topk', 'imbalance')
+COMBOS = [(f, s) for f in FAMILIES for s in (('base', 'boundary'), ('base', 'topk'), STAGES[:3])] + [('orig', ('boundary', 'topk'))]
+# appended, so that the cases above keep their ids: the imbalance stage behind each base, behind all stages, without a base, and alone
+COMBOS += [(f, s) for f in FAMILIES for s in (('base', 'imbalance'), STAGES)]
+COMBOS += [('orig', s) for s in (('boundary', 'imbalance'), ('topk', 'imbalance'), ('imbalance',))]
 
 
 @functools.lru_cache(maxsize=None)
@@ -34,6 +38,8 @@ def _stage(family, name, phi):
         return (phi, (1, 2), (0.05, 0.02), None)
     if name == 'topk':
         return (0.7, 0.2, None)
+    if name == 'imbalance':      # a focal Tversky term of classes 1 and 2, which every family's prediction has, and a focal cross-entropy
+        return (((1, 2), (0.6, 0.4), {'gamma': 4.0 / 3.0}), (0.5, 2.0, None))
     if family == 'ext':
         return ('ltu_loss_ext', ops.loss_ext_cfg({'CE': 1.0, 'FOCAL': 1.0, 'DICE': 0.5}))
     wd = (0.0, 1.0, 1.0, 0.5, 0.5) if family == 'orig' else (0.0, 1.0, 1.0, 0.0, 1.0, 0.5)
@@ -41,7 +47,7 @@ def _stage(family, name, phi):
 
 
 def _run(family, stages, B, spatial):
-    """-> (total, gradient, reports of the three stages) of the chain of `stages`"""
+    """-> (total, gradient, reports of the four stages) of the chain of `stages`"""
     from lintransunet_amd import ops
     p, lab, phi = _inputs(B, spatial, FAMILIES[family])
     pg = p.clone().requires_grad_(True)
@@ -67,6 +73,8 @@ def test_chain_is_the_sum_of_its_stages(family, stages, B, spatial):
             want = alone[stages.index(name)][2][k]
             assert not reports[k].requires_grad and torch.equal(reports[k], want), name
     want = sum(t.item() for t, _, _ in alone)
+    # the boundary term is signed: the relative bound below means something only if the stages' totals do not cancel
+    assert abs(want) >= 0.5 * sum(abs(t.item()) for t, _, _ in alone)
     gsum = sum(g.double() for _, g, _ in alone)
     eg = (grad.double() - gsum).abs().max().item() / gsum.abs().max().item()
     print(f'{family} {"+".join(stages)} B={B} {spatial}: total {total.item():.8f} separate {want:.8f}, gradient max |diff| / max {eg:.2e}')
