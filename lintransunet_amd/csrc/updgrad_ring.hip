@@ -50,7 +50,10 @@ __global__ void __launch_bounds__(256) updgrad_ring_bf16_kernel(const UpDgradArg
     const int hd = hv % 9, hw = (hv / 9) % 9, hh = hv / 81;
     const int fh = 2 * (h0 + hh), fw = 2 * (w0 + hw), fd = 2 * (d0 + hd);
     const int lc = (lane & 3) ^ (hw & 3);
-    hoffs[s] = hv < 405 ? ((((long long)b * Hf + fh) * Wf + fw) * Df + fd) * a.Co + lc * 8 : -1;
+    // a row past 2 H or 2 W serves no class (class p reads one voxel back at most): padding too.  The last brick's halo reaches
+    // 8 cdiv(H, 4) and 16 cdiv(W, 8) - 1024 from H = 509, W = 505 on, one bit more than the 10-bit fields below hold
+    const bool row = hv < 405 && fh <= Hf && fw <= Wf;
+    hoffs[s] = row ? ((((long long)b * Hf + fh) * Wf + fw) * Df + fd) * a.Co + lc * 8 : -1;
     hfc[s] = fh | (fw << 10) | (fd << 20);
   }
   auto issue_halo = [&](int chunk, auto PP) {

@@ -387,12 +387,20 @@ def test_every_row_is_needed():
         assert only, f'{c.name}: every kernel / obligation it covers is covered by another case too'
 
 
+def csrc_text():
+    return ''.join(open(p).read() for p in sorted(glob.glob(os.path.join(CSRC, '*.hip'))))
+
+
+def is_global(fn, src):
+    """a __global__ void fn( is defined in src"""
+    return re.search(r'__global__\s+void\s+(?:__launch_bounds__\([^()]*(?:\([^()]*\))?[^()]*\)\s+)?' + re.escape(fn) + r'\s*\(', src)
+
+
 def test_named_kernels_exist_in_sources():
-    src = ''.join(open(p).read() for p in sorted(glob.glob(os.path.join(CSRC, '*.hip'))))
+    src = csrc_text()
     for k in sorted(named_kernels() | set(NOT_CONV)):
         fn = k.split('<')[0]
-        assert re.search(r'__global__\s+void\s+(?:__launch_bounds__\([^()]*(?:\([^()]*\))?[^()]*\)\s+)?' + re.escape(fn) + r'\s*\(', src), \
-            f'{k}: no __global__ {fn} in lintransunet_amd/csrc'
+        assert is_global(fn, src), f'{k}: no __global__ {fn} in lintransunet_amd/csrc'
 
 
 def test_steady_state_geometry():
@@ -475,12 +483,13 @@ def _upconv_classes(x, weff, b):
 _REF = {}
 
 
-def reference(case):
-    """operands (bf16-exact, float64, channels-first) and the float64 CPU reference of one case, cached per case"""
+def reference(case, seed=None):
+    """operands (bf16-exact, float64, channels-first) and the float64 CPU reference of one case, cached per case; seed: of the
+    operands (default: from the case's name)"""
     if case.name in _REF:
         return _REF[case.name]
     s = case.shape
-    g = _gen(sum(map(ord, case.name)))
+    g = _gen(sum(map(ord, case.name)) if seed is None else seed)
     B, H, W, D = s['B'], s['H'], s['W'], s['D']
     r = {}
     if case.op == 'conv3d':
@@ -561,12 +570,15 @@ def check_f32(what, got, ref):
     return err / WGRAD_TOL
 
 
-def run_case(case):
-    """runs one case on the GPU; returns {'seen': {'fwd', 'bwd'}, 'ratio': {output: worst error / bound}}; raises on a bound"""
+def run_case(case, witness=True, backward=True, seed=None):
+    """runs one case on the GPU; returns {'seen': {'fwd', 'bwd'}, 'ratio': {output: worst error / bound}, 'fails': [...]}.
+    witness = False skips the profiler windows (seen stays empty); backward = False runs and checks the forward alone"""
     from lintransunet_amd import ops
-    r = reference(case)
+    r = reference(case, seed)
     s = case.shape
     seen, ratios, fails = {}, {}, []
+
+    window = launched if witness else (lambda fn: (fn(), set()))
 
     class _Ratio(dict):
         def __setitem__(self, k, thunk):
@@ -583,32 +595,35 @@ def run_case(case):
             x1 = _cl(r['x1']).requires_grad_(True) if r['x1'] is not None else None
             w = r['w'].float().to(DEV).requires_grad_(True)
             b = r['b'].float().to(DEV).requires_grad_(True)
-            y, seen['fwd'] = launched(lambda: ops.conv3d(x0, w, b, stride=s['stride'], x1=x1, cop=cop))
+            y, seen['fwd'] = window(lambda: ops.conv3d(x0, w, b, stride=s['stride'], x1=x1, cop=cop))
             go = _cl(r['go'])
             if cop:
                 assert y.shape[-1] == cop
                 pad = torch.zeros(y.shape, device=DEV, dtype=torch.bfloat16)
                 pad[..., :s['Co']] = go
                 go = pad
-                assert y[..., s['Co']:].float().abs().max().item() == 0.0, 'padded head columns must be exactly 0'
-            _, seen['bwd'] = launched(lambda: (y.backward(go), ops.flush_deferred()))
+                assert y[..., s['Co']:].float().abs().sum().item() == 0.0, 'padded head columns must be exactly 0'    # none at cop = Co
             ratio['y'] = lambda: check_bf16('y', _cf(y)[:, :s['Co']], r['y'][0])
-            ratio['dx0'] = lambda: check_bf16('dx0', _cf(x0.grad), r['dx'][0])
-            if x1 is not None:
-                ratio['dx1'] = lambda: check_bf16('dx1', _cf(x1.grad), r['dx'][1])
-            ratio['dw'] = lambda: check_f32('dw', w.grad, r['dw'][0])
-            ratio['db'] = lambda: check_f32('db', b.grad, r['db'][0])
+            if backward:
+                _, seen['bwd'] = window(lambda: (y.backward(go), ops.flush_deferred()))
+                ratio['dx0'] = lambda: check_bf16('dx0', _cf(x0.grad), r['dx'][0])
+                if x1 is not None:
+                    ratio['dx1'] = lambda: check_bf16('dx1', _cf(x1.grad), r['dx'][1])
+                ratio['dw'] = lambda: check_f32('dw', w.grad, r['dw'][0])
+                ratio['db'] = lambda: check_f32('db', b.grad, r['db'][0])
+        elif not backward:
+            raise ValueError('backward = False: conv3d cases only')
         elif case.op == 'pair':
             n1, Cb = s['n1'], s['Cb']
             x = _cl(r['x']).requires_grad_(True)
             p = [r[k].float().to(DEV).requires_grad_(True) for k in ('wa', 'ba', 'wb', 'bb')]
             prep = ops.conv_pair_prep(*(t.detach() for t in p), n1, torch.bfloat16)
-            (y0, y1), seen['fwd'] = launched(lambda: ops.conv3d_pair(x, *p, prep))
+            (y0, y1), seen['fwd'] = window(lambda: ops.conv3d_pair(x, *p, prep))
             assert y1.shape[-1] == n1
-            assert y1[..., Cb:].float().abs().max().item() == 0.0, 'padded head columns must be exactly 0'
+            assert y1[..., Cb:].float().abs().sum().item() == 0.0, 'padded head columns must be exactly 0'    # none at n1 = Cb
             g1 = torch.zeros(y1.shape, device=DEV, dtype=torch.bfloat16)
             g1[..., :Cb] = _cl(r['gb'])
-            _, seen['bwd'] = launched(lambda: (torch.autograd.backward([y0, y1], [_cl(r['ga']), g1]), ops.flush_deferred()))
+            _, seen['bwd'] = window(lambda: (torch.autograd.backward([y0, y1], [_cl(r['ga']), g1]), ops.flush_deferred()))
             ratio['y0'] = lambda: check_bf16('y0', _cf(y0), r['y'][0])
             ratio['y1'] = lambda: check_bf16('y1', _cf(y1)[:, :Cb], r['y'][1])
             ratio['dx'] = lambda: check_bf16('dx', _cf(x.grad), r['dx'][0])
@@ -625,8 +640,8 @@ def run_case(case):
             assert torch.equal(wf, ref_wf), 'sub-pixel forward weights differ from the fp32-summed, bf16-rounded class weights'
             wd = prep.wd.double().cpu()                                   # [Ci][class * 8 + slot][Co]
             assert torch.equal(wd, ref_wf.permute(3, 0, 2, 1).reshape(wd.shape)), 'sub-pixel data-gradient weights differ'
-            y, seen['fwd'] = launched(lambda: ops.upconv3d(x, w, b, prep))
-            _, seen['bwd'] = launched(lambda: (y.backward(_cl(r['go'])), ops.flush_deferred()))
+            y, seen['fwd'] = window(lambda: ops.upconv3d(x, w, b, prep))
+            _, seen['bwd'] = window(lambda: (y.backward(_cl(r['go'])), ops.flush_deferred()))
             ratio['y'] = lambda: check_bf16('y', _cf(y), r['y'][0])
             ratio['dx'] = lambda: check_bf16('dx', _cf(x.grad), r['dx'][0])
             ratio['dw'] = lambda: check_f32('dw', w.grad, r['dw'][0])
