@@ -788,6 +788,24 @@ int ltu_resample_grid(const void* src_img, int src_dtype, const uint8_t* src_lab
 int ltu_resample_argmax(const float* probs, int C, long long cs, int S0, int S1, int S2, long long ss0, long long ss1, long long ss2,
                         uint8_t* out_lab, float* out_prob, int class_mask, long long ocs, int O0, int O1, int O2, long long os0,
                         long long os1, long long os2, const double* mat, int lane_axis, ltu_stream_t s);
+/* resample_vote: the label by class vote, nnU-Net's label resampling ("one-hot, order 1": every class's indicator map interpolated
+ *   linearly, then the arg-max) without a one-hot volume, a class count or a float volume.  src_lab (u8, shape S0 x S1 x S2, element
+ *   strides ss0..2), out_lab (u8, shape O0 x O1 x O2, strides os0..2), mat and lane_axis as resample_grid's.  The rule, for one
+ *   output voxel: the coordinate c = M (p, 1), its clamp to [0, size - 1], the lower tap index floor(c) and the fp32 upper weights
+ *   t[s] = (float)(c[s] - floor(c[s])) are resample_grid's image path; the 8 taps are taken in its order k = 0 .. 7 (bit 0 of k:
+ *   source axis 0, bit 1: axis 1, bit 2: axis 2; the upper tap of an axis at its last index is that index again, weight t).
+ *     tap k has the weight w_k = (k & 1 ? t[0] : 1 - t[0]) * (k & 2 ? t[1] : 1 - t[1]) * (k & 4 ? t[2] : 1 - t[2]) in fp32, rounded
+ *       before it is added, and the label l_k, the u8 voxel at the tap (the coordinate is clamped: there is no outside);
+ *     the score of a value v is s_v = sum of w_k over the taps with l_k == v, added in tap order with plain fp32 adds;
+ *     out_lab = the SMALLEST v whose score is maximal, compared exactly on the fp32 scores (torch.argmax's first maximum).
+ *   Every u8 value 0 .. 255 is a class of its own.  s_c has the bits of resample_argmax's value on the float32 one-hot channel of c
+ *   (each w * 1 rounded, then added; added zeros change nothing): the label equals resample_argmax's on the one-hot channels byte
+ *   for byte.  A matrix that lands on integer coordinates gives weights 1 and 0: the nearest label.  The same 64 x 64 LDS transpose
+ *   when lane_axis is not the output's fastest axis; 8 byte loads per voxel, the vote in registers: no workspace, no atomics, two
+ *   calls give the same bytes.  LTU_E_ARG: NULL src_lab, out_lab or mat, lane_axis outside 0..2; LTU_E_SHAPE: a size or stride < 1. */
+int ltu_resample_vote(const uint8_t* src_lab, int S0, int S1, int S2, long long ss0, long long ss1, long long ss2, uint8_t* out_lab,
+                      int O0, int O1, int O2, long long os0, long long os1, long long os2, const double* mat, int lane_axis,
+                      ltu_stream_t s);
 /* ---- cubic B-spline resampling (csrc/spline.hip; nnU-Net's image interpolation, no reference counterpart: the driver's Spacingd is
  * trilinear).  Two calls: spline_prefilter turns a stored scan into B-spline coefficients, resample_spline gathers them through the
  * pull matrix of resample_grid.  order0..2 (one per SOURCE axis, each 0, 1 or 3) mean the same in both calls.
@@ -964,6 +982,23 @@ int ltu_normalize_masked(const void* img, int dtype, const uint8_t* mask, int S0
  *   Refused before any launch: everything sample_channels refuses, with its codes; NULL coef, cubic, lo or hi, lo[c] > hi[c] or a
  *   NaN bound LTU_E_ARG; a scan of 2^31 voxels or more per channel LTU_E_SHAPE (tap offsets are 32-bit, and spline_prefilter builds
  *   no larger volume).
+ * sample_vote: the label half of sample_channels with the label taken by class vote instead of nearest (nnU-Net's spatial transform
+ *   interpolates the label "one-hot, order 1"): lab u8 [H][W][D] -> out_lab u8 [n][h][w][d] through mats and, with phi != NULL, the
+ *   lattice, both as in sample_channels (phi NULL: the affine kernels, gh, gw, gd ignored).  The coordinate, its fp32 bracket, the
+ *   lower tap index i0 and the upper weights t are formed by the code of the trilinear image path (the z-decoupled and the general
+ *   affine kernel, the elastic kernel; 4 voxels per lane when d % 4 == 0; 32- or 64-bit offsets), and the 8 taps are taken in its
+ *   order r = 0 .. 7 (bit 2 of r: axis H, bit 1: W, bit 0: D).  The rule is resample_vote's:
+ *     tap r has the weight w_r = (r & 4 ? t[0] : 1 - t[0]) * (r & 2 ? t[1] : 1 - t[1]) * (r & 1 ? t[2] : 1 - t[2]) in fp32, rounded
+ *       before it is added, and the label l_r, the u8 voxel at the tap, 0 for a tap outside the scan (the nearest path's "0
+ *       outside" and the image's fill; its load goes to the nearest voxel inside the scan and is discarded);
+ *     the score of a value v is s_v = sum of w_r over the taps with l_r == v, in tap order, plain fp32 adds;
+ *     out_lab = the smallest v of maximal score, compared exactly.  Every u8 value is a class.
+ *   A matrix with integer entries (crop, flip, rot90, axis permutation) and no or an all-zero lattice gives weights 1 and 0: the
+ *   label of sample_channels byte for byte.  The bracket is the trilinear one whatever interpolates the image of the same patches
+ *   (sample_spline).  The coordinate lies within ~2e-5 voxel of fp64 (sample_affine), so a margin between the two best scores moves
+ *   by at most 1.2e-4 against an fp64 evaluation of the rule.  The vote runs in registers (8 x 8 compares): no LDS beyond the elastic
+ *   kernel's lattice, no atomics, no workspace, no synchronisation: capturable; two calls give the same bytes.
+ *   Refused before any launch as sample_channels refuses a K == 1 label-only call; NULL lab or out_lab LTU_E_ARG.
  * gauss_blur3: out [n][H][W][D] f32 = mul_k * (3-D Gaussian blur of x [n][H][W][D]), out of place, one launch.  weights: HOST float
  *   [n][3][LTU_BLUR_MAX_RADIUS + 1], the half tables w[0 .. r] of the axes H, W, D (normalised so that w[0] + 2 sum w[t] = 1; entries
  *   beyond r are ignored); radii: HOST int [n][3], 0 = that axis untouched; mul: HOST float [n] or NULL (= 1), applied in the store.
@@ -990,6 +1025,8 @@ int ltu_sample_spline(const float* img, const float* coef, const uint8_t* lab, f
                       const float* phi, int gh, int gw, int gd, const float* noise_sigma, const unsigned long long* seeds,
                       const float* fill, const float* lo, const float* hi, const unsigned char* cubic, int n, int K, int H, int W,
                       int D, int h, int w, int d, int order_d, ltu_stream_t s);
+int ltu_sample_vote(const uint8_t* lab, uint8_t* out_lab, const double* mats, const float* phi, int gh, int gw, int gd, int n, int H,
+                    int W, int D, int h, int w, int d, ltu_stream_t s);
 int ltu_gauss_blur3(const float* x, float* out, const float* weights, const int* radii, const float* mul, int n, int H, int W, int D,
                     ltu_stream_t s);
 

@@ -112,6 +112,7 @@ SIGNATURES = {
     'ltu_crop_flip': [P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_resample_grid': [P, I, P, I, I, I, L, L, L, P, P, I, I, I, L, L, L, P, I, F, F, F, F, P],
     'ltu_resample_argmax': [P, I, L, I, I, I, L, L, L, P, P, I, L, I, I, I, L, L, L, P, I, P],
+    'ltu_resample_vote': [P, I, I, I, L, L, L, P, I, I, I, L, L, L, P, I, P],
     'ltu_spline_prefilter': [P, I, I, I, I, L, L, L, P, I, I, I, F, F, F, F, P],
     'ltu_resample_spline': [P, I, I, I, I, I, I, P, I, I, I, L, L, L, P, I, F, F, P],
     'ltu_crop_orient': [P, P, P, P, P, I, I, I, I, I, I, I, P],
@@ -127,6 +128,7 @@ SIGNATURES = {
     'ltu_sample_elastic': [P, P, P, P, P, P, I, I, I, P, P, I, I, I, I, I, I, I, F, P],
     'ltu_sample_channels': [P, P, P, P, P, P, I, I, I, P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_sample_spline': [P, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
+    'ltu_sample_vote': [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     'ltu_gauss_blur3': [P, P, P, P, P, I, I, I, I, P],
     'ltu_patch_stats_parts_elems': [I, L],
     'ltu_patch_stats': [P, I, L, P, L, P, P],

@@ -4,7 +4,9 @@
 // blurs a batch of patches in one launch (three 1-D passes inside a workgroup).  ltu_sample_channels is either gather for a scan of
 // up to four channels on one grid: the same kernels, instantiated per channel count.  ltu_sample_spline is ltu_sample_channels with
 // a cubic B-spline image interpolation (64 or 32 taps on prefiltered coefficients) for the patches that ask for it: the same kernels
-// again, instantiated per tap count along D, with the cubic taps as a workgroup-uniform branch.
+// again, instantiated per tap count along D, with the cubic taps as a workgroup-uniform branch.  ltu_sample_vote is the label half of
+// either gather with the label taken by class vote over the 8 trilinear taps (nnU-Net's "one-hot, order 1") instead of nearest: the
+// same kernels once more, a compile-time choice instantiated for the label-only, one-channel case alone.
 //
 // ---- the noise generator (restated in numpy by lintransunet_amd/data.py::noise_reference) ------------------------------------
 // Stateless like the dropout masks: the normal deviate of voxel i (the linear index (x * w + y) * d + z inside its patch, < 2^32)
@@ -112,6 +114,28 @@ __device__ __forceinline__ uint8_t sa_label(const uint8_t* __restrict__ lab, con
 __device__ __forceinline__ float sa_rounded(float v) {
   asm volatile("" : "+v"(v));
   return v;
+}
+
+// the label of one voxel by class vote (ltu_sample_vote): the 8 taps of sa_taps in its order r = 0 .. 7 with its weight expression,
+// a tap outside the scan holding label 0 (sa_label's "0 outside", the image's fill), then label_vote8 (resample_coords.h).  Every
+// tap is loaded, at its index clamped into the scan, and replaced by 0 when it was outside: 8 loads in flight together instead of
+// 8 branches with a load each.
+template <typename IDX>
+__device__ __forceinline__ uint8_t sa_vote(const uint8_t* __restrict__ lab, const int (&i0)[3], const float (&t)[3], int H, int W,
+                                           int D) {
+  int l[8];
+  float wt[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int bx = r >> 2, by = (r >> 1) & 1, bz = r & 1;
+    const int xi = i0[0] + bx, yi = i0[1] + by, zi = i0[2] + bz;
+    const bool in = (unsigned)xi < (unsigned)H && (unsigned)yi < (unsigned)W && (unsigned)zi < (unsigned)D;
+    wt[r] = sa_rounded((bx ? t[0] : 1.f - t[0]) * (by ? t[1] : 1.f - t[1]) * (bz ? t[2] : 1.f - t[2]));
+    const int xc = min(max(xi, 0), H - 1), yc = min(max(yi, 0), W - 1), zc = min(max(zi, 0), D - 1);
+    const int v = lab[((IDX)xc * W + yc) * D + zc];
+    l[r] = in ? v : 0;
+  }
+  return label_vote8(l, wt);
 }
 
 // the 8 trilinear taps of one voxel (lower corner i0, upper weights t): bounds test, weight and offset once, then every channel's
@@ -272,10 +296,14 @@ __device__ __forceinline__ void sa_store(float* __restrict__ oimg, uint8_t* __re
 // ND != 0 (ltu_sample_spline): a patch with c.cubic[k] takes the cubic taps at the general kernel's coordinates (with a z-decoupled
 // matrix they are the z-decoupled kernel's: fmaf(0, ., fr) == fr); every other patch runs the code below as it stands, so it has
 // the bits of the ND == 0 kernel the same call would have chosen.  A workgroup belongs to one patch: the branch is uniform.
-template <bool ZDEC, int VEC, int NCH, typename IDX, int ND = 0>
+// VOTE (ltu_sample_vote; img == nullptr, NCH == 1, ND == 0): the label by class vote over the 8 trilinear taps.  The z-decoupled
+// path forms tap (r, e)'s weight as wxy[r] * (e ? tz : 1 - tz), which is sa_vote's product (x y) z, in sa_vote's tap order 2 r + e:
+// the same bytes as the general kernel on the same matrices.
+template <bool ZDEC, int VEC, int NCH, typename IDX, int ND = 0, bool VOTE = false>
 __global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lab,
                                                             float* __restrict__ oimg, uint8_t* __restrict__ olab, SaArgs<NCH, ND> c,
                                                             int H, int W, int D, int h, int w, int d, int zl_log2, int ty_log2) {
+  static_assert(!VOTE || (NCH == 1 && ND == 0), "the vote is instantiated for the label-only call alone");
   const int k = blockIdx.z;
   const int zl = 1 << zl_log2, ty = 1 << ty_log2;
   const int x = (int)(blockIdx.y << (8 - zl_log2 - ty_log2)) + (int)(threadIdx.x >> (zl_log2 + ty_log2));
@@ -359,7 +387,20 @@ __global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restr
           vi[ch][j] = sa_rounded(sa_rounded(1.f - tz) * p[0]) + sa_rounded(tz * p[1]);
         }
       }
-      if (lab != nullptr) {
+      if constexpr (VOTE) {
+        int l[8];
+        float wt[8];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const int zi = iz + e;
+            wt[2 * r + e] = sa_rounded(wxy[r] * (e ? tz : 1.f - tz));
+            const int v = lab[row[r] + min(max(zi, 0), D - 1)];            // row[r] is 0 for a row outside: a valid address
+            l[2 * r + e] = (in[r] && (unsigned)zi < (unsigned)D) ? v : 0;
+          }
+        vl[j] = label_vote8(l, wt);
+      } else if (lab != nullptr) {
         const int zr = sa_round(iz, tz);
         vl[j] = (lin && (unsigned)zr < (unsigned)D) ? lab[lrow + zr] : (uint8_t)0;
       }
@@ -372,13 +413,14 @@ __global__ void __launch_bounds__(256) sample_affine_kernel(const float* __restr
 #pragma unroll
       for (int s = 0; s < 3; ++s) sa_split(ax[s], fmaf(my[s], (float)yl, fmaf(mz[s], (float)(zq + j), ax[s].fr)), &i0[s], &t[s]);
       if (img != nullptr) sa_taps<NCH, IDX>(img, HWD, fill, i0, t, H, W, D, j, vi);
-      if (lab != nullptr) vl[j] = sa_label<IDX>(lab, i0, t, H, W, D);
+      if constexpr (VOTE) vl[j] = sa_vote<IDX>(lab, i0, t, H, W, D);
+      else if (lab != nullptr) vl[j] = sa_label<IDX>(lab, i0, t, H, W, D);
     }
   }
   sa_store<VEC, NCH>(oimg, olab, img != nullptr, lab != nullptr, vi, vl, c.seed[k], c.sigma[k], k, x, y, z, h, w, d);
 }
 
-template <bool ZDEC, int VEC, int NCH, typename IDX, int ND>
+template <bool ZDEC, int VEC, int NCH, typename IDX, int ND, bool VOTE>
 static void sample_affine_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SaArgs<NCH, ND>& c, int n, int H,
                                  int W, int D, int h, int w, int d, hipStream_t st) {
   const int per_lane = (d + VEC - 1) / VEC;
@@ -388,8 +430,8 @@ static void sample_affine_launch(const float* img, const uint8_t* lab, float* oi
   while ((1 << ty_log2) < w && zl_log2 + ty_log2 < 8) ++ty_log2;
   const int zl = 1 << zl_log2, ty = 1 << ty_log2, tx = 256 >> (zl_log2 + ty_log2);
   const unsigned tiles = cdiv(w, ty) * cdiv(d, zl * VEC);
-  hipLaunchKernelGGL((sample_affine_kernel<ZDEC, VEC, NCH, IDX, ND>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c, H,
-                     W, D, h, w, d, zl_log2, ty_log2);
+  hipLaunchKernelGGL((sample_affine_kernel<ZDEC, VEC, NCH, IDX, ND, VOTE>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol,
+                     c, H, W, D, h, w, d, zl_log2, ty_log2);
 }
 
 // ---- ltu_sample_elastic --------------------------------------------------------------------------------------------------------
@@ -443,13 +485,14 @@ __device__ __forceinline__ float se_dot4(const float (&w)[4], const float* p, in
   return fmaf(w[3], p[3 * stride], fmaf(w[2], p[2 * stride], fmaf(w[1], p[stride], w[0] * p[0])));
 }
 
-template <int VEC, int NC, int NCH, typename IDX, int ND = 0>
+template <int VEC, int NC, int NCH, typename IDX, int ND = 0, bool VOTE = false>
 __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __restrict__ img, const uint8_t* __restrict__ lab,
                                                              float* __restrict__ oimg, uint8_t* __restrict__ olab, SaArgs<NCH, ND> c,
                                                              const float* __restrict__ phi, int gh, int gw, int gd, float sx, float sy,
                                                              float sz, int H, int W, int D, int h, int w, int d, int zl_log2,
                                                              int ty_log2, int tx_log2) {
   static_assert(NC >= 4 && NC <= LTU_ELASTIC_MAX_GRID && (VEC == 4 || NC == 4), "NC columns cover a run of VEC voxels");
+  static_assert(!VOTE || (NCH == 1 && ND == 0), "the vote is instantiated for the label-only call alone");
   __shared__ float A[SE_TX_MAX * 3 * SE_PLANE];
   const int k = blockIdx.z;
   const int zl = 1 << zl_log2, ty = 1 << ty_log2, tx = 1 << tx_log2;
@@ -555,12 +598,13 @@ __global__ void __launch_bounds__(256) sample_elastic_kernel(const float* __rest
         sa_taps<NCH, IDX>(img, HWD, fill, i0, t, H, W, D, j, vi);
       }
     }
-    if (lab != nullptr) vl[j] = sa_label<IDX>(lab, i0, t, H, W, D);
+    if constexpr (VOTE) vl[j] = sa_vote<IDX>(lab, i0, t, H, W, D);
+    else if (lab != nullptr) vl[j] = sa_label<IDX>(lab, i0, t, H, W, D);
   }
   sa_store<VEC, NCH>(oimg, olab, img != nullptr, lab != nullptr, vi, vl, c.seed[k], c.sigma[k], k, x, y, z, h, w, d);
 }
 
-template <int VEC, int NC, int NCH, typename IDX, int ND>
+template <int VEC, int NC, int NCH, typename IDX, int ND, bool VOTE>
 static void sample_elastic_launch(const float* img, const uint8_t* lab, float* oi, uint8_t* ol, const SaArgs<NCH, ND>& c,
                                   const float* phi, int gh, int gw, int gd, int n, int H, int W, int D, int h, int w, int d,
                                   hipStream_t st) {
@@ -577,8 +621,8 @@ static void sample_elastic_launch(const float* img, const uint8_t* lab, float* o
   const float sx = h > 1 ? (float)((double)(gh - 3) / (double)(h - 1)) : 0.f;
   const float sy = w > 1 ? (float)((double)(gw - 3) / (double)(w - 1)) : 0.f;
   const float sz = d > 1 ? (float)((double)(gd - 3) / (double)(d - 1)) : 0.f;
-  hipLaunchKernelGGL((sample_elastic_kernel<VEC, NC, NCH, IDX, ND>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol, c,
-                     phi, gh, gw, gd, sx, sy, sz, H, W, D, h, w, d, zl_log2, ty_log2, tx_log2);
+  hipLaunchKernelGGL((sample_elastic_kernel<VEC, NC, NCH, IDX, ND, VOTE>), dim3(tiles, cdiv(h, tx), n), dim3(256), 0, st, img, lab, oi, ol,
+                     c, phi, gh, gw, gd, sx, sy, sz, H, W, D, h, w, d, zl_log2, ty_log2, tx_log2);
 }
 
 // ---- the three entry points ------------------------------------------------------------------------------------------------------
@@ -643,7 +687,7 @@ static int sample_check(const SampleCall& q, bool elastic, bool* run) {
 // a checked call as launches of at most SampleArgs<NCH>::MAXN patches; the kernel variant is chosen from the whole call, so that a
 // patch has the same bits wherever the call is split.  ND != 0 (ltu_sample_spline) chooses as ND == 0 does, so that its trilinear
 // patches run the expressions ltu_sample_channels would run on them; its scans are below 2^31 voxels: 32-bit indices only.
-template <int NCH, int ND>
+template <int NCH, int ND, bool VOTE = false>
 static void sample_go(const SampleCall& q, hipStream_t st) {
   bool zdec = true;
   for (int k = 0; k < q.n; ++k) {
@@ -677,18 +721,19 @@ static void sample_go(const SampleCall& q, hipStream_t st) {
     uint8_t* ol = q.ol != nullptr ? q.ol + k0 * hwd : nullptr;
 #define SA_GO(Z, V)                                                                                                          \
   do {                                                                                                                       \
-    if (small) sample_affine_launch<Z, V, NCH, int, ND>(q.img, q.lab, oi, ol, c, n, q.H, q.W, q.D, q.h, q.w, q.d, st);        \
+    if (small) sample_affine_launch<Z, V, NCH, int, ND, VOTE>(q.img, q.lab, oi, ol, c, n, q.H, q.W, q.D, q.h, q.w, q.d, st); \
     else if constexpr (ND == 0)                                                                                              \
-      sample_affine_launch<Z, V, NCH, long long, ND>(q.img, q.lab, oi, ol, c, n, q.H, q.W, q.D, q.h, q.w, q.d, st);           \
+      sample_affine_launch<Z, V, NCH, long long, ND, VOTE>(q.img, q.lab, oi, ol, c, n, q.H, q.W, q.D, q.h, q.w, q.d, st);    \
   } while (0)
-#define SE_GO(V, NCOL)                                                                                                                     \
-  do {                                                                                                                                     \
-    const float* pk = q.phi + (long long)k0 * 3 * q.gh * q.gw * q.gd;                                                                      \
-    if (small)                                                                                                                             \
-      sample_elastic_launch<V, NCOL, NCH, int, ND>(q.img, q.lab, oi, ol, c, pk, q.gh, q.gw, q.gd, n, q.H, q.W, q.D, q.h, q.w, q.d, st);     \
-    else if constexpr (ND == 0)                                                                                                            \
-      sample_elastic_launch<V, NCOL, NCH, long long, ND>(q.img, q.lab, oi, ol, c, pk, q.gh, q.gw, q.gd, n, q.H, q.W, q.D, q.h, q.w, q.d,    \
-                                                         st);                                                                              \
+#define SE_GO(V, NCOL)                                                                                                               \
+  do {                                                                                                                               \
+    const float* pk = q.phi + (long long)k0 * 3 * q.gh * q.gw * q.gd;                                                                \
+    if (small)                                                                                                                       \
+      sample_elastic_launch<V, NCOL, NCH, int, ND, VOTE>(q.img, q.lab, oi, ol, c, pk, q.gh, q.gw, q.gd, n, q.H, q.W, q.D, q.h, q.w,  \
+                                                         q.d, st);                                                                   \
+    else if constexpr (ND == 0)                                                                                                      \
+      sample_elastic_launch<V, NCOL, NCH, long long, ND, VOTE>(q.img, q.lab, oi, ol, c, pk, q.gh, q.gw, q.gd, n, q.H, q.W, q.D, q.h, \
+                                                               q.w, q.d, st);                                                        \
   } while (0)
     if (q.phi != nullptr) {
       if (vec == 1) SE_GO(1, 4);
@@ -713,10 +758,14 @@ static void sample_go_channels(const SampleCall& q, hipStream_t st) {
   }
 }
 
-static int sample_run(const SampleCall& q, bool elastic, ltu_stream_t s) {
+static int sample_run(const SampleCall& q, bool elastic, ltu_stream_t s, bool vote = false) {
   bool run;
   const int rc = sample_check(q, elastic, &run);
   if (rc != LTU_OK || !run) return rc;
+  if (vote) {                          // label only, one "channel": the patch-count splitting of a K == 1 call
+    sample_go<1, 0, true>(q, (hipStream_t)s);
+    return ltu_check_launch();
+  }
   static_assert(LTU_MAX_INPUT_CHANNELS == 4, "one instantiation per channel count");
   switch (q.nd) {
     case 0: sample_go_channels<0>(q, (hipStream_t)s); break;
@@ -760,6 +809,15 @@ extern "C" int ltu_sample_spline(const float* img, const float* coef, const uint
   const SampleCall q = {img, lab, out_img, out_lab, mats, phi, gh, gw, gd, noise_sigma, seeds, fill, n, K, H, W, D, h, w, d,
                         order_d == 3 ? 4 : 2, coef, lo, hi, cubic};
   return sample_run(q, phi != nullptr, s);
+}
+
+// the label half of ltu_sample_channels by class vote: the same matrices, lattice, checks and launches, no image, no noise
+extern "C" int ltu_sample_vote(const uint8_t* lab, uint8_t* out_lab, const double* mats, const float* phi, int gh, int gw, int gd, int n,
+                               int H, int W, int D, int h, int w, int d, ltu_stream_t s) {
+  if (lab == nullptr || out_lab == nullptr) return LTU_E_ARG;
+  const float fill = 0.f;
+  const SampleCall q = {nullptr, lab, nullptr, out_lab, mats, phi, gh, gw, gd, nullptr, nullptr, &fill, n, 1, H, W, D, h, w, d};
+  return sample_run(q, phi != nullptr, s, true);
 }
 
 // ---- ltu_gauss_blur3 -----------------------------------------------------------------------------------------------------------

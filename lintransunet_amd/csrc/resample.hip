@@ -169,6 +169,93 @@ extern "C" int ltu_resample_grid(const void* src_img, int src_dtype, const uint8
   return ltu_check_launch();
 }
 
+// ---- label by class vote: lab[p] = argmax_v sum of the trilinear weights of the taps that hold v ---------------------------------
+// nnU-Net's label resampling ("one-hot, order 1") without the one-hot volume: clamp_coords, tap_setup and tap_sum's weight
+// expression and tap order k = 0 .. 7, then label_vote8 (resample_coords.h).  The score of a class has the bits of tap_sum on its
+// float32 indicator map with the identity map (each w * 1 rounded, then added; an added 0 changes nothing), so the label is
+// ltu_resample_argmax's on the one-hot channels, for any u8 values and without a class count.  Same tile as resample_grid_kernel,
+// with the u8 tile alone in LDS when it is transposed.
+template <typename IDX>
+__device__ __forceinline__ uint8_t vote_one(const ResampleArgs& a, double c0, double c1, double c2) {
+  double c[3];
+  clamp_coords(a.S, c0, c1, c2, c);
+  IDX o0[3], o1[3];
+  float t[3];
+  tap_setup<IDX>(a.S, a.ss, c, o0, o1, t);
+  int l[8];
+  float w[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int bx = k & 1, by = (k >> 1) & 1, bz = k >> 2;
+    w[k] = (bx ? t[0] : 1.f - t[0]) * (by ? t[1] : 1.f - t[1]) * (bz ? t[2] : 1.f - t[2]);
+    asm("" : "+v"(w[k]));            // rounded before it is added, as tap_sum's product is
+    l[k] = a.src_lab[(bx ? o1[0] : o0[0]) + (by ? o1[1] : o0[1]) + (bz ? o1[2] : o0[2])];
+  }
+  return label_vote8(l, w);
+}
+
+template <typename IDX>
+__global__ void __launch_bounds__(256) resample_vote_kernel(ResampleArgs a) {
+  __shared__ uint8_t slab[RS_T][RS_T + 4];
+  const int tilesP = (a.O[a.P] + RS_T - 1) / RS_T, tilesQ = (a.O[a.Q] + RS_T - 1) / RS_T;
+  long long b = blockIdx.x;
+  const int tp = (int)(b % tilesP); b /= tilesP;
+  const int tq = (int)(b % tilesQ);
+  const int r = (int)(b / tilesQ);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int pP = tp * RS_T + lane;
+  const double m[3][4] = {{a.mat[0], a.mat[1], a.mat[2], a.mat[3]}, {a.mat[4], a.mat[5], a.mat[6], a.mat[7]},
+                          {a.mat[8], a.mat[9], a.mat[10], a.mat[11]}};
+  double base[3];
+#pragma unroll
+  for (int s = 0; s < 3; ++s) base[s] = fma(m[s][a.R], (double)r, m[s][3]) + m[s][a.P] * (double)pP;
+  const long long obase = (long long)r * a.os[a.R];
+  for (int row = wv; row < RS_T; row += 4) {
+    const int pQ = tq * RS_T + row;
+    uint8_t vl = 0;
+    const bool in = pP < a.O[a.P] && pQ < a.O[a.Q];
+    if (in)
+      vl = vote_one<IDX>(a, fma(m[0][a.Q], (double)pQ, base[0]), fma(m[1][a.Q], (double)pQ, base[1]),
+                         fma(m[2][a.Q], (double)pQ, base[2]));
+    if (a.transpose) slab[row][lane] = vl;
+    else if (in) a.out_lab[obase + (long long)pP * a.os[a.P] + (long long)pQ * a.os[a.Q]] = vl;
+  }
+  if (!a.transpose) return;
+  __syncthreads();
+  const int qQ = tq * RS_T + lane;
+  if (qQ >= a.O[a.Q]) return;
+  const int cols = min(RS_T, a.O[a.P] - tp * RS_T);
+  for (int col = wv; col < cols; col += 4)
+    a.out_lab[obase + (long long)(tp * RS_T + col) * a.os[a.P] + (long long)qQ * a.os[a.Q]] = slab[lane][col];
+}
+
+extern "C" int ltu_resample_vote(const uint8_t* src_lab, int S0, int S1, int S2, long long ss0, long long ss1, long long ss2,
+                                 uint8_t* out_lab, int O0, int O1, int O2, long long os0, long long os1, long long os2,
+                                 const double* mat, int lane_axis, ltu_stream_t s) {
+  if (mat == nullptr || src_lab == nullptr || out_lab == nullptr || lane_axis < 0 || lane_axis > 2) return LTU_E_ARG;
+  if (S0 < 1 || S1 < 1 || S2 < 1 || O0 < 1 || O1 < 1 || O2 < 1 || ss0 < 1 || ss1 < 1 || ss2 < 1 || os0 < 1 || os1 < 1 || os2 < 1)
+    return LTU_E_SHAPE;
+  ResampleArgs a;
+  a.src_img = nullptr; a.src_lab = src_lab; a.out_img = nullptr; a.out_lab = out_lab; a.mat = mat;
+  a.ss[0] = ss0; a.ss[1] = ss1; a.ss[2] = ss2;
+  a.os[0] = os0; a.os[1] = os1; a.os[2] = os2;
+  a.S[0] = S0; a.S[1] = S1; a.S[2] = S2;
+  a.O[0] = O0; a.O[1] = O1; a.O[2] = O2;
+  a.alpha = 1.f; a.beta = 0.f; a.lo = -INFINITY; a.hi = INFINITY;
+  a.P = lane_axis;
+  const int u = (lane_axis + 1) % 3, v = (lane_axis + 2) % 3;
+  a.Q = a.os[u] <= a.os[v] ? u : v;
+  a.R = 3 - a.P - a.Q;
+  a.transpose = a.os[a.Q] < a.os[a.P] ? 1 : 0;
+  const long long blocks = (long long)cdiv(a.O[a.P], RS_T) * cdiv(a.O[a.Q], RS_T) * a.O[a.R];
+  if (blocks >= (1LL << 31)) return LTU_E_SHAPE;
+  const dim3 grid((unsigned)blocks), block(256);
+  const bool small = (long long)(S0 - 1) * ss0 + (long long)(S1 - 1) * ss1 + (long long)(S2 - 1) * ss2 < (1LL << 31);
+  if (small) hipLaunchKernelGGL((resample_vote_kernel<int>), grid, block, 0, (hipStream_t)s, a);
+  else hipLaunchKernelGGL((resample_vote_kernel<long long>), grid, block, 0, (hipStream_t)s, a);
+  return ltu_check_launch();
+}
+
 // ---- arg-max of resampled probabilities: lab[p] = argmax_c sample(probs[c], M (p, 1)) ------------------------------------------
 // The way back of a prediction (data.to_native_probs): C planar f32 channels on the RAS grid are pulled onto the file's grid and the
 // arg-max is taken there.  The coordinate, the tap offsets and the weights do not depend on the channel: they are formed once per

@@ -10,6 +10,34 @@ __device__ __forceinline__ void clamp_coords(const int* S, double c0, double c1,
   c[2] = fmin(fmax(c2, 0.0), (double)(S[2] - 1));
 }
 
+// ---- the label vote ("one-hot, order 1"), shared by resample.hip's ltu_resample_vote and augment.hip's ltu_sample_vote ---------------
+// The 8 trilinear taps of a voxel hold at most 8 distinct labels, so interpolating every class's indicator map and taking the arg-max
+// needs no one-hot volume: the score of a value v is s_v = sum of w[q] over the taps with l[q] == v, added in tap order q = 0 .. 7
+// with plain fp32 adds, and the smallest v of maximal score wins (torch.argmax's first maximum, ltu_resample_argmax's rule).  The
+// score of tap r's label is formed as sum_q (l[q] == l[r] ? w[q] : 0): the weights are >= +0, so an added 0 changes no bit.  64
+// selects and adds in registers, no LDS.  The caller makes every w[q] opaque first (the product that forms it must be rounded before
+// it is added: -ffp-contract=fast would otherwise fuse it into the sum where the select folds away, q == r).  8 equal taps need no
+// scores (theirs is the only one): where that holds in every lane of a wave - the inside of a structure, the background - the wave
+// skips the vote.
+__device__ __forceinline__ uint8_t label_vote8(const int (&l)[8], const float (&w)[8]) {
+  bool same = true;
+#pragma unroll
+  for (int q = 1; q < 8; ++q) same = same && l[q] == l[0];
+  if (same) return (uint8_t)l[0];
+  float best = -1.f;                 // below every score: tap 0 always takes it
+  int lab = 0;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) s += l[q] == l[r] ? w[q] : 0.f;
+    const bool take = s > best || (s == best && l[r] < lab);
+    best = take ? s : best;
+    lab = take ? l[r] : lab;
+  }
+  return (uint8_t)lab;
+}
+
 // ---- cubic B-spline taps, shared by spline.hip's resampler and augment.hip's patch gather ----------------------------------------
 // whole-sample mirror of a tap index in -1 .. n + 1 (all that occurs once the coordinate lies in [0, n - 1])
 __device__ __forceinline__ int sp_mirror(int i, int n) {

@@ -421,6 +421,18 @@ def resolve_order(order):
     return orders
 
 
+LABEL_ORDERS = (0, 1)                 # the label's interpolation: nearest, or the class vote over the 8 trilinear taps
+
+
+def label_order_of(label_order):
+    """a `label_order` argument as 0 (nearest, the default everywhere) or 1 (the class vote: every class's indicator map interpolated
+    linearly and the arg-max taken, nnU-Net's "one-hot, order 1"; ltu_resample_vote / ltu_sample_vote); anything else is a
+    ValueError"""
+    if isinstance(label_order, (int, np.integer)) and not isinstance(label_order, bool) and int(label_order) in LABEL_ORDERS:
+        return int(label_order)
+    raise ValueError(f'label_order is 0 (nearest) or 1 (class vote), got {label_order!r}')
+
+
 def _source_layout(src, src_strides):
     """(shape, element strides) per source axis of a device source: x fastest ([S2][S1][S0]) unless strides are given"""
     if src_strides is None:
@@ -448,15 +460,21 @@ def spline_coefficients(src, orders, imap=(1.0, 0.0, -np.inf, np.inf), src_dtype
 
 
 def resample(src_img, src_lab, matrix, out_shape, imap=(1.0, 0.0, -np.inf, np.inf), src_dtype=0, src_strides=None,
-             out_strides=None, lane_axis=None, order=1, out=None):
+             out_strides=None, lane_axis=None, order=1, out=None, label_order=0):
     """ltu_resample_grid: device sources (image of src_dtype / u8 label, either None) of shape (S0, S1, S2) read through
     `src_strides` (default: x fastest, i.e. a [S2][S1][S0] array), resampled through the 3x4 float64 pull matrix to outputs of
     out_shape (default layout: [O0][O1][O2], the last axis fastest).  Returns (f32 image or None, u8 label or None).
     order: the image's interpolation, 1 (trilinear, the call as it always was), 3 (cubic B-spline) or one of 0 / 1 / 3 per source
     axis (resolve_order).  Anything but 1 prefilters the mapped scan (spline_coefficients) and gathers the coefficients through the
     same matrix (ltu_resample_spline), clamped to the map's [lo, hi]; the label still goes nearest through ltu_resample_grid.
+    label_order: 0, the default, is that nearest label (round half even of the clamped coordinate).  1 takes the label by class
+    vote (ltu_resample_vote, a launch of its own; the image goes through its present call with the label left out): the 8 trilinear
+    taps and fp32 weights of the order-1 image path, the weights summed per label value, the smallest value of maximal score wins.
+    That is the arg-max of the linearly interpolated one-hot maps, byte for byte resample_argmax on float32 one-hot channels, for
+    any u8 values and without the one-hot volume.
     out: (f32 image or None, u8 label or None) to write into instead of fresh tensors: device tensors (views allowed) whose
     element [0, 0, 0] is output voxel (0, 0, 0) and whose memory `out_strides` describes, e.g. a box of a larger volume."""
+    vote = label_order_of(label_order) == 1 and src_lab is not None
     src = src_img if src_img is not None else src_lab
     if src is None or not src.is_cuda:
         raise _lib.LtuError('data.resample runs on the GPU only (no CPU fallback)')
@@ -491,8 +509,12 @@ def resample(src_img, src_lab, matrix, out_shape, imap=(1.0, 0.0, -np.inf, np.in
             return oi, ol
     gi, go = (None, None) if spline else (src_img, oi)          # after the spline gather only the label is left, nearest
     lane = geometry.lane_axis(m, src_strides) if lane_axis is None else lane_axis
-    _lib.call('ltu_resample_grid', _p(gi), int(src_dtype), _p(src_lab), *S, *src_strides, _p(go), _p(ol),
-              *O, *(int(s) for s in out_strides), _p(mat), lane, *(float(v) for v in imap), _s())
+    gl, gol = (None, None) if vote else (src_lab, ol)           # a voted label is a launch of its own
+    if gi is not None or gl is not None:
+        _lib.call('ltu_resample_grid', _p(gi), int(src_dtype), _p(gl), *S, *src_strides, _p(go), _p(gol),
+                  *O, *(int(s) for s in out_strides), _p(mat), lane, *(float(v) for v in imap), _s())
+    if vote:
+        _lib.call('ltu_resample_vote', _p(src_lab), *S, *src_strides, _p(ol), *O, *(int(s) for s in out_strides), _p(mat), lane, _s())
     return oi, ol
 
 
@@ -913,14 +935,15 @@ def _masked_zscore(raw, mask, slope, inter):
     return window, float(slope) / sd, (float(inter) - st['mean']) / sd
 
 
-def _load_channel(ri, rl, code, spec, slope, inter, mask, box, plan, order):
+def _load_channel(ri, rl, code, spec, slope, inter, mask, box, plan, order, label_order=0):
     """one channel of a scan, for every crop and every spec: (f32 image, u8 label or None, window).  ri / rl: the device volumes as
     stored [Z, Y, X] (rl None: no label, or not channel 0); box: the part to load in their axes, the whole volume without a crop;
     mask: the scan's nonzero mask, None where it needs none; plan: (matrix, shape) of the box's resampling.
     The box is read through the stored volume's strides, no copy; the whole volume's box is the layout data.resample assumes of a
     source without strides.  'zscore_nonzero' normalises the box first (normalize_masked) and resamples the f32 result with the
     identity map, the label from its box in a call of its own; every other spec resamples image and label in ONE call (at order 1
-    one launch).  The label is nearest."""
+    one launch).  The label is nearest at label_order 0 and the class vote at 1 (data.resample's label_order; read from the box
+    like the image)."""
     matrix, shape = plan
     Z, Y, X = (int(n) for n in ri.shape)
     (z0, z1), (y0, y1), (x0, x1) = box
@@ -929,13 +952,13 @@ def _load_channel(ri, rl, code, spec, slope, inter, mask, box, plan, order):
     def boxed(t):                                     # the box as a view with x first, as `strides` describes it
         return None if t is None else t[z0:z1, y0:y1, x0:x1].permute(2, 1, 0)
     if _masked_spec(spec):
-        ol = resample(None, boxed(rl), matrix, shape, src_strides=strides)[1] if rl is not None else None
+        ol = resample(None, boxed(rl), matrix, shape, src_strides=strides, label_order=label_order)[1] if rl is not None else None
         window, alpha, beta = _masked_zscore(ri, mask, slope, inter)
         oi, _ = resample(normalize_masked(ri, mask, box, alpha, beta, code), None, matrix, shape, order=order)
     else:
         window = _resolve_intensity(spec, ri, slope, inter)
         oi, ol = resample(boxed(ri), boxed(rl), matrix, shape, intensity_map(window, slope, inter), code, src_strides=strides,
-                          order=order)
+                          order=order, label_order=label_order)
     return oi, ol, window
 
 
@@ -967,6 +990,9 @@ class SpacedScan:
     order: the image's interpolation as data.resample takes it (1: trilinear, the driver's; 3: cubic B-spline; a 3-tuple per FILE
     axis), or 'auto' for geometry.resample_orders of the file's voxel sizes and pixdim (nnU-Net's rule: the coarse axis of an
     anisotropic scan goes nearest); the attribute `order` keeps the resolved 3-tuple.  The label is nearest whatever the order.
+    label_order: 0 (nearest, the default) or 1: the label resampled by class vote (data.resample's label_order; nnU-Net resamples
+    labels "one-hot, order 1"), also from the box of a cropped scan; the attribute `label_order` keeps it, crop_index and label_host
+    follow from `lab` as before.
     crop='nonzero' (nnU-Net's crop_to_nonzero; for skull-stripped MR, where most voxels are exact zeros): the scan's nonzero mask
     (data.nonzero_mask: scaled value != 0, holes filled) is built on the device, and image and label are resampled from its
     bounding box only: matrix, shape and affine are then those of the box (geometry.crop_plan, then spacing_plan), matrix: RAS voxel
@@ -980,16 +1006,18 @@ class SpacedScan:
     the scan that data.sample(augment=) fills with, 0.0 under 'zscore_nonzero', else None (the window's floor)."""
 
     def __init__(self, img_path, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda',
-                 order=1, crop=None):
-        img, (self.intensity,), (self.outside,) = self._load([img_path], lab_path, pixdim, axcodes, [intensity], device, order, crop)
+                 order=1, crop=None, label_order=0):
+        img, (self.intensity,), (self.outside,) = self._load([img_path], lab_path, pixdim, axcodes, [intensity], device, order, crop,
+                                                             label_order)
         self.img = img[0]
 
-    def _load(self, paths, lab_path, pixdim, axcodes, specs, device, order, crop):
+    def _load(self, paths, lab_path, pixdim, axcodes, specs, device, order, crop, label_order=0):
         """the loader of SpacedScan and MultiScan: K files with one intensity spec each -> (img f32 [K, H, W, D], the K windows, the
         K `outside` values); every other attribute is set here.  A scan that needs no nonzero mask is uploaded, resampled and
         released one channel at a time; a crop or a 'zscore_nonzero' channel uploads all K volumes first, because the mask is their
         union.  The label is resampled with channel 0."""
         _check_scan_options(crop, specs)
+        self.label_order = label_order_of(label_order)
         nis = [nifti.load(p) for p in paths]
         nl = nifti.load(lab_path) if lab_path is not None else None
         ni, K = nis[0], len(nis)
@@ -1023,7 +1051,7 @@ class SpacedScan:
         for c, (nc, spec) in enumerate(zip(nis, specs)):
             ri, code = raws.pop(0) if raws else upload(nc)
             oi, ol, window = _load_channel(ri, rl if c == 0 else None, code, spec, nc.slope, nc.inter, mask, box,
-                                           (self.matrix, self.shape), self.order)
+                                           (self.matrix, self.shape), self.order, self.label_order)
             del ri                                       # every stored volume is dropped after its channel
             if c == 0:
                 self.lab = ol
@@ -1084,12 +1112,12 @@ class MultiScan(SpacedScan):
     label_host, matrix, affine, shape, pixdim as on SpacedScan, native / native_shape / native_affine are channel 0's.
     intensity: one spec for all channels (a window 4-tuple, None, an IntensityFingerprint or 'zscore') or a sequence of K specs;
     the attribute `intensity` is the list of the K resulting tuples (or None).  channels == K.  order: as SpacedScan's, one for all
-    channels.  crop and 'zscore_nonzero' as SpacedScan's: ONE nonzero mask, the union over all K channels, crops the scan and selects
-    the voxels of every channel's statistics; crop_box, nonzero_count, nonzero_fraction as there, outside: a list of K (0.0 for a
-    'zscore_nonzero' channel, else None)."""
+    channels, and label_order as SpacedScan's.  crop and 'zscore_nonzero' as SpacedScan's: ONE nonzero mask, the union over all K
+    channels, crops the scan and selects the voxels of every channel's statistics; crop_box, nonzero_count, nonzero_fraction as
+    there, outside: a list of K (0.0 for a 'zscore_nonzero' channel, else None)."""
 
     def __init__(self, img_paths, lab_path=None, pixdim=(0.5, 0.5, 2.0), axcodes='RAS', intensity=MONAI_CT_WINDOW, device='cuda',
-                 order=1, crop=None):
+                 order=1, crop=None, label_order=0):
         paths = [img_paths] if isinstance(img_paths, (str, bytes)) or hasattr(img_paths, '__fspath__') else list(img_paths)
         K = len(paths)
         if not 1 <= K <= _lib.MAX_INPUT_CHANNELS:
@@ -1099,7 +1127,7 @@ class MultiScan(SpacedScan):
         specs = [intensity] * K if one else list(intensity)
         if len(specs) != K:
             raise ValueError(f'intensity is one spec or one per image: {len(specs)} specs for {K} images')
-        self.img, self.intensity, self.outside = self._load(paths, lab_path, pixdim, axcodes, specs, device, order, crop)
+        self.img, self.intensity, self.outside = self._load(paths, lab_path, pixdim, axcodes, specs, device, order, crop, label_order)
         self.channels = K
 
 
@@ -1262,7 +1290,8 @@ def _channel_bounds(clamp, K):
     return np.ascontiguousarray(c[:, 0]), np.ascontiguousarray(c[:, 1])
 
 
-def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, elastic=None, order=1, coef=None, clamp=None):
+def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, elastic=None, order=1, coef=None, clamp=None,
+                  label_order=0):
     """ltu_sample_channels (order 1) or ltu_sample_spline (any other order), for every image: device patches ([n,1,h,w,d] f32 or
     None, [n,1,h,w,d] u8 or None) gathered from img / lab [H,W,D] through mats [n,3,4] (float64 pull matrices, patch voxel -> scan
     voxel): image trilinear with `fill` outside the scan, label nearest (round half even) with 0 outside.  noise_sigma [n] with
@@ -1282,8 +1311,14 @@ def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, 
     of img in its shape (SpacedScan.spline_coefficients(order) caches them); None builds them here with spline_coefficients, per
     channel.  clamp: (lo, hi) or one pair per channel, applied to the tap sum, not to fill (the spline rings past a clipped
     intensity window); None = no clamp.  A patch is cubic unless all 12 entries of its matrix are integers and it has no lattice or
-    an all-zero one: such a patch keeps the trilinear expressions, that is the source voxels.  The label is order 1's, byte for byte."""
+    an all-zero one: such a patch keeps the trilinear expressions, that is the source voxels.  The label is order 1's, byte for byte.
+    label_order: 0, the default, is the nearest label above.  1 takes it by class vote (ltu_sample_vote, a second, label-only launch
+    through the same matrices and lattice; the image is gathered as above with the label left out, so it has the bits of the
+    label_order 0 call whatever order, coef, elastic and K are): the 8 taps and fp32 weights of the TRILINEAR bracket (also under a
+    cubic image), a tap outside the scan counting for label 0, the weights summed per label value, the smallest value of maximal
+    score wins: nnU-Net's "one-hot, order 1".  An integer matrix gives the nearest label byte for byte."""
     orders = sample_order(order)
+    vote = label_order_of(label_order) == 1 and lab is not None
     if elastic is not None:
         elastic = _check_lattice(elastic)
     vol = img if img is not None else lab
@@ -1335,14 +1370,17 @@ def sample_affine(img, lab, mats, size, fill=0.0, noise_sigma=None, seeds=None, 
         if a is None:
             return 0
         return a.data_ptr() + s * a.stride(0) * a.element_size() if torch.is_tensor(a) else a.ctypes.data + s * a.strides[0]
+    gl, gol = (None, None) if vote else (lab, ol)          # a voted label is a launch of its own, behind the image's
     for s in range(0, n, _lib.SAMPLE_AFFINE_MAX):
         e = min(n, s + _lib.SAMPLE_AFFINE_MAX)
-        common = (row(oi, s), row(ol, s), row(m, s), row(lat, s), *g, row(sg, s), row(sd, s), fl.ctypes.data)
+        common = (row(oi, s), row(gol, s), row(m, s), row(lat, s), *g, row(sg, s), row(sd, s), fl.ctypes.data)
         if cubic:
-            _lib.call('ltu_sample_spline', _p(img), _p(coef), _p(lab), *common, lo.ctypes.data, hi.ctypes.data, row(which, s),
+            _lib.call('ltu_sample_spline', _p(img), _p(coef), _p(gl), *common, lo.ctypes.data, hi.ctypes.data, row(which, s),
                       e - s, K, H, W, D, h, w, d, orders[2], _s())
-        else:
-            _lib.call('ltu_sample_channels', _p(img), _p(lab), *common, e - s, K, H, W, D, h, w, d, _s())
+        elif img is not None or gl is not None:
+            _lib.call('ltu_sample_channels', _p(img), _p(gl), *common, e - s, K, H, W, D, h, w, d, _s())
+        if vote:
+            _lib.call('ltu_sample_vote', _p(lab), row(ol, s), row(m, s), row(lat, s), *g, e - s, H, W, D, h, w, d, _s())
     return oi, ol
 
 
@@ -1565,6 +1603,8 @@ class Augmentation:
     per scan axis H, W, D): the image interpolation of the patches that rotate, zoom or deform; 1, the default, is trilinear, any
     other is sample_affine's cubic B-spline from scan.spline_coefficients(order) (nnU-Net interpolates at order 3), clamped to each
     channel's intensity window.  It makes no draw: draw() returns the same values and leaves the generator in the same state.
+    label_order: 0 (nearest, the default) or 1: the label of every patch by class vote (sample_affine's label_order), carried into
+    data.sample's gather.  It makes no draw either.
     contrast_prob, lowres_prob, invgamma_prob > 0 add nnU-Net's contrast (data.contrast, factor from `contrast`), low-resolution
     simulation (data.simulate_lowres, scale from lowres_scale on the patch axes lowres_axes) and gamma on the inverted image
     (data.gamma_transform(invert=True), exponent from invgamma); each draws (fire, value) behind the elastic draws, in this order,
@@ -1576,7 +1616,8 @@ class Augmentation:
                  noise_std=(0.0, 0.1), blur_prob=0.2, blur_sigma=(0.5, 1.0), brightness_prob=0.15, brightness=(0.75, 1.25),
                  gamma_prob=0.3, gamma=(0.7, 1.5), fill=None, elastic_prob=0.0, elastic_mm=(0.0, 4.0), elastic_grid=(6, 6, 4), order=1,
                  contrast_prob=0.0, contrast=(0.75, 1.25), lowres_prob=0.0, lowres_scale=(0.5, 1.0), lowres_axes=(0, 1, 2),
-                 invgamma_prob=0.0, invgamma=(0.7, 1.5), retain_stats=False):
+                 invgamma_prob=0.0, invgamma=(0.7, 1.5), retain_stats=False, label_order=0):
+        self.label_order = label_order_of(label_order)
         self.contrast_prob, self.contrast = contrast_prob, tuple(float(v) for v in contrast)
         self.lowres_prob, self.lowres_scale = lowres_prob, tuple(float(v) for v in lowres_scale)
         self.lowres_axes = tuple(int(a) for a in lowres_axes)
@@ -1635,7 +1676,8 @@ class Augmentation:
     def nnunet(cls, **overrides):
         """nnU-Net's default training augmentation: rotation 0.2, zoom 0.2 over (0.7, 1.4), noise 0.1, blur 0.2, brightness 0.15,
         contrast 0.15, low resolution 0.25 over (0.5, 1), inverted gamma 0.1 and gamma 0.3 over (0.7, 1.5) with retain_stats, order-3
-        interpolation.  overrides replace any of them."""
+        interpolation.  overrides replace any of them.  nnU-Net's own spatial transform interpolates the label at order 1 on
+        one-hot maps; this record keeps label_order 0 (nearest), as it always has: pass label_order=1 for nnU-Net's label."""
         kw = dict(rot_prob=0.2, zoom_prob=0.2, zoom_range=(0.7, 1.4), noise_prob=0.1, blur_prob=0.2, brightness_prob=0.15,
                   contrast_prob=0.15, contrast=(0.75, 1.25), lowres_prob=0.25, lowres_scale=(0.5, 1.0), invgamma_prob=0.1,
                   invgamma=(0.7, 1.5), gamma_prob=0.3, gamma=(0.7, 1.5), retain_stats=True, order=3)
@@ -1698,7 +1740,7 @@ def _augmented(scan, draws, params, spatial_size, augment, spacing):
     fill = _scan_fill(scan, augment)
     if params is None:
         mats = [patch_matrix([max(c[a] - size[a] // 2, 0) for a in range(3)], size, f, k) for c, f, k in draws]
-        return sample_affine(scan.img, scan.lab, np.stack(mats), size, fill)
+        return sample_affine(scan.img, scan.lab, np.stack(mats), size, fill)          # integer matrices: either label_order's bytes
     mats = [patch_matrix([max(c[a] - size[a] // 2, 0) for a in range(3)], size, f, k,
                          p['angles'] if p['rotate'] else (0.0, 0.0, 0.0), p['zoom_factor'] if p['zoom'] else 1.0, spacing)
             for (c, f, k), p in zip(draws, params)]
@@ -1722,7 +1764,8 @@ def _augmented(scan, draws, params, spatial_size, augment, spacing):
                      clamp=[intensity_map(wd)[2:4] for wd in _channels(scan)[1]])
     img, lab = sample_affine(scan.img, scan.lab, np.stack(mats), size, fill,
                              [p['noise_std'] if p['noise'] else 0.0 for p in params] if noisy else None,
-                             [p['seed'] for p in params] if noisy else None, elastic=lattice, **cubic)
+                             [p['seed'] for p in params] if noisy else None, elastic=lattice, label_order=augment.label_order,
+                             **cubic)
     shape, K = img.shape, img.shape[1]
     img = img.view(-1, 1, *size)
 
@@ -1802,10 +1845,12 @@ def sample(scan, spatial_size, rand_state, num_samples=1, flip_prob=0.5, rot90_p
     return _augmented(scan, draws, params, spatial_size, augment, getattr(scan, 'pixdim', (1.0, 1.0, 1.0)))
 
 
-def to_native(label_map, scan):
+def to_native(label_map, scan, order=0):
     """nearest resampling of an RAS u8 label map [H,W,D] (leading size-1 axes allowed; e.g. evaluate_multiclass's 'label_map')
     back onto the file's grid through the inverse pull matrix: u8 [Z][Y][X] on the device, ready for nifti.save(...,
-    scan.native_affine, like=scan.native)"""
+    scan.native_affine, like=scan.native).  order: 0 is that nearest label; 1 pulls the label map back by class vote
+    (data.resample's label_order 1), into the whole file grid and into the box of a cropped scan alike."""
+    order = label_order_of(order)
     lm = label_map.reshape(scan.shape)
     if lm.dtype != torch.uint8:
         raise ValueError(f'to_native takes a uint8 label map, got {lm.dtype}')
@@ -1814,13 +1859,14 @@ def to_native(label_map, scan):
     X, Y, Z = scan.native_shape
     box = getattr(scan, 'crop_box', None)
     if box is None:
-        _, out = resample(None, lm, geometry.invert(scan.matrix), (X, Y, Z), src_strides=(W * D, D, 1), out_strides=(1, X, X * Y))
+        _, out = resample(None, lm, geometry.invert(scan.matrix), (X, Y, Z), src_strides=(W * D, D, 1), out_strides=(1, X, X * Y),
+                          label_order=order)
         return out
     # a cropped scan: its matrix leads into the box, which is written in place inside a file-sized volume of zeros
     (z0, z1), (y0, y1), (x0, x1) = box
     out = torch.zeros((Z, Y, X), device=lm.device, dtype=torch.uint8)
     resample(None, lm, geometry.invert(scan.matrix), (x1 - x0, y1 - y0, z1 - z0), src_strides=(W * D, D, 1),
-             out_strides=(1, X, X * Y), out=(None, out[z0:z1, y0:y1, x0:x1]))
+             out_strides=(1, X, X * Y), out=(None, out[z0:z1, y0:y1, x0:x1]), label_order=order)
     return out
 
 
