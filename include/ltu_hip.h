@@ -519,6 +519,48 @@ int ltu_loss_imb_fwd(const float* p, const uint8_t* label, float* sums, long lon
                      int B, long long S, int C, ltu_stream_t s);
 int ltu_loss_imb_bwd(const float* p, const uint8_t* label, const float* coef, long long coef_floats, float focal_gamma,
                      const float* gscale, float* dp, int accumulate, int B, long long S, int C, ltu_stream_t s);
+/* ---- soft morphology, soft skeleton and soft-clDice (csrc/softmorph.hip) ---------------------------------------------------------
+ * Volumes are f32 [N][H][W][D], N any leading product, H W D < 2^31.  op 0, erode: the minimum over the 7-voxel cross (centre, -H, +H,
+ * -W, +W, -D, +D); op 1, dilate: the maximum over the 3 x 3 x 3 cube.  Taps outside the volume are left out.  tap u8 [N][H][W][D]
+ * receives the code of the first tap that attains the extremum, centre first (erode: 0 centre, 1 .. 6 in the order above; dilate:
+ * 9 (dh + 1) + 3 (dw + 1) + (dd + 1), centre 13, the others visited in raster order), and the backward gives the whole gradient of an
+ * output voxel to that tap, as a gather: no atomics, two calls agree bit for bit.
+ * Skeleton, 1 <= iters <= 10: I_0 = x, I_{j+1} = erode(I_j), D_j = dilate(I_{j+1}), delta_j = relu(I_j - D_j), s_0 = delta_0, s_j =
+ * s_{j-1} + relu(delta_j - s_{j-1} delta_j), y = s_iters, relu'(0) = 0.  scratch: ltu_soft_skeleton_scratch_elems(..) 4-byte elements,
+ * no initialisation; the forward leaves I_1 .. I_{iters+1} and the taps in it (6 bytes per voxel and erosion) and the backward, which
+ * reads the scratch its forward wrote, uses the rest (4 bytes per voxel and erosion, and 8).
+ * ltu_label_skeletons: out u8 [B][K][H][W][D] = the skeleton of the 0 / 1 maps [label == classes[k]], byte for byte what the float
+ * chain gives on them, computed on the bytes of `out` alone (no scratch).
+ * LTU_E_SHAPE: an extent < 1, H W D >= 2^31; LTU_E_ARG: a NULL pointer, op outside {0, 1}, iters outside 1 .. 10, K outside 1 .. 8,
+ * a class listed twice, a short scratch; all before anything is launched. */
+long long ltu_soft_skeleton_scratch_elems(long long N, int H, int W, int D, int iters);
+int ltu_soft_morph_fwd(const float* x, float* y, uint8_t* tap, int op, long long N, int H, int W, int D, ltu_stream_t s);
+int ltu_soft_morph_bwd(const float* g_out, const uint8_t* tap, float* dx, int op, long long N, int H, int W, int D, ltu_stream_t s);
+int ltu_soft_skeleton_fwd(const float* x, float* y, void* scratch, long long scratch_elems, long long N, int H, int W, int D,
+                          int iters, ltu_stream_t s);
+int ltu_soft_skeleton_bwd(const float* x, const float* g_out, float* dx, void* scratch, long long scratch_elems, long long N, int H,
+                          int W, int D, int iters, ltu_stream_t s);
+int ltu_label_skeletons(const uint8_t* label, const int* classes, int K, uint8_t* out, int B, int H, int W, int D, int iters,
+                        ltu_stream_t s);
+/* The fifth stage of a level's loss chain: soft-clDice (Shit et al., CVPR 2021), one term per named class.  p f32 [B][H][W][D][C]
+ * probabilities (2 <= C <= 8), label u8 [B][H][W][D], skel u8 [B][K][H][W][D] (ltu_label_skeletons with the same classes and iters).
+ * Term k, c = classes[k] (distinct, < C): P = p[..., c], G = [label == c], S_P = skeleton(P), S_G = skel[:, k], sums over the batch:
+ *     Tprec = (sum S_P G + 1) / (sum S_P + 1)    Tsens = (sum S_G P + 1) / (sum S_G + 1)    value_k = 1 - 2 Tprec Tsens / (Tprec + Tsens)
+ * values [K + 1] = {total, value_0 ..}, total = (base_total ? base_total[0] : 0) + scale sum_k w[k] value_k, scale = scale_dev ?
+ * scale_dev[0] : 1 read on the device.  bwd: dp[..., c] gets gscale[0] times the gradient (through S_P, and S_G / (sum S_G + 1)
+ * directly), written with zeros in every other channel (accumulate == 0) or added into what dp holds.  The sums are taken in double
+ * and folded in a fixed order; no atomics, no host read, capturable; two calls agree bit for bit.
+ * scratch: ltu_loss_cldice_scratch_elems(..) 4-byte elements on an 8-byte boundary (else LTU_E_ALIGN), no initialisation; the backward reads the
+ * scratch its forward wrote (with the same classes and iters).
+ * LTU_E_SHAPE: C outside 2 .. 8, K outside 1 .. 8, an extent < 1; LTU_E_ARG: a NULL pointer (base_total and scale_dev may be), iters
+ * outside 1 .. 10, a class >= C or listed twice, a non-finite weight, a short scratch; all before anything is launched. */
+long long ltu_loss_cldice_scratch_elems(int B, int H, int W, int D, int K, int iters);
+int ltu_loss_cldice_fwd(const float* p, const uint8_t* label, const uint8_t* skel, const int* classes, const float* w, int K, int iters,
+                        void* scratch, long long scratch_elems, float* values /* K + 1 */, const float* base_total,
+                        const float* scale_dev, int B, int H, int W, int D, int C, ltu_stream_t s);
+int ltu_loss_cldice_bwd(const float* p, const uint8_t* label, const int* classes, int K, int iters, void* scratch,
+                        long long scratch_elems, const float* gscale, float* dp, int accumulate, int B, int H, int W, int D, int C,
+                        ltu_stream_t s);
 /* label pyramid (utils/utils_3D_embed_full.py:64,73-76): u8 [B,H,W,D] -> max over (2,2,kd) windows */
 int ltu_label_maxpool(const uint8_t* x, uint8_t* y, int B, int H, int W, int D, int kd, ltu_stream_t s);
 

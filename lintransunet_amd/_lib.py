@@ -187,6 +187,15 @@ SIGNATURES = {
     'ltu_loss_imb_ws_floats': [I, L, I],
     'ltu_loss_imb_fwd': [P, P, P, L, P, P, P, P, P, I, P, F, F, P, P, I, L, I, P],
     'ltu_loss_imb_bwd': [P, P, P, L, F, P, P, I, I, L, I, P],
+    'ltu_soft_skeleton_scratch_elems': [L, I, I, I, I],
+    'ltu_soft_morph_fwd': [P, P, P, I, L, I, I, I, P],
+    'ltu_soft_morph_bwd': [P, P, P, I, L, I, I, I, P],
+    'ltu_soft_skeleton_fwd': [P, P, P, L, L, I, I, I, I, P],
+    'ltu_soft_skeleton_bwd': [P, P, P, P, L, L, I, I, I, I, P],
+    'ltu_label_skeletons': [P, P, I, P, I, I, I, I, I, P],
+    'ltu_loss_cldice_scratch_elems': [I, I, I, I, I, I],
+    'ltu_loss_cldice_fwd': [P, P, P, P, P, I, I, P, L, P, P, P, I, I, I, I, I, P],
+    'ltu_loss_cldice_bwd': [P, P, P, I, I, P, L, P, P, I, I, I, I, I, I, P],
     'ltu_label_maxpool': [P, P, I, I, I, I, I, P],
     'ltu_comm_load': [ctypes.c_char_p],
     'ltu_comm_unique_id': [P],
@@ -224,7 +233,8 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = args
         fn.restype = c_longlong if (name.endswith(('_ws_floats', '_ws_elems')) or name in ('ltu_layer_tail_blocks', 'ltu_grad_sumsq_parts', 'ltu_crop_index_elems', 'ltu_distmap_scratch_elems',
-                                                                                           'ltu_loss_boundary_sums_floats', 'ltu_loss_topk_scratch_elems',
+                                                                                           'ltu_loss_boundary_sums_floats', 'ltu_loss_topk_scratch_elems', 'ltu_soft_skeleton_scratch_elems',
+                                                                                           'ltu_loss_cldice_scratch_elems',
                                                                                            'ltu_patch_stats_parts_elems')) else c_int
     for name, args in EXPERIMENT_SIGNATURES.items():
         fn = getattr(lib, name, None)

@@ -9,6 +9,7 @@ decoder level share one streaming reduction (`LevelCriterion`).
 """
 import dataclasses
 import math
+import types
 from typing import Optional, Tuple
 
 import torch
@@ -95,6 +96,10 @@ class LevelCriterion(nn.Module):
       (class 1), 'TverskyLoss2' .. 'TverskyLoss7' and 'TverskyLoss0c' (class 0) are (1 - TI_c)^(1 / gamma) with TI the Tversky index
       of the class, per sample or over the batch; 'FocalCELoss' is the mean of alpha[label] (1 - p[label])^gamma (-log max(p[label],
       1e-6)) over all voxels (see ops.level_loss_imbalance).
+    cldice - 'ClDiceLoss' (class 1), 'ClDiceLoss2' .. 'ClDiceLoss7' and 'ClDiceLoss0c' (class 0): the soft-clDice of Shit et al. of the
+      class, 1 - 2 Tprec Tsens / (Tprec + Tsens) on soft skeletons of `cldice_iters` (1 .. 10) iterations, sums over the batch
+      (ops.level_loss_cldice; csrc/softmorph.hip).  Needs 3-D patches; the label skeletons are built from the label patch
+      (ops.label_skeletons) or given to forward as `skeletons` [B,K,...] in the order of `cldice_classes`.
     Returns (total, {name: w * value}) with values detached: what the reference scripts log (`criterions_w * l(...)`,
     utils_3D_multi_class.py:85; all weights are 1 in the single-class script).
     """
@@ -110,12 +115,13 @@ class LevelCriterion(nn.Module):
     TOPK = 'TopKCELoss'     # top-k cross-entropy (csrc/loss_topk.hip)
     TVERSKY = _class_names('TverskyLoss')       # Tversky term (csrc/loss_imbalance.hip) of class ...
     FOCALCE = 'FocalCELoss'     # focal cross-entropy (csrc/loss_imbalance.hip)
+    CLDICE = _class_names('ClDiceLoss')         # soft-clDice term (csrc/softmorph.hip) of class ...
     # the names each stage of ops.level_loss_chain owns, in chain order, and the class a name stands for (None: no single class)
     OWNED = {'base': dict(dict.fromkeys([*_TERM, *EXT]), **_class_names('DiceClassLoss')), 'boundary': BOUNDARY,
-             'topk': {TOPK: None}, 'imbalance': dict(TVERSKY, **{FOCALCE: None})}
+             'topk': {TOPK: None}, 'imbalance': dict(TVERSKY, **{FOCALCE: None}), 'cldice': CLDICE}
 
     def __init__(self, spec: dict, scale: float = 1.0, scale_dev=None, params=None, spacing=(1.0, 1.0, 1.0), term_scale_dev=None,
-                 topk_fraction: float = 0.1, topk_fraction_dev=None, imbalance=None):
+                 topk_fraction: float = 0.1, topk_fraction_dev=None, imbalance=None, cldice_iters: int = 3):
         super().__init__()
         if 'DistributionLoss' in spec:
             raise KeyError(_DISTRIBUTION_REFUSED)
@@ -140,6 +146,13 @@ class LevelCriterion(nn.Module):
         if self.topk and topk_fraction_dev is None and not 0.0 < self.topk_fraction <= 1.0:
             raise ValueError(f'topk_fraction {topk_fraction} outside (0, 1]')
         self.topk_fraction_dev = topk_fraction_dev      # 1-element fp32 device tensor: the fraction, read at run time
+        self.cldice = self.names['cldice']
+        self.cldice_iters = ops._check_iters(cldice_iters, 'cldice_iters')      # of the soft skeletons; raises ValueError
+
+    @property
+    def cldice_classes(self):
+        """the classes of the spec's clDice names, in the order of the label skeletons that forward builds or takes"""
+        return tuple(self.CLDICE[name] for name in self.cldice)
 
     @property
     def boundary_classes(self):
@@ -168,7 +181,7 @@ class LevelCriterion(nn.Module):
                 wd[n if cls == self.FG else cls] += self.spec[name] * self.scale
         return wd
 
-    def forward(self, predict, target, params=None, phi=None):
+    def forward(self, predict, target, params=None, phi=None, skeletons=None):
         C = predict.shape[1]
         self._check_classes(C)
         if self.extended and C > self.EXT_MAXC:
@@ -179,7 +192,8 @@ class LevelCriterion(nn.Module):
         p = _channels_last(predict)
         lab = _labels(target, C)
         present = [key for key, names in self.names.items() if names] or ['base']      # no name at all: the base, at weight 0
-        args = {key: arg(self, C, lab, params, phi) for key, _, arg, _ in self._STAGES if key in present}
+        side = types.SimpleNamespace(phi=phi, skeletons=skeletons)      # what a stage may take ready-made instead of building it from the label
+        args = {key: arg(self, C, lab, params, side) for key, _, arg, _ in self._STAGES if key in present}
         total, *reports = ops.level_loss_chain(p, lab, scale_dev=self.scale_dev, **args)
         value = {}
         for (key, _, _, entries), report in zip(self._STAGES, reports):
@@ -211,36 +225,49 @@ class LevelCriterion(nn.Module):
         cls = self._DICE[name]
         return 3 + ((4 if C <= 4 else C) if cls == self.FG else cls)
 
-    def _boundary_arg(self, C, lab, params, phi):
+    def _boundary_arg(self, C, lab, params, side):
+        phi = side.phi
         if phi is None:
             if lab.dim() != 4:
                 raise ValueError('the boundary term builds its distance maps from 3-D label patches [B,1,H,W,D]; pass `phi` otherwise')
             phi = ops.signed_distance_maps(lab, self.boundary_classes, self.spacing)
         return phi, self.boundary_classes, [self.spec[name] * self.scale for name in self.boundary], self.term_scale_dev
 
-    def _imbalance_arg(self, C, lab, params, phi):
+    def _imbalance_arg(self, C, lab, params, side):
         im = self.imbalance or Imbalance()
         tversky = [self.TVERSKY[name] for name in self.tversky], [self.spec[name] * self.scale for name in self.tversky], im.tversky_params
         focal = self.spec.get(self.FOCALCE, 0.0) * self.scale, im.focal_gamma, im.focal_alpha
         return tversky if self.tversky else None, focal if self.focalce else None
 
+    def _cldice_arg(self, C, lab, params, side):
+        if lab.dim() != 4:
+            raise ValueError('the clDice term skeletonises 3-D patches: predict [B,C,H,W,D], target [B,1,H,W,D]')
+        return side.skeletons, self.cldice_classes, [self.spec[name] * self.scale for name in self.cldice], self.cldice_iters
+
     # one row per stage of ops.level_loss_chain, in chain order: its keyword there, what the check of its names' classes says,
-    # (self, C, lab, params, phi) -> its argument, (self, C) -> where its report holds the value of each of its names
+    # (self, C, lab, params, side: the maps and skeletons given to forward) -> its argument, (self, C) -> where its report holds the value of each of its names
     _STAGES = (('base', 'the Dice of a class the prediction does not have',
-                lambda self, C, lab, params, phi: self._base_entry(C, dict(self.params, **(params or {}))),
+                lambda self, C, lab, params, side: self._base_entry(C, dict(self.params, **(params or {}))),
                 lambda self, C: [self._value_index(name, C) for name in self.base_names]),
                ('boundary', 'the boundary term of a class the prediction does not have', _boundary_arg,
                 lambda self, C: range(len(self.boundary))),
                ('topk', 'needs a prediction of at least 2 classes',
-                lambda self, C, lab, params, phi: (self.spec[self.TOPK] * self.scale, self.topk_fraction, self.topk_fraction_dev),
+                lambda self, C, lab, params, side: (self.spec[self.TOPK] * self.scale, self.topk_fraction, self.topk_fraction_dev),
                 lambda self, C: [0]),
                ('imbalance', 'a term of a class the prediction does not have', _imbalance_arg,
-                lambda self, C: [self.tversky.index(name) if name != self.FOCALCE else len(self.tversky) for name in self.names['imbalance']]))
+                lambda self, C: [self.tversky.index(name) if name != self.FOCALCE else len(self.tversky) for name in self.names['imbalance']]),
+               ('cldice', 'the clDice term of a class the prediction does not have', _cldice_arg,
+                lambda self, C: range(len(self.cldice))))
 
 
 def stage_names(spec):
     """{stage of ops.level_loss_chain: the names of `spec` that it owns, in spec order}, the stages in chain order"""
     return {key: [name for name in spec if name in owned] for key, owned in LevelCriterion.OWNED.items()}
+
+
+def cldice_classes(spec):
+    """the classes of the clDice names of `spec`, in the order of the label skeletons a LevelCriterion of it builds or takes"""
+    return tuple(LevelCriterion.CLDICE[name] for name in stage_names(spec)['cldice'])
 
 
 def boundary_classes(spec):
@@ -460,6 +487,24 @@ class FocalCELoss(nn.Module):
         return self.impl(predict, target)[0]
 
 
+def cldice_name(class_index: int) -> str:
+    """the spec name of the clDice term of class `class_index`: 'ClDiceLoss0c', 'ClDiceLoss', 'ClDiceLoss2' .. 'ClDiceLoss7'"""
+    return _class_name('ClDiceLoss', class_index)
+
+
+class ClDiceLoss(nn.Module):
+    """Shit et al., "clDice - a novel topology-preserving loss function for tubular structure segmentation" (CVPR 2021; no reference
+    counterpart): the soft-clDice of class `class_index` on soft skeletons of `iters` iterations (ops.level_loss_cldice, which lists
+    the differences from the published loss: one class per term, smooth fixed at 1)"""
+
+    def __init__(self, class_index: int = 1, iters: int = 3):
+        super().__init__()
+        self.impl = LevelCriterion({cldice_name(class_index): 1.0}, cldice_iters=iters)
+
+    def forward(self, predict, target, skeletons=None):
+        return self.impl(predict, target, skeletons=skeletons)[0]
+
+
 class _EvalMetric(nn.Module):
     """the evaluation losses train3D.py:143 requests besides the Dice losses (`eval_list`): computed on the un-thresholded class
     probabilities by the metric kernels of the inference driver (csrc/infer.hip); evaluation only, no gradient"""
@@ -520,6 +565,7 @@ Loss_Dict = {
     'TopKCELoss': TopKCELoss,
     'TverskyLoss': TverskyLoss,
     'FocalCELoss': FocalCELoss,
+    'ClDiceLoss': ClDiceLoss,
     'Recall': Recall,
     'Precision': Precision,
 }
@@ -528,8 +574,8 @@ Loss_Dict = {
 def get_criterions(name_list):
     """loss/criterions.py:773-782, and the training losses of loss/multi_criterions.py that a `--criterion_list` can name
     (BalanceDiceLoss2, CrossEntroLoss0, ClassifyLoss, DiceClassLoss0, DiceClassLoss2), and BoundaryLoss (class 1, unit spacing) and
-    TopKCELoss (k = 10 percent), and TverskyLoss (class 1, alpha 0.3, beta 0.7) and FocalCELoss (gamma 2).  DistributionLoss is
-    refused."""
+    TopKCELoss (k = 10 percent), and TverskyLoss (class 1, alpha 0.3, beta 0.7) and FocalCELoss (gamma 2), and ClDiceLoss (class 1, 3
+    iterations).  DistributionLoss is refused."""
     if 'DistributionLoss' in name_list:
         raise KeyError(_DISTRIBUTION_REFUSED)
     return {name: Loss_Dict[name]() for name in name_list}

@@ -1857,6 +1857,62 @@ def imbalance_stage(tversky=None, focal=None, C=None):
     return _ImbalanceStage((tversky, focal), C)
 
 
+SOFT_SKELETON_MAX_ITERS = 10      # SM_MAX_ITERS of csrc/softmorph.hip
+CLDICE_MAX_TERMS = 8        # most clDice terms of one ltu_loss_cldice_* call
+
+
+def _check_iters(iters, what):
+    if int(iters) != iters or not 1 <= int(iters) <= SOFT_SKELETON_MAX_ITERS:
+        raise ValueError(f'{what}: iters {iters} outside 1 .. {SOFT_SKELETON_MAX_ITERS}')
+    return int(iters)
+
+
+class _ClDiceStage(_Stage):
+    """cldice = (skeletons, classes, weights, iters), see level_loss_cldice (csrc/softmorph.hip); every check raises ValueError.
+    buf = [total, value_0 .. value_{K-1}]; the one saved tensor is the scratch, which also keeps the label skeletons"""
+
+    def __init__(self, cldice, C):
+        self.skel, classes, weights, iters = cldice
+        self.iters = _check_iters(iters, 'clDice stage')
+        self.K = len(classes)
+        if len(weights) != self.K or not 1 <= self.K <= CLDICE_MAX_TERMS:
+            raise ValueError(f'clDice stage: 1 .. {CLDICE_MAX_TERMS} classes, one weight each')
+        if len(set(int(c) for c in classes)) != self.K or any(int(c) < 0 or (C is not None and int(c) >= C) for c in classes):
+            raise ValueError(f'clDice stage: classes {tuple(classes)} must be distinct and inside the {C} classes of the prediction')
+        if not all(math.isfinite(float(w)) for w in weights):
+            raise ValueError('clDice stage: non-finite weight')
+        self.classes = tuple(int(c) for c in classes)
+        self.cls, self.wv = _int_array(classes), _float_array(weights)
+
+    def check(self, p, label, phi):
+        if p.dim() != 5 or not 2 <= p.shape[-1] <= LOSS_WIDE_MAXC:
+            raise ValueError(f'clDice stage: p must be [B, H, W, D, C] with 2 .. {LOSS_WIDE_MAXC} classes, got {tuple(p.shape)}')
+        if p.dtype != torch.float32 or label.dtype != torch.uint8 or tuple(label.shape) != tuple(p.shape[:-1]):
+            raise ValueError('clDice stage: p must be fp32 and label uint8 [B, H, W, D] over the voxels of p')
+        if self.skel is not None:
+            _chk(self.skel, 'skeletons')
+            if self.skel.dtype != torch.uint8 or tuple(self.skel.shape) != (p.shape[0], self.K, *p.shape[1:4]):
+                raise ValueError(f'clDice stage: skeletons must be uint8 [B, {self.K}, H, W, D] (label_skeletons)')
+        self.dims = tuple(p.shape[1:4])
+
+    def forward(self, p, label, phi, before, scale_dev, B, S, C):
+        skel, self.skel = self.skel, None      # not kept past the forward: the scratch carries what the backward reads
+        if skel is None:
+            skel = label_skeletons(label, self.classes, self.iters)
+        need = _lib.load().ltu_loss_cldice_scratch_elems(B, *self.dims, self.K, self.iters)
+        if need <= 0:
+            raise _lib.LtuError('ltu_loss_cldice_scratch_elems: a shape the calls refuse')
+        scratch = torch.empty((need + 1) // 2, device=p.device, dtype=torch.float64).view(torch.float32)      # doubles first: 8-byte aligned, no fill
+        buf = torch.empty(self.K + 1, device=p.device, dtype=torch.float32)
+        _lib.call('ltu_loss_cldice_fwd', _p(p), _p(label), _p(skel), self.cls, self.wv, self.K, self.iters, _p(scratch), _n(scratch),
+                  _p(buf), _p(before), _p(scale_dev), B, *self.dims, C, _s())
+        return buf, scratch
+
+    def backward(self, scratch, p, label, g, dp, written, scale_dev, B, S, C):
+        _lib.call('ltu_loss_cldice_bwd', _p(p), _p(label), self.cls, self.K, self.iters, _p(scratch), _n(scratch), _p(g), _p(dp), written,
+                  B, *self.dims, C, _s())
+
+
 class _LevelLossChain(torch.autograd.Function):
     """The loss of one decoder level as a chain of stages (objects of the classes above, in the order level_loss_chain gives them)
     on the maps `phi` (None without a boundary stage).  Each forward adds the total before it and each backward adds into the dp
@@ -1890,20 +1946,21 @@ class _LevelLossChain(torch.autograd.Function):
         return (dp,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
-def level_loss_chain(p, label, base=None, boundary=None, topk=None, scale_dev=None, imbalance=None):
+def level_loss_chain(p, label, base=None, boundary=None, topk=None, scale_dev=None, imbalance=None, cldice=None):
     """p fp32 [B,...,C] channels-last probabilities, label uint8 [B,...]: the sum of the given stages, at least one, in one autograd
     node.  base = ('ltu_loss' | 'ltu_loss_wide', (w_ce, w_bal, w_dice)) or ('ltu_loss_ext', loss_ext_cfg(..)), as level_loss /
     level_loss_wide / level_loss_ext launch it; boundary = (phi, classes, weights, term_scale_dev), see level_loss_boundary; topk =
-    (weight, frac, frac_dev), see level_loss_topk; imbalance = (tversky, focal), see level_loss_imbalance, runs last.  scale_dev:
-    optional 1-element fp32 device tensor multiplying all weights at run time.  Returns (total, base values, boundary values, top-k
-    values, imbalance values), None for a stage not given, values detached; every check is made before the first launch and there
-    is no host synchronisation."""
+    (weight, frac, frac_dev), see level_loss_topk; imbalance = (tversky, focal), see level_loss_imbalance; cldice = (skeletons or
+    None, classes, weights, iters), see level_loss_cldice, runs last and needs p as [B,H,W,D,C].  scale_dev: optional 1-element fp32
+    device tensor multiplying all weights at run time.  Returns (total, base values, boundary values, top-k values, imbalance
+    values, clDice values), None for a stage not given, values detached; every check is made before the first launch and there is
+    no host synchronisation."""
     phi, *_ = boundary or [None]      # the maps travel beside the stages: the chain saves them for the backward
-    args = {_BaseStage: base, _BoundaryStage: boundary, _TopkStage: topk, _ImbalanceStage: imbalance}      # in chain order
+    args = {_BaseStage: base, _BoundaryStage: boundary, _TopkStage: topk, _ImbalanceStage: imbalance, _ClDiceStage: cldice}      # in chain order
     if all(arg is None for arg in args.values()):
-        raise ValueError('level_loss_chain: at least one of base, boundary, topk and imbalance')
+        raise ValueError('level_loss_chain: at least one of base, boundary, topk, imbalance and cldice')
+    stages = [stage(arg, p.shape[-1]) for stage, arg in args.items() if arg is not None]      # the host checks of the arguments
     _chk(p, 'p'); _chk(label, 'label')
-    stages = [stage(arg, p.shape[-1]) for stage, arg in args.items() if arg is not None]
     for stage in stages:
         stage.check(p, label, phi)
     out = iter(_LevelLossChain.apply(p, label, phi, scale_dev, stages))
@@ -1981,7 +2038,7 @@ def level_loss_topk(p, label, weight, frac=0.1, frac_dev=None, base=None, scale_
     Returns (total, base values or None, (value, tau)), values detached; no host synchronisation.
     boundary = (phi, classes, weights, term_scale_dev) puts the boundary terms of level_loss_boundary between the two; their values
     are then returned as a fourth entry."""
-    total, base_values, bnd_values, values, _ = level_loss_chain(p, label, base, boundary, (weight, frac, frac_dev), scale_dev)
+    total, base_values, bnd_values, values, *_ = level_loss_chain(p, label, base, boundary, (weight, frac, frac_dev), scale_dev)
     return (total, base_values, values) if boundary is None else (total, base_values, values, bnd_values)
 
 
@@ -1997,5 +2054,112 @@ def level_loss_imbalance(p, label, tversky=None, focal=None, base=None, scale_de
     label >= C belong to no class: they add to FP only, add 0 to the focal term and count in B S.  Two calls agree bit for bit.
     Returns (total, base values or None, (Tversky values .., focal value)), values detached; every check is made before the first
     launch and there is no host synchronisation."""
-    total, base_values, _, _, values = level_loss_chain(p, label, base, scale_dev=scale_dev, imbalance=(tversky, focal))
+    total, base_values, _, _, values, _ = level_loss_chain(p, label, base, scale_dev=scale_dev, imbalance=(tversky, focal))
+    return total, base_values, values
+
+
+class _SoftMorph(torch.autograd.Function):
+    """op 0: soft_erode, 1: soft_dilate; the saved tensor is the tap code of every output voxel"""
+
+    @staticmethod
+    def forward(ctx, x, op):
+        N, (H, W, D) = x.numel() // (x.shape[-3] * x.shape[-2] * x.shape[-1]), x.shape[-3:]
+        y = torch.empty_like(x)
+        tap = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
+        _lib.call('ltu_soft_morph_fwd', _p(x), _p(y), _p(tap), op, N, H, W, D, _s())
+        ctx.op, ctx.dims = op, (N, H, W, D)
+        ctx.save_for_backward(tap)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        tap, = ctx.saved_tensors
+        g = g.contiguous()
+        dx = torch.empty_like(g)
+        _lib.call('ltu_soft_morph_bwd', _p(g), _p(tap), _p(dx), ctx.op, *ctx.dims, _s())
+        return dx, None
+
+
+class _SoftSkeleton(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, iters):
+        N, (H, W, D) = x.numel() // (x.shape[-3] * x.shape[-2] * x.shape[-1]), x.shape[-3:]
+        need = _lib.load().ltu_soft_skeleton_scratch_elems(N, H, W, D, iters)
+        if need <= 0:
+            raise _lib.LtuError('ltu_soft_skeleton_scratch_elems: a shape the calls refuse')
+        scratch = torch.empty(need, device=x.device, dtype=torch.float32)      # I_1 .., the taps, the backward's volumes: no fill
+        y = torch.empty_like(x)
+        _lib.call('ltu_soft_skeleton_fwd', _p(x), _p(y), _p(scratch), _n(scratch), N, H, W, D, iters, _s())
+        ctx.iters, ctx.dims = iters, (N, H, W, D)
+        ctx.save_for_backward(x, scratch)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, scratch = ctx.saved_tensors
+        g = g.contiguous()
+        dx = torch.empty_like(x)
+        _lib.call('ltu_soft_skeleton_bwd', _p(x), _p(g), _p(dx), _p(scratch), _n(scratch), *ctx.dims, ctx.iters, _s())
+        return dx, None
+
+
+def _volume(x, what):
+    _chk(x, 'x')
+    if x.dtype != torch.float32 or x.dim() < 3:
+        raise ValueError(f'{what}: x must be fp32 [..., H, W, D]')
+    return x
+
+
+def soft_erode(x):
+    """x fp32 [..., H, W, D] -> the minimum over the 7-voxel cross (centre, -H, +H, -W, +W, -D, +D), the published 3-D soft_erode;
+    taps outside the volume are left out.  Backward: the whole gradient of an output voxel goes to the first tap that attains the
+    minimum, the centre first (csrc/softmorph.hip); a gather, two calls agree bit for bit."""
+    return _SoftMorph.apply(_volume(x, 'soft_erode'), 0)
+
+
+def soft_dilate(x):
+    """x fp32 [..., H, W, D] -> the maximum over the 3 x 3 x 3 cube; taps and ties as soft_erode, the centre first and then the other
+    26 in raster order of (dh, dw, dd)."""
+    return _SoftMorph.apply(_volume(x, 'soft_dilate'), 1)
+
+
+def soft_skeleton(x, iters):
+    """x fp32 [..., H, W, D], 1 <= iters <= 10 -> the soft skeleton of clDice: I_0 = x, I_{j+1} = erode(I_j), delta_j = relu(I_j -
+    dilate(I_{j+1})), s_0 = delta_0, s_j = s_{j-1} + relu(delta_j - s_{j-1} delta_j), result s_iters (the published soft_skel with
+    soft_open(I_j) = dilate(erode(I_j))); differentiable, tie rule of soft_erode / soft_dilate, relu'(0) = 0."""
+    iters = _check_iters(iters, 'soft_skeleton')
+    return _SoftSkeleton.apply(_volume(x, 'soft_skeleton'), iters)
+
+
+def label_skeletons(label, classes, iters):
+    """label uint8 [B,H,W,D], classes: K distinct class ids (1 <= K <= 8) -> uint8 [B,K,H,W,D], byte for byte the soft skeleton of
+    the 0 / 1 maps [label == classes[k]] (on which every value of the chain stays 0 or 1), computed on the bytes of the result
+    alone: no float volume, no other allocation, no host read."""
+    _chk(label, 'label')
+    if label.dtype != torch.uint8 or label.dim() != 4:
+        raise ValueError('label_skeletons: label must be uint8 [B,H,W,D]')
+    K = len(classes)
+    if not 1 <= K <= CLDICE_MAX_TERMS or len(set(int(c) for c in classes)) != K or any(not 0 <= int(c) <= 255 for c in classes):
+        raise ValueError(f'label_skeletons: 1 .. {CLDICE_MAX_TERMS} distinct classes')
+    iters = _check_iters(iters, 'label_skeletons')
+    B, H, W, D = label.shape
+    out = torch.empty((B, K, H, W, D), device=label.device, dtype=torch.uint8)
+    _lib.call('ltu_label_skeletons', _p(label), _int_array(classes), K, _p(out), B, H, W, D, iters, _s())
+    return out
+
+
+def level_loss_cldice(p, label, classes, weights, iters=3, base=None, scale_dev=None, skeletons=None):
+    """p fp32 [B,H,W,D,C] channels-last probabilities (2 <= C <= 8), label uint8 [B,H,W,D]: the level's existing loss `base` (as
+    level_loss_boundary takes it, or None) plus scale_dev[0] * sum_k weights[k] * value_k, the soft-clDice of Shit et al. (CVPR
+    2021) for each named class c = classes[k] (1 .. 8 distinct classes): with P = p[..., c], G = [label == c], S_P =
+    soft_skeleton(P, iters), S_G = the label skeleton (label_skeletons; `skeletons` [B,K,H,W,D] if built elsewhere) and sums over
+    the whole batch, Tprec = (sum S_P G + 1) / (sum S_P + 1), Tsens = (sum S_G P + 1) / (sum S_G + 1), value = 1 - 2 Tprec Tsens /
+    (Tprec + Tsens).  Differences from the published loss: one term per named class, not one over all foreground channels merged
+    (the same for a single foreground class); smooth is fixed at 1; labels >= C belong to no class.  A class absent from the label
+    gives Tsens = 1.  The gradient reaches p[..., c] only, through S_P and directly.  Two calls agree bit for bit.
+    Returns (total, base values or None, clDice values [K]), values detached; every check is made before the first launch and there
+    is no host synchronisation."""
+    if p.dim() != 5:
+        raise ValueError(f'level_loss_cldice: p must be [B, H, W, D, C], got {tuple(p.shape)}')
+    total, base_values, *_, values = level_loss_chain(p, label, base, scale_dev=scale_dev, cldice=(skeletons, classes, weights, iters))
     return total, base_values, values

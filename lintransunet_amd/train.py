@@ -15,7 +15,7 @@ import torch.distributed as dist
 
 from . import comm as _comm
 from . import ops
-from .losses import LevelCriterion, boundary_classes, stage_names
+from .losses import LevelCriterion, boundary_classes, cldice_classes, stage_names
 
 
 def get_weight(t, T, default_weight=0.2, initial_weight=1.0, final_weight=1.0):
@@ -75,6 +75,16 @@ def boundary_maps(pyr, specs, spacing=(1.0, 1.0, 1.0)):
     return phis
 
 
+def skeleton_maps(pyr, specs, iters=3):
+    """label skeletons for the levels whose spec has a clDice name (losses.cldice_classes), from the pyramid's labels: a list over
+    levels of uint8 [B,K,h,w,d] (ops.label_skeletons with `iters` iterations) or None"""
+    skels = []
+    for lvl in range(len(pyr)):
+        classes = cldice_classes(specs[-lvl - 1])
+        skels.append(ops.label_skeletons(pyr[lvl], classes, iters) if classes else None)
+    return skels
+
+
 def has_boundary(specs):
     return any(stage_names(spec)['boundary'] for spec in specs)
 
@@ -84,7 +94,7 @@ def has_topk(specs):
 
 
 def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0, level_scale=None, pyr=None, spacing=(1.0, 1.0, 1.0),
-                          boundary_scale=None, phis=None, topk_fraction=0.1, imbalance=None):
+                          boundary_scale=None, phis=None, topk_fraction=0.1, imbalance=None, cldice_iters=3, skels=None):
     """Per-level fused losses (utils/utils_3D_embed_full.py:66-82).  Returns (list of weighted level totals,
     list of {name: value}); `sum(totals)` is the reference's total_loss * scale.
     level_scale: optional fp32 device tensor [n_levels] that REPLACES `weights[lvl] * scale` at run time (a captured graph
@@ -95,47 +105,53 @@ def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0,
     topk_fraction: the fraction of the hardest voxels that 'TopKCELoss' averages over, the same at every level: a number, or a
     1-element fp32 device tensor read at run time.
     imbalance: a losses.Imbalance record, the parameters of the 'TverskyLoss..' and 'FocalCELoss' names at every level (None: its
-    defaults)."""
+    defaults).
+    cldice_iters: iterations of the soft skeletons of the 'ClDiceLoss..' names at every level (1 .. 10); skels: the levels' label
+    skeletons, already built (skeleton_maps with the same iters).  A spec list without clDice names uses neither."""
     n = len(weights)
     specs = specs or level_specs(n)
     pyr = pyr or label_pyramid(label, n)      # pyr: the pyramid, already built (train_step builds it beside the encoder)
     if phis is None:
         phis = boundary_maps(pyr, specs, spacing)      # None at the levels without a boundary name: nothing is launched for them
+    if skels is None:
+        skels = skeleton_maps(pyr, specs, cldice_iters)
     kw = {'topk_fraction_dev': topk_fraction} if torch.is_tensor(topk_fraction) else {'topk_fraction': topk_fraction}
     totals, named = [], []
     for lvl in range(n):
         pred = predict if lvl == 0 else masks[-lvl]
         crit = LevelCriterion(specs[-lvl - 1], scale=weights[lvl] * scale if level_scale is None else 1.0,
                               scale_dev=None if level_scale is None else level_scale[lvl:lvl + 1], term_scale_dev=boundary_scale,
-                              imbalance=imbalance, **kw)
-        tot, vals = crit(pred, pyr[lvl].unsqueeze(1), phi=phis[lvl])
+                              imbalance=imbalance, cldice_iters=cldice_iters, **kw)
+        tot, vals = crit(pred, pyr[lvl].unsqueeze(1), phi=phis[lvl], skeletons=skels[lvl])
         totals.append(tot)
         named.append(vals)
     return totals, named
 
 
 def train_step(model, images, labels, weights, step_times=1, specs=None, reducer=None, ctx=None, level_scale=None, reduce=True,
-               spacing=(1.0, 1.0, 1.0), boundary_scale=None, topk_fraction=0.1, imbalance=None):
+               spacing=(1.0, 1.0, 1.0), boundary_scale=None, topk_fraction=0.1, imbalance=None, cldice_iters=3):
     """forward + 5-level loss + backward for one batch of patches (one `j` of utils_3D_embed_full.py:55-86).
     Returns the list of weighted level losses (device scalars, no host sync).
     Gradient accumulation (utils_3D_embed_full.py:85-91): call `step_times` times with reduce=False except on the last
     micro-step; the caller zeroes the gradients before the first one.
     spacing, boundary_scale: see deep_supervision_loss; the distance maps of the levels with a boundary name are built behind the
-    label pyramid on the side stream.  topk_fraction, imbalance: see deep_supervision_loss."""
+    label pyramid on the side stream, as are the label skeletons of the levels with a clDice name.  topk_fraction, imbalance,
+    cldice_iters: see deep_supervision_loss."""
     lc = ctx or ops.current()
     with ops.use(lc):
         lc.begin_step(images.device)
-        pyr, phis = [], []
+        pyr, phis, skels = [], [], []
 
         def side():
             pyr.extend(label_pyramid(labels, len(weights)))
             phis.extend(boundary_maps(pyr, specs or level_specs(len(weights)), spacing))
+            skels.extend(skeleton_maps(pyr, specs or level_specs(len(weights)), cldice_iters))
         lc.side_run(side)                    # beside the encoder (joined inside the model's forward)
         predict, masks = model(images)
         lc.side_join()
         totals, named = deep_supervision_loss(predict, masks, labels, weights, specs, scale=1.0 / step_times, level_scale=level_scale,
                                               pyr=pyr, spacing=spacing, boundary_scale=boundary_scale, phis=phis,
-                                              topk_fraction=topk_fraction, imbalance=imbalance)
+                                              topk_fraction=topk_fraction, imbalance=imbalance, cldice_iters=cldice_iters, skels=skels)
         if reducer is not None:
             reducer.prepare(lc, reduce=reduce)
         one = lc.one(images.device)
@@ -344,16 +360,18 @@ class GraphedStep:
       the patch's voxels) lives in another: `set_boundary_scale(a)`.  The fraction of 'TopKCELoss' (the same at all levels) lives in
       a third: `set_topk_fraction(f)`, e.g. annealed from 1.0 (plain cross-entropy) down to 0.1.  The parameters of the
       'TverskyLoss..' and 'FocalCELoss' names (`imbalance`, a losses.Imbalance record) are host arguments of their kernels and are
-      baked into the capture: there is no run-time setter for them; build a new step to change them.
+      baked into the capture: there is no run-time setter for them; build a new step to change them.  The same holds for
+      `cldice_iters`, the iterations of the soft skeletons of the 'ClDiceLoss..' names.
     * every replay first checks that parameter and gradient storage is where it was at capture time (e.g. an optimizer built
       afterwards that re-homes `p.data`); if not, the step is captured again.
     * the step owns its `ops.Context` (scratch arena frozen after capture), so other graphs / eager steps cannot move it.
     """
 
     def __init__(self, model, images, labels, weights, reducer, step_times=1, specs=None, warmup=2, overlap=None,
-                 spacing=(1.0, 1.0, 1.0), boundary_scale=1.0, topk_fraction=0.1, imbalance=None):
+                 spacing=(1.0, 1.0, 1.0), boundary_scale=1.0, topk_fraction=0.1, imbalance=None, cldice_iters=3):
         self.model, self.reducer = model, reducer
         self.imbalance = imbalance
+        self.cldice_iters = ops._check_iters(cldice_iters, 'cldice_iters')
         self.spacing = tuple(float(v) for v in spacing)
         self.step_times, self.specs, self.warmup = int(step_times), specs, warmup
         self.n_levels = len(weights)
@@ -429,7 +447,8 @@ class GraphedStep:
                               reducer=self.reducer, ctx=self.ctx, level_scale=self.level_scale,
                               reduce=reduce and self.overlap in ('graph', 'segments'), spacing=self.spacing,
                               boundary_scale=self.boundary_scale,
-                              topk_fraction=0.1 if self.topk_fraction is None else self.topk_fraction, imbalance=self.imbalance)
+                              topk_fraction=0.1 if self.topk_fraction is None else self.topk_fraction, imbalance=self.imbalance,
+                              cldice_iters=self.cldice_iters)
         finally:
             self.ctx.wq_install(None)
 
