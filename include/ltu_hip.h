@@ -696,6 +696,45 @@ int ltu_lesion_stats(const float* pred, const uint8_t* target, int* ints, float*
 long long ltu_fill_holes_ws_elems(int B, int H, int W, int D);
 int ltu_fill_holes(const uint8_t* mask, uint8_t* out, int* scratch, long long scratch_elems, int B, int H, int W, int D,
                    int connectivity, ltu_stream_t s);
+/* The cavities of a mask: counts int32 [B] = the 6-connected background components of mask[b] that reach no face of the volume
+ * (the second Betti number of the object under 26-connectivity).  The labelling and face marking of ltu_fill_holes at
+ * connectivity 1, counted instead of filled; scratch: ltu_fill_holes_ws_elems(B, H, W, D) int32.  Same refusals. */
+int ltu_count_cavities(const uint8_t* mask, int* counts, int* scratch, long long scratch_elems, int B, int H, int W, int D,
+                       ltu_stream_t s);
+
+/* ---- topology: curve skeleton, clDice overlap counts, Euler characteristic (csrc/thinning.hip) ---------------------------------
+ * Volumes are u8 [N][H][W][D], nonzero = object, everything beyond a volume is background.  N in 1 .. 65535, H W D < 2^31 and
+ * N H W D < 2^32, else LTU_E_SHAPE; a NULL pointer or a short scratch is LTU_E_ARG; nothing is launched on a refusal.  Integer
+ * work only: two calls give the same bytes.
+ *   code     of a voxel p: bit 9 (dh + 1) + 3 (dw + 1) + (dd + 1) is set when p + (dh, dw, dd) is object; bit 13 is ignored.
+ *   simple_codes: flags[i] bit 0 = codes[i] is simple for the (26, 6) pair (its 26 neighbours hold exactly one 26-component of
+ *            object, and exactly one 6-component of the background of its 18-neighbourhood holds a face neighbour), bit 1 = it is
+ *            an endpoint (exactly one object neighbour).  The device function the thinning calls.
+ *   thinning: 8-subfield sequential curve thinning.  One iteration marks the object voxels with a background face neighbour as
+ *            candidates, then for s = 0 .. 7 deletes, in place, every candidate of subfield (h & 1) | (w & 1) << 1 | (d & 1) << 2
+ *            == s that is simple and not an endpoint in the current image.  The result does not depend on scheduling.
+ *            count: counts int64 [8] (device) = the object voxels per subfield over all N volumes; their sum sizes the scratch.
+ *            iterate: enqueues `iters` (1 .. 64) iterations on vol, 10 launches each; deleted int64 [iters] (device) receives the
+ *            voxels each of them deleted.  An iteration on a converged volume deletes nothing, so the host may read `deleted` as
+ *            rarely as it likes and stop at the first zero.  counts must be ltu_thin_count's of vol before its first iteration,
+ *            objects their sum.  scratch: ltu_thin_ws_elems(N, H, W, D, objects) int32 (0 for what the call refuses).
+ *   clDice   for column kk of K and class k: binarize writes out u8 [2][B][K][H][W][D], side 0 = pred[b][k] >= threshold (pred
+ *            f32 [B][C][H][W][D]), side 1 = target[b] == k (target u8 [B][H][W][D]); overlap takes the thinned copy of that
+ *            array and writes counts int32 [B][K][4] = |S_P|, |S_P n G|, |S_G|, |S_G n P| and rates f32 [3][B][K] = clDice
+ *            2 Tp Ts / (Tp + Ts) (0 when Tp + Ts = 0), Tprec |S_P n G| / |S_P|, Tsens |S_G n P| / |S_G| (quotients in fp64, one
+ *            rounding to f32); both skeletons empty: 1, 1, 1; exactly one empty: 0, 0, 0.  2 B K volumes follow the rules above.
+ *   euler    chi int64 [N] (device) = V - E + F - C of the union of the closed unit cubes of the object voxels: the cell complex of
+ *            26-connectivity, so chi = b0 - b1 + b2. */
+int ltu_thin_simple_codes(const uint32_t* codes, uint8_t* flags, long long n, ltu_stream_t s);
+int ltu_thin_count(const uint8_t* vol, long long* counts, int N, int H, int W, int D, ltu_stream_t s);
+long long ltu_thin_ws_elems(int N, int H, int W, int D, long long objects);
+int ltu_thin_iterate(uint8_t* vol, const long long* counts, long long* deleted, int iters, int* scratch, long long scratch_elems,
+                     long long objects, int N, int H, int W, int D, ltu_stream_t s);
+int ltu_topology_binarize(const float* pred, const uint8_t* target, uint8_t* out, int B, int C, int k, int kk, int K, int H, int W,
+                          int D, float threshold, ltu_stream_t s);
+int ltu_topology_overlap(const float* pred, const uint8_t* target, const uint8_t* skel, int* counts, float* rates, int B, int C, int k,
+                         int kk, int K, int H, int W, int D, float threshold, ltu_stream_t s);
+int ltu_euler_characteristic(const uint8_t* vol, long long* chi, int N, int H, int W, int D, ltu_stream_t s);
 
 /* ---- optimizer (train3D.py:193: torch.optim.AdamW(lr=1e-4)) -----------------------------------------------------
  * One AdamW step on flat, 16-byte aligned fp32 buffers (a gradient bucket and the parameters / moments laid out the same way):

@@ -108,6 +108,14 @@ SIGNATURES = {
     'ltu_lesion_stats': [P, P, P, P, P, L, L, I, I, I, I, I, I, I, I, F, I, P],
     'ltu_fill_holes_ws_elems': [I, I, I, I],
     'ltu_fill_holes': [P, P, P, L, I, I, I, I, I, P],
+    'ltu_count_cavities': [P, P, P, L, I, I, I, I, P],
+    'ltu_thin_simple_codes': [P, P, L, P],
+    'ltu_thin_count': [P, P, I, I, I, I, P],
+    'ltu_thin_ws_elems': [I, I, I, I, L],
+    'ltu_thin_iterate': [P, P, P, I, P, L, L, I, I, I, I, P],
+    'ltu_topology_binarize': [P, P, P, I, I, I, I, I, I, I, I, F, P],
+    'ltu_topology_overlap': [P, P, P, P, P, I, I, I, I, I, I, I, I, F, P],
+    'ltu_euler_characteristic': [P, P, I, I, I, I, P],
     'ltu_ct_preprocess': [P, P, P, P, I, I, I, F, F, F, F, P],
     'ltu_crop_flip': [P, P, P, I, I, I, I, I, I, I, I, P],
     'ltu_resample_grid': [P, I, P, I, I, I, L, L, L, P, P, I, I, I, L, L, L, P, I, F, F, F, F, P],

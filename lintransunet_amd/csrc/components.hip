@@ -569,6 +569,41 @@ extern "C" int ltu_fill_holes(const uint8_t* mask, uint8_t* out, int* scratch, l
   return ltu_check_launch();
 }
 
+// counts[b] += the background components of sample b whose root carries no mark: a root's slot holds its own index until
+// cc_faces_kernel stores CC_OPEN there.  Integer atomics; counts zero before.  grid = (nb, B)
+__global__ void __launch_bounds__(256) cc_closed_kernel(const int* __restrict__ par, int* __restrict__ counts, long long S) {
+  __shared__ int red[4];
+  const int* pb = par + (long long)blockIdx.y * S;
+  const long long base = (long long)blockIdx.x * CC_RB;
+  int n = 0;
+  for (int j = 0; j < CC_RB / 256; ++j) {
+    const long long v = base + j * 256 + threadIdx.x;
+    if (v >= S) break;
+    n += pb[v] == (int)v;
+  }
+  n = cc_block_sum(n, red);
+  if (threadIdx.x == 0 && n) atomicAdd(&counts[blockIdx.y], n);
+}
+
+// the cavities of a mask (its second Betti number): the 6-connected background components that reach no face of the volume, by
+// the labelling and face marking of ltu_fill_holes (the same scratch, ltu_fill_holes_ws_elems), counted instead of filled
+extern "C" int ltu_count_cavities(const uint8_t* mask, int* counts, int* scratch, long long scratch_elems, int B, int H, int W, int D,
+                                  ltu_stream_t s) {
+  if (!cc_shape_ok(B, H, W, D)) return LTU_E_SHAPE;
+  if (mask == nullptr || counts == nullptr) return LTU_E_ARG;
+  if (scratch == nullptr || scratch_elems < ltu_fill_holes_ws_elems(B, H, W, D)) return LTU_E_ARG;
+  hipStream_t st = (hipStream_t)s;
+  const long long S = (long long)H * W * D;
+  const long long faces = 2 * ((long long)W * D + (long long)H * D + (long long)H * W);
+  const hipError_t e = hipMemsetAsync(counts, 0, (size_t)B * sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  const cc_src src{mask, S, 5, 0, 0.f};
+  cc_label_roots(src, scratch, nullptr, B, H, W, D, 1, st);
+  hipLaunchKernelGGL(cc_faces_kernel, dim3(cdiv(faces, 256), B), dim3(256), 0, st, scratch, H, W, D);
+  hipLaunchKernelGGL(cc_closed_kernel, dim3((unsigned)cc_nblocks(H, W, D), B), dim3(256), 0, st, scratch, counts, S);
+  return ltu_check_launch();
+}
+
 // ---- lesion statistics ---------------------------------------------------------------------------------------------------
 // v is a head of the set X (in(v) and no half-neighbour n with in(n)); in() takes a flat index inside the sample
 template <int NOFF, typename In>
