@@ -329,6 +329,17 @@ int ltu_head_softmax_bwd(const float* dp, const float* p, void* dz, long long M,
 int ltu_final_softmax_fwd(const void* z, float* p, int B, int h, int w, int D, int C, int CP, int dtype, ltu_stream_t s);   /* z rows of CP >= 4C channels (padded conv output) */
 int ltu_final_softmax_bwd(const float* dp, const float* p, void* dz, int B, int h, int w, int D, int C, int CP, int dtype,
                           ltu_stream_t s);
+/* The heads of a region model (csrc/region.hip): channel r is the sigmoid of logit r, p = 1 / (1 + exp(-z)), finite and in [0, 1] for
+ * every finite logit; arguments, padded columns (CP), dtypes and window un-embedding of the softmax heads above, 1 <= R <= 8.  The
+ * backward forms dz = (dp p) (1 - p) from the saved p and writes the padding columns as zero; every launch form of a row (vector or
+ * scalar accesses) gives the same bits. */
+int ltu_head_sigmoid_fwd(const void* z, float* p, long long M, int R, int CP, int dtype, ltu_stream_t s);
+int ltu_head_sigmoid_bwd(const float* dp, const float* p, void* dz, long long M, int R, int CP, int dtype, ltu_stream_t s);
+int ltu_final_sigmoid_fwd(const void* z, float* p, int B, int h, int w, int D, int R, int CP, int dtype, ltu_stream_t s);
+int ltu_final_sigmoid_bwd(const float* dp, const float* p, void* dz, int B, int h, int w, int D, int R, int CP, int dtype,
+                          ltu_stream_t s);
+/* eval branch of a region model: o[i] = p[i] > thr ? 1 : 0, f32, i < n */
+int ltu_prob_indicator(const float* p, float* o, long long n, float thr, ltu_stream_t s);
 /* eval branch (model/trans_3DUnet.py:199-202): one-hot of the arg-max class, p/o f32 [M][C] */
 int ltu_onehot_argmax(const float* p, float* o, long long M, int C, ltu_stream_t s);
 
@@ -364,6 +375,10 @@ int ltu_dwconv_bwd(const void* dy, const void* dy2, const void* x, const float* 
 int ltu_roi_plan_size(int B, int H, int W, int roi_size, long long* n_int, long long* n_float, long long* n_hist);
 int ltu_roi_plan(const float* prob, int B, int H, int W, int D, int C, int roi_size, float thr, float* box, int* plan_i,
                  float* plan_f, int* hist, ltu_stream_t s);
+/* the plan of a region model (csrc/region.hip): foreground = (max_r prob[...,r]) >= thr over the C <= 8 region channels; the
+ * comparison, the plan kernel, the buffers and ltu_roi_plan_size are those of ltu_roi_plan */
+int ltu_roi_plan_union(const float* prob, int B, int H, int W, int D, int C, int roi_size, float thr, float* box, int* plan_i,
+                       float* plan_f, int* hist, ltu_stream_t s);
 /* which = 0: image [B,H,W,D,C] -> ROI grid [B,eh,ew,D,C] (roi_alignment2); which = 1: ROI grid -> image
  * (post_processing2).  adjoint != 0 applies the transposed operator to a gradient (in has the shape of the
  * forward output, out the shape of the forward input). */
@@ -563,6 +578,48 @@ int ltu_loss_cldice_bwd(const float* p, const uint8_t* label, const int* classes
                         ltu_stream_t s);
 /* label pyramid (utils/utils_3D_embed_full.py:64,73-76): u8 [B,H,W,D] -> max over (2,2,kd) windows */
 int ltu_label_maxpool(const uint8_t* x, uint8_t* y, int B, int H, int W, int D, int kd, ltu_stream_t s);
+
+/* ---- region-based training (csrc/region.hip): R <= 8 overlapping label regions, one sigmoid channel each -------------------------
+ * Region r is a set of u8 label values; a voxel's membership of all regions is one byte, bits = lut[label], lut[v] = sum_r [v in
+ * region r] << r (a label in no region is background for every channel).
+ * ltu_region_bits: out[i] = lut[label[i]], i < n; lut: 256 bytes of HOST memory, passed to the kernel by value.
+ * ltu_bits_orpool: u8 [B,H,W,D] -> bitwise OR over the (2, 2, kd) windows of ltu_label_maxpool, kd in {1, 2}: every region's
+ * indicator max-pooled on its own.  LTU_E_SHAPE: kd outside {1, 2}, H or W odd, D % kd != 0, an empty output. */
+int ltu_region_bits(const uint8_t* label, const uint8_t* lut /* 256 host bytes */, uint8_t* out, long long n, ltu_stream_t s);
+int ltu_bits_orpool(const uint8_t* x, uint8_t* y, int B, int H, int W, int D, int kd, ltu_stream_t s);
+/* The region stage of a level's loss chain: p f32 [B][S][R] sigmoid probabilities (channels-last), bits u8 [B][S], t_r = (bits >> r)
+ * & 1.  Per (sample, region), each sum accumulated directly:
+ *     I = sum p t   FP = sum p (1 - t)   FN = sum t (1 - p)   E = sum -[t log max(p, 1e-6) + (1 - t) log max(1 - p, 1e-6)]
+ *     BCE  = sum_{b, r} E / (B S R)
+ *     D_r  = (FP + FN) / (2 I + FP + FN + 2 eps)     batch != 0: I, FP, FN summed over b first; else the mean over b of the ratio
+ *     Dice = (1 / R) sum_r D_r           (D_r: the Tversky term of ltu_loss_imb_fwd at alpha = beta = 0.5, same eps)
+ * values [R + 4] = {total, BCE, Dice, D_0 .. D_{R-1}, total again}, total = (base_total ? base_total[0] : 0) + scale (w_bce BCE +
+ * w_dice Dice), scale = scale_dev ? scale_dev[0] : 1 read on the device.  coef [B][R][3], already weighted and scaled, serves the
+ * backward: dp[b][s][r] = gscale[0] (A + t Bc + G e'(p, t)), e' the derivative of the clamped expression (-1 / p where t = 1 and p >
+ * 1e-6, 1 / (1 - p) where t = 0 and 1 - p > 1e-6, else 0), written (accumulate == 0) or added into what dp holds.
+ * nnU-Net applies its BCE to the logits; on probabilities clamped at 1e-6 the two differ only where |z| > 13.8.
+ * Per-workgroup partials folded in a fixed order, no floating-point atomics: two calls agree bit for bit; no host read, capturable.
+ * sums: ltu_loss_region_ws_floats(B, S, R) floats, no initialisation (0: a shape the calls refuse).
+ * LTU_E_SHAPE: R outside 1 .. 8, B < 1, S < 1, B R 4 > 256; LTU_E_ARG: a NULL pointer (base_total and scale_dev may be NULL), short
+ * sums or coef, a non-finite weight, eps not > 0, batch outside {0, 1}; all before anything is launched. */
+long long ltu_loss_region_ws_floats(int B, long long S, int R);
+int ltu_loss_region_fwd(const float* p, const uint8_t* bits, float* sums, long long sums_floats, float* values /* R + 4 */,
+                        float* coef /* [B][R][3] */, const float* base_total, float w_bce, float w_dice, int batch, float eps,
+                        const float* scale_dev, int B, long long S, int R, ltu_stream_t s);
+int ltu_loss_region_bwd(const float* p, const uint8_t* bits, const float* coef, long long coef_floats, const float* gscale, float* dp,
+                        int accumulate, int B, long long S, int R, ltu_stream_t s);
+/* Back to labels and scoring.  p f32: channels-last [B][N][R] (planes == 0) or planes [B][R][N] (planes == 1).
+ * ltu_region_labels: nnU-Net's rule - out u8 [B][N] starts at 0; for r = 0 .. R-1 in order, class_order[r] (host ints, 0 .. 255) is
+ * written where p_r > thr, so a later region wins.  ltu_region_prob_bits: out[b][i] = sum_r [p_r > thr] << r.
+ * ltu_region_counts: counts i64 [B][R][3] = {TP, FP, FN} between two bit-mask volumes u8 [B][N], ZERO on entry (integer atomics; the
+ * library issues no memsets), then dice f32 [B][R] = 2 TP / (2 TP + FP + FN), 1 where both sides are empty.
+ * LTU_E_SHAPE: R outside 1 .. 8, B outside 1 .. 65535, N < 1; LTU_E_ARG: a NULL pointer, planes outside {0, 1}, a NaN threshold, a
+ * class_order entry outside 0 .. 255. */
+int ltu_region_labels(const float* p, int planes, const int* class_order, float thr, uint8_t* out, int B, long long N, int R,
+                      ltu_stream_t s);
+int ltu_region_prob_bits(const float* p, int planes, float thr, uint8_t* out, int B, long long N, int R, ltu_stream_t s);
+int ltu_region_counts(const uint8_t* pred_bits, const uint8_t* true_bits, long long* counts, float* dice, int B, long long N, int R,
+                      ltu_stream_t s);
 
 /* ---- sliding-window whole-volume inference (inference_embed_attn.py:92-185; monai 0.7.0 sliding_window_inference) --------
  * The windows live in the PADDED image Hp x Wp x Dp (a dimension smaller than the window is padded symmetrically with zeros:

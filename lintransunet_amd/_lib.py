@@ -205,6 +205,20 @@ SIGNATURES = {
     'ltu_loss_cldice_fwd': [P, P, P, P, P, I, I, P, L, P, P, P, I, I, I, I, I, P],
     'ltu_loss_cldice_bwd': [P, P, P, I, I, P, L, P, P, I, I, I, I, I, I, P],
     'ltu_label_maxpool': [P, P, I, I, I, I, I, P],
+    'ltu_region_bits': [P, ctypes.c_char_p, P, L, P],
+    'ltu_bits_orpool': [P, P, I, I, I, I, I, P],
+    'ltu_loss_region_ws_floats': [I, L, I],
+    'ltu_loss_region_fwd': [P, P, P, L, P, P, P, F, F, I, F, P, I, L, I, P],
+    'ltu_loss_region_bwd': [P, P, P, L, P, P, I, I, L, I, P],
+    'ltu_region_labels': [P, I, P, F, P, I, L, I, P],
+    'ltu_region_prob_bits': [P, I, F, P, I, L, I, P],
+    'ltu_region_counts': [P, P, P, P, I, L, I, P],
+    'ltu_head_sigmoid_fwd': [P, P, L, I, I, I, P],
+    'ltu_head_sigmoid_bwd': [P, P, P, L, I, I, I, P],
+    'ltu_final_sigmoid_fwd': [P, P, I, I, I, I, I, I, I, P],
+    'ltu_final_sigmoid_bwd': [P, P, P, I, I, I, I, I, I, I, P],
+    'ltu_prob_indicator': [P, P, L, F, P],
+    'ltu_roi_plan_union': [P, I, I, I, I, I, I, F, P, P, P, P, P],
     'ltu_comm_load': [ctypes.c_char_p],
     'ltu_comm_unique_id': [P],
     'ltu_comm_init': [P, P, I, I],

@@ -532,6 +532,170 @@ extern "C" int ltu_final_softmax_bwd(const float* dp, const float* p, void* dz, 
   return ltu_check_launch();
 }
 
+// ------------------------------------------------------------------------------------------------ region sigmoid heads
+// The heads of a region model (region.hip): channel r is the sigmoid of logit r, p = 1 / (1 + exp(-z)), on the rows, padded columns,
+// dtypes and window un-embedding of the softmax heads above, 1 <= R <= 8.  exp(-z) overflows to +inf below z = -88.7 and the quotient
+// is then exactly 0; every finite logit gives a finite p in [0, 1].  Backward from the saved p: dz = (dp p) (1 - p), both products
+// rounded on their own and 1 - p one rounded difference, so every launch form of a row gives the same bits.
+// e^x with the range reduction written out.  Not expf: the library is built with -ffp-contract=fast, and the backend then fuses the
+// product of expf's own reduction, ph = x log2(e), into the difference ph - rint(ph) that is meant to be the exact difference of two
+// floats; the rounding error of ph is counted twice and the result is off by about |x| ulps (23 ulps measured at x = 27, where
+// torch.exp has 0.8: p = 1e-12 of a confident background voxel carries it in full).  Here ph passes through a register, so the
+// difference is exact, the low part pl = (x c - ph) + x c_lo is two fused multiply-adds, and v_exp_f32 sees |ph - n + pl| <= 0.5.
+// x is clamped to where the result saturates (e^-104 rounds to 0, e^89 to +inf); a NaN stays a NaN.
+__device__ __forceinline__ float exp_reduced(float x) {
+  x = x < -104.f ? -104.f : (x > 89.f ? 89.f : x);
+  float ph = x * 1.44269502e+0f;                       // log2(e), high part 0x3fb8aa3b
+  asm("" : "+v"(ph));
+  const float pl = fmaf(x, 1.92596299e-8f, fmaf(x, 1.44269502e+0f, -ph));      // .. and low part 0x32a57060
+  const float n = rintf(ph);
+  return ldexpf(__builtin_amdgcn_exp2f((ph - n) + pl), (int)n);
+}
+__device__ __forceinline__ float sigmoid1(float z) { return 1.f / (1.f + exp_reduced(-z)); }
+__device__ __forceinline__ float sigmoid_grad(float g, float p) { return fmaf(fmaf(g, p, 0.f), 1.f - p, 0.f); }
+
+// logits T [M][CP] (first R live) -> p f32 [M][R].  VEC: ldlogits may read the row (see the launcher); otherwise R scalar loads
+template <typename T, int C, bool VEC>
+__global__ void __launch_bounds__(256) head_sigmoid_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, long long M, int CP) {
+  constexpr int W = HEAD_W(C);
+  GRID_STRIDE(m, M) {
+    float v[W];
+    if constexpr (VEC) ldlogits<T, C>(z + m * CP, v);
+    else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) v[c] = ld1<T>(z + m * CP + c);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = sigmoid1(v[c]);
+    stprobs<C>(p + m * C, v, 1.f);
+  }
+}
+// one thread per row.  VEC: every row starts on a Vec4<T> boundary and CP % 4 == 0: 4-wide stores, zeros behind the first HEAD_W(C)
+// columns; otherwise scalar stores
+template <typename T, int C, bool VEC>
+__global__ void __launch_bounds__(256) head_sigmoid_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz,
+                                                               long long M, int CP) {
+  constexpr int W = HEAD_W(C);
+  GRID_STRIDE(m, M) {
+    float a[W], b[W], g[W];
+    ldrow<C>(dp + m * C, a);
+    ldrow<C>(p + m * C, b);
+#pragma unroll
+    for (int c = 0; c < W; ++c) g[c] = c < C ? sigmoid_grad(a[c], b[c]) : 0.f;
+    T* o = dz + m * CP;
+    if constexpr (VEC) {
+#pragma unroll
+      for (int k = 0; k < W; k += 4) Vec4<T>::store(o + k, make_float4(g[k], g[k + 1], g[k + 2], g[k + 3]));
+      for (int k = W; k < CP; k += 4) Vec4<T>::store(o + k, make_float4(0.f, 0.f, 0.f, 0.f));
+    } else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) st1<T>(o + c, g[c]);
+      for (int c = C; c < CP; ++c) st1<T>(o + c, 0.f);
+    }
+  }
+}
+extern "C" int ltu_head_sigmoid_fwd(const void* z, float* p, long long M, int R, int CP, int dtype, ltu_stream_t s) {
+  if (R < 1 || R > LTU_WIDE_MAXC || CP < R) return LTU_E_SHAPE;
+  LTU_DISPATCH_T(dtype, {
+    LTU_DISPATCH_C(R, {
+      if (rows_aligned(z, CP, sizeof(T), CT <= 4 ? 4 * sizeof(T) : 16))
+        hipLaunchKernelGGL((head_sigmoid_fwd_kernel<T, CT, true>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
+      else hipLaunchKernelGGL((head_sigmoid_fwd_kernel<T, CT, false>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
+    });
+  });
+  return ltu_check_launch();
+}
+extern "C" int ltu_head_sigmoid_bwd(const float* dp, const float* p, void* dz, long long M, int R, int CP, int dtype,
+                                    ltu_stream_t s) {
+  if (R < 1 || R > LTU_WIDE_MAXC || CP < R) return LTU_E_SHAPE;
+  LTU_DISPATCH_T(dtype, {
+    const bool vec = rows_aligned(dz, CP, sizeof(T), 4 * sizeof(T));      // CP % 4 == 0 and CP >= R make CP >= HEAD_W(R)
+    LTU_DISPATCH_C(R, {
+      if (vec) hipLaunchKernelGGL((head_sigmoid_bwd_kernel<T, CT, true>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, M, CP);
+      else hipLaunchKernelGGL((head_sigmoid_bwd_kernel<T, CT, false>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, M, CP);
+    });
+  });
+  return ltu_check_launch();
+}
+
+// final head of a region model: z T [B,h,w,D,CP >= 4R] -> window un-embedding + sigmoid -> p f32 [B,2h,2w,D,R], the channel map of
+// final_softmax_fwd_kernel.  One thread per coarse voxel.
+template <typename T, int C>
+__global__ void __launch_bounds__(256) final_sigmoid_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, int B, int h, int w, int D, int CP) {
+  const long long n = (long long)B * h * w * D;
+  GRID_STRIDE(i, n) {
+    const int d = (int)(i % D);
+    long long t = i / D;
+    const int ww = (int)(t % w); t /= w;
+    const int hh = (int)(t % h);
+    const int b = (int)(t / h);
+    float v[4 * C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float4 t4 = Vec4<T>::load(z + i * CP + 4 * c);
+      v[4 * c] = t4.x; v[4 * c + 1] = t4.y; v[4 * c + 2] = t4.z; v[4 * c + 3] = t4.w;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float e[HEAD_W(C)];
+#pragma unroll
+      for (int c = 0; c < C; ++c) e[c] = sigmoid1(v[4 * c + q]);
+      stprobs<C>(p + ((((long long)b * 2 * h + 2 * hh + (q >> 1)) * 2 * w + 2 * ww + (q & 1)) * D + d) * C, e, 1.f);
+    }
+  }
+}
+template <typename T, int C>
+__global__ void __launch_bounds__(256) final_sigmoid_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz,
+                                                                int B, int h, int w, int D, int CP) {
+  constexpr int W = HEAD_W(C);
+  const long long n = (long long)B * h * w * D;
+  GRID_STRIDE(i, n) {
+    const int d = (int)(i % D);
+    long long t = i / D;
+    const int ww = (int)(t % w); t /= w;
+    const int hh = (int)(t % h);
+    const int b = (int)(t / h);
+    float gv[4][W], pv[4][W];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {                 // all loads of the four fine voxels first
+      const long long o = ((((long long)b * 2 * h + 2 * hh + (q >> 1)) * 2 * w + 2 * ww + (q & 1)) * D + d) * C;
+      ldrow<C>(dp + o, gv[q]);
+      ldrow<C>(p + o, pv[q]);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+      Vec4<T>::store(dz + i * CP + 4 * c, make_float4(sigmoid_grad(gv[0][c], pv[0][c]), sigmoid_grad(gv[1][c], pv[1][c]),
+                                                      sigmoid_grad(gv[2][c], pv[2][c]), sigmoid_grad(gv[3][c], pv[3][c])));
+    for (int k = 4 * C; k < CP; k += 4) Vec4<T>::store(dz + i * CP + k, make_float4(0.f, 0.f, 0.f, 0.f));      // padded conv columns
+  }
+}
+extern "C" int ltu_final_sigmoid_fwd(const void* z, float* p, int B, int h, int w, int D, int R, int CP, int dtype, ltu_stream_t s) {
+  if (R < 1 || R > LTU_WIDE_MAXC || CP < 4 * R || CP % 4) return LTU_E_SHAPE;
+  LTU_DISPATCH_T(dtype, {
+    const dim3 grid(sgrid((long long)B * h * w * D));
+    LTU_DISPATCH_C(R, { hipLaunchKernelGGL((final_sigmoid_fwd_kernel<T, CT>), grid, dim3(256), 0, (hipStream_t)s, (const T*)z, p, B, h, w, D, CP); });
+  });
+  return ltu_check_launch();
+}
+extern "C" int ltu_final_sigmoid_bwd(const float* dp, const float* p, void* dz, int B, int h, int w, int D, int R, int CP,
+                                     int dtype, ltu_stream_t s) {
+  if (R < 1 || R > LTU_WIDE_MAXC || CP < 4 * R || CP % 4) return LTU_E_SHAPE;
+  LTU_DISPATCH_T(dtype, {
+    const dim3 grid(sgrid((long long)B * h * w * D));
+    LTU_DISPATCH_C(R, { hipLaunchKernelGGL((final_sigmoid_bwd_kernel<T, CT>), grid, dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, B, h, w, D, CP); });
+  });
+  return ltu_check_launch();
+}
+// eval branch of a region model: the indicator [p > thr] as f32, elementwise (any layout)
+__global__ void __launch_bounds__(256) prob_indicator_kernel(const float* __restrict__ p, float* __restrict__ o, long long n, float thr) {
+  GRID_STRIDE(i, n) o[i] = p[i] > thr ? 1.f : 0.f;
+}
+extern "C" int ltu_prob_indicator(const float* p, float* o, long long n, float thr, ltu_stream_t s) {
+  if (n < 1) return LTU_E_SHAPE;
+  hipLaunchKernelGGL(prob_indicator_kernel, dim3(sgrid(n)), dim3(256), 0, (hipStream_t)s, p, o, n, thr);
+  return ltu_check_launch();
+}
+
 // eval branch (model/trans_3DUnet.py:199-202): one-hot of the arg-max class (first maximum)
 __global__ void onehot_argmax_kernel(const float* __restrict__ p, float* __restrict__ o, long long M, int C) {
   GRID_STRIDE(m, M) {

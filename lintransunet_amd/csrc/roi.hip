@@ -148,9 +148,10 @@ __device__ void build_axis(const AxisPlan& p, int b, bool forward, float x0, flo
 }
 
 // foreground histograms over h and w: grid (nblk, B); hist [B][2][ROI_MAX_LEN] zero on entry.  A block counts a contiguous
-// range of voxels in LDS and flushes its non-zero bins (a range touches few h rows) with integer atomics.
-__global__ void __launch_bounds__(256) roi_hist_kernel(const float* __restrict__ prob, int H, int W, int D, int C, float thr,
-                                                       int* __restrict__ hist) {
+// range of voxels in LDS and flushes its non-zero bins (a range touches few h rows) with integer atomics.  fg(row of C
+// probabilities) is the voxel's foreground value, compared as fg >= thr.
+template <class Fg>
+__device__ __forceinline__ void roi_hist_walk(const float* __restrict__ prob, int H, int W, int D, int C, float thr, int* __restrict__ hist, Fg fg) {
   __shared__ int hx[ROI_MAX_LEN], hy[ROI_MAX_LEN];
   const int b = blockIdx.y;
   for (int i = threadIdx.x; i < ROI_MAX_LEN; i += blockDim.x) { hx[i] = 0; hy[i] = 0; }
@@ -161,8 +162,7 @@ __global__ void __launch_bounds__(256) roi_hist_kernel(const float* __restrict__
   const long long i1 = i0 + per < n ? i0 + per : n;
   const float* pb = prob + (long long)b * n * C;
   for (long long i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
-    const float fg = fsub(1.f, pb[i * C]);
-    if (fg >= thr) {
+    if (fg(pb + i * C) >= thr) {
       const long long hw = i / D;
       atomicAdd(&hx[(int)(hw / W)], 1);
       atomicAdd(&hy[(int)(hw % W)], 1);
@@ -174,6 +174,20 @@ __global__ void __launch_bounds__(256) roi_hist_kernel(const float* __restrict__
     if (hx[i]) atomicAdd(hb + i, hx[i]);
     if (hy[i]) atomicAdd(hb + ROI_MAX_LEN + i, hy[i]);
   }
+}
+// class model: everything but the background channel
+__global__ void __launch_bounds__(256) roi_hist_kernel(const float* __restrict__ prob, int H, int W, int D, int C, float thr,
+                                                       int* __restrict__ hist) {
+  roi_hist_walk(prob, H, W, D, C, thr, hist, [](const float* row) { return fsub(1.f, row[0]); });
+}
+// region model (region.hip): no background channel, the foreground is the union of the regions, max_r prob[..., r]
+__global__ void __launch_bounds__(256) roi_hist_union_kernel(const float* __restrict__ prob, int H, int W, int D, int C, float thr,
+                                                             int* __restrict__ hist) {
+  roi_hist_walk(prob, H, W, D, C, thr, hist, [C](const float* row) {
+    float m = row[0];
+    for (int r = 1; r < C; ++r) m = fmaxf(m, row[r]);
+    return m;
+  });
 }
 
 __global__ void roi_plan_kernel(const RoiArgs a, const int* __restrict__ hist) {
@@ -236,8 +250,8 @@ extern "C" int ltu_roi_plan_size(int B, int H, int W, int roi_size, long long* n
 // hist: B * 2 * ROI_MAX_LEN ints, ZERO on entry (caller-provided scratch, like the loss sums).  It used to be the tail of plan_i,
 // cleared here with hipMemsetAsync; inside a captured HIP graph that memset node was not reliably ordered before the histogram
 // kernel on replays (the plan then saw an empty histogram and fell back to the empty-mask box), so the library issues no memsets.
-extern "C" int ltu_roi_plan(const float* prob, int B, int H, int W, int D, int C, int roi_size, float thr, float* box, int* plan_i,
-                            float* plan_f, int* hist, ltu_stream_t s) {
+static int roi_plan(const float* prob, int B, int H, int W, int D, int C, int roi_size, float thr, float* box, int* plan_i, float* plan_f,
+                    int* hist, bool fg_union, ltu_stream_t s) {
   if (H > ROI_MAX_LEN || W > ROI_MAX_LEN) return LTU_E_SHAPE;
   RoiArgs a;
   a.prob = prob; a.B = B; a.H = H; a.W = W; a.D = D; a.C = C; a.thr = thr; a.box = box;
@@ -252,9 +266,20 @@ extern "C" int ltu_roi_plan(const float* prob, int B, int H, int W, int D, int C
   if (hist == nullptr) return LTU_E_ARG;
   const long long n = (long long)H * W * D;
   const int nblk = (int)(n / 4096 < 1 ? 1 : (n / 4096 > 256 ? 256 : n / 4096));
-  hipLaunchKernelGGL(roi_hist_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)s, prob, H, W, D, C, thr, hist);
+  if (fg_union) hipLaunchKernelGGL(roi_hist_union_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)s, prob, H, W, D, C, thr, hist);
+  else hipLaunchKernelGGL(roi_hist_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)s, prob, H, W, D, C, thr, hist);
   hipLaunchKernelGGL(roi_plan_kernel, dim3(B, 4), dim3(256), 0, (hipStream_t)s, a, (const int*)hist);
   return ltu_check_launch();
+}
+extern "C" int ltu_roi_plan(const float* prob, int B, int H, int W, int D, int C, int roi_size, float thr, float* box, int* plan_i,
+                            float* plan_f, int* hist, ltu_stream_t s) {
+  return roi_plan(prob, B, H, W, D, C, roi_size, thr, box, plan_i, plan_f, hist, false, s);
+}
+// the plan of a region model: foreground = max_r prob[..., r] >= thr (1 <= C <= 8 region channels); everything else as ltu_roi_plan
+extern "C" int ltu_roi_plan_union(const float* prob, int B, int H, int W, int D, int C, int roi_size, float thr, float* box, int* plan_i,
+                                  float* plan_f, int* hist, ltu_stream_t s) {
+  if (C < 1 || C > LTU_WIDE_MAXC) return LTU_E_SHAPE;
+  return roi_plan(prob, B, H, W, D, C, roi_size, thr, box, plan_i, plan_f, hist, true, s);
 }
 
 // ------------------------------------------------------------------------------------------------ resamplers

@@ -378,6 +378,69 @@ def evaluate_multiclass(predict, masks, threshold=None, return_label_map=False):
     return res
 
 
+def _region_probs(p, R, what):
+    """fp32 probabilities [B,R,...] (or [R,...]: one sample) of a region model -> (tensor, planes, B, N, spatial shape, one sample) as
+    csrc/region.hip reads it: channels-last memory behind the view (what the model and infer_volume return; planes 0) as it is,
+    anything else as contiguous planes [B][R][N] (what data.to_native_probs returns; planes 1)"""
+    if p.dtype != torch.float32 or not p.is_cuda or p.dim() < 2:
+        raise ValueError(f'{what}: fp32 device probabilities [B,R,...] or [R,...]')
+    single = p.dim() == 4 and p.shape[0] == R      # [R,H,W,D]
+    if single:
+        p = p.unsqueeze(0)
+    if p.shape[1] != R:
+        raise ValueError(f'{what}: {p.shape[1]} channels for the {R} regions of the record')
+    B, spatial = p.shape[0], tuple(p.shape[2:])
+    N = math.prod(spatial)
+    if p.permute(0, *range(2, p.dim()), 1).is_contiguous() and R > 1:
+        return p, 0, B, N, spatial, single
+    return p.contiguous(), 1, B, N, spatial, single
+
+
+def region_labels(p, regions, threshold=0.5):
+    """The label map of a region model's probabilities by nnU-Net's rule (csrc/region.hip): p fp32 [B,R,...] in either memory
+    layout (channels-last behind the view, as the model and infer_volume return it, or planes, as data.to_native_probs does), or
+    [R,H,W,D] for one volume; the label starts at 0 and for r = 0 .. R-1 in order regions.class_order[r] is written where p_r >
+    threshold, so a later region wins and p == threshold is not painted.  Returns uint8 [B,...] (or [H,W,D]); no host read."""
+    if regions.class_order is None:
+        raise ValueError('region_labels: the record has no class_order to paint the regions with')
+    R = len(regions.members)
+    p, planes, B, N, spatial, single = _region_probs(p, R, 'region_labels')
+    out = torch.empty((B, *spatial), device=p.device, dtype=torch.uint8)
+    ops._lib.call('ltu_region_labels', p.data_ptr(), planes, ops._int_array(regions.class_order), float(threshold), out.data_ptr(), B, N, R,
+                  torch.cuda.current_stream().cuda_stream)
+    return out[0] if single else out
+
+
+def region_metrics(predict, masks, regions, threshold=0.5):
+    """Per (sample, region) overlap of a prediction with the label `masks` (uint8 [B,1,...] or [B,...]) under the record
+    `regions`: predict is a uint8 label map of that shape, scored through the record's membership table, or fp32 probabilities
+    [B,R,...] (either memory layout), region r predicted where p_r > threshold.  Returns {'Dice', 'TP', 'FP', 'FN'} as [B, R] device
+    tensors (Dice fp32, the counts int64): Dice = 2 TP / (2 TP + FP + FN), and 1 where the region is empty on both sides (BraTS's
+    convention).  Integer counts with integer atomics (csrc/region.hip); no host read."""
+    R = len(regions.members)
+    if masks.dtype != torch.uint8 or not masks.is_cuda:
+        raise ValueError('region_metrics: masks must be a uint8 device label volume')
+    B = masks.shape[0]
+    truth = ops.region_bits(masks.contiguous(), regions.lut)
+    N = truth.numel() // B
+    if predict.dtype == torch.uint8:
+        if predict.numel() != truth.numel() or predict.shape[0] != B:
+            raise ValueError('region_metrics: the predicted label map must have the shape of masks')
+        pred = ops.region_bits(predict.contiguous(), regions.lut)
+    else:
+        p, planes, pB, pN, _, _ = _region_probs(predict, R, 'region_metrics')
+        if (pB, pN) != (B, N):
+            raise ValueError('region_metrics: the probabilities must cover the voxels of masks')
+        pred = torch.empty_like(truth)
+        ops._lib.call('ltu_region_prob_bits', p.data_ptr(), planes, float(threshold), pred.data_ptr(), B, N, R,
+                      torch.cuda.current_stream().cuda_stream)
+    counts = torch.zeros((B, R, 3), device=masks.device, dtype=torch.int64)
+    dice = torch.empty((B, R), device=masks.device, dtype=torch.float32)
+    ops._lib.call('ltu_region_counts', pred.data_ptr(), truth.data_ptr(), counts.data_ptr(), dice.data_ptr(), B, N, R,
+                  torch.cuda.current_stream().cuda_stream)
+    return {'Dice': dice, 'TP': counts[:, :, 0], 'FP': counts[:, :, 1], 'FN': counts[:, :, 2]}
+
+
 def _connectivity(connectivity):
     if connectivity not in (1, 2, 3):
         raise _lib.LtuError(f'connectivity must be 1, 2 or 3 (6-, 18-, 26-neighbourhood), got {connectivity}')
@@ -728,10 +791,20 @@ def segment_scan(models, scan, classes=(), **infer_volume_kwargs):
     member order, then one data.to_native_probs.  Defaults here: mode='gaussian', mirror_axes=(0, 1); every other default is
     infer_volume's.  The sum is not divided for the label (the arg-max does not change under a positive scale); with `classes` it is
     scaled by 1 / len(models) first, so the returned probabilities are the members' mean.
-    Returns to_native_probs' pair (u8 label [Z][Y][X], f32 [K][Z][Y][X] or None)."""
+    Returns to_native_probs' pair (u8 label [Z][Y][X], f32 [K][Z][Y][X] or None).
+    Region models (MaskTransUnet(..., regions=...); all members must carry equal records, with a class_order and R >= 2 regions,
+    which is what to_native_probs takes): the members' sigmoids are summed and always divided by the member count, every region's
+    plane goes through to_native_probs(classes=range(R)), and region_labels paints the label from the planes on the file's grid
+    (threshold 0.5; outside a cropped scan's box every region is 0).  `classes` is not used.  Returns (u8 label [Z][Y][X], f32
+    [R][Z][Y][X])."""
     members = [models] if isinstance(models, torch.nn.Module) else list(models)
     if not members:
         raise ValueError('segment_scan needs at least one model')
+    regions = getattr(members[0], 'regions', None)
+    if any(getattr(model, 'regions', None) != regions for model in members):
+        raise ValueError('segment_scan: the members of an ensemble must all be class models or carry equal Regions records')
+    if regions is not None and (regions.class_order is None or len(regions.members) < 2):
+        raise ValueError('segment_scan: a region model needs a class_order and at least 2 regions (data.to_native_probs takes 2 .. 8 planes)')
     kw = dict(mode='gaussian', mirror_axes=(0, 1))
     kw.update(infer_volume_kwargs)
     total = None
@@ -739,6 +812,17 @@ def segment_scan(models, scan, classes=(), **infer_volume_kwargs):
     for model in members:
         p = infer_volume(model, images, probs=True, **kw)
         total = p if total is None else total.add_(p)
+    if regions is not None:
+        if len(members) > 1:
+            total.mul_(1.0 / len(members))
+        _, planes = data.to_native_probs(total, scan, classes=range(len(regions.members)))
+        box = getattr(scan, 'crop_box', None)
+        if box is not None:      # to_native_probs fills plane 0 with 1 outside the box (a class model's background): no region lives there
+            (z0, z1), (y0, y1), (x0, x1) = box
+            inside = planes[:, z0:z1, y0:y1, x0:x1]
+            planes = torch.zeros_like(planes)
+            planes[:, z0:z1, y0:y1, x0:x1].copy_(inside)
+        return region_labels(planes, regions), planes
     if classes and len(members) > 1:
         total.mul_(1.0 / len(members))
     return data.to_native_probs(total, scan, classes)

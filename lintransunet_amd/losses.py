@@ -46,6 +46,57 @@ class Imbalance:
         return {'alpha': self.alpha, 'beta': self.beta, 'gamma': self.tversky_gamma, 'eps': self.eps, 'batch': bool(self.batch)}
 
 
+@dataclasses.dataclass(frozen=True)
+class Regions:
+    """Overlapping label regions for region-based training (nnU-Net's `regions_class_order`; csrc/region.hip), checked on the host
+    (ValueError).  members: 1 .. 8 tuples of uint8 label values; region r is the set of labels whose voxels are positive for
+    sigmoid channel r, and a label in no region is background for all of them.  class_order: None, or one label per region, used
+    only on the way back to a label map (infer.region_labels): starting from 0, the label of region r = 0, 1, .. in order is
+    written where p_r > threshold, so a later region wins.  batch: the Dice sums of 'RegionDiceLoss' run over the batch (nnU-Net's
+    batch_dice; the batch is this rank's), False: per-sample ratios, averaged; eps > 0 of that ratio.  The record is fixed when a
+    step is captured."""
+    members: Tuple[Tuple[int, ...], ...]
+    class_order: Optional[Tuple[int, ...]] = None
+    batch: bool = True
+    eps: float = 1e-5
+
+    def __post_init__(self):
+        try:
+            members = tuple(tuple(int(v) for v in region) for region in self.members)
+            order = None if self.class_order is None else tuple(int(v) for v in self.class_order)
+        except TypeError as e:
+            raise ValueError(f'Regions: members is a sequence of sequences of labels, class_order a sequence of labels ({e})')
+        if not 1 <= len(members) <= ops.REGION_MAX:
+            raise ValueError(f'Regions: 1 .. {ops.REGION_MAX} regions (one bit each of a byte), got {len(members)}')
+        if any(not region for region in members):
+            raise ValueError('Regions: an empty region')
+        if any(not 0 <= v <= 255 for region in members for v in region):
+            raise ValueError('Regions: labels are uint8, 0 .. 255')
+        if order is not None and (len(order) != len(members) or any(not 0 <= v <= 255 for v in order)):
+            raise ValueError(f'Regions: class_order needs one uint8 label for each of the {len(members)} regions')
+        if not (math.isfinite(float(self.eps)) and float(self.eps) > 0.0):
+            raise ValueError(f'Regions: eps {self.eps} must be positive')
+        object.__setattr__(self, 'members', members)
+        object.__setattr__(self, 'class_order', order)
+        object.__setattr__(self, 'batch', bool(self.batch))
+        object.__setattr__(self, 'eps', float(self.eps))
+
+    @property
+    def lut(self):
+        """256 bytes, lut[v] = sum_r [v in members[r]] << r: a label's membership of every region (ops.region_bits)"""
+        table = bytearray(256)
+        for r, region in enumerate(self.members):
+            for v in region:
+                table[v] |= 1 << r
+        return bytes(table)
+
+    @classmethod
+    def brats(cls):
+        """nnU-Net's BraTS21 convention - labels 0 background, 1 edema, 2 non-enhancing tumour, 3 enhancing tumour: whole tumour =
+        {1, 2, 3}, tumour core = {2, 3}, enhancing tumour = {3}, painted back in that order"""
+        return cls(members=((1, 2, 3), (2, 3), (3,)), class_order=(1, 2, 3))
+
+
 def _channels_last(predict):
     """[N,C,...] (any strides) -> contiguous fp32 [N,...,C]"""
     nd = predict.dim()
@@ -100,6 +151,11 @@ class LevelCriterion(nn.Module):
       class, 1 - 2 Tprec Tsens / (Tprec + Tsens) on soft skeletons of `cldice_iters` (1 .. 10) iterations, sums over the batch
       (ops.level_loss_cldice; csrc/softmorph.hip).  Needs 3-D patches; the label skeletons are built from the label patch
       (ops.label_skeletons) or given to forward as `skeletons` [B,K,...] in the order of `cldice_classes`.
+    region - with a `regions` record (`Regions`; csrc/region.hip), on a prediction of one sigmoid channel per region: 'RegionBCELoss',
+      the mean over all voxels and regions of the binary cross-entropy against the region's membership mask, and 'RegionDiceLoss',
+      the mean over the regions of (FP + FN) / (2 I + FP + FN + 2 eps) (ops.level_loss_region).  The two run alone: a spec that
+      mixes them with a class name is refused, as every other stage reads class indicators and softmax probabilities.  forward
+      takes the label [B,1,...] or, as `bits`, its bit-masks already built (ops.region_bits).
     Returns (total, {name: w * value}) with values detached: what the reference scripts log (`criterions_w * l(...)`,
     utils_3D_multi_class.py:85; all weights are 1 in the single-class script).
     """
@@ -116,12 +172,14 @@ class LevelCriterion(nn.Module):
     TVERSKY = _class_names('TverskyLoss')       # Tversky term (csrc/loss_imbalance.hip) of class ...
     FOCALCE = 'FocalCELoss'     # focal cross-entropy (csrc/loss_imbalance.hip)
     CLDICE = _class_names('ClDiceLoss')         # soft-clDice term (csrc/softmorph.hip) of class ...
-    # the names each stage of ops.level_loss_chain owns, in chain order, and the class a name stands for (None: no single class)
-    OWNED = {'base': dict(dict.fromkeys([*_TERM, *EXT]), **_class_names('DiceClassLoss')), 'boundary': BOUNDARY,
-             'topk': {TOPK: None}, 'imbalance': dict(TVERSKY, **{FOCALCE: None}), 'cldice': CLDICE}
+    REGION = {'RegionBCELoss': 1, 'RegionDiceLoss': 2}      # region terms (csrc/region.hip) -> where the stage's report holds them
+    # the names each stage of ops.level_loss_chain owns and the class a name stands for (None: no single class): the region stage,
+    # which runs alone, then the stages that combine, in chain order
+    OWNED = {'region': dict.fromkeys(REGION), 'base': dict(dict.fromkeys([*_TERM, *EXT]), **_class_names('DiceClassLoss')),
+             'boundary': BOUNDARY, 'topk': {TOPK: None}, 'imbalance': dict(TVERSKY, **{FOCALCE: None}), 'cldice': CLDICE}
 
     def __init__(self, spec: dict, scale: float = 1.0, scale_dev=None, params=None, spacing=(1.0, 1.0, 1.0), term_scale_dev=None,
-                 topk_fraction: float = 0.1, topk_fraction_dev=None, imbalance=None, cldice_iters: int = 3):
+                 topk_fraction: float = 0.1, topk_fraction_dev=None, imbalance=None, cldice_iters: int = 3, regions=None):
         super().__init__()
         if 'DistributionLoss' in spec:
             raise KeyError(_DISTRIBUTION_REFUSED)
@@ -148,6 +206,15 @@ class LevelCriterion(nn.Module):
         self.topk_fraction_dev = topk_fraction_dev      # 1-element fp32 device tensor: the fraction, read at run time
         self.cldice = self.names['cldice']
         self.cldice_iters = ops._check_iters(cldice_iters, 'cldice_iters')      # of the soft skeletons; raises ValueError
+        if regions is not None and not isinstance(regions, Regions):
+            raise ValueError('regions: a losses.Regions record')
+        self.regions = regions          # the record of the region names (None: a class model)
+        self.region = self.names['region']
+        if self.region and regions is None:
+            raise ValueError(f'{self.region}: region names need a `regions` record')
+        if self.region and len(self.region) != len(self.spec):
+            raise ValueError(f'{sorted(set(self.spec) - set(self.region))} beside {self.region}: the region terms run alone, every other '
+                             'name reads class indicators and softmax probabilities')
 
     @property
     def cldice_classes(self):
@@ -165,7 +232,7 @@ class LevelCriterion(nn.Module):
         for key, what, _, _ in self._STAGES:
             names, limit = self.names[key], C if key != 'base' or self.extended or C > 4 else 4
             absent = [name for name in names if (self.OWNED[key][name] or 0) >= limit]
-            if absent or (names and key != 'base' and C < 2):
+            if absent or (names and key not in ('base', 'region') and C < 2):
                 raise ValueError(f'{absent or names}: {what} ({C} classes)')
         fa = self.imbalance.focal_alpha if self.imbalance is not None else None
         if self.focalce and fa is not None and len(fa) != C:
@@ -181,16 +248,27 @@ class LevelCriterion(nn.Module):
                 wd[n if cls == self.FG else cls] += self.spec[name] * self.scale
         return wd
 
-    def forward(self, predict, target, params=None, phi=None, skeletons=None):
+    def forward(self, predict, target, params=None, phi=None, skeletons=None, bits=None):
         C = predict.shape[1]
         self._check_classes(C)
+        if self.region and C != len(self.regions.members):
+            raise ValueError(f'{self.region}: the prediction has {C} channels, the record {len(self.regions.members)} regions')
+        if self.regions is not None and not self.region and self.spec:
+            raise ValueError(f'{sorted(self.spec)}: class names on the prediction of a region model (use {sorted(self.REGION)})')
         if self.extended and C > self.EXT_MAXC:
             ext = sorted(name for name in self.spec if name in self.EXT)
             raise ValueError(f'{ext}: the wider loss family has kernels for C <= {self.EXT_MAXC} classes only, the prediction has {C}')
         if C > ops.LOSS_WIDE_MAXC:
             raise ValueError(f'the level losses have kernels for C <= {ops.LOSS_WIDE_MAXC} classes, the prediction has {C}')
         p = _channels_last(predict)
-        lab = _labels(target, C)
+        if not self.region:
+            lab = _labels(target, C)
+        elif bits is not None:
+            lab = bits
+        else:
+            if target.dim() < 2 or target.shape[1] != 1:
+                raise ValueError(f'{self.region}: target must be an integer label volume [N,1,...]')
+            lab = ops.region_bits(_labels(target, 1), self.regions.lut)      # the region stage reads bit-masks where the others read labels
         present = [key for key, names in self.names.items() if names] or ['base']      # no name at all: the base, at weight 0
         side = types.SimpleNamespace(phi=phi, skeletons=skeletons)      # what a stage may take ready-made instead of building it from the label
         args = {key: arg(self, C, lab, params, side) for key, _, arg, _ in self._STAGES if key in present}
@@ -257,7 +335,11 @@ class LevelCriterion(nn.Module):
                ('imbalance', 'a term of a class the prediction does not have', _imbalance_arg,
                 lambda self, C: [self.tversky.index(name) if name != self.FOCALCE else len(self.tversky) for name in self.names['imbalance']]),
                ('cldice', 'the clDice term of a class the prediction does not have', _cldice_arg,
-                lambda self, C: range(len(self.cldice))))
+                lambda self, C: range(len(self.cldice))),
+               ('region', 'a region term',
+                lambda self, C, lab, params, side: (self.spec.get('RegionBCELoss', 0.0) * self.scale, self.spec.get('RegionDiceLoss', 0.0) * self.scale,
+                                                    self.regions.batch, self.regions.eps),
+                lambda self, C: [self.REGION[name] for name in self.region]))
 
 
 def stage_names(spec):
@@ -490,6 +572,32 @@ class FocalCELoss(nn.Module):
 def cldice_name(class_index: int) -> str:
     """the spec name of the clDice term of class `class_index`: 'ClDiceLoss0c', 'ClDiceLoss', 'ClDiceLoss2' .. 'ClDiceLoss7'"""
     return _class_name('ClDiceLoss', class_index)
+
+
+class _RegionSingle(nn.Module):
+    NAME = None
+
+    def __init__(self, regions):
+        super().__init__()
+        self.impl = LevelCriterion({self.NAME: 1.0}, regions=regions)
+
+    def forward(self, predict, target):
+        return self.impl(predict, target)[0]
+
+
+class RegionBCELoss(_RegionSingle):
+    """The binary cross-entropy of nnU-Net's region-based training (no reference counterpart) on the sigmoid channels `predict`
+    [N,R,...] of the record `regions` against the membership masks of the label `target` [N,1,...], averaged over all voxels and
+    regions (ops.level_loss_region, which says where it differs from a cross-entropy on logits).  Not in Loss_Dict: it needs the
+    record."""
+    NAME = 'RegionBCELoss'
+
+
+class RegionDiceLoss(_RegionSingle):
+    """The soft Dice loss of nnU-Net's region-based training (no reference counterpart): the mean over the regions of (FP + FN) /
+    (2 I + FP + FN + 2 eps), on batch sums or per sample as the record says (ops.level_loss_region).  Not in Loss_Dict: it needs the
+    record."""
+    NAME = 'RegionDiceLoss'
 
 
 class ClDiceLoss(nn.Module):

@@ -204,10 +204,20 @@ class _WeightStore:
 
 class MaskTransUnet(nn.Module):
     def __init__(self, num_layers, roi_size_list, is_roi_list, dim_input, dim_output, kernel_size=3, dropout=0.3,
-                 act_dtype=torch.float32):
+                 act_dtype=torch.float32, regions=None):
+        """regions: a losses.Regions record makes this a region model (nnU-Net's region-based training): dim_output = the number
+        of regions, every head a sigmoid per region where a class model has a softmax over classes, and the ROI foreground the
+        union of the regions.  Parameters, state_dict keys and shapes are those of the class model with the same dim_output."""
         super().__init__()
         if kernel_size != 3:
             raise ValueError('only the reference default kernel_size=3 is supported')
+        if regions is not None:
+            from .losses import Regions
+            if not isinstance(regions, Regions):
+                raise ValueError('regions: a losses.Regions record')
+            if dim_output != len(regions.members):
+                raise ValueError(f'dim_output {dim_output} must equal the {len(regions.members)} regions of the record')
+        self.regions = regions
         # the reference's windows_embedding reshape assumes one channel (Unet_3Dblock.py:131-132); here channel c of the input fills
         # the stem's channels 4c .. 4c + 3, the inverse of its windows_unembedding
         ops.embed_channels(dim_input)        # ValueError outside 1 .. 4
@@ -395,7 +405,7 @@ class MaskTransUnet(nn.Module):
 
     def _roi_bridge(self, br, skip, mask, roi_size, p, seeds):
         """model/Unet_3Dblock.py:717-755"""
-        plan = ops.RoiPlan(mask, roi_size, 0.5)
+        plan = ops.RoiPlan(mask, roi_size, 0.5, union=self.regions is not None)
         self.last_boxes.append(plan.box)
         tr = br.transformer
         g = ops.roi_warp(skip, plan)
@@ -410,7 +420,8 @@ class MaskTransUnet(nn.Module):
     # ------------------------------------------------------------------ forward
     def forward(self, x, probs=False):
         """training: (probabilities, masks) in the reference's shape; eval: the one-hot arg-max [B, C, H, W, D] (channels-last
-        memory), or with probs=True the fp32 softmax it is taken from (same layout; refused in training mode)"""
+        memory), or with probs=True the fp32 softmax it is taken from (same layout; refused in training mode).  A region model
+        returns its sigmoid probabilities in both places, and in eval mode without probs their indicator p > 0.5 as fp32"""
         if probs and self.training:
             raise ValueError('probs=True is an eval-mode output; call model.eval() first')
         if not x.is_cuda:
@@ -431,6 +442,7 @@ class MaskTransUnet(nn.Module):
 
     def _forward(self, x, probs=False):
         L, nl, C = self.num_layers, len(self.num_layers), self.dim_output
+        head, final = (ops.head_softmax, ops.final_softmax) if self.regions is None else (ops.head_sigmoid, ops.final_sigmoid)
         p = float(self.dropout) if self.training else 0.0
         self._step += 1
         seeds = _SeedStream(torch.initial_seed() * 1000003 + self._step)
@@ -486,7 +498,7 @@ class MaskTransUnet(nn.Module):
             mc = dec.mask_conv_list[lvl]
             blk = dec.block_list[i - 1]
             t1, zm = ops.conv3d_pair(t, blk.conv1.weight, blk.conv1.bias, mc.weight, mc.bias, store.pair[lvl])
-            m = ops.head_softmax(zm, C)
+            m = head(zm, C)
             masks.append(m)
             ag = dec.att_conv_list[lvl]
             skip = ops.attention_gate(skips[-i], t_gate, ag.W_x[0].weight, ag.W_x[0].bias, ag.W_g[0].weight, ag.W_g[0].bias,
@@ -497,12 +509,12 @@ class MaskTransUnet(nn.Module):
             t = ops.instnorm_act(t1, act=ops.ACT_LRELU)
             t = self._conv_in_act(t, blk.conv2, x1=skip, p=p, seeds=seeds)
         z = ops.conv3d(t, dec.final_block.weight, dec.final_block.bias, cop=self._final_cop(), prep=store.conv[id(dec.final_block)])
-        out = ops.final_softmax(z, C)
+        out = final(z, C)
         if self.training:
             return _cl(out), [_cl(m) for m in masks]
         if probs:
             return _cl(out.detach())
-        return _cl(ops.onehot_argmax(out.detach()))
+        return _cl(ops.onehot_argmax(out.detach()) if self.regions is None else ops.prob_indicator(out.detach(), 0.5))
 
 
 Model_Dict = {'MaskTransUnet': MaskTransUnet}

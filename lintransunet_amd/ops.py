@@ -580,6 +580,36 @@ def label_maxpool(lab, kd):
     return y
 
 
+REGION_MAX = 8      # REG_MAXR of csrc/region.hip: most regions of a record (one bit each of a byte)
+
+
+def region_bits(label, lut):
+    """uint8 labels (any shape), lut: 256 bytes (losses.Regions.lut) -> uint8 bit-masks lut[label], bit r = membership of region r."""
+    _chk(label, 'label')
+    if label.dtype != torch.uint8 or len(lut) != 256:
+        raise ValueError('region_bits: label must be uint8 and lut 256 bytes')
+    out = torch.empty_like(label)
+    _lib.call('ltu_region_bits', _p(label), bytes(lut), _p(out), label.numel(), _s())
+    return out
+
+
+def bits_orpool(bits, kd):
+    """uint8 bit-masks [B,H,W,D] -> bitwise OR over the (2,2,kd) windows of label_maxpool."""
+    _chk(bits, 'bits')
+    B, H, W, D = bits.shape
+    y = torch.empty((B, H // 2, W // 2, D // kd), device=bits.device, dtype=torch.uint8)
+    _lib.call('ltu_bits_orpool', _p(bits), _p(y), B, H, W, D, kd, _s())
+    return y
+
+
+def prob_indicator(p, thr=0.5):
+    """fp32 probabilities (any shape) -> fp32 indicator of p > thr."""
+    _chk(p, 'p')
+    o = torch.empty_like(p)
+    _lib.call('ltu_prob_indicator', _p(p), _p(o), p.numel(), float(thr), _s())
+    return o
+
+
 def onehot_argmax(p):
     """probabilities [..., C] fp32 -> one-hot of the arg-max class."""
     o = torch.empty_like(p)
@@ -591,7 +621,9 @@ def onehot_argmax(p):
 class RoiPlan:
     """Per-sample boxes and the separable sampling plans of one ROI bridge (device resident)."""
 
-    def __init__(self, prob, roi_size, thr=0.5):
+    def __init__(self, prob, roi_size, thr=0.5, union=False):
+        """union: prob holds the channels of a region model; the foreground is max_r prob[..., r] where a class model's is 1 -
+        prob[..., 0] (ltu_roi_plan_union)"""
         _chk(prob, 'prob')
         B, H, W, D, C = prob.shape
         ni, nf, nh = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_longlong(0)
@@ -604,7 +636,7 @@ class RoiPlan:
         self.fbuf = torch.empty(nf.value, device=prob.device, dtype=torch.float32)
         self.box = torch.empty((B, 6), device=prob.device, dtype=torch.float32)
         hist = current().scratch_zeros((nh.value,), prob.device)          # zero bits: read as int32 by the kernels
-        _lib.call('ltu_roi_plan', _p(prob), B, H, W, D, C, roi_size, float(thr), _p(self.box), _p(self.ibuf), _p(self.fbuf),
+        _lib.call('ltu_roi_plan_union' if union else 'ltu_roi_plan', _p(prob), B, H, W, D, C, roi_size, float(thr), _p(self.box), _p(self.ibuf), _p(self.fbuf),
                   _p(hist), _s())
 
 
@@ -1569,6 +1601,62 @@ def final_softmax(z, C):
     return _FinalSoftmax.apply(z, C)
 
 
+class _HeadSigmoid(torch.autograd.Function):
+    """_HeadSoftmax on the sigmoid entries: the heads of a region model"""
+
+    @staticmethod
+    def forward(ctx, z, R):
+        _chk(z, 'z')
+        CP = z.shape[-1]
+        p = torch.empty(z.shape[:-1] + (R,), device=z.device, dtype=torch.float32)
+        _lib.call('ltu_head_sigmoid_fwd', _p(z), _p(p), z.numel() // CP, R, CP, _dt(z), _s())
+        ctx.save_for_backward(p)
+        ctx.cfg = (R, CP, z.dtype)
+        return p
+
+    @staticmethod
+    def backward(ctx, g):
+        (p,) = ctx.saved_tensors
+        R, CP, zdt = ctx.cfg
+        g = g.contiguous()
+        dz = torch.empty(p.shape[:-1] + (CP,), device=p.device, dtype=zdt)
+        _lib.call('ltu_head_sigmoid_bwd', _p(g), _p(p), _p(dz), p.numel() // R, R, CP, _dt(dz), _s())
+        return dz, None
+
+
+def head_sigmoid(z, R):
+    """one sigmoid per region over the first R <= 8 of the (padded) channels of z -> fp32 probabilities [..., R]."""
+    return _HeadSigmoid.apply(z, R)
+
+
+class _FinalSigmoid(torch.autograd.Function):
+    """_FinalSoftmax on the sigmoid entries"""
+
+    @staticmethod
+    def forward(ctx, z, R):
+        _chk(z, 'z')
+        B, h, w, D, CP = z.shape
+        p = torch.empty((B, 2 * h, 2 * w, D, R), device=z.device, dtype=torch.float32)
+        _lib.call('ltu_final_sigmoid_fwd', _p(z), _p(p), B, h, w, D, R, CP, _dt(z), _s())
+        ctx.save_for_backward(p)
+        ctx.cfg = (B, h, w, D, R, CP, z.dtype)
+        return p
+
+    @staticmethod
+    def backward(ctx, g):
+        (p,) = ctx.saved_tensors
+        B, h, w, D, R, CP, zdt = ctx.cfg
+        g = g.contiguous()
+        dz = torch.empty((B, h, w, D, CP), device=p.device, dtype=zdt)
+        _lib.call('ltu_final_sigmoid_bwd', _p(g), _p(p), _p(dz), B, h, w, D, R, CP, _dt(dz), _s())
+        return dz, None
+
+
+def final_sigmoid(z, R):
+    """window un-embedding + one sigmoid per region: z [B,h,w,D,CP >= 4R], R <= 8 -> fp32 probabilities [B,2h,2w,D,R]."""
+    return _FinalSigmoid.apply(z, R)
+
+
 class _Gate(torch.autograd.Function):
     """skip * sigmoid(psi . relu(IN(Wx skip) + IN(Wg up)) + b)   (model/Unet_3Dblock.py:217-221, 1385)."""
 
@@ -1913,6 +2001,44 @@ class _ClDiceStage(_Stage):
                   B, *self.dims, C, _s())
 
 
+class _RegionStage(_Stage):
+    """region = (weight_bce, weight_dice, batch, eps), see level_loss_region (csrc/region.hip); every check raises ValueError.  The
+    chain's `label` is the bit-mask volume (region_bits) and its `p` the R sigmoid channels.  buf = [total, BCE, Dice, D_0 .. D_{R-1},
+    total]: buf[:-1] is the report and buf[-1] repeats the total as the differentiable output, as the base's does"""
+    REPORT, TOTAL = slice(None, -1), -1
+
+    def __init__(self, region, R=None):
+        w_bce, w_dice, batch, eps = region
+        self.w_bce, self.w_dice, self.batch, self.eps = float(w_bce), float(w_dice), int(bool(batch)), float(eps)
+        if not (math.isfinite(self.w_bce) and math.isfinite(self.w_dice)):
+            raise ValueError('region stage: non-finite weight')
+        if not (math.isfinite(self.eps) and self.eps > 0.0):
+            raise ValueError(f'region stage: eps {eps} must be positive')
+        if R is not None and not 1 <= R <= REGION_MAX:
+            raise ValueError(f'region stage: 1 .. {REGION_MAX} region channels, got {R}')
+
+    def check(self, p, label, phi):
+        B, R = p.shape[0], p.shape[-1]
+        if not 1 <= R <= REGION_MAX or B * R * 4 > 256:
+            raise ValueError(f'region stage: 1 .. {REGION_MAX} regions and batch * regions <= 64, got {B} x {R}')
+        if p.dtype != torch.float32 or label.dtype != torch.uint8 or label.numel() * R != p.numel():
+            raise ValueError('region stage: p must be fp32 [B,...,R] and the bit-masks uint8 [B,...] over the voxels of p')
+
+    def forward(self, p, label, phi, before, scale_dev, B, S, C):
+        need = _lib.load().ltu_loss_region_ws_floats(B, S, C)
+        if need <= 0:
+            raise _lib.LtuError('ltu_loss_region_ws_floats: 1 <= R <= 8 regions and B * R * 4 <= 256')
+        sums = torch.empty(need, device=p.device, dtype=torch.float32)      # partials + sums: no zero fill
+        buf = torch.empty(C + 4, device=p.device, dtype=torch.float32)
+        coef = torch.empty((B, C, 3), device=p.device, dtype=torch.float32)
+        _lib.call('ltu_loss_region_fwd', _p(p), _p(label), _p(sums), _n(sums), _p(buf), _p(coef), _p(before), self.w_bce, self.w_dice,
+                  self.batch, self.eps, _p(scale_dev), B, S, C, _s())
+        return buf, coef
+
+    def backward(self, coef, p, label, g, dp, written, scale_dev, B, S, C):
+        _lib.call('ltu_loss_region_bwd', _p(p), _p(label), _p(coef), _n(coef), _p(g), _p(dp), written, B, S, C, _s())
+
+
 class _LevelLossChain(torch.autograd.Function):
     """The loss of one decoder level as a chain of stages (objects of the classes above, in the order level_loss_chain gives them)
     on the maps `phi` (None without a boundary stage).  Each forward adds the total before it and each backward adds into the dp
@@ -1946,25 +2072,33 @@ class _LevelLossChain(torch.autograd.Function):
         return (dp,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
-def level_loss_chain(p, label, base=None, boundary=None, topk=None, scale_dev=None, imbalance=None, cldice=None):
+def level_loss_chain(p, label, base=None, boundary=None, topk=None, scale_dev=None, imbalance=None, cldice=None, region=None):
     """p fp32 [B,...,C] channels-last probabilities, label uint8 [B,...]: the sum of the given stages, at least one, in one autograd
     node.  base = ('ltu_loss' | 'ltu_loss_wide', (w_ce, w_bal, w_dice)) or ('ltu_loss_ext', loss_ext_cfg(..)), as level_loss /
     level_loss_wide / level_loss_ext launch it; boundary = (phi, classes, weights, term_scale_dev), see level_loss_boundary; topk =
     (weight, frac, frac_dev), see level_loss_topk; imbalance = (tversky, focal), see level_loss_imbalance; cldice = (skeletons or
-    None, classes, weights, iters), see level_loss_cldice, runs last and needs p as [B,H,W,D,C].  scale_dev: optional 1-element fp32
+    None, classes, weights, iters), see level_loss_cldice, needs p as [B,H,W,D,C]; region = (weight_bce, weight_dice, batch, eps),
+    see level_loss_region, runs alone: p then holds the R sigmoid channels of a region model and `label` the bit-masks of
+    region_bits, which no other stage can read (ValueError).  scale_dev: optional 1-element fp32
     device tensor multiplying all weights at run time.  Returns (total, base values, boundary values, top-k values, imbalance
-    values, clDice values), None for a stage not given, values detached; every check is made before the first launch and there is
-    no host synchronisation."""
+    values, clDice values), None for a stage not given, values detached; with `region` the tuple is one entry longer, the region
+    values at its end behind five None (a call without it returns what it always returned).  Every check is made before the first
+    launch and there is no host synchronisation."""
     phi, *_ = boundary or [None]      # the maps travel beside the stages: the chain saves them for the backward
-    args = {_BaseStage: base, _BoundaryStage: boundary, _TopkStage: topk, _ImbalanceStage: imbalance, _ClDiceStage: cldice}      # in chain order
+    args = {_BaseStage: base, _BoundaryStage: boundary, _TopkStage: topk, _ImbalanceStage: imbalance, _ClDiceStage: cldice,
+            _RegionStage: region}      # in chain order
     if all(arg is None for arg in args.values()):
-        raise ValueError('level_loss_chain: at least one of base, boundary, topk, imbalance and cldice')
+        raise ValueError('level_loss_chain: at least one of base, boundary, topk, imbalance, cldice and region')
+    if region is not None and any(arg is not None for stage, arg in args.items() if stage is not _RegionStage):
+        raise ValueError('level_loss_chain: the region stage runs alone: every other stage reads class indicators and softmax probabilities')
     stages = [stage(arg, p.shape[-1]) for stage, arg in args.items() if arg is not None]      # the host checks of the arguments
     _chk(p, 'p'); _chk(label, 'label')
     for stage in stages:
         stage.check(p, label, phi)
-    out = iter(_LevelLossChain.apply(p, label, phi, scale_dev, stages))
-    return (next(out), *(None if arg is None else next(out) for arg in args.values()))
+    total, *out = _LevelLossChain.apply(p, label, phi, scale_dev, stages)
+    out = iter(out)
+    reports = [None if arg is None else next(out) for arg in args.values()]
+    return (total, *(reports if region is not None else reports[:-1]))      # the sixth entry only where the sixth stage runs
 
 
 def level_loss(p, label, w_ce=0.0, w_bal=0.0, w_dice=(), scale_dev=None):
@@ -2056,6 +2190,18 @@ def level_loss_imbalance(p, label, tversky=None, focal=None, base=None, scale_de
     launch and there is no host synchronisation."""
     total, base_values, _, _, values, _ = level_loss_chain(p, label, base, scale_dev=scale_dev, imbalance=(tversky, focal))
     return total, base_values, values
+
+
+def level_loss_region(p, bits, weight_bce=1.0, weight_dice=1.0, batch=True, eps=1e-5, scale_dev=None):
+    """p fp32 [B,...,R] channels-last sigmoid probabilities of R <= 8 regions (B * R <= 64), bits uint8 [B,...] (region_bits): with
+    t_r = (bits >> r) & 1, scale_dev[0] * (weight_bce * BCE + weight_dice * Dice) (csrc/region.hip).  BCE is the mean over all B S R
+    entries of -[t log max(p, 1e-6) + (1 - t) log max(1 - p, 1e-6)] (nnU-Net applies it to the logits: the two differ only where
+    |z| > 13.8); Dice = (1 / R) sum_r D_r with D_r = (FP + FN) / (2 I + FP + FN + 2 eps) on I = sum p t, FP = sum p (1 - t), FN =
+    sum t (1 - p), with `batch` on sums over the whole batch (nnU-Net's batch_dice), else per sample and averaged.  The gradient
+    is that of the clamped expression.  Two calls agree bit for bit.  Returns (total, [total, BCE, Dice, D_0 .. D_{R-1}]), the
+    values detached; every check is made before the first launch and there is no host synchronisation."""
+    total, *_, values = level_loss_chain(p, bits, scale_dev=scale_dev, region=(weight_bce, weight_dice, batch, eps))
+    return total, values
 
 
 class _SoftMorph(torch.autograd.Function):

@@ -62,6 +62,48 @@ def label_pyramid(label, n_levels=5):
     return out
 
 
+def region_pyramid(label, regions, n_levels=5):
+    """label_pyramid for a region model: uint8 [B,1,H,W,D] -> the bit-masks (ops.region_bits with the record's table) of level 0 and
+    their OR-pooled levels 1..n-1 over label_pyramid's windows, so that every region's indicator is max-pooled on its own (a max
+    of the raw label would be wrong for regions that are not nested in label order)"""
+    lab = label.reshape(label.shape[0], *label.shape[2:]).to(torch.uint8).contiguous()
+    out = [ops.region_bits(lab, regions.lut)]
+    cur = ops.bits_orpool(out[0], 1)
+    for lvl in range(1, n_levels):
+        out.append(cur)
+        if lvl < n_levels - 1:
+            cur = ops.bits_orpool(cur, 2 if lvl % 2 == 0 else 1)
+    return out
+
+
+REGION_CRITERIA = ('RegionBCELoss', 'RegionDiceLoss')
+
+
+def region_specs(specs, n_levels, regions):
+    """the specs of a step, checked against the model's kind before anything is launched (ValueError): a region model (`regions` a
+    losses.Regions record) takes region names only, at every level, and by default BCE + Dice at weight 1; a class model takes none"""
+    if regions is None:
+        specs = specs or level_specs(n_levels)
+        named = [name for spec in specs for name in stage_names(spec)['region']]
+        if named:
+            raise ValueError(f'{sorted(set(named))}: region names need a region model (MaskTransUnet(..., regions=...))')
+        return specs
+    specs = specs or level_specs(n_levels, REGION_CRITERIA, criterion_weight=[1.0, 1.0])
+    other = [name for spec in specs for name in spec if name not in stage_names(spec)['region']]
+    if other:
+        raise ValueError(f'{sorted(set(other))}: class names in the specs of a region model (its heads are sigmoids per region: use '
+                         f'{list(REGION_CRITERIA)})')
+    return specs
+
+
+def _model_regions(model, regions):
+    """the record a step runs with: the model's; a `regions` argument must agree with it"""
+    own = getattr(model, 'regions', None)
+    if regions is not None and regions != own:
+        raise ValueError('regions: the step reads the record from model.regions; the argument differs from it')
+    return own
+
+
 def boundary_maps(pyr, specs, spacing=(1.0, 1.0, 1.0)):
     """signed distance maps for the levels whose spec has a boundary name (losses.boundary_classes), from the pyramid's
     labels: a list over levels of fp32 [B,K,h,w,d] or None.  The voxels of level l are `spacing` * (H_0 / H_l, W_0 / W_l,
@@ -94,7 +136,7 @@ def has_topk(specs):
 
 
 def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0, level_scale=None, pyr=None, spacing=(1.0, 1.0, 1.0),
-                          boundary_scale=None, phis=None, topk_fraction=0.1, imbalance=None, cldice_iters=3, skels=None):
+                          boundary_scale=None, phis=None, topk_fraction=0.1, imbalance=None, cldice_iters=3, skels=None, regions=None):
     """Per-level fused losses (utils/utils_3D_embed_full.py:66-82).  Returns (list of weighted level totals,
     list of {name: value}); `sum(totals)` is the reference's total_loss * scale.
     level_scale: optional fp32 device tensor [n_levels] that REPLACES `weights[lvl] * scale` at run time (a captured graph
@@ -107,9 +149,14 @@ def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0,
     imbalance: a losses.Imbalance record, the parameters of the 'TverskyLoss..' and 'FocalCELoss' names at every level (None: its
     defaults).
     cldice_iters: iterations of the soft skeletons of the 'ClDiceLoss..' names at every level (1 .. 10); skels: the levels' label
-    skeletons, already built (skeleton_maps with the same iters).  A spec list without clDice names uses neither."""
+    skeletons, already built (skeleton_maps with the same iters).  A spec list without clDice names uses neither.
+    regions: the losses.Regions record of a region model, whose predictions are sigmoid channels per region: the specs hold region
+    names only (default BCE + Dice), and pyr, when given, is the region_pyramid."""
     n = len(weights)
-    specs = specs or level_specs(n)
+    specs = region_specs(specs, n, regions)
+    if regions is not None:
+        pyr = pyr or region_pyramid(label, regions, n)
+        phis, skels = [None] * n, [None] * n
     pyr = pyr or label_pyramid(label, n)      # pyr: the pyramid, already built (train_step builds it beside the encoder)
     if phis is None:
         phis = boundary_maps(pyr, specs, spacing)      # None at the levels without a boundary name: nothing is launched for them
@@ -121,37 +168,44 @@ def deep_supervision_loss(predict, masks, label, weights, specs=None, scale=1.0,
         pred = predict if lvl == 0 else masks[-lvl]
         crit = LevelCriterion(specs[-lvl - 1], scale=weights[lvl] * scale if level_scale is None else 1.0,
                               scale_dev=None if level_scale is None else level_scale[lvl:lvl + 1], term_scale_dev=boundary_scale,
-                              imbalance=imbalance, cldice_iters=cldice_iters, **kw)
-        tot, vals = crit(pred, pyr[lvl].unsqueeze(1), phi=phis[lvl], skeletons=skels[lvl])
+                              imbalance=imbalance, cldice_iters=cldice_iters, regions=regions, **kw)
+        tot, vals = crit(pred, pyr[lvl].unsqueeze(1), phi=phis[lvl], skeletons=skels[lvl], bits=None if regions is None else pyr[lvl])
         totals.append(tot)
         named.append(vals)
     return totals, named
 
 
 def train_step(model, images, labels, weights, step_times=1, specs=None, reducer=None, ctx=None, level_scale=None, reduce=True,
-               spacing=(1.0, 1.0, 1.0), boundary_scale=None, topk_fraction=0.1, imbalance=None, cldice_iters=3):
+               spacing=(1.0, 1.0, 1.0), boundary_scale=None, topk_fraction=0.1, imbalance=None, cldice_iters=3, regions=None):
     """forward + 5-level loss + backward for one batch of patches (one `j` of utils_3D_embed_full.py:55-86).
     Returns the list of weighted level losses (device scalars, no host sync).
     Gradient accumulation (utils_3D_embed_full.py:85-91): call `step_times` times with reduce=False except on the last
     micro-step; the caller zeroes the gradients before the first one.
     spacing, boundary_scale: see deep_supervision_loss; the distance maps of the levels with a boundary name are built behind the
     label pyramid on the side stream, as are the label skeletons of the levels with a clDice name.  topk_fraction, imbalance,
-    cldice_iters: see deep_supervision_loss."""
+    cldice_iters: see deep_supervision_loss.  A region model (model.regions; `regions`, when given, must equal it) trains on region
+    names only; its region_pyramid is built where the label pyramid is."""
     lc = ctx or ops.current()
+    regions = _model_regions(model, regions)
+    specs = region_specs(specs, len(weights), regions)      # raises before the first launch
     with ops.use(lc):
         lc.begin_step(images.device)
         pyr, phis, skels = [], [], []
 
         def side():
+            if regions is not None:
+                pyr.extend(region_pyramid(labels, regions, len(weights)))
+                return
             pyr.extend(label_pyramid(labels, len(weights)))
-            phis.extend(boundary_maps(pyr, specs or level_specs(len(weights)), spacing))
-            skels.extend(skeleton_maps(pyr, specs or level_specs(len(weights)), cldice_iters))
+            phis.extend(boundary_maps(pyr, specs, spacing))
+            skels.extend(skeleton_maps(pyr, specs, cldice_iters))
         lc.side_run(side)                    # beside the encoder (joined inside the model's forward)
         predict, masks = model(images)
         lc.side_join()
         totals, named = deep_supervision_loss(predict, masks, labels, weights, specs, scale=1.0 / step_times, level_scale=level_scale,
-                                              pyr=pyr, spacing=spacing, boundary_scale=boundary_scale, phis=phis,
-                                              topk_fraction=topk_fraction, imbalance=imbalance, cldice_iters=cldice_iters, skels=skels)
+                                              pyr=pyr, spacing=spacing, boundary_scale=boundary_scale, phis=phis or None,
+                                              topk_fraction=topk_fraction, imbalance=imbalance, cldice_iters=cldice_iters,
+                                              skels=skels or None, regions=regions)
         if reducer is not None:
             reducer.prepare(lc, reduce=reduce)
         one = lc.one(images.device)
@@ -368,8 +422,10 @@ class GraphedStep:
     """
 
     def __init__(self, model, images, labels, weights, reducer, step_times=1, specs=None, warmup=2, overlap=None,
-                 spacing=(1.0, 1.0, 1.0), boundary_scale=1.0, topk_fraction=0.1, imbalance=None, cldice_iters=3):
+                 spacing=(1.0, 1.0, 1.0), boundary_scale=1.0, topk_fraction=0.1, imbalance=None, cldice_iters=3, regions=None):
         self.model, self.reducer = model, reducer
+        self.regions = _model_regions(model, regions)      # of a region model: baked into the capture, as `imbalance` is
+        specs = region_specs(specs, len(weights), self.regions) if self.regions is not None or specs is not None else None
         self.imbalance = imbalance
         self.cldice_iters = ops._check_iters(cldice_iters, 'cldice_iters')
         self.spacing = tuple(float(v) for v in spacing)
@@ -448,7 +504,7 @@ class GraphedStep:
                               reduce=reduce and self.overlap in ('graph', 'segments'), spacing=self.spacing,
                               boundary_scale=self.boundary_scale,
                               topk_fraction=0.1 if self.topk_fraction is None else self.topk_fraction, imbalance=self.imbalance,
-                              cldice_iters=self.cldice_iters)
+                              cldice_iters=self.cldice_iters, regions=self.regions)
         finally:
             self.ctx.wq_install(None)
 
