@@ -331,8 +331,8 @@ int ltu_final_softmax_bwd(const float* dp, const float* p, void* dz, int B, int 
                           ltu_stream_t s);
 /* The heads of a region model (csrc/region.hip): channel r is the sigmoid of logit r, p = 1 / (1 + exp(-z)), finite and in [0, 1] for
  * every finite logit; arguments, padded columns (CP), dtypes and window un-embedding of the softmax heads above, 1 <= R <= 8.  The
- * backward forms dz = (dp p) (1 - p) from the saved p and writes the padding columns as zero; every launch form of a row (vector or
- * scalar accesses) gives the same bits. */
+ * backward forms dz = (dp p) (1 - p) from the saved p and writes the padding columns as zero; every launch form of a row (one
+ * 16-byte store per 8 bf16 columns, vector or scalar accesses) gives the same bits. */
 int ltu_head_sigmoid_fwd(const void* z, float* p, long long M, int R, int CP, int dtype, ltu_stream_t s);
 int ltu_head_sigmoid_bwd(const float* dp, const float* p, void* dz, long long M, int R, int CP, int dtype, ltu_stream_t s);
 int ltu_final_sigmoid_fwd(const void* z, float* p, int B, int h, int w, int D, int R, int CP, int dtype, ltu_stream_t s);

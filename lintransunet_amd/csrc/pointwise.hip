@@ -277,8 +277,11 @@ extern "C" int ltu_gelu_dropout_bwd(const void* dh, const void* u, void* du, lon
   return ltu_check_launch();
 }
 
-// ------------------------------------------------------------------------------------------------ class softmax heads
-// One kernel family for 1 .. 8 classes.  The class count is a template argument everywhere: per-thread arrays are indexed by unrolled
+// ------------------------------------------------------------------------------------------------ class and region heads
+// One kernel family for 1 .. 8 classes (softmax) or regions (one sigmoid each, region.hip).  The activation is a policy type, Softmax or
+// Sigmoid below, that holds the arithmetic of one row - its probabilities and its gradient - and nothing else: loads, stores, index
+// arithmetic, the zero stores behind the live columns and the grids exist once.
+// The class count is a template argument everywhere: per-thread arrays are indexed by unrolled
 // loops only (a run-time class loop over them would put them in scratch memory or serialise the loads: 16 dependent round trips per
 // thread in the final backward), and all loads of a row / coarse voxel are issued before the arithmetic.  A thread holds a row in
 // HEAD_W(C) registers, 4 up to four classes and 8 above; what lies behind the live classes is constant zero.
@@ -343,200 +346,36 @@ __device__ __forceinline__ void ldlogits(const T* __restrict__ q, float (&v)[HEA
 // rows of CP elements of `elt` bytes, the first at `base`, all start on a multiple of `unit` bytes
 static bool rows_aligned(const void* base, int CP, int elt, int unit) { return CP * elt % unit == 0 && (uintptr_t)base % unit == 0; }
 
-// mask head (model/Unet_3Dblock.py:1380-1381): logits T [M][CP] (CP = padded conv width, first C live) -> probs f32 [M][C].
-// VEC: ldlogits may read the row (see the launcher); otherwise C scalar loads
-template <typename T, int C, bool VEC>
-__global__ void __launch_bounds__(256) head_softmax_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, long long M, int CP) {
-  constexpr int W = HEAD_W(C);
-  GRID_STRIDE(m, M) {
-    float v[W];
-    if constexpr (VEC) ldlogits<T, C>(z + m * CP, v);
-    else {
-#pragma unroll
-      for (int c = 0; c < C; ++c) v[c] = ld1<T>(z + m * CP + c);
-    }
+// ---- the activations.  A policy has two members: probs<C>(v) turns the logits of a row, in place, into numerators and returns the
+// divisor stprobs takes with them; grad<C, FUSED>(dp, p, g) forms the row's logit gradient from dp and the saved p, g[c >= C] = 0.
+struct Softmax {
+  // e^(v - max) and their sum
+  template <int C>
+  static __device__ __forceinline__ float probs(float (&v)[HEAD_W(C)]) {
     float mx = -INFINITY, sum = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) mx = fmaxf(mx, v[c]);
 #pragma unroll
     for (int c = 0; c < C; ++c) { v[c] = expf(v[c] - mx); sum += v[c]; }
-    stprobs<C>(p + m * C, v, sum);
+    return sum;
   }
-}
-// g[c] = p_c (dp_c - sum_k dp_k p_k) for c < C, 0 behind.  The rounding of the sum is written out, not left to -ffp-contract=fast (which
-// fuses or packs the products differently from one instantiation to the next), and is the one the results at C = 2, 3 have always
-// carried: an fma chain in the row kernels (FUSED; what the loop over a run-time C compiled to, and what the final head does), every
-// product rounded before it is added - fmaf(x, y, 0) - in the 16-byte-store kernel (what its packed multiplies gave)
-template <int C, bool FUSED>
-__device__ __forceinline__ void head_grad(const float* __restrict__ dp, const float* __restrict__ p, long long m, float (&g)[HEAD_W(C)]) {
-  constexpr int W = HEAD_W(C);
-  float a[W], b[W];
-  ldrow<C>(dp + m * C, a);
-  ldrow<C>(p + m * C, b);
-  float dot = 0.f;
+  // g[c] = p_c (dp_c - sum_k dp_k p_k).  The rounding of the sum is written out, not left to -ffp-contract=fast (which fuses or packs the
+  // products differently from one instantiation to the next), and is the one the results at C = 2, 3 have always carried: an fma chain
+  // in the row kernels and in the final head (FUSED; what the loop over a run-time C compiled to), every product rounded before it is
+  // added - fmaf(x, y, 0) - in the 16-byte-store kernel (what its packed multiplies gave)
+  template <int C, bool FUSED>
+  static __device__ __forceinline__ void grad(const float (&a)[HEAD_W(C)], const float (&b)[HEAD_W(C)], float (&g)[HEAD_W(C)]) {
+    float dot = 0.f;
 #pragma unroll
-  for (int c = 0; c < C; ++c) dot = FUSED ? fmaf(a[c], b[c], dot) : dot + fmaf(a[c], b[c], 0.f);
+    for (int c = 0; c < C; ++c) dot = FUSED ? fmaf(a[c], b[c], dot) : dot + fmaf(a[c], b[c], 0.f);
 #pragma unroll
-  for (int c = 0; c < W; ++c) g[c] = c < C ? b[c] * (a[c] - dot) : 0.f;
-}
-// bf16 rows of CP = 8k padded logits: one thread and one 16-byte store per 8 columns (the fused conv pairs pad the heads to 16 / 32
-// columns); the first group holds the C gradients, every other word is a constant zero
-template <int C>
-__global__ void __launch_bounds__(256) head_softmax_bwd_bf16x8_kernel(const float* __restrict__ dp, const float* __restrict__ p,
-                                                                      uint4* __restrict__ dz, long long M, int CP) {
-  const int v8 = CP / 8;
-  GRID_STRIDE(i, M * v8) {
-    const long long m = i / v8;
-    uint4 o = make_uint4(0u, 0u, 0u, 0u);
-    if (i - m * v8 == 0) {
-      float g[HEAD_W(C)];
-      head_grad<C, false>(dp, p, m, g);
-      o.x = pack_bf16x2(g[0], g[1]);
-      o.y = pack_bf16x2(g[2], g[3]);
-      if constexpr (C > 4) {
-        o.z = pack_bf16x2(g[4], g[5]);
-        o.w = pack_bf16x2(g[6], g[7]);
-      }
-    }
-    dz[i] = o;
+    for (int c = 0; c < HEAD_W(C); ++c) g[c] = c < C ? b[c] * (a[c] - dot) : 0.f;
   }
-}
-// one thread per row.  VEC: every row starts on a Vec4<T> boundary and CP % 4 == 0: 4-wide stores, zeros behind the first HEAD_W(C)
-// columns; otherwise scalar stores
-template <typename T, int C, bool VEC>
-__global__ void __launch_bounds__(256) head_softmax_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz,
-                                                               long long M, int CP) {
-  constexpr int W = HEAD_W(C);
-  GRID_STRIDE(m, M) {
-    float g[W];
-    head_grad<C, true>(dp, p, m, g);
-    T* o = dz + m * CP;
-    if constexpr (VEC) {
-#pragma unroll
-      for (int k = 0; k < W; k += 4) Vec4<T>::store(o + k, make_float4(g[k], g[k + 1], g[k + 2], g[k + 3]));
-      for (int k = W; k < CP; k += 4) Vec4<T>::store(o + k, make_float4(0.f, 0.f, 0.f, 0.f));
-    } else {
-#pragma unroll
-      for (int c = 0; c < C; ++c) st1<T>(o + c, g[c]);
-      for (int c = C; c < CP; ++c) st1<T>(o + c, 0.f);
-    }
-  }
-}
-extern "C" int ltu_head_softmax_fwd(const void* z, float* p, long long M, int C, int CP, int dtype, ltu_stream_t s) {
-  if (C < 1 || C > LTU_WIDE_MAXC || CP < C) return LTU_E_SHAPE;
-  LTU_DISPATCH_T(dtype, {
-    LTU_DISPATCH_C(C, {
-      // ldlogits reads HEAD_W(C) logits in units of a Vec4<T> (C <= 4) or of 16 bytes; a multiple of the unit that holds C logits holds those
-      if (rows_aligned(z, CP, sizeof(T), CT <= 4 ? 4 * sizeof(T) : 16))
-        hipLaunchKernelGGL((head_softmax_fwd_kernel<T, CT, true>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
-      else hipLaunchKernelGGL((head_softmax_fwd_kernel<T, CT, false>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
-    });
-  });
-  return ltu_check_launch();
-}
-extern "C" int ltu_head_softmax_bwd(const float* dp, const float* p, void* dz, long long M, int C, int CP, int dtype,
-                                    ltu_stream_t s) {
-  if (C < 1 || C > LTU_WIDE_MAXC || CP < C) return LTU_E_SHAPE;
-  if (dtype == LTU_BF16 && rows_aligned(dz, CP, 2, 16)) {
-    LTU_DISPATCH_C(C, {
-      hipLaunchKernelGGL(head_softmax_bwd_bf16x8_kernel<CT>, dim3(sgrid(M * (CP / 8))), dim3(256), 0, (hipStream_t)s, dp, p, (uint4*)dz, M, CP);
-    });
-    return ltu_check_launch();
-  }
-  LTU_DISPATCH_T(dtype, {
-    const bool vec = rows_aligned(dz, CP, sizeof(T), 4 * sizeof(T));      // CP % 4 == 0 and CP >= C make CP >= HEAD_W(C)
-    LTU_DISPATCH_C(C, {
-      if (vec) hipLaunchKernelGGL((head_softmax_bwd_kernel<T, CT, true>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, M, CP);
-      else hipLaunchKernelGGL((head_softmax_bwd_kernel<T, CT, false>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, M, CP);
-    });
-  });
-  return ltu_check_launch();
-}
-
-// final head (model/Unet_3Dblock.py:1392-1394): z T [B,h,w,D,CP >= 4C] -> window un-embedding + softmax over classes
-// -> probs f32 [B,2h,2w,D,C];  channel c*4 + kh*2 + kw of coarse voxel (h,w) is class c of fine voxel (2h+kh, 2w+kw), so the 4-wide
-// load at channel 4c is class c of the four fine voxels.  One thread per coarse voxel.
-template <typename T, int C>
-__global__ void __launch_bounds__(256) final_softmax_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, int B, int h, int w, int D, int CP) {
-  const long long n = (long long)B * h * w * D;
-  GRID_STRIDE(i, n) {
-    const int d = (int)(i % D);
-    long long t = i / D;
-    const int ww = (int)(t % w); t /= w;
-    const int hh = (int)(t % h);
-    const int b = (int)(t / h);
-    float v[4 * C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const float4 t4 = Vec4<T>::load(z + i * CP + 4 * c);
-      v[4 * c] = t4.x; v[4 * c + 1] = t4.y; v[4 * c + 2] = t4.z; v[4 * c + 3] = t4.w;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float mx = -INFINITY, sum = 0.f, e[HEAD_W(C)];
-#pragma unroll
-      for (int c = 0; c < C; ++c) mx = fmaxf(mx, v[4 * c + q]);
-#pragma unroll
-      for (int c = 0; c < C; ++c) { e[c] = expf(v[4 * c + q] - mx); sum += e[c]; }
-      stprobs<C>(p + ((((long long)b * 2 * h + 2 * hh + (q >> 1)) * 2 * w + 2 * ww + (q & 1)) * D + d) * C, e, sum);
-    }
-  }
-}
-template <typename T, int C>
-__global__ void __launch_bounds__(256) final_softmax_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz,
-                                                                int B, int h, int w, int D, int CP) {
-  constexpr int W = HEAD_W(C);
-  const long long n = (long long)B * h * w * D;
-  GRID_STRIDE(i, n) {
-    const int d = (int)(i % D);
-    long long t = i / D;
-    const int ww = (int)(t % w); t /= w;
-    const int hh = (int)(t % h);
-    const int b = (int)(t / h);
-    float gv[4][W], pv[4][W];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {                 // all loads of the four fine voxels first
-      const long long o = ((((long long)b * 2 * h + 2 * hh + (q >> 1)) * 2 * w + 2 * ww + (q & 1)) * D + d) * C;
-      ldrow<C>(dp + o, gv[q]);
-      ldrow<C>(p + o, pv[q]);
-    }
-    float dot[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      dot[q] = 0.f;
-#pragma unroll
-      for (int c = 0; c < C; ++c) dot[q] = fmaf(gv[q][c], pv[q][c], dot[q]);      // the chain -ffp-contract=fast has always made of it, written out
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-      Vec4<T>::store(dz + i * CP + 4 * c, make_float4(pv[0][c] * (gv[0][c] - dot[0]), pv[1][c] * (gv[1][c] - dot[1]),
-                                                      pv[2][c] * (gv[2][c] - dot[2]), pv[3][c] * (gv[3][c] - dot[3])));
-    for (int k = 4 * C; k < CP; k += 4) Vec4<T>::store(dz + i * CP + k, make_float4(0.f, 0.f, 0.f, 0.f));      // padded conv columns
-  }
-}
-extern "C" int ltu_final_softmax_fwd(const void* z, float* p, int B, int h, int w, int D, int C, int CP, int dtype, ltu_stream_t s) {
-  if (C < 1 || C > LTU_WIDE_MAXC || CP < 4 * C || CP % 4) return LTU_E_SHAPE;
-  LTU_DISPATCH_T(dtype, {
-    const dim3 grid(sgrid((long long)B * h * w * D));
-    LTU_DISPATCH_C(C, { hipLaunchKernelGGL((final_softmax_fwd_kernel<T, CT>), grid, dim3(256), 0, (hipStream_t)s, (const T*)z, p, B, h, w, D, CP); });
-  });
-  return ltu_check_launch();
-}
-extern "C" int ltu_final_softmax_bwd(const float* dp, const float* p, void* dz, int B, int h, int w, int D, int C, int CP,
-                                     int dtype, ltu_stream_t s) {
-  if (C < 1 || C > LTU_WIDE_MAXC || CP < 4 * C || CP % 4) return LTU_E_SHAPE;
-  LTU_DISPATCH_T(dtype, {
-    const dim3 grid(sgrid((long long)B * h * w * D));
-    LTU_DISPATCH_C(C, { hipLaunchKernelGGL((final_softmax_bwd_kernel<T, CT>), grid, dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, B, h, w, D, CP); });
-  });
-  return ltu_check_launch();
-}
-
-// ------------------------------------------------------------------------------------------------ region sigmoid heads
-// The heads of a region model (region.hip): channel r is the sigmoid of logit r, p = 1 / (1 + exp(-z)), on the rows, padded columns,
-// dtypes and window un-embedding of the softmax heads above, 1 <= R <= 8.  exp(-z) overflows to +inf below z = -88.7 and the quotient
-// is then exactly 0; every finite logit gives a finite p in [0, 1].  Backward from the saved p: dz = (dp p) (1 - p), both products
-// rounded on their own and 1 - p one rounded difference, so every launch form of a row gives the same bits.
+};
+// The heads of a region model (region.hip): channel r is the sigmoid of logit r, p = 1 / (1 + exp(-z)).  exp(-z) overflows to +inf
+// below z = -88.7 and the quotient is then exactly 0; every finite logit gives a finite p in [0, 1].  Backward from the saved p:
+// dz = (dp p) (1 - p), both products rounded on their own and 1 - p one rounded difference, whatever FUSED says, so every launch form
+// of a row gives the same bits.
 // e^x with the range reduction written out.  Not expf: the library is built with -ffp-contract=fast, and the backend then fuses the
 // product of expf's own reduction, ph = x log2(e), into the difference ph - rint(ph) that is meant to be the exact difference of two
 // floats; the rounding error of ph is counted twice and the result is off by about |x| ulps (23 ulps measured at x = 27, where
@@ -553,35 +392,74 @@ __device__ __forceinline__ float exp_reduced(float x) {
 }
 __device__ __forceinline__ float sigmoid1(float z) { return 1.f / (1.f + exp_reduced(-z)); }
 __device__ __forceinline__ float sigmoid_grad(float g, float p) { return fmaf(fmaf(g, p, 0.f), 1.f - p, 0.f); }
+struct Sigmoid {
+  template <int C>
+  static __device__ __forceinline__ float probs(float (&v)[HEAD_W(C)]) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = sigmoid1(v[c]);
+    return 1.f;
+  }
+  template <int C, bool FUSED>
+  static __device__ __forceinline__ void grad(const float (&a)[HEAD_W(C)], const float (&b)[HEAD_W(C)], float (&g)[HEAD_W(C)]) {
+#pragma unroll
+    for (int c = 0; c < HEAD_W(C); ++c) g[c] = c < C ? sigmoid_grad(a[c], b[c]) : 0.f;
+  }
+};
 
-// logits T [M][CP] (first R live) -> p f32 [M][R].  VEC: ldlogits may read the row (see the launcher); otherwise R scalar loads
-template <typename T, int C, bool VEC>
-__global__ void __launch_bounds__(256) head_sigmoid_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, long long M, int CP) {
-  constexpr int W = HEAD_W(C);
+// mask head (model/Unet_3Dblock.py:1380-1381): logits T [M][CP] (CP = padded conv width, first C live) -> probs f32 [M][C].
+// VEC: ldlogits may read the row (see the launcher); otherwise C scalar loads
+template <typename A, typename T, int C, bool VEC>
+__global__ void __launch_bounds__(256) head_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, long long M, int CP) {
   GRID_STRIDE(m, M) {
-    float v[W];
+    float v[HEAD_W(C)];
     if constexpr (VEC) ldlogits<T, C>(z + m * CP, v);
     else {
 #pragma unroll
       for (int c = 0; c < C; ++c) v[c] = ld1<T>(z + m * CP + c);
     }
-#pragma unroll
-    for (int c = 0; c < C; ++c) v[c] = sigmoid1(v[c]);
-    stprobs<C>(p + m * C, v, 1.f);
+    const float div = A::template probs<C>(v);
+    stprobs<C>(p + m * C, v, div);
+  }
+}
+// the logit gradient of row m from dp and the saved p, both f32 [M][C]
+template <typename A, int C, bool FUSED>
+__device__ __forceinline__ void head_grad(const float* __restrict__ dp, const float* __restrict__ p, long long m, float (&g)[HEAD_W(C)]) {
+  float a[HEAD_W(C)], b[HEAD_W(C)];
+  ldrow<C>(dp + m * C, a);
+  ldrow<C>(p + m * C, b);
+  A::template grad<C, FUSED>(a, b, g);
+}
+// bf16 rows of CP = 8k padded logits: one thread and one 16-byte store per 8 columns (the fused conv pairs pad the heads to 16 / 32
+// columns); the first group holds the C gradients, every other word is a constant zero
+template <typename A, int C>
+__global__ void __launch_bounds__(256) head_bwd_bf16x8_kernel(const float* __restrict__ dp, const float* __restrict__ p,
+                                                              uint4* __restrict__ dz, long long M, int CP) {
+  const int v8 = CP / 8;
+  GRID_STRIDE(i, M * v8) {
+    const long long m = i / v8;
+    uint4 o = make_uint4(0u, 0u, 0u, 0u);
+    if (i - m * v8 == 0) {
+      float g[HEAD_W(C)];
+      head_grad<A, C, false>(dp, p, m, g);
+      o.x = pack_bf16x2(g[0], g[1]);
+      o.y = pack_bf16x2(g[2], g[3]);
+      if constexpr (C > 4) {
+        o.z = pack_bf16x2(g[4], g[5]);
+        o.w = pack_bf16x2(g[6], g[7]);
+      }
+    }
+    dz[i] = o;
   }
 }
 // one thread per row.  VEC: every row starts on a Vec4<T> boundary and CP % 4 == 0: 4-wide stores, zeros behind the first HEAD_W(C)
 // columns; otherwise scalar stores
-template <typename T, int C, bool VEC>
-__global__ void __launch_bounds__(256) head_sigmoid_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz,
-                                                               long long M, int CP) {
+template <typename A, typename T, int C, bool VEC>
+__global__ void __launch_bounds__(256) head_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz,
+                                                       long long M, int CP) {
   constexpr int W = HEAD_W(C);
   GRID_STRIDE(m, M) {
-    float a[W], b[W], g[W];
-    ldrow<C>(dp + m * C, a);
-    ldrow<C>(p + m * C, b);
-#pragma unroll
-    for (int c = 0; c < W; ++c) g[c] = c < C ? sigmoid_grad(a[c], b[c]) : 0.f;
+    float g[W];
+    head_grad<A, C, true>(dp, p, m, g);
     T* o = dz + m * CP;
     if constexpr (VEC) {
 #pragma unroll
@@ -594,41 +472,75 @@ __global__ void __launch_bounds__(256) head_sigmoid_bwd_kernel(const float* __re
     }
   }
 }
-extern "C" int ltu_head_sigmoid_fwd(const void* z, float* p, long long M, int R, int CP, int dtype, ltu_stream_t s) {
-  if (R < 1 || R > LTU_WIDE_MAXC || CP < R) return LTU_E_SHAPE;
+template <typename A>
+static int head_fwd(const void* z, float* p, long long M, int C, int CP, int dtype, ltu_stream_t s) {
+  if (C < 1 || C > LTU_WIDE_MAXC || CP < C) return LTU_E_SHAPE;
   LTU_DISPATCH_T(dtype, {
-    LTU_DISPATCH_C(R, {
+    LTU_DISPATCH_C(C, {
+      // ldlogits reads HEAD_W(C) logits in units of a Vec4<T> (C <= 4) or of 16 bytes; a multiple of the unit that holds C logits holds those
       if (rows_aligned(z, CP, sizeof(T), CT <= 4 ? 4 * sizeof(T) : 16))
-        hipLaunchKernelGGL((head_sigmoid_fwd_kernel<T, CT, true>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
-      else hipLaunchKernelGGL((head_sigmoid_fwd_kernel<T, CT, false>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
+        hipLaunchKernelGGL((head_fwd_kernel<A, T, CT, true>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
+      else hipLaunchKernelGGL((head_fwd_kernel<A, T, CT, false>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, (const T*)z, p, M, CP);
     });
   });
   return ltu_check_launch();
+}
+template <typename A>
+static int head_bwd(const float* dp, const float* p, void* dz, long long M, int C, int CP, int dtype, ltu_stream_t s) {
+  if (C < 1 || C > LTU_WIDE_MAXC || CP < C) return LTU_E_SHAPE;
+  if (dtype == LTU_BF16 && rows_aligned(dz, CP, 2, 16)) {
+    LTU_DISPATCH_C(C, {
+      hipLaunchKernelGGL((head_bwd_bf16x8_kernel<A, CT>), dim3(sgrid(M * (CP / 8))), dim3(256), 0, (hipStream_t)s, dp, p, (uint4*)dz, M, CP);
+    });
+    return ltu_check_launch();
+  }
+  LTU_DISPATCH_T(dtype, {
+    const bool vec = rows_aligned(dz, CP, sizeof(T), 4 * sizeof(T));      // CP % 4 == 0 and CP >= C make CP >= HEAD_W(C)
+    LTU_DISPATCH_C(C, {
+      if (vec) hipLaunchKernelGGL((head_bwd_kernel<A, T, CT, true>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, M, CP);
+      else hipLaunchKernelGGL((head_bwd_kernel<A, T, CT, false>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, M, CP);
+    });
+  });
+  return ltu_check_launch();
+}
+extern "C" int ltu_head_softmax_fwd(const void* z, float* p, long long M, int C, int CP, int dtype, ltu_stream_t s) {
+  return head_fwd<Softmax>(z, p, M, C, CP, dtype, s);
+}
+extern "C" int ltu_head_softmax_bwd(const float* dp, const float* p, void* dz, long long M, int C, int CP, int dtype,
+                                    ltu_stream_t s) {
+  return head_bwd<Softmax>(dp, p, dz, M, C, CP, dtype, s);
+}
+extern "C" int ltu_head_sigmoid_fwd(const void* z, float* p, long long M, int R, int CP, int dtype, ltu_stream_t s) {
+  return head_fwd<Sigmoid>(z, p, M, R, CP, dtype, s);
 }
 extern "C" int ltu_head_sigmoid_bwd(const float* dp, const float* p, void* dz, long long M, int R, int CP, int dtype,
                                     ltu_stream_t s) {
-  if (R < 1 || R > LTU_WIDE_MAXC || CP < R) return LTU_E_SHAPE;
-  LTU_DISPATCH_T(dtype, {
-    const bool vec = rows_aligned(dz, CP, sizeof(T), 4 * sizeof(T));      // CP % 4 == 0 and CP >= R make CP >= HEAD_W(R)
-    LTU_DISPATCH_C(R, {
-      if (vec) hipLaunchKernelGGL((head_sigmoid_bwd_kernel<T, CT, true>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, M, CP);
-      else hipLaunchKernelGGL((head_sigmoid_bwd_kernel<T, CT, false>), dim3(sgrid(M)), dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, M, CP);
-    });
-  });
-  return ltu_check_launch();
+  return head_bwd<Sigmoid>(dp, p, dz, M, R, CP, dtype, s);
 }
 
-// final head of a region model: z T [B,h,w,D,CP >= 4R] -> window un-embedding + sigmoid -> p f32 [B,2h,2w,D,R], the channel map of
-// final_softmax_fwd_kernel.  One thread per coarse voxel.
-template <typename T, int C>
-__global__ void __launch_bounds__(256) final_sigmoid_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, int B, int h, int w, int D, int CP) {
+// final head (model/Unet_3Dblock.py:1392-1394): z T [B,h,w,D,CP >= 4C] -> window un-embedding + activation over classes
+// -> probs f32 [B,2h,2w,D,C];  channel c*4 + kh*2 + kw of coarse voxel (h,w) is class c of fine voxel (2h+kh, 2w+kw), so the 4-wide
+// load at channel 4c is class c of the four fine voxels.  One thread per coarse voxel.
+// coarse voxel i of [B,h,w,D]; row<C>(q): the offset of its fine voxel q = 2 kh + kw in an f32 tensor [B,2h,2w,D,C]
+struct CoarseVoxel {
+  int h, w, D, b, hh, ww, d;
+  __device__ __forceinline__ CoarseVoxel(long long i, int h_, int w_, int D_) : h(h_), w(w_), D(D_) {
+    d = (int)(i % D);
+    long long t = i / D;
+    ww = (int)(t % w); t /= w;
+    hh = (int)(t % h);
+    b = (int)(t / h);
+  }
+  template <int C>
+  __device__ __forceinline__ long long row(int q) const {
+    return ((((long long)b * 2 * h + 2 * hh + (q >> 1)) * 2 * w + 2 * ww + (q & 1)) * D + d) * C;
+  }
+};
+template <typename A, typename T, int C>
+__global__ void __launch_bounds__(256) final_fwd_kernel(const T* __restrict__ z, float* __restrict__ p, int B, int h, int w, int D, int CP) {
   const long long n = (long long)B * h * w * D;
   GRID_STRIDE(i, n) {
-    const int d = (int)(i % D);
-    long long t = i / D;
-    const int ww = (int)(t % w); t /= w;
-    const int hh = (int)(t % h);
-    const int b = (int)(t / h);
+    const CoarseVoxel cv(i, h, w, D);
     float v[4 * C];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -639,52 +551,64 @@ __global__ void __launch_bounds__(256) final_sigmoid_fwd_kernel(const T* __restr
     for (int q = 0; q < 4; ++q) {
       float e[HEAD_W(C)];
 #pragma unroll
-      for (int c = 0; c < C; ++c) e[c] = sigmoid1(v[4 * c + q]);
-      stprobs<C>(p + ((((long long)b * 2 * h + 2 * hh + (q >> 1)) * 2 * w + 2 * ww + (q & 1)) * D + d) * C, e, 1.f);
+      for (int c = 0; c < C; ++c) e[c] = v[4 * c + q];
+      const float div = A::template probs<C>(e);
+      stprobs<C>(p + cv.row<C>(q), e, div);
     }
   }
 }
-template <typename T, int C>
-__global__ void __launch_bounds__(256) final_sigmoid_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz,
-                                                                int B, int h, int w, int D, int CP) {
+template <typename A, typename T, int C>
+__global__ void __launch_bounds__(256) final_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, T* __restrict__ dz,
+                                                        int B, int h, int w, int D, int CP) {
   constexpr int W = HEAD_W(C);
   const long long n = (long long)B * h * w * D;
   GRID_STRIDE(i, n) {
-    const int d = (int)(i % D);
-    long long t = i / D;
-    const int ww = (int)(t % w); t /= w;
-    const int hh = (int)(t % h);
-    const int b = (int)(t / h);
-    float gv[4][W], pv[4][W];
+    const CoarseVoxel cv(i, h, w, D);
+    float gv[4][W], pv[4][W], g[4][W];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                 // all loads of the four fine voxels first
-      const long long o = ((((long long)b * 2 * h + 2 * hh + (q >> 1)) * 2 * w + 2 * ww + (q & 1)) * D + d) * C;
+      const long long o = cv.row<C>(q);
       ldrow<C>(dp + o, gv[q]);
       ldrow<C>(p + o, pv[q]);
     }
 #pragma unroll
-    for (int c = 0; c < C; ++c)
-      Vec4<T>::store(dz + i * CP + 4 * c, make_float4(sigmoid_grad(gv[0][c], pv[0][c]), sigmoid_grad(gv[1][c], pv[1][c]),
-                                                      sigmoid_grad(gv[2][c], pv[2][c]), sigmoid_grad(gv[3][c], pv[3][c])));
+    for (int q = 0; q < 4; ++q) A::template grad<C, true>(gv[q], pv[q], g[q]);      // the chain -ffp-contract=fast has always made of it
+#pragma unroll
+    for (int c = 0; c < C; ++c) Vec4<T>::store(dz + i * CP + 4 * c, make_float4(g[0][c], g[1][c], g[2][c], g[3][c]));
     for (int k = 4 * C; k < CP; k += 4) Vec4<T>::store(dz + i * CP + k, make_float4(0.f, 0.f, 0.f, 0.f));      // padded conv columns
   }
 }
-extern "C" int ltu_final_sigmoid_fwd(const void* z, float* p, int B, int h, int w, int D, int R, int CP, int dtype, ltu_stream_t s) {
-  if (R < 1 || R > LTU_WIDE_MAXC || CP < 4 * R || CP % 4) return LTU_E_SHAPE;
+template <typename A>
+static int final_fwd(const void* z, float* p, int B, int h, int w, int D, int C, int CP, int dtype, ltu_stream_t s) {
+  if (C < 1 || C > LTU_WIDE_MAXC || CP < 4 * C || CP % 4) return LTU_E_SHAPE;
   LTU_DISPATCH_T(dtype, {
     const dim3 grid(sgrid((long long)B * h * w * D));
-    LTU_DISPATCH_C(R, { hipLaunchKernelGGL((final_sigmoid_fwd_kernel<T, CT>), grid, dim3(256), 0, (hipStream_t)s, (const T*)z, p, B, h, w, D, CP); });
+    LTU_DISPATCH_C(C, { hipLaunchKernelGGL((final_fwd_kernel<A, T, CT>), grid, dim3(256), 0, (hipStream_t)s, (const T*)z, p, B, h, w, D, CP); });
   });
   return ltu_check_launch();
 }
-extern "C" int ltu_final_sigmoid_bwd(const float* dp, const float* p, void* dz, int B, int h, int w, int D, int R, int CP,
-                                     int dtype, ltu_stream_t s) {
-  if (R < 1 || R > LTU_WIDE_MAXC || CP < 4 * R || CP % 4) return LTU_E_SHAPE;
+template <typename A>
+static int final_bwd(const float* dp, const float* p, void* dz, int B, int h, int w, int D, int C, int CP, int dtype, ltu_stream_t s) {
+  if (C < 1 || C > LTU_WIDE_MAXC || CP < 4 * C || CP % 4) return LTU_E_SHAPE;
   LTU_DISPATCH_T(dtype, {
     const dim3 grid(sgrid((long long)B * h * w * D));
-    LTU_DISPATCH_C(R, { hipLaunchKernelGGL((final_sigmoid_bwd_kernel<T, CT>), grid, dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, B, h, w, D, CP); });
+    LTU_DISPATCH_C(C, { hipLaunchKernelGGL((final_bwd_kernel<A, T, CT>), grid, dim3(256), 0, (hipStream_t)s, dp, p, (T*)dz, B, h, w, D, CP); });
   });
   return ltu_check_launch();
+}
+extern "C" int ltu_final_softmax_fwd(const void* z, float* p, int B, int h, int w, int D, int C, int CP, int dtype, ltu_stream_t s) {
+  return final_fwd<Softmax>(z, p, B, h, w, D, C, CP, dtype, s);
+}
+extern "C" int ltu_final_softmax_bwd(const float* dp, const float* p, void* dz, int B, int h, int w, int D, int C, int CP,
+                                     int dtype, ltu_stream_t s) {
+  return final_bwd<Softmax>(dp, p, dz, B, h, w, D, C, CP, dtype, s);
+}
+extern "C" int ltu_final_sigmoid_fwd(const void* z, float* p, int B, int h, int w, int D, int R, int CP, int dtype, ltu_stream_t s) {
+  return final_fwd<Sigmoid>(z, p, B, h, w, D, R, CP, dtype, s);
+}
+extern "C" int ltu_final_sigmoid_bwd(const float* dp, const float* p, void* dz, int B, int h, int w, int D, int R, int CP,
+                                     int dtype, ltu_stream_t s) {
+  return final_bwd<Sigmoid>(dp, p, dz, B, h, w, D, R, CP, dtype, s);
 }
 // eval branch of a region model: the indicator [p > thr] as f32, elementwise (any layout)
 __global__ void __launch_bounds__(256) prob_indicator_kernel(const float* __restrict__ p, float* __restrict__ o, long long n, float thr) {

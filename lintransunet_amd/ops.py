@@ -1543,118 +1543,71 @@ def roi_unwarp(x, plan):
 
 # ---------------------------------------------------------------------------------------------- heads
 
-class _HeadSoftmax(torch.autograd.Function):
+class _Head(torch.autograd.Function):
+    """a mask head on the ltu_head_<act>_* entries, act = 'softmax' (classes) or 'sigmoid' (the regions of a region model)"""
+
     @staticmethod
-    def forward(ctx, z, C):
-        lc = ctx.lc = current()
+    def forward(ctx, z, C, act):
         _chk(z, 'z')
         CP = z.shape[-1]
-        M = z.numel() // CP
         p = torch.empty(z.shape[:-1] + (C,), device=z.device, dtype=torch.float32)
-        _lib.call('ltu_head_softmax_fwd', _p(z), _p(p), M, C, CP, _dt(z), _s())
+        _lib.call(f'ltu_head_{act}_fwd', _p(z), _p(p), z.numel() // CP, C, CP, _dt(z), _s())
         ctx.save_for_backward(p)
-        ctx.cfg = (C, CP, z.dtype)
+        ctx.cfg = (C, CP, z.dtype, act)
         return p
 
     @staticmethod
     def backward(ctx, g):
-        lc = ctx.lc
         (p,) = ctx.saved_tensors
-        C, CP, zdt = ctx.cfg
+        C, CP, zdt, act = ctx.cfg
         g = g.contiguous()
         dz = torch.empty(p.shape[:-1] + (CP,), device=p.device, dtype=zdt)
-        _lib.call('ltu_head_softmax_bwd', _p(g), _p(p), _p(dz), p.numel() // C, C, CP, _dt(dz), _s())
-        return dz, None
+        _lib.call(f'ltu_head_{act}_bwd', _p(g), _p(p), _p(dz), p.numel() // C, C, CP, _dt(dz), _s())
+        return dz, None, None
+
+
+class _FinalHead(torch.autograd.Function):
+    """the final head (window un-embedding + activation) on the ltu_final_<act>_* entries"""
+
+    @staticmethod
+    def forward(ctx, z, C, act):
+        _chk(z, 'z')
+        B, h, w, D, CP = z.shape
+        p = torch.empty((B, 2 * h, 2 * w, D, C), device=z.device, dtype=torch.float32)
+        _lib.call(f'ltu_final_{act}_fwd', _p(z), _p(p), B, h, w, D, C, CP, _dt(z), _s())
+        ctx.save_for_backward(p)
+        ctx.cfg = (B, h, w, D, C, CP, z.dtype, act)
+        return p
+
+    @staticmethod
+    def backward(ctx, g):
+        (p,) = ctx.saved_tensors
+        B, h, w, D, C, CP, zdt, act = ctx.cfg
+        g = g.contiguous()
+        dz = torch.empty((B, h, w, D, CP), device=p.device, dtype=zdt)
+        _lib.call(f'ltu_final_{act}_bwd', _p(g), _p(p), _p(dz), B, h, w, D, C, CP, _dt(dz), _s())
+        return dz, None, None
 
 
 def head_softmax(z, C):
     """class softmax over the first C <= 8 of the (padded) channels of z -> fp32 probabilities [..., C]."""
-    return _HeadSoftmax.apply(z, C)
-
-
-class _FinalSoftmax(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, z, C):
-        lc = ctx.lc = current()
-        _chk(z, 'z')
-        B, h, w, D, CP = z.shape
-        p = torch.empty((B, 2 * h, 2 * w, D, C), device=z.device, dtype=torch.float32)
-        _lib.call('ltu_final_softmax_fwd', _p(z), _p(p), B, h, w, D, C, CP, _dt(z), _s())
-        ctx.save_for_backward(p)
-        ctx.cfg = (B, h, w, D, C, CP, z.dtype)
-        return p
-
-    @staticmethod
-    def backward(ctx, g):
-        lc = ctx.lc
-        (p,) = ctx.saved_tensors
-        B, h, w, D, C, CP, zdt = ctx.cfg
-        g = g.contiguous()
-        dz = torch.empty((B, h, w, D, CP), device=p.device, dtype=zdt)
-        _lib.call('ltu_final_softmax_bwd', _p(g), _p(p), _p(dz), B, h, w, D, C, CP, _dt(dz), _s())
-        return dz, None
+    return _Head.apply(z, C, 'softmax')
 
 
 def final_softmax(z, C):
     """window un-embedding + class softmax: z [B,h,w,D,CP >= 4C] (conv output, possibly padded), C <= 8 -> fp32 probabilities
     [B,2h,2w,D,C]."""
-    return _FinalSoftmax.apply(z, C)
-
-
-class _HeadSigmoid(torch.autograd.Function):
-    """_HeadSoftmax on the sigmoid entries: the heads of a region model"""
-
-    @staticmethod
-    def forward(ctx, z, R):
-        _chk(z, 'z')
-        CP = z.shape[-1]
-        p = torch.empty(z.shape[:-1] + (R,), device=z.device, dtype=torch.float32)
-        _lib.call('ltu_head_sigmoid_fwd', _p(z), _p(p), z.numel() // CP, R, CP, _dt(z), _s())
-        ctx.save_for_backward(p)
-        ctx.cfg = (R, CP, z.dtype)
-        return p
-
-    @staticmethod
-    def backward(ctx, g):
-        (p,) = ctx.saved_tensors
-        R, CP, zdt = ctx.cfg
-        g = g.contiguous()
-        dz = torch.empty(p.shape[:-1] + (CP,), device=p.device, dtype=zdt)
-        _lib.call('ltu_head_sigmoid_bwd', _p(g), _p(p), _p(dz), p.numel() // R, R, CP, _dt(dz), _s())
-        return dz, None
+    return _FinalHead.apply(z, C, 'softmax')
 
 
 def head_sigmoid(z, R):
     """one sigmoid per region over the first R <= 8 of the (padded) channels of z -> fp32 probabilities [..., R]."""
-    return _HeadSigmoid.apply(z, R)
-
-
-class _FinalSigmoid(torch.autograd.Function):
-    """_FinalSoftmax on the sigmoid entries"""
-
-    @staticmethod
-    def forward(ctx, z, R):
-        _chk(z, 'z')
-        B, h, w, D, CP = z.shape
-        p = torch.empty((B, 2 * h, 2 * w, D, R), device=z.device, dtype=torch.float32)
-        _lib.call('ltu_final_sigmoid_fwd', _p(z), _p(p), B, h, w, D, R, CP, _dt(z), _s())
-        ctx.save_for_backward(p)
-        ctx.cfg = (B, h, w, D, R, CP, z.dtype)
-        return p
-
-    @staticmethod
-    def backward(ctx, g):
-        (p,) = ctx.saved_tensors
-        B, h, w, D, R, CP, zdt = ctx.cfg
-        g = g.contiguous()
-        dz = torch.empty((B, h, w, D, CP), device=p.device, dtype=zdt)
-        _lib.call('ltu_final_sigmoid_bwd', _p(g), _p(p), _p(dz), B, h, w, D, R, CP, _dt(dz), _s())
-        return dz, None
+    return _Head.apply(z, R, 'sigmoid')
 
 
 def final_sigmoid(z, R):
     """window un-embedding + one sigmoid per region: z [B,h,w,D,CP >= 4R], R <= 8 -> fp32 probabilities [B,2h,2w,D,R]."""
-    return _FinalSigmoid.apply(z, R)
+    return _FinalHead.apply(z, R, 'sigmoid')
 
 
 class _Gate(torch.autograd.Function):

@@ -89,7 +89,7 @@ def test_head_softmax_wide(ops, C, dtype, CP):
 def test_head_softmax_misaligned_base(ops, C, dtype, CP):
     """contiguous rows whose base lies one element behind a 16-byte boundary take the scalar variants of both passes; the results
     equal those of the vector variants on the aligned copy bit for bit.  (bf16 backward: the aligned run is the 16-byte-store kernel,
-    which sums dp p from rounded products where the row kernels run an fma chain - head_grad in csrc/pointwise.hip; the two differ
+    which sums dp p from rounded products where the row kernels run an fma chain - Softmax::grad in csrc/pointwise.hip; the two differ
     in about one bf16 gradient in 10^5, in none of these seeded rows)"""
     from lintransunet_amd import _lib
     M = 1031

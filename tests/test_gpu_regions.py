@@ -16,6 +16,7 @@ from oracle import net as O_net          # noqa: E402
 from oracle import seedgen               # noqa: E402
 from oracle import step as O_step        # noqa: E402
 from tests import region_common as RC
+from tests.test_gpu_conv_paths import launched
 
 pytestmark = pytest.mark.gpu
 
@@ -131,9 +132,14 @@ def test_head_sigmoid(R, dt):
             ref_p = p
         assert torch.equal(p, ref_p), CP                             # vector and scalar launches of the same rows: the same bits
         assert torch.equal(_head_fwd(_offset_copy(z), R), ref_p), CP   # a misaligned base pointer: the scalar launch
-        dz = _head_bwd(dp, p, torch.full((M, CP), float('nan'), device=DEV, dtype=tdt))
-        dz_off = _head_bwd(dp, p, _offset_copy(torch.full((M, CP), float('nan'), device=DEV, dtype=tdt)))
+        named = dt == BF16 and CP == 16                              # one case records what the two launches were
+        run = launched if named else (lambda fn: (fn(), None))
+        dz, k_dz = run(lambda: _head_bwd(dp, p, torch.full((M, CP), float('nan'), device=DEV, dtype=tdt)))
+        dz_off, k_off = run(lambda: _head_bwd(dp, p, _offset_copy(torch.full((M, CP), float('nan'), device=DEV, dtype=tdt))))
         assert torch.equal(dz, dz_off), CP
+        if named:                                                    # .. so that comparison is one between two kernels
+            assert f'head_bwd_bf16x8_kernel<Sigmoid, {R}>' in k_dz, k_dz
+            assert f'head_bwd_kernel<Sigmoid, bf16_t, {R}, false>' in k_off, k_off
         dzh = dz.float().cpu().numpy()
         assert not dzh[:, R:].any() and not np.signbit(dzh[:, R:]).any()      # padded columns: exactly 0
         d64 = RC.sigmoid_grad_ref(dp_h, ph)

@@ -280,10 +280,10 @@ CASES = [
 
 # kernels of the newest profile whose element-wise bf16 tests live elsewhere
 ELSEWHERE = {
-    'final_softmax_fwd_kernel<bf16_t, 2>': 'tests/test_gpu_manyclass.py::test_final_softmax',
-    'final_softmax_bwd_kernel<bf16_t, 2>': 'tests/test_gpu_manyclass.py::test_final_softmax',
-    'head_softmax_fwd_kernel<bf16_t, 2, true>': 'tests/test_gpu_manyclass.py::test_head_softmax_wide',
-    'head_softmax_bwd_bf16x8_kernel<2>': 'tests/test_gpu_manyclass.py::test_head_softmax_wide',
+    'final_fwd_kernel<Softmax, bf16_t, 2>': 'tests/test_gpu_manyclass.py::test_final_softmax',
+    'final_bwd_kernel<Softmax, bf16_t, 2>': 'tests/test_gpu_manyclass.py::test_final_softmax',
+    'head_fwd_kernel<Softmax, bf16_t, 2, true>': 'tests/test_gpu_manyclass.py::test_head_softmax_wide',
+    'head_bwd_bf16x8_kernel<Softmax, 2>': 'tests/test_gpu_manyclass.py::test_head_softmax_wide',
     'loss_sums_kernel<2, true>': 'tests/test_gpu_manyclass.py::test_level_loss_narrow',
     'loss_bwd_kernel<2, true>': 'tests/test_gpu_manyclass.py::test_level_loss_narrow',
     'loss_finalize_kernel<2>': 'tests/test_gpu_manyclass.py::test_level_loss_narrow',
@@ -291,9 +291,14 @@ ELSEWHERE = {
     'window_embed_kernel<bf16_t>': 'tests/test_gpu_multichannel.py::test_window_embed',
 }
 # names of the profile that the sources have since merged or re-templated (the two table kernels of the trilinear adjoint became
-# one; the vector forms of the softmax head and of the level losses became a template argument; the finalizer got its class count)
+# one; the vector forms of the softmax head and of the level losses became a template argument; the finalizer got its class count;
+# the softmax heads became the Softmax instantiations of the head family)
 RENAMED = {'tri_table_kernel': 'tri_tables_kernel', 'tri_pair_table_kernel': 'tri_tables_kernel',
-           'head_softmax_fwd_vec_kernel<bf16_t, 2>': 'head_softmax_fwd_kernel<bf16_t, 2, true>',
+           'head_softmax_fwd_vec_kernel<bf16_t, 2>': 'head_fwd_kernel<Softmax, bf16_t, 2, true>',
+           'head_softmax_fwd_kernel<bf16_t, 2, true>': 'head_fwd_kernel<Softmax, bf16_t, 2, true>',
+           'head_softmax_bwd_bf16x8_kernel<2>': 'head_bwd_bf16x8_kernel<Softmax, 2>',
+           'final_softmax_fwd_kernel<bf16_t, 2>': 'final_fwd_kernel<Softmax, bf16_t, 2>',
+           'final_softmax_bwd_kernel<bf16_t, 2>': 'final_bwd_kernel<Softmax, bf16_t, 2>',
            'loss_sums_v4_kernel<2>': 'loss_sums_kernel<2, true>', 'loss_bwd_v4_kernel<2>': 'loss_bwd_kernel<2, true>',
            'loss_finalize_kernel': 'loss_finalize_kernel<2>'}
 TORCH_OWN = ('at::native::', '__amd_rocclr_')

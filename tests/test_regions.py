@@ -254,12 +254,12 @@ def test_cabi_surface():
         assert helper in code, helper
     mk = open(os.path.join(ROOT, 'lintransunet_amd', 'csrc', 'Makefile')).read()
     assert 'region.hip' in mk
-    # the kernels the path tables pin keep their names and template lists; the new ones are siblings
+    # the kernels the path tables pin keep their names and template lists; the sigmoid heads are the Sigmoid policy of the head family
     pw = open(os.path.join(ROOT, 'lintransunet_amd', 'csrc', 'pointwise.hip')).read()
     roi = open(os.path.join(ROOT, 'lintransunet_amd', 'csrc', 'roi.hip')).read()
-    for text, name in ((pw, 'template <typename T, int C, bool VEC>\n__global__ void __launch_bounds__(256) head_softmax_fwd_kernel('),
-                       (pw, 'template <typename T, int C>\n__global__ void __launch_bounds__(256) final_softmax_fwd_kernel('),
-                       (pw, 'head_sigmoid_fwd_kernel('), (pw, 'final_sigmoid_bwd_kernel('),
+    for text, name in ((pw, 'template <typename A, typename T, int C, bool VEC>\n__global__ void __launch_bounds__(256) head_fwd_kernel('),
+                       (pw, 'template <typename A, typename T, int C>\n__global__ void __launch_bounds__(256) final_fwd_kernel('),
+                       (pw, 'struct Sigmoid {'), (pw, 'head_fwd<Sigmoid>('), (pw, 'final_bwd<Sigmoid>('),
                        (roi, '__global__ void __launch_bounds__(256) roi_hist_kernel(const float* __restrict__ prob, int H, int W, int D, int C, float thr,'),
                        (roi, 'roi_hist_union_kernel('), (roi, '__global__ void roi_plan_kernel(const RoiArgs a, const int* __restrict__ hist)')):
         assert name in text, name
